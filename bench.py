@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- Gsamples/s of the fused baseline + Savitzky-Golay filter + threshold-hit pass.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--records R] [--preset v1725|vx2730]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--records R] [--preset v1725|vx2730] [--dump-outputs DIR]
+
+The inputs are synthetic and seeded: the same arguments give the same chunk on every run.  --dump-outputs DIR writes the
+hit rows of the last timed step to DIR (dump_hit_rows), so that two builds can be compared output for output.
 
 One *step* = one pass of the hot path over one resident chunk: the streaming kernel (baseline estimate over the first 40
 samples, SG(11,2) filter evaluated on the fly, threshold mask -> ordered run events), the scan of the per-span hit
@@ -70,7 +73,15 @@ def parse_args() -> argparse.Namespace:
     ap.add_argument("--c4-records", type=int, default=333_334,
                     help="N > 1 only: records per GPU of the untimed config-4 leg (256-ch VX2730, x1500 = 5e8 samples); 0 = skip")
     ap.add_argument("--master-port", type=int, default=int(os.environ.get("WFA_BENCH_PORT", "29613")))
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the hit rows of the last timed step to DIR/*.npy (one array per field, at most 64 MB in all: "
+                         "a fixed, seeded sample of the records' rows when they do not all fit)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return args
 
 
 def launch_ranks(args: argparse.Namespace) -> int:
@@ -186,6 +197,53 @@ def row_digest(rows) -> tuple[int, int]:
     with np.errstate(over="ignore"):
         total = (buf.view(np.uint64) * mult[None, :]).sum(dtype=np.uint64)
     return n, int(total)
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+DUMP_SEED = 20251015
+# canonical row order (a pass may deliver its rows in any order): by record, then position in it, then every other field
+DUMP_ORDER = ("record_id", "position", "edge_start", "edge_end", "timestamp", "board", "channel", "dt", "height",
+              "integral", "width", "rise_time", "fall_time")
+
+
+def dump_hit_rows(rows, record_ids, out_dir: str, prefix: str = "", budget: int = DUMP_BUDGET_BYTES) -> dict:
+    """Write a hit-row table as `<prefix>hit_threshold_<field>.npy` (integer fields as float64 -- exact, checked -- float
+    fields as float32) in canonical order, plus `<prefix>hit_threshold_n.npy`, the table's row count.  When the rows do not
+    fit `budget` bytes, those of a seeded random order of the INPUT records (record_ids) are taken record by record while
+    they fit: the choice depends on the inputs only, so two builds that compute the same rows dump the same sample."""
+    import numpy as np
+
+    names = rows.dtype.names
+    assert sorted(names) == sorted(DUMP_ORDER), names
+    n_total = len(rows)
+    rows = rows[np.lexsort([rows[f] for f in reversed(DUMP_ORDER)])] if n_total else rows
+    row_bytes = sum(8 if rows.dtype[f].kind in "iu" else 4 for f in names)
+    max_rows = max(0, (budget - 4096 * (len(names) + 1)) // row_bytes)  # npy headers: well under 4 KiB each
+    sampled = n_total > max_rows
+    if sampled:
+        rid = np.ascontiguousarray(rows["record_id"])
+        order = np.random.default_rng(DUMP_SEED).permutation(np.asarray(record_ids, dtype=np.int64))
+        per_record = np.searchsorted(rid, order, "right") - np.searchsorted(rid, order, "left")
+        chosen = np.sort(order[np.cumsum(per_record) <= max_rows])
+        rows = rows[np.isin(rid, chosen)]
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for f in names:
+        col = rows[f]
+        if col.dtype.kind in "iu":
+            if len(col) and int(np.abs(col.astype(np.int64)).max()) > 1 << 53:
+                raise ValueError(f"{f}: values beyond 2^53 are not exact in float64")
+            col = col.astype(np.float64)
+        else:
+            col = col.astype(np.float32)
+        path = os.path.join(out_dir, f"{prefix}hit_threshold_{f}.npy")
+        np.save(path, col)
+        written += os.path.getsize(path)
+    path = os.path.join(out_dir, f"{prefix}hit_threshold_n.npy")
+    np.save(path, np.array([n_total], dtype=np.float64))
+    written += os.path.getsize(path)
+    return {"dir": os.path.abspath(out_dir), "rows": int(n_total), "rows_written": int(len(rows)), "sampled": bool(sampled),
+            "bytes": int(written)}
 
 
 def config4_leg(args, DeviceSession, dist, rank: int, world: int, device_id: int) -> dict:
@@ -346,6 +404,8 @@ def rank_main(args: argparse.Namespace) -> int:
     elapsed = time.perf_counter() - t0
     n_hits = sess.hits_wait()  # row count of the last pass (already complete)
     prof = sess.profile_report()
+    # the rows of the last timed pass, copied out before anything else runs on the session
+    last_rows = sess._fill_hits(n_hits) if args.dump_outputs else None
     # per-kernel breakdown of a pass: three more passes with every launch timed, outside the timed region
     sess.profile(1)
     for _ in range(3):
@@ -540,6 +600,11 @@ def rank_main(args: argparse.Namespace) -> int:
         except Exception as exc:  # noqa: BLE001
             two = {"error": f"{type(exc).__name__}: {exc}"}
 
+    dump = None
+    if last_rows is not None:
+        dump = dump_hit_rows(last_rows, records["record_id"], args.dump_outputs,
+                             prefix=f"rank{rank}_" if world > 1 else "", budget=DUMP_BUDGET_BYTES // world)
+
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = n_samples * n_gpus / (elapsed / args.steps) / 1e9
@@ -603,6 +668,8 @@ def rank_main(args: argparse.Namespace) -> int:
             out["end_to_end"] = e2e
         if two:
             out["two_sessions"] = two
+        if dump:
+            out["dump_outputs"] = dump
         if gather is not None:
             out["gather_ok"] = gather_ok
             out["gather"] = gather
