@@ -74,8 +74,16 @@ int wfa_sync(wfa_ctx* ctx);
 int wfa_release_scratch(wfa_ctx* ctx, int64_t* freed_bytes);
 /* Choice between code paths that produce identical results (no counterpart in the reference: its plugins have one
  * code path).  For tests, which compare the paths with each other, and for measurement; a caller never needs it.
- * Names: "no_fast" (literal float64 hit kernel), "no_span" (per-record mask kernel), "no_pad" (no padded shadow
- * layout), "no_runs32" (bitmap route instead of the run-event kernel), "no_speculate" (exact row launches). */
+ * Names (any other name: WFA_E_INVALID):
+ *   "no_fast"        literal float64 hit kernel instead of the integer kernels
+ *   "no_span"        per-record mask kernel instead of the uniform-record kernels
+ *   "no_pad"         no padded shadow layout
+ *   "no_runs32"      bitmap route instead of the run-event (streaming) kernel
+ *   "no_speculate"   exact row launches (host round trip for the hit count)
+ *   "no_deposit"     streaming kernel: the flush reads the records' last samples from memory again
+ *   "span_records"   streaming kernel: records per span (value; 0 = the library's choice)
+ *   "no_peak_hot"    find_peaks: the plateau machine over every sample, no height prefilter
+ *   "no_peak_slots"  find_peaks: count + fill walks instead of one walk into per-record slots */
 int wfa_set_option(wfa_ctx* ctx, const char* name, int value);
 /* GB/s of the last pool upload through the pinned staging ring (uploads of >= 4 MiB are copied chunk by chunk into two
  * pinned 32-MiB buffers while the previous chunk is on the wire; reference: the plugins hold host arrays only). */

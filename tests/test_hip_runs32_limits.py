@@ -136,10 +136,9 @@ def test_one_busy_span_among_quiet_ones():
 
 
 @pytest.mark.parametrize("preset,n", [("v1725", 6000), ("vx2730", 3000)])
-def test_flat_rows_kernel_equals_grouped_rows_kernel(preset, n):
-    """The chunk-per-lane row kernel (default) against the 8-lanes-per-hit kernel of rounds 1-2 (`rows_grouped`): same
-    extremum (float32 order, first index), same rows; the float64 window sums are added in another order (tolerance of
-    the float fields 1e-6, north_star), everything else is bit-identical.  Both against the oracle."""
+def test_flat_rows_kernel_matches_oracle(preset, n):
+    """The chunk-per-lane row kernel against the oracle: same extremum (float32 order, first index), same rows; the float64
+    window sums are added in another order (tolerance of the float fields 1e-6, north_star)."""
     rec, pool = synth.make_run(n, preset, cfg=31)
     want = O.threshold_hits_chunked(rec, O.filter_wave_pool(rec, pool))
     with DeviceSession(0) as sess:
@@ -149,17 +148,8 @@ def test_flat_rows_kernel_equals_grouped_rows_kernel(preset, n):
         sess.profile(True)
         flat = sess.threshold_hits(_lib.SRC_SG_FUSED, 2, 2)
         assert "k_hit_rows_flat" in sess.profile_report()
-        sess.set_option("rows_grouped", True)
-        sess.profile(True)
-        grouped = sess.threshold_hits(_lib.SRC_SG_FUSED, 2, 2)
-        assert "k_hit_rows_grp" in sess.profile_report()
         G.assert_struct_equal(flat, want, float_rtol=1e-6, what="flat rows vs oracle")
-        G.assert_struct_equal(grouped, want, float_rtol=1e-6, what="grouped rows vs oracle")
-        for name in flat.dtype.names:
-            if name != "integral":
-                np.testing.assert_array_equal(flat[name], grouped[name], err_msg=name)
         # wide extensions: windows that reach both record edges and the zero padding
-        sess.set_option("rows_grouped", False)
         wide = sess.threshold_hits(_lib.SRC_SG_FUSED, 900, 900)
         G.assert_struct_equal(wide, O.threshold_hits_chunked(rec, O.filter_wave_pool(rec, pool), left_extension=900,
                                                              right_extension=900), float_rtol=1e-6, what="wide windows")
@@ -243,3 +233,42 @@ def test_queued_passes_overflow_regrow_and_control_words():
         G.assert_struct_equal(queued(10.0, 2), want[10.0], float_rtol=1e-6, what="next upload: streaming route again")
         assert "k_sg_runs32" in sess.profile_report() and "k_hit_runs" not in sess.profile_report()
         G.assert_struct_equal(sess.threshold_hits(_lib.SRC_SG_FUSED, 2, 2), want[10.0], float_rtol=1e-6, what="waited pass after queued ones")
+
+
+def test_group_sums_of_a_longer_pass_are_cleared_for_the_next_one():
+    """Control words and group sums are zero between passes, whatever mix of waited and queued passes on uploads of
+    different sizes came before.  v1725 records of L = 800 samples: a span holds 64 records and a group 64 spans (4096
+    records), so R = 20 000 records fill 5 groups and R / 4 = 5 000 only 2.  A pass on R leaves group sums 2..4 behind that
+    the pass on R / 4 never touches; a later pass on R must not count them into its row offsets.  (a) dense: more hits than
+    the speculative launch after the R / 4 pass covers; (b) sparse: every pass far below the 4096 rows of slack, where a
+    stale offset would go unnoticed by the count."""
+    R = 20_000
+    rec, pool = synth.make_run(R, "v1725", cfg=5)
+    assert np.all(rec["event_length"] == 800)
+    filt = O.filter_wave_pool(rec, pool)
+    part = {R: rec, R // 4: rec[: R // 4]}
+    want = {(thr, n): O.threshold_hits_chunked(part[n], filt[: n * 800], threshold=thr)
+            for thr in (10.0, 1000.0) for n in part}
+    assert len(want[10.0, R // 4]) * 1.125 + 4096 < len(want[10.0, R])   # (a): the waited pass on R is redone exactly
+    assert len(want[1000.0, R]) * 2 < 4096                                 # (b): far inside the slack
+    with DeviceSession(0) as sess:
+        sess.upload_pool(pool)
+        sess.set_sg_plan(11, 2)
+
+        def waited(thr, n):
+            sess.upload_records(part[n], thr)
+            return sess.threshold_hits(_lib.SRC_SG_FUSED, 2, 2)
+
+        def queued(thr, n):
+            sess.upload_records(part[n], thr)
+            sess.hits_enqueue(_lib.SRC_SG_FUSED, (0, 0), 2, 2)
+            return sess._fill_hits(sess.hits_wait())
+
+        sess.profile(True)
+        for thr, steps in ((10.0, [(waited, R), (queued, R // 4), (waited, R), (queued, R)]),
+                           (1000.0, [(waited, R), (queued, R // 4), (queued, R)])):
+            for k, (run, n) in enumerate(steps):
+                G.assert_struct_equal(run(thr, n), want[thr, n], float_rtol=1e-6,
+                                      what=f"thr={thr} pass {k}: {run.__name__} on {n} records")
+        names = sess.profile_report()
+        assert "k_sg_runs32" in names and "k_hit_runs" not in names, sorted(names)   # every pass on the streaming route

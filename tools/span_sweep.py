@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Streaming kernel and step time against session options on the bench chunk, at the sustained clock (150 queued passes in
 front of every measurement, alternating settings):  python tools/span_sweep.py [preset] [name=value ...]
-default settings: span_records = 64 .. 45; e.g. `no_deposit=1`, `rows_grouped=1`."""
+default settings: span_records = 64 .. 45; e.g. `no_deposit=1`, `no_speculate=1`."""
 import json
 import sys
 import time

@@ -172,8 +172,104 @@ static int ensure_shadow(wfa_ctx* c) {
 }
 
 
-// Uniform records (span mode), Savitzky-Golay source: streaming kernel with ordered run events (wfa_stream.hip).
-//   k_sg_runs32 -> scan of the per-span hit counts -> k_runs_to_desc -> row kernels
+// ---- row stage of the fused hit pass (both routes) ----------------------------------------------------------------
+// Speculative launch: a pass usually finds about as many hits as the previous one on this context.  When the row buffers
+// already hold that many (+12 %, + 4096), the descriptor kernel and the row kernels are launched for that bound straight
+// away and take the real count from the device; the host reads it once, after everything is queued, or not at all
+// (enqueue_only: wfa_hits_wait does).  Without one (first pass on this context, buffers too small, no_speculate), or when
+// the pass finds more, the host reads the count and launches the rows for exactly that many, into row buffers sized with
+// the same head room so that the next pass can speculate.
+static int64_t rows_bound(int64_t hits) { return hits + hits / 8 + 4096; }
+
+// accept-or-redo of a speculative launch: its rows stand when the pass found no more hits than the launch covered and no
+// span's events overflowed (flags: RunsParams::flags of the streaming route, 0 on the bitmap route)
+static bool spec_rows_stand(int64_t total, int64_t bound, int flags) { return total <= bound && flags == 0; }
+
+// What a route supplies:
+//   desc(rp)  enqueues its descriptor kernel (k_runs_to_desc / k_hit_runs) for the row bound in rp;
+//   count()   without a speculative launch: enqueues what leaves the exact row count in *d_total (nothing on the bitmap
+//             route, whose per-record scan has done so already);
+//   ctrl      streaming route: its control words ([1]: event-overflow flags) and `groups` its group sums, both reported
+//             and cleared by the last kernel of a queued pass; null on the bitmap route.
+// *done = false: a span's events overflowed, the caller takes the general route.
+template <class Desc, class Count>
+static int run_rows(wfa_ctx* c, const PoolView& pv, const RecView& rv, const SgParams& sg, RowParams rp,
+                    const int64_t* d_total, unsigned long long* ctrl, unsigned long long* groups, Desc desc, Count count,
+                    wfa_ctx::PendingPass pend, bool enqueue_only, int64_t* n_hits, bool* done) {
+    int rc;
+    auto rows = [&](int64_t n_rows) -> int {
+        int r2;
+        if ((r2 = desc(rp))) return r2;
+        {
+            LaunchTimer t(c);
+            WFA_HIP_CHECK(launch_hit_rows_fast(c->stream, pv, rv, sg, rp, c->hit_desc.as<int4>(), n_rows,
+                                               c->hit_out.as<uint8_t>()));
+            if ((r2 = t.end("k_hit_rows_flat"))) return r2;
+        }
+        LaunchTimer t(c);
+        WFA_HIP_CHECK(launch_hit_rows_literal(c->stream, WFA_SRC_SG_FUSED, pv, rv, sg, rp, c->hit_desc.as<int4>(), n_rows,
+                                              true, c->hit_out.as<uint8_t>()));
+        return t.end("k_hit_rows_literal");
+    };
+    auto finish = [&](int64_t total) {
+        c->n_hits = total;
+        *n_hits = total;
+        *done = true;
+        return WFA_OK;
+    };
+    const int64_t held = (int64_t)std::min(c->hit_out.cap / 60, c->hit_desc.cap / sizeof(int4));
+    const int64_t bound = rows_bound(c->last_hits);
+    const bool spec = c->last_hits >= 0 && held >= bound && !c->opt.no_speculate;
+    if (spec) {
+        rp.cap = bound;
+        rp.n_dev = d_total;
+        if (enqueue_only) {  // nobody waits here: the row count goes to the pinned words
+            if (ctrl) {  // written there by the pass's last kernel, with the control words; it clears them and the group sums
+                rp.pass_report = c->h_total;
+                rp.pass_ctrl = ctrl;
+                rp.pass_groups = groups;
+                rp.pass_n_groups = c->run_dirty_groups;
+            }
+            if ((rc = rows(bound))) return rc;
+            if (ctrl) c->run_dirty_groups = 0;  // (bound >= 4096: the literal kernel, and its clear, are queued)
+            else WFA_HIP_CHECK(hipMemcpyAsync(c->h_total, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+            pend.bound = bound;
+            pend.runs32 = ctrl != nullptr;
+            c->pending = true;
+            c->pend = pend;
+            c->n_hits = -1;
+            *done = true;
+            return WFA_OK;
+        }
+        if ((rc = rows(bound))) return rc;
+    } else if ((rc = count())) {
+        return rc;
+    }
+    int64_t total = 0;
+    unsigned long long ctl = 0;
+    WFA_HIP_CHECK(hipMemcpyAsync(&total, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (ctrl) WFA_HIP_CHECK(hipMemcpyAsync(&ctl, ctrl + 1, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    const int flags = (int)(ctl & 0xffffffffull);
+    if (flags) {  // a span outgrew the event buffer of its wave or its slot: the general route for this upload
+        c->no_runs32 = true;
+        return WFA_OK;
+    }
+    c->last_hits = total;
+    if (spec && spec_rows_stand(total, bound, flags)) return finish(total);
+    rp.cap = 0;
+    rp.n_dev = nullptr;
+    const int64_t want = rows_bound(total);
+    if ((rc = c->hit_out.ensure((size_t)want * 60))) return rc;
+    if ((rc = c->hit_desc.ensure((size_t)want * sizeof(int4)))) return rc;
+    if ((rc = rows(total))) return rc;
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return finish(total);
+}
+
+// Uniform records (span mode), Savitzky-Golay source: streaming kernel with ordered run events (wfa_stream.hip), then the
+// row stage: k_sg_runs32 -> k_runs_to_desc -> row kernels (plus a scan of the per-span hit counts when the host needs the
+// row count first).
 // *done = false: the layout / options are outside what that kernel covers, or a span outgrew its event buffer --
 // the caller takes the general route (per-record mask kernel + bitmap).
 static int run_hits_runs32(wfa_ctx* c, bool fused_bl, int32_t bl_start, int32_t bl_end, int32_t le, int32_t re,
@@ -205,11 +301,13 @@ static int run_hits_runs32(wfa_ctx* c, bool fused_bl, int32_t bl_start, int32_t 
     if ((rc = c->run_span_row0.ensure((size_t)ns * sizeof(int64_t)))) return rc;
     if ((rc = c->run_scan_blocks.ensure((size_t)(nb + 1) * sizeof(int64_t)))) return rc;
     const int64_t n_groups = (ns + 63) / 64;
-    if (c->run_groups.cap < (size_t)n_groups * sizeof(unsigned long long)) c->run_groups_n = 0;  // (a new allocation is not zero)
+    // a new allocation of the group sums or the control words may hold anything: dirty over its whole size
+    const bool new_ctrl = c->run_ctrl.cap < 256 + sizeof(RunsCold);
+    const bool new_groups = c->run_groups.cap < (size_t)n_groups * sizeof(unsigned long long);
     if ((rc = c->run_groups.ensure((size_t)n_groups * sizeof(unsigned long long)))) return rc;
-    if (n_groups > c->run_groups_n) c->run_ctrl_clean = false;  // sums beyond what has ever been cleared
-    if (c->run_ctrl.cap < 256 + sizeof(RunsCold)) { c->run_cold_valid = false; c->run_ctrl_clean = false; }
     if ((rc = c->run_ctrl.ensure(256 + sizeof(RunsCold)))) return rc;
+    if (new_ctrl) c->run_cold_valid = false;
+    if (new_ctrl || new_groups) c->run_dirty_groups = (int64_t)(c->run_groups.cap / sizeof(unsigned long long));
 
     PoolView pvf = pool_view(c);
     RecView rvf = rec_view(c);
@@ -225,156 +323,75 @@ static int run_hits_runs32(wfa_ctx* c, bool fused_bl, int32_t bl_start, int32_t 
     auto* ctrl = c->run_ctrl.as<unsigned long long>();  // [0] event cursor, [1] flags, [2] hits listed for the literal kernel
     constexpr int kLitCap = 65536;
     if ((rc = c->run_lit.ensure((size_t)kLitCap * sizeof(int32_t)))) return rc;
-    if (!c->opt.rows_grouped) {  // (the 8-lanes-per-hit kernel only flags)
-        rp.lit_cnt = reinterpret_cast<uint32_t*>(ctrl + 2);
-        rp.lit_list = c->run_lit.as<int32_t>();
-        rp.lit_cap = kLitCap;
-    }
+    rp.lit_cnt = reinterpret_cast<uint32_t*>(ctrl + 2);
+    rp.lit_list = c->run_lit.as<int32_t>();
+    rp.lit_cap = kLitCap;
 
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        // speculative tail (see run_hits): row buffers sized from the previous pass on this context
-        const int64_t held = (int64_t)std::min(c->hit_out.cap / 60, c->hit_desc.cap / sizeof(int4));
-        const int64_t bound = c->last_hits + c->last_hits / 8 + 4096;
-        const bool spec = c->last_hits >= 0 && held >= bound && !c->opt.no_speculate && attempt == 0;
-        // every span owns a fixed slot of the event buffer (8 KiB: 160 MB per 10^9 samples, only the lines that hold
-        // events are ever touched)
-        const int64_t ev_want = ns * sg_runs32_event_slot();
-        if ((int64_t)(c->run_ev.cap / sizeof(uint32_t)) < ev_want)
-            if ((rc = c->run_ev.ensure((size_t)ev_want * sizeof(uint32_t)))) return rc;
-        RunsParams rn{};
-        rn.ev = c->run_ev.as<uint32_t>();
-        rn.ev_cap = (int64_t)(c->run_ev.cap / sizeof(uint32_t));
-        rn.cursor = ctrl;
-        rn.flags = reinterpret_cast<int32_t*>(ctrl + 1);
-        rn.span_off = c->run_span_off.as<int64_t>();
-        rn.span_cnt = c->run_span_cnt.as<int32_t>();
-        rn.group_sum = c->run_groups.as<unsigned long long>();
-        rn.lit_cnt = c->opt.rows_grouped ? nullptr : reinterpret_cast<uint32_t*>(ctrl + 2);
-        // the control words are cleared by the last kernel of a queued pass (RowParams::pass_ctrl); a memset only when the
-        // pass before did not end that way
-        if (!c->run_ctrl_clean) {
-            WFA_HIP_CHECK(hipMemsetAsync(ctrl, 0, 16, c->stream));
-            WFA_HIP_CHECK(hipMemsetAsync(c->run_groups.ptr, 0, (size_t)n_groups * sizeof(unsigned long long), c->stream));
-            if (n_groups > c->run_groups_n) c->run_groups_n = n_groups;
-        }
-        c->run_ctrl_clean = false;
-        RunsArgs ra{};
-        ra.pool = pvf.u16; ra.thr = rvf.thr; ra.baseline = rvf.baseline_rw; ra.R = R;
-        ra.itab = sp0.itab; ra.den = sp0.den; ra.margin = sp0.margin;
-        ra.den_edge = sp0.den_edge; ra.margin_edge = sp0.margin_edge;
-        // sg_plan.py: guard = 8 eps den^2 2^24 + 1 with eps = bound on |scipy's float64 chain - exact rational|; here in
-        // numerator units with a factor 4 of head room (and never below 1e-6)
-        ra.delta = std::max(4.0 * (double)sp0.guard / (8.0 * (double)sp0.den * 16777216.0), 1e-6);
-        ra.W = sp0.W; ra.L = sp.L; ra.S = sp.S; ra.positive = sp.positive; ra.rs = sp.rs;
-        ra.wstride = g_wstride; ra.nseg = g_nseg; ra.segw = g_segw;
-        ra.dep = (!c->opt.no_deposit && sg_runs32_deposit(sp.L, sp.S, sp0.W, sp.rs, g_wstride)) ? 1 : 0;
-        ra.off0 = sp.off0; ra.n_spans = ns;
-        ra.ev = rn.ev; ra.ev_cap = rn.ev_cap; ra.cursor = rn.cursor; ra.span_off = rn.span_off; ra.span_cnt = rn.span_cnt;
-        ra.flags = rn.flags;
-        ra.group_sum = rn.group_sum;
-        ra.cold = reinterpret_cast<const RunsCold*>(ctrl + 32);  // 256 bytes behind the atomically updated words
-        {
-            // what the float64 reference paths read: a device copy next to the control words, refreshed when it changes
-            RunsCold cold{pvf, sp0};
-            if (!c->run_cold_valid || memcmp(&cold, &c->run_cold_host, sizeof(cold)) != 0) {
-                memcpy(c->h_cold, &cold, sizeof(cold));
-                WFA_HIP_CHECK(hipMemcpyAsync(ctrl + 32, c->h_cold, sizeof(cold), hipMemcpyHostToDevice, c->stream));
-                WFA_HIP_CHECK(hipStreamSynchronize(c->stream));  // h_cold may be rewritten by the next pass
-                c->run_cold_host = cold;
-                c->run_cold_valid = true;
-            }
-        }
-        {
-            LaunchTimer t(c, true);
-            WFA_HIP_CHECK(launch_sg_runs32(c->stream, fused_bl, ra));
-            if ((rc = t.end(fused_bl ? "k_sg_runs32<baseline>" : "k_sg_runs32"))) return rc;
-        }
-        auto rows = [&](int64_t n_rows) -> int {
-            {
-                LaunchTimer t(c);
-                WFA_HIP_CHECK(launch_runs_to_desc(c->stream, rn, ns, sp.rs, d_total, rp.cap, c->hit_desc.as<int4>()));
-                if (int r2 = t.end("k_runs_to_desc")) return r2;
-            }
-            {
-                LaunchTimer t(c);
-                WFA_HIP_CHECK(launch_hit_rows_fast(c->stream, pvf, rvf, sp0, rp, c->hit_desc.as<int4>(), n_rows,
-                                                   c->hit_out.as<uint8_t>(), c->opt.rows_grouped));
-                if (int r2 = t.end(c->opt.rows_grouped ? "k_hit_rows_grp" : "k_hit_rows_flat")) return r2;
-            }
-            {
-                LaunchTimer t(c);
-                WFA_HIP_CHECK(launch_hit_rows_literal(c->stream, WFA_SRC_SG_FUSED, pvf, rvf, sp0, rp,
-                                                      c->hit_desc.as<int4>(), n_rows, true, c->hit_out.as<uint8_t>()));
-                if (int r2 = t.end("k_hit_rows_literal")) return r2;
-            }
-            return WFA_OK;
-        };
-        int64_t total = 0;
-        unsigned long long ctl[2] = {0, 0};
-        if (spec && enqueue_only) {
-            // total, cursor and flags are written to the pinned words by the pass's last kernel, which also clears the
-            // control words for the next pass; nobody waits here
-            rp.cap = bound;
-            rp.n_dev = d_total;
-            rp.pass_report = c->h_total;
-            rp.pass_ctrl = ctrl;
-            rp.pass_groups = rn.group_sum;
-            rp.pass_n_groups = n_groups;
-            if ((rc = rows(bound))) return rc;
-            c->run_ctrl_clean = true;
-            {
-                c->pending = true;
-                c->pend = {WFA_SRC_SG_FUSED, fused_bl, bl_start, bl_end, le, re, max_len, bound, true};
-                c->n_hits = -1;
-                *done = true;
-                return WFA_OK;
-            }
-        }
-        if (spec) {
-            rp.cap = bound;
-            rp.n_dev = d_total;
-            if ((rc = rows(bound))) return rc;
-        } else {
-            // no speculative row launch (first pass on this context, buffers too small): the host needs the row count
-            // before it can size and launch the rows -- the one case that still scans the span counts
-            LaunchTimer t(c);
-            WFA_HIP_CHECK(launch_scan(c->stream, rn.span_cnt, ns, c->run_scan_blocks.as<int64_t>(),
-                                      c->run_span_row0.as<int64_t>()));
-            if ((rc = t.end("k_scan(span hit counts)"))) return rc;
-        }
-        WFA_HIP_CHECK(hipMemcpyAsync(&total, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        WFA_HIP_CHECK(hipMemcpyAsync(ctl, ctrl, 16, hipMemcpyDeviceToHost, c->stream));
-        WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-        const int flags = (int)(ctl[1] & 0xffffffffull);
-        if (flags & 1) {  // a span holds more events than a wave buffers: general route for this upload
-            c->no_runs32 = true;
-            return WFA_OK;
-        }
-        if (flags & 2) {  // a span's patched events outgrew its slot (cannot happen for W <= 11): general route
-            c->no_runs32 = true;
-            return WFA_OK;
-        }
-        c->last_hits = total;
-        if (spec && total <= bound) {
-            c->n_hits = total;
-            *n_hits = total;
-            *done = true;
-            return WFA_OK;
-        }
-        // first pass on this context, or more hits than the guess: exact sizes (with head room for the next pass)
-        rp.cap = 0;
-        rp.n_dev = nullptr;
-        const int64_t want = total + total / 8 + 4096;
-        if ((rc = c->hit_out.ensure((size_t)want * 60))) return rc;
-        if ((rc = c->hit_desc.ensure((size_t)want * sizeof(int4)))) return rc;
-        if ((rc = rows(total))) return rc;
-        WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-        c->n_hits = total;
-        *n_hits = total;
-        *done = true;
-        return WFA_OK;
+    // every span owns a fixed slot of the event buffer (8 KiB: 160 MB per 10^9 samples, only the lines that hold events
+    // are ever touched)
+    const int64_t ev_want = ns * sg_runs32_event_slot();
+    if ((int64_t)(c->run_ev.cap / sizeof(uint32_t)) < ev_want)
+        if ((rc = c->run_ev.ensure((size_t)ev_want * sizeof(uint32_t)))) return rc;
+    RunsParams rn{};
+    rn.ev = c->run_ev.as<uint32_t>();
+    rn.ev_cap = (int64_t)(c->run_ev.cap / sizeof(uint32_t));
+    rn.cursor = ctrl;
+    rn.flags = reinterpret_cast<int32_t*>(ctrl + 1);
+    rn.span_off = c->run_span_off.as<int64_t>();
+    rn.span_cnt = c->run_span_cnt.as<int32_t>();
+    rn.group_sum = c->run_groups.as<unsigned long long>();
+    rn.lit_cnt = rp.lit_cnt;
+    // control words and group sums are zero between passes: a pass that finds them dirty clears the whole recorded extent
+    if (c->run_dirty_groups > 0) {
+        WFA_HIP_CHECK(hipMemsetAsync(ctrl, 0, 16, c->stream));
+        WFA_HIP_CHECK(hipMemsetAsync(rn.group_sum, 0, (size_t)c->run_dirty_groups * sizeof(unsigned long long), c->stream));
+        c->run_dirty_groups = 0;
     }
-    return fail(WFA_E_NOMEM, "event buffer of the streaming hit pass did not converge");
+    RunsArgs ra{};
+    ra.pool = pvf.u16; ra.thr = rvf.thr; ra.baseline = rvf.baseline_rw; ra.R = R;
+    ra.itab = sp0.itab; ra.den = sp0.den; ra.margin = sp0.margin;
+    ra.den_edge = sp0.den_edge; ra.margin_edge = sp0.margin_edge;
+    // sg_plan.py: guard = 8 eps den^2 2^24 + 1 with eps = bound on |scipy's float64 chain - exact rational|; here in
+    // numerator units with a factor 4 of head room (and never below 1e-6)
+    ra.delta = std::max(4.0 * (double)sp0.guard / (8.0 * (double)sp0.den * 16777216.0), 1e-6);
+    ra.W = sp0.W; ra.L = sp.L; ra.S = sp.S; ra.positive = sp.positive; ra.rs = sp.rs;
+    ra.wstride = g_wstride; ra.nseg = g_nseg; ra.segw = g_segw;
+    ra.dep = (!c->opt.no_deposit && sg_runs32_deposit(sp.L, sp.S, sp0.W, sp.rs, g_wstride)) ? 1 : 0;
+    ra.off0 = sp.off0; ra.n_spans = ns;
+    ra.ev = rn.ev; ra.ev_cap = rn.ev_cap; ra.cursor = rn.cursor; ra.span_off = rn.span_off; ra.span_cnt = rn.span_cnt;
+    ra.flags = rn.flags;
+    ra.group_sum = rn.group_sum;
+    ra.cold = reinterpret_cast<const RunsCold*>(ctrl + 32);  // 256 bytes behind the atomically updated words
+    {
+        // what the float64 reference paths read: a device copy next to the control words, refreshed when it changes
+        RunsCold cold{pvf, sp0};
+        if (!c->run_cold_valid || memcmp(&cold, &c->run_cold_host, sizeof(cold)) != 0) {
+            memcpy(c->h_cold, &cold, sizeof(cold));
+            WFA_HIP_CHECK(hipMemcpyAsync(ctrl + 32, c->h_cold, sizeof(cold), hipMemcpyHostToDevice, c->stream));
+            WFA_HIP_CHECK(hipStreamSynchronize(c->stream));  // h_cold may be rewritten by the next pass
+            c->run_cold_host = cold;
+            c->run_cold_valid = true;
+        }
+    }
+    c->run_dirty_groups = n_groups;  // what the streaming kernel is about to write
+    {
+        LaunchTimer t(c, true);
+        WFA_HIP_CHECK(launch_sg_runs32(c->stream, fused_bl, ra));
+        if ((rc = t.end(fused_bl ? "k_sg_runs32<baseline>" : "k_sg_runs32"))) return rc;
+    }
+    auto desc = [&](const RowParams& r) -> int {
+        LaunchTimer t(c);
+        WFA_HIP_CHECK(launch_runs_to_desc(c->stream, rn, ns, sp.rs, d_total, r.cap, c->hit_desc.as<int4>()));
+        return t.end("k_runs_to_desc");
+    };
+    auto count = [&]() -> int {
+        LaunchTimer t(c);
+        WFA_HIP_CHECK(launch_scan(c->stream, rn.span_cnt, ns, c->run_scan_blocks.as<int64_t>(),
+                                  c->run_span_row0.as<int64_t>()));
+        return t.end("k_scan(span hit counts)");
+    };
+    return run_rows(c, pvf, rvf, sp0, rp, d_total, ctrl, rn.group_sum, desc, count,
+                    {WFA_SRC_SG_FUSED, fused_bl, bl_start, bl_end, le, re, max_len, 0, true}, enqueue_only, n_hits, done);
 }
 
 // enqueue_only: when the pass can take the speculative row launch, queue it and return without waiting for the row
@@ -468,8 +485,6 @@ static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int
                                       c->rec_out_start.as<int64_t>()));
             if ((rc = t.end("k_scan(hit counts)"))) return rc;
         }
-        int64_t total = 0;
-        const int64_t* d_total = c->scan_blocks.as<int64_t>() + nb;
         RowParams rp{le, re, max_len, sp0.W / 2};
         if (padded) { rp.uni_L = c->pad_L; rp.uni_S = c->pad_S; rp.uni_positive = c->pad_positive ? 1 : 0; rp.uni_off0 = 0; }
         else if (c->span_ok) { rp.uni_L = c->span_L; rp.uni_positive = c->span_positive ? 1 : 0; rp.uni_off0 = c->span_off0; }
@@ -479,81 +494,15 @@ static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int
             const int64_t need = (per_rec * hit_runs_block() + 16 + 1023) / 1024 * 1024;
             rp.stage_bytes = need <= 48 * 1024 ? (int32_t)need : 48 * 1024;
         }
-        // Speculative tail: a pass usually finds about as many hits as the previous one on this context.  When the
-        // row buffers already hold that many (+12 %), the row kernels are launched for that bound straight away and
-        // take the real count from the device; the host reads it once, after everything is queued.  A pass that
-        // finds more is redone the exact way below.
-        const int64_t held = (int64_t)std::min(c->hit_out.cap / 60, c->hit_desc.cap / sizeof(int4));
-        const int64_t bound = c->last_hits + c->last_hits / 8 + 4096;
-        if (c->last_hits >= 0 && held >= bound && !c->opt.no_speculate) {
-            rp.cap = bound;
-            rp.n_dev = d_total;
-            {
-                LaunchTimer t(c);
-                WFA_HIP_CHECK(launch_hit_runs(c->stream, rvf, c->bitmap.as<uint8_t>(), c->rec_nhits.as<int32_t>(),
-                                              c->rec_out_start.as<int64_t>(), c->hit_desc.as<int4>(), rp));
-                if ((rc = t.end("k_hit_runs"))) return rc;
-            }
-            {
-                LaunchTimer t(c);
-                WFA_HIP_CHECK(launch_hit_rows_fast(c->stream, pvf, rvf, sp0, rp, c->hit_desc.as<int4>(), bound,
-                                                   c->hit_out.as<uint8_t>(), c->opt.rows_grouped));
-                if ((rc = t.end(c->opt.rows_grouped ? "k_hit_rows_grp" : "k_hit_rows_flat"))) return rc;
-            }
-            {
-                LaunchTimer t(c);
-                WFA_HIP_CHECK(launch_hit_rows_literal(c->stream, WFA_SRC_SG_FUSED, pvf, rvf, sp0, rp,
-                                                      c->hit_desc.as<int4>(), bound, true, c->hit_out.as<uint8_t>()));
-                if ((rc = t.end("k_hit_rows_literal"))) return rc;
-            }
-            if (enqueue_only) {  // the count goes to the pinned word; nobody waits here
-                WFA_HIP_CHECK(hipMemcpyAsync(c->h_total, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-                c->pending = true;
-                c->pend = {source, fused_bl, bl_start, bl_end, le, re, max_len, bound, false};
-                c->n_hits = -1;
-                return WFA_OK;
-            }
-            WFA_HIP_CHECK(hipMemcpyAsync(&total, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-            WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-            if (total <= bound) {
-                c->last_hits = total;
-                c->n_hits = total;
-                *n_hits = total;
-                return WFA_OK;
-            }
-            rp.cap = 0;
-            rp.n_dev = nullptr;
-        }
-        WFA_HIP_CHECK(hipMemcpyAsync(&total, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-        c->last_hits = total;
-        // first pass on this context (or a pass that outgrew the guess): size the row buffers with head room so
-        // that the next pass can take the speculative tail
-        const int64_t want = total + total / 8 + 4096;
-        if ((rc = c->hit_out.ensure((size_t)want * 60))) return rc;
-        if ((rc = c->hit_desc.ensure((size_t)want * sizeof(int4)))) return rc;
-        {
+        auto desc = [&](const RowParams& r) -> int {
             LaunchTimer t(c);
             WFA_HIP_CHECK(launch_hit_runs(c->stream, rvf, c->bitmap.as<uint8_t>(), c->rec_nhits.as<int32_t>(),
-                                          c->rec_out_start.as<int64_t>(), c->hit_desc.as<int4>(), rp));
-            if ((rc = t.end("k_hit_runs"))) return rc;
-        }
-        {
-            LaunchTimer t(c);
-            WFA_HIP_CHECK(launch_hit_rows_fast(c->stream, pvf, rvf, sp0, rp, c->hit_desc.as<int4>(), total,
-                                               c->hit_out.as<uint8_t>(), c->opt.rows_grouped));
-            if ((rc = t.end(c->opt.rows_grouped ? "k_hit_rows_grp" : "k_hit_rows_flat"))) return rc;
-        }
-        {
-            LaunchTimer t(c);
-            WFA_HIP_CHECK(launch_hit_rows_literal(c->stream, WFA_SRC_SG_FUSED, pvf, rvf, sp0, rp,
-                                                  c->hit_desc.as<int4>(), total, true, c->hit_out.as<uint8_t>()));
-            if ((rc = t.end("k_hit_rows_literal"))) return rc;
-        }
-        WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-        c->n_hits = total;
-        *n_hits = total;
-        return WFA_OK;
+                                          c->rec_out_start.as<int64_t>(), c->hit_desc.as<int4>(), r));
+            return t.end("k_hit_runs");
+        };
+        bool done = false;  // (no event buffers on this route: always done)
+        return run_rows(c, pvf, rvf, sp0, rp, c->scan_blocks.as<int64_t>() + nb, nullptr, nullptr, desc, [] { return WFA_OK; },
+                        {source, fused_bl, bl_start, bl_end, le, re, max_len, 0, false}, enqueue_only, n_hits, &done);
     }
 
     HitParams hp{};
@@ -820,7 +769,6 @@ int wfa_set_option(wfa_ctx* c, const char* name, int value) {
     else if (n == "no_peak_slots") c->opt.no_peak_slots = v;
     else if (n == "no_peak_hot") c->opt.no_peak_hot = v;
     else if (n == "no_deposit") c->opt.no_deposit = v;
-    else if (n == "rows_grouped") c->opt.rows_grouped = v;
     else if (n == "span_records") c->opt.span_records = value;  // streaming kernel: records per span (0 = chosen by the library)
     else return fail(WFA_E_INVALID, "unknown option '%s'", name);
     return WFA_OK;
@@ -1234,17 +1182,14 @@ int wfa_hits_wait(wfa_ctx* c, int64_t* n_hits) {
         WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
         c->pending = false;
         const int64_t total = *c->h_total;
-        const bool runs_bad = c->pend.runs32 && (c->h_total[2] & 0xffffffffll) != 0;  // event buffers overflowed
-        if (runs_bad) c->no_runs32 = true;  // a span outgrew its LDS buffer or its slot: the general route from now on
-        if (total <= c->pend.bound && !runs_bad) {
-            c->last_hits = total;
-            c->n_hits = total;
-        } else {  // more rows than the speculative launch covered: the exact route, now
-            c->last_hits = total;
+        const int flags = c->pend.runs32 ? (int)(c->h_total[2] & 0xffffffffll) : 0;  // event buffers overflowed
+        if (flags) c->no_runs32 = true;  // a span outgrew its LDS buffer or its slot: the general route from now on
+        c->last_hits = total;
+        if (!spec_rows_stand(total, c->pend.bound, flags)) {  // redone the exact way, now
             const auto p = c->pend;
-            if ((rc = run_hits(c, p.source, p.fused_bl, p.bl_start, p.bl_end, p.le, p.re, p.max_len, n_hits))) return rc;
-            return WFA_OK;
+            return run_hits(c, p.source, p.fused_bl, p.bl_start, p.bl_end, p.le, p.re, p.max_len, n_hits);
         }
+        c->n_hits = total;
     }
     if (c->n_hits < 0) return fail(WFA_E_STATE, "no hit pass has been run");
     *n_hits = c->n_hits;

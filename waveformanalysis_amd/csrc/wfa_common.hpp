@@ -124,7 +124,6 @@ struct wfa_ctx {
         int span_records = 0;       // streaming kernel: records per span (measurement; 0 = library's choice)
         bool no_peak_hot = false;   // find_peaks: the plateau machine over every sample (k_find_peaks_staged), no height prefilter
         bool no_peak_slots = false; // find_peaks: count + fill walks instead of one walk into per-record slots
-        bool rows_grouped = false;  // hit rows: the 8-lanes-per-hit kernel instead of the flat chunk-per-lane kernel
     } opt;
     wfa::RunsCold* h_cold = nullptr;   // pinned staging (lives behind h_total)
     wfa::RunsCold run_cold_host{};     // what the device copy holds
@@ -184,10 +183,11 @@ struct wfa_ctx {
     // enqueue-only hit passes (wfa_hits_enqueue / wfa_hits_wait): the row count of the last enqueued pass lands in a
     // pinned host word; the pass's arguments are kept in case it outgrew its speculative row bound and must be redone
     int64_t* h_total = nullptr;
-    int64_t run_groups_n = 0;     // group sums that are known to be zero between passes
-    bool run_ctrl_clean = false;  // the streaming pass's control words were cleared by the previous pass's last kernel
+    // streaming route: the group sums [0, run_dirty_groups) of run_groups, and with any of them the two control words of
+    // run_ctrl, may be non-zero.  Raised before k_sg_runs32, lowered only once a clear of the whole extent is enqueued.
+    int64_t run_dirty_groups = 0;
     bool pending = false;
-    struct { int source; bool fused_bl; int32_t bl_start, bl_end, le, re, max_len; int64_t bound; bool runs32; } pend{};
+    struct PendingPass { int source; bool fused_bl; int32_t bl_start, bl_end, le, re, max_len; int64_t bound; bool runs32; } pend{};
 
     // rccl (opaque, owned by wfa_rccl.hip)
     void* comm = nullptr;

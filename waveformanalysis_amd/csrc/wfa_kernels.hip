@@ -1163,217 +1163,10 @@ __global__ __launch_bounds__(kBlock) void k_hit_rows_literal(PoolView pool, RecV
     write_hit_row(out, hh, rec, r, L, start, end, seg_start, seg_end, acc.best_i, acc.best, acc.sum);
 }
 
-// fast path: 8 lanes per hit.  Lane q of a group loads the aligned 16-byte chunk (c + q) and produces its 8 outputs
-// from exact integer numerators (halo over DPP; the chunks either side of the round from a second load that lanes 0
-// and 7 use).  64 window samples per round, one coalesced 128-byte read per group (+ the two halo chunks).
-// Hit windows are strongly bimodal (fragments of a few samples vs. pulses of 100-300), and a wave iterates
-// as long as its longest hit.  Each 1024-thread block therefore ranks its 128 hits by window length in
-// LDS first, so that the 8 hits sharing a wave need about the same number of rounds.
-constexpr int kRowsBlock = 256;  // 32 hits ranked per block; 1024 / 512 / 128 / 64 threads measured 0.58 / 0.50 / 0.49 / 0.59 ms against 0.47
-constexpr int kRowsHits = kRowsBlock / 8;
-
-template <int W>
-__global__ __launch_bounds__(kRowsBlock) void k_hit_rows_grp(PoolView pool, RecView rec, SgParams sg, RowParams rp,
-                                                             int4* __restrict__ desc, int64_t n_hits,
-                                                             uint8_t* __restrict__ out) {
-    constexpr int H = W / 2;
-    __shared__ int s_len[kRowsHits];
-    __shared__ int s_perm[kRowsHits];
-    const int q = threadIdx.x & 7;
-    const int grp = threadIdx.x >> 3;
-    const int64_t h_base = (int64_t)blockIdx.x * kRowsHits;
-    if (rp.n_dev && *rp.n_dev < n_hits) n_hits = *rp.n_dev;
-    if (h_base >= n_hits) return;  // whole block beyond the rows of this pass (uniform: before any barrier)
-    {
-        // window length of the hit in this group's slot (0 = nothing to do), then rank = position in
-        // descending order (ties by slot), computed by the group's 8 lanes over 16 slots each
-        const int64_t h0 = h_base + grp;
-        int len = 0;
-        if (h0 < n_hits) {
-            const int4 d0 = desc[h0];
-            if (d0.w == 0) len = d0.z - d0.y + rp.le + rp.re;
-        }
-        if (q == 0) s_len[grp] = len;
-        __syncthreads();
-        int cnt = 0;
-        for (int j = q; j < kRowsHits; j += 8) {
-            const int lj = s_len[j];
-            cnt += (lj > len || (lj == len && j < grp)) ? 1 : 0;
-        }
-        cnt += dpp_i32(cnt, 0);
-        cnt += dpp_i32(cnt, 1);
-        cnt += dpp_i32(cnt, 2);
-        if (q == 0) s_perm[cnt] = grp;
-        __syncthreads();
-    }
-    const int64_t h = h_base + s_perm[grp];
-    const bool live = h < n_hits;
-    int4 d = make_int4(0, 0, 0, 1);
-    if (live) d = desc[h];
-    const bool work = live && d.w == 0;
-
-    const int c0 = sg.itab[0];
-    uint32_t cq[H];
-#pragma unroll
-    for (int m = 0; m < H; ++m) cq[m] = ((uint32_t)sg.itab[2 * m + 1] & 0xffffu) | ((uint32_t)sg.itab[2 * m + 2] << 16);
-    const int bias_i = 32768 * sg.den;
-    const int guard = sg.guard > INT32_MAX ? INT32_MAX : (int)sg.guard;
-
-    const int64_t r = d.x;
-    const int start = d.y, end = d.z;
-    int L = 0;
-    int64_t off = 0;
-    double baseline = 0.0;
-    bool positive = false;
-    if (work) {
-        baseline = rec.baseline[r];
-        if (rp.uni_L > 0) {  // nothing else to wait for before the first chunk load
-            L = rp.uni_L;
-            off = rp.uni_off0 + r * (int64_t)(rp.uni_S ? rp.uni_S : rp.uni_L);
-            positive = rp.uni_positive != 0;
-        } else {
-            L = rec.len[r];
-            off = rec.off[r];
-            positive = rec.pol[r] == WFA_POL_POSITIVE;
-        }
-    }
-    const int seg_start = start - rp.le > 0 ? start - rp.le : 0;
-    const int seg_end = end + rp.re < rp.max_len ? end + rp.re : rp.max_len;
-    // interior part of the window (integer numerators); the <= 2H edge samples and the zero padding
-    // beyond the record (reference's dense matrix) are evaluated literally below
-    const int ilo = seg_start > H ? seg_start : H;
-    const int ihi = seg_end < L - H ? seg_end : L - H;
-    const bool has_int = work && ihi > ilo;
-    const int64_t g0 = off + ilo, g1 = off + ihi;
-    const int64_t c_first = g0 >> 3, c_last = has_int ? ((g1 - 1) >> 3) : -1;
-    const uint4* __restrict__ p16 = reinterpret_cast<const uint4*>(pool.u16);
-
-    HitAccAny acc{-__builtin_huge_val(), 0x7fffffff, 0.0};
-    bool need_literal = false;
-    // Interior samples: sig = +-(b - f64(y32)) is strictly monotone in y32 as long as the float64
-    // subtraction is exact, which holds for |b| < 2^18 and |y| < 2^17 (difference needs < 53 bits).
-    // Then the first maximum of sig is the first extremum of y32: a float32 compare per sample
-    // instead of a float64 compare chain; sig itself is only needed for the integral.  Both polarities run the
-    // same code on t = +-y32 (one xor on the sign bit): sig = sb - f64(t) with sb = +-b, first minimum of t.
-    // Per sample the body is selects only (an earlier form with per-lane branches cost 15 scalar instructions and two
-    // jumps per sample); what remains is one wave-level skip per sample index.  A baseline outside the exact range sends
-    // the hit to the literal kernel.
-    const bool y_order = fabs(baseline) < 262144.0;
-    if (work && !y_order) need_literal = true;
-    const uint32_t sign_mask = positive ? 0x80000000u : 0u;
-    const double sb = positive ? -baseline : baseline;
-    float ext_t = __builtin_huge_valf();
-    int ext_i = 0x7fffffff;
-    const int wlen = ihi - ilo;
-    int y_num_min = INT32_MAX;
-    // rounds: the whole wave iterates while any group has chunks left
-    // unconditional load at a clamped index (a load behind a branch drags an `s_waitcnt vmcnt(0)` with it): chunks
-    // outside [0, c_last + 1] only feed samples that are not in the window (record edges, finished groups); the pool
-    // buffer has 256 B of slack behind its end
-    const int64_t c_hi_load = has_int ? c_last + 1 : 0;
-    // all 8 lanes of a group evaluate a chunk (64 window samples per round): the halo in front of the round's first
-    // chunk and behind its last one comes from a second load that only lanes 0 and 7 need (the others read their own
-    // chunk again, an L1 hit).  With lanes 0 and 7 as pure halo providers a round covered 48 samples for the same
-    // per-round cost.
-    auto clampc = [&](int64_t m) { return m < 0 ? (int64_t)0 : (m > c_hi_load ? c_hi_load : m); };
-    auto load_own = [&](int64_t c) { return p16[clampc(c + q)]; };
-    auto load_edge = [&](int64_t c) { return p16[clampc(q == 0 ? c - 1 : (q == 7 ? c + 8 : c + q))]; };
-    auto do_round = [&](int64_t c, const uint4& v, const uint4& ve) {
-        const int64_t mine = c + q;
-        uint32_t E[12];
-        E[4] = v.x ^ 0x80008000u; E[5] = v.y ^ 0x80008000u; E[6] = v.z ^ 0x80008000u; E[7] = v.w ^ 0x80008000u;
-        const uint32_t X[4] = {ve.x ^ 0x80008000u, ve.y ^ 0x80008000u, ve.z ^ 0x80008000u, ve.w ^ 0x80008000u};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t pv = dpp_from_prev_lane(0u, E[4 + k]), nv = dpp_from_next_lane(0u, E[4 + k]);
-            E[k] = q == 0 ? X[k] : pv;
-            E[8 + k] = q == 7 ? X[k] : nv;
-        }
-        int Z[8];  // numerators of the unbiased samples: n . x
-        sg_chunk_numerators_add<W>(E, c0, cq, bias_i, Z);
-        const bool lane_ok = mine <= c_last;
-        const int rel0 = (int)(mine * 8 - g0);  // window-relative index of this chunk's sample 0
-        // a sample outside the window gets t = +inf: it never wins the extremum and its signal is -inf, clamped to 0
-        const int idx0 = ilo + rel0;
-        {
-            // integer guard: the smallest numerator of every chunk a working lane evaluates (the samples of a chunk that
-            // lie outside the window are ordinary neighbours of the same record: at worst a hit goes to the literal
-            // kernel that did not have to)
-            int zm = Z[0] < Z[1] ? Z[0] : Z[1];
-#pragma unroll
-            for (int j = 2; j < 8; ++j) zm = Z[j] < zm ? Z[j] : zm;
-            zm = lane_ok ? zm : INT32_MAX;
-            y_num_min = zm < y_num_min ? zm : y_num_min;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const bool in = lane_ok && (unsigned)(rel0 + j) < (unsigned)wlen;
-            const int y_num = Z[j];
-            const float y32 = (float)((double)y_num * sg.rden);
-            // (the compiler branches around this block when no lane of the wave has sample j in its window; forcing a
-            // straight-line loop measured 0.475 ms against 0.456: short hits leave most of a round's slots empty)
-            const float t = in ? __uint_as_float(__float_as_uint(y32) ^ sign_mask) : __builtin_huge_valf();
-            const bool better = t < ext_t;  // ascending index: the first extremum is kept
-            ext_t = better ? t : ext_t;
-            ext_i = better ? idx0 + j : ext_i;
-            acc.sum += fmax(sb - (double)t, 0.0);
-        }
-    };
-    // one round's loads in flight ahead of the round being evaluated; a ring of 3 (two ahead) measured 0.480 ms against
-    // 0.472: the kernel is bound by instruction issue, not by the latency of its loads
-    {
-        uint4 v = load_own(c_first), ve = load_edge(c_first);
-        for (int64_t c = c_first; __ballot(c <= c_last) != 0; c += 8) {
-            const uint4 cur = v, cur_e = ve;
-            // the scheduler must not lift the next loads above the reads of `v`: the compiler cannot count a load that
-            // is in flight across the back-edge and would wait for `vmcnt(0)`, i.e. for the prefetch it has just issued
-            __builtin_amdgcn_sched_barrier(0);
-            v = load_own(c + 8);
-            ve = load_edge(c + 8);
-            __builtin_amdgcn_sched_barrier(0);
-            do_round(c, cur, cur_e);
-        }
-    }
-    need_literal |= y_num_min < guard;
-    if (ext_i != 0x7fffffff) {
-        acc.best = sb - (double)ext_t;
-        acc.best_i = ext_i;
-    }
-    if (__ballot(work && (seg_start < H || seg_end > L - H)) != 0) {
-        if (work && (seg_start < H || seg_end > L - H)) {
-            WaveSrc<WFA_SRC_SG_FUSED> src = make_src<WFA_SRC_SG_FUSED>(pool, sg, off, L);
-            HitCtx hc;
-            hc.L = L; hc.max_len = rp.max_len; hc.le = rp.le; hc.re = rp.re;
-            hc.thr = 0.0; hc.positive = positive; hc.baseline = baseline;
-            const int l_end = seg_end < H ? seg_end : H;              // left edge samples [seg_start, l_end)
-            for (int i = seg_start + q; i < l_end; i += 8) acc.add(hit_signal<WFA_SRC_SG_FUSED>(src, hc, i), i);
-            const int r_beg = seg_start > L - H ? seg_start : L - H;  // right edge + padding [r_beg, seg_end)
-            for (int i = r_beg + q; i < seg_end; i += 8) acc.add(hit_signal<WFA_SRC_SG_FUSED>(src, hc, i), i);
-        }
-    }
-    // combine the 8 lanes of the group (butterfly over xor 1, xor 2, mirror)
-#pragma unroll
-    for (int step = 0; step < 3; ++step) {
-        const double ov = dpp_f64(acc.best, step);
-        const int oi = dpp_i32(acc.best_i, step);
-        const double os = dpp_f64(acc.sum, step);
-        const int on = dpp_i32((int)need_literal, step);
-        const bool take = (ov > acc.best) || (ov == acc.best && oi < acc.best_i);
-        acc.best = take ? ov : acc.best;
-        acc.best_i = take ? oi : acc.best_i;
-        acc.sum += os;
-        need_literal |= on != 0;
-    }
-    if (work && q == 0) {
-        if (need_literal) desc[h].w = 2;  // below the integer guard: the literal kernel redoes this hit
-        else write_hit_row(out, h, rec, r, L, start, end, seg_start, seg_end, acc.best_i, acc.best, acc.sum);
-    }
-}
-
 // fast path, flat form (round 3): the window samples of 64 consecutive hits as ONE list of aligned 8-sample chunks, a chunk per
-// lane.  The grouped kernel above gives every hit 8 lanes and iterates as long as the longest hit of a wave: half of all
-// hits are fragments of a few samples that fill one or two of their 8 lanes, and it issued 4.4 x the instructions the
-// window samples need (profiles/r02_pmc_sq_counters.txt: 257.6e6 for 2.1e6 hits).  Here every wave works on its own 64
+// lane.  It replaced a kernel that gave every hit 8 lanes and iterated as long as the longest hit of a wave: half of all
+// hits are fragments of a few samples that fill one or two of their 8 lanes, and that kernel issued 4.4 x the instructions
+// the window samples need (profiles/r02_pmc_sq_counters.txt: 257.6e6 for 2.1e6 hits).  Here every wave works on its own 64
 // hits, one wave per workgroup, no block barriers:
 //   A  lane = hit: window, first chunk, chunk count; a prefix sum of the counts numbers the wave's chunks, a bit per chunk
 //      that starts a hit + a popcount turn a chunk number back into its hit;
@@ -3671,14 +3464,12 @@ hipError_t launch_hit_runs(hipStream_t st, const RecView& rec, const uint8_t* bi
 }
 
 hipError_t launch_hit_rows_fast(hipStream_t st, const PoolView& pool, const RecView& rec, const SgParams& sg,
-                                const RowParams& rp, int4* desc, int64_t n_hits, uint8_t* out, bool grouped) {
+                                const RowParams& rp, int4* desc, int64_t n_hits, uint8_t* out) {
     if (n_hits == 0) return hipSuccess;
-    const unsigned grid = (unsigned)((n_hits + kRowsHits - 1) / kRowsHits);
-    const unsigned grid_flat = (unsigned)((n_hits + kFlatHits - 1) / kFlatHits);
-#define WFA_ROWS(WW)                                                                                                              \
-    case WW:                                                                                                                      \
-        if (grouped) hipLaunchKernelGGL((k_hit_rows_grp<WW>), dim3(grid), dim3(kRowsBlock), 0, st, pool, rec, sg, rp, desc, n_hits, out); \
-        else hipLaunchKernelGGL((k_hit_rows_flat<WW>), dim3(grid_flat), dim3(kWave), 0, st, pool, rec, sg, rp, desc, n_hits, out);       \
+    const unsigned grid = (unsigned)((n_hits + kFlatHits - 1) / kFlatHits);
+#define WFA_ROWS(WW)                                                                                                   \
+    case WW:                                                                                                           \
+        hipLaunchKernelGGL((k_hit_rows_flat<WW>), dim3(grid), dim3(kWave), 0, st, pool, rec, sg, rp, desc, n_hits, out); \
         break;
     switch (sg.W) {
         WFA_ROWS(5)
