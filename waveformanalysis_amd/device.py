@@ -51,6 +51,13 @@ def polarity_codes(records: np.ndarray) -> np.ndarray:
     return out
 
 
+def _check_out(out: np.ndarray, dtype: np.dtype, n: int) -> None:
+    """A caller-provided output table: the kernels write n rows of `dtype` through its pointer."""
+    if not isinstance(out, np.ndarray) or out.dtype != dtype or out.shape != (n,) or not out.flags.c_contiguous \
+            or not out.flags.writeable:
+        raise ValueError(f"out must be a writeable contiguous array of {n} rows of {dtype}")
+
+
 def device_count() -> int:
     n = C.c_int(0)
     _lib.check(_lib.load().wfa_device_count(C.byref(n)))
@@ -288,6 +295,12 @@ class DeviceSession:
         out = np.empty(n, dtype=THRESHOLD_HIT_DTYPE)
         _lib.check(self._lib.wfa_threshold_hits_fill(self._h, _ptr(out), n))
         return out
+
+    def download_hits(self, out: np.ndarray) -> None:
+        """Rows of the last hit pass (run with download=False) straight into `out`: a contiguous THRESHOLD_HIT_DTYPE array
+        of exactly the pass's row count, e.g. one shard's slice of a run's table."""
+        _check_out(out, THRESHOLD_HIT_DTYPE, len(out))
+        _lib.check(self._lib.wfa_threshold_hits_fill(self._h, _ptr(out), len(out)))
 
     def threshold_hits(self, source: int = _lib.SRC_RAW, left_extension: int = 2, right_extension: int = 2,
                        max_len: int = 0, download: bool = True) -> np.ndarray | int:
@@ -531,8 +544,12 @@ class DeviceSession:
         return order, offset
 
     def basic_features(self, source: int = _lib.SRC_RAW, height_range=(40, 90), area_range=(0, None),
-                       fixed_baseline: np.ndarray | None = None) -> np.ndarray:
-        out = np.zeros(self.n_records, dtype=BASIC_FEATURES_DTYPE)
+                       fixed_baseline: np.ndarray | None = None, out: np.ndarray | None = None) -> np.ndarray:
+        """out: optional contiguous BASIC_FEATURES_DTYPE array of n_records rows to write into (a shard's slice)."""
+        if out is None:
+            out = np.zeros(self.n_records, dtype=BASIC_FEATURES_DTYPE)
+        else:
+            _check_out(out, BASIC_FEATURES_DTYPE, self.n_records)
         h0, h1 = height_range
         a0, a1 = area_range
         fb = None if fixed_baseline is None else np.ascontiguousarray(fixed_baseline, dtype=np.float64)
@@ -544,8 +561,12 @@ class DeviceSession:
         return out
 
     def width_integral(self, source: int = _lib.SRC_RAW, q_low: float = 0.1, q_high: float = 0.9,
-                       dt: float = 2.0) -> np.ndarray:
-        out = np.zeros(self.n_records, dtype=WAVEFORM_WIDTH_INTEGRAL_DTYPE)
+                       dt: float = 2.0, out: np.ndarray | None = None) -> np.ndarray:
+        """out: optional contiguous WAVEFORM_WIDTH_INTEGRAL_DTYPE array of n_records rows to write into."""
+        if out is None:
+            out = np.zeros(self.n_records, dtype=WAVEFORM_WIDTH_INTEGRAL_DTYPE)
+        else:
+            _check_out(out, WAVEFORM_WIDTH_INTEGRAL_DTYPE, self.n_records)
         _lib.check(self._lib.wfa_width_integral(self._h, int(source), float(q_low), float(q_high),
                                                 float(dt), _ptr(out)))
         return out

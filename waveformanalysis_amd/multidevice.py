@@ -1,0 +1,347 @@
+"""Per-record plugins across several GPUs from one process: one contiguous record range per device.
+
+Hits, basic features and width integrals depend on one record alone (the run-wide padded width of the hit pass is
+passed to every shard explicitly, hit_finder.py:354-370), so a run splits into contiguous record ranges with no exchange
+between devices.  Each shard's rows are the rows of its records in record order; placing the shards' tables one after
+another in shard order is the reference's order (record index, then start sample) with no sort and no gather.
+
+`ShardedRun` keeps one `DeviceSession` and one long-lived worker thread per entry of `device_ids`.  A run is:
+  1. every worker puts its shard's pool slice on its device (skipped when it is still resident),
+  2. uploads its records (wave_offset shifted to the slice) and runs the pass, rows left on the device,
+  3. the caller allocates the run's table once,
+  4. every worker downloads its rows straight into its slice of that table.
+The uploads and downloads are ctypes calls, which release the GIL: the links of different devices work at once.
+
+This is the in-process path.  `bench.py --gpus N` keeps its multi-process route (one rank per GPU, channel shards, hit
+rows gathered over RCCL) for the event-grouping chain, which needs the rows of every channel on one device.
+"""
+
+from __future__ import annotations
+
+import threading
+import weakref
+from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass
+from typing import Callable, Sequence
+
+import numpy as np
+
+# A shard's pool slice starts on a multiple of this many samples, so every record keeps the alignment of its offset
+# (the upload picks its layout routes -- span mode, padded shadow -- from it) and a shard computes what the whole run
+# computes on its records.
+POOL_ALIGN = 8
+
+
+@dataclass(frozen=True)
+class RecordShard:
+    """Records [r0, r1) and the pool span [span_start, span_end) that holds their samples."""
+
+    r0: int
+    r1: int
+    span_start: int
+    span_end: int
+
+    @property
+    def n_records(self) -> int:
+        return self.r1 - self.r0
+
+
+def split_records(records: np.ndarray, n_shards: int) -> list[RecordShard]:
+    """Contiguous record ranges balanced by sample count (cumulative event_length), one per shard.
+
+    A shard's span is [min wave_offset, max(wave_offset + event_length)) over its records: exactly its slice for the
+    builders' layout (offsets non-decreasing and disjoint), wider than needed for anything else (offsets out of order,
+    gaps, overlaps) but always holding every sample of its records.  With fewer records than shards, or samples that
+    cannot be balanced, some shards are empty (r0 == r1, span (0, 0))."""
+    n_shards = int(n_shards)
+    if n_shards < 1:
+        raise ValueError("n_shards must be >= 1")
+    n = len(records)
+    # one strided read per column (the records rows are ~100 B wide), everything after it on contiguous arrays
+    lengths = np.ascontiguousarray(records["event_length"]) if n else np.zeros(0, np.int64)
+    offsets = np.ascontiguousarray(records["wave_offset"]) if n else np.zeros(0, np.int64)
+    if n and int(lengths.min()) < 0:  # negative lengths hold no samples
+        lengths = np.maximum(lengths, 0)
+    cum = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(lengths, dtype=np.int64, out=cum[1:])
+    total = int(cum[-1])
+    if total > 0:
+        # boundary k: the record start whose cumulative sample count is nearest to k / n_shards of the run
+        target = np.arange(n_shards + 1, dtype=np.float64) * (total / n_shards)
+        hi = np.clip(np.searchsorted(cum, target, side="left"), 0, n)
+        lo = np.maximum(hi - 1, 0)
+        bounds = np.where(np.abs(cum[lo] - target) <= np.abs(cum[hi] - target), lo, hi)
+    else:  # nothing to balance: by record count
+        bounds = (np.arange(n_shards + 1, dtype=np.int64) * n) // n_shards
+    bounds[0], bounds[-1] = 0, n
+    bounds = np.maximum.accumulate(bounds)
+    shards = []
+    for k in range(n_shards):
+        r0, r1 = int(bounds[k]), int(bounds[k + 1])
+        if r1 > r0:
+            off = offsets[r0:r1].astype(np.int64, copy=False)
+            s0 = int(off.min())
+            s1 = int((off + lengths[r0:r1]).max())
+            shards.append(RecordShard(r0, r1, s0, max(s1, s0)))
+        else:
+            shards.append(RecordShard(r0, r0, 0, 0))
+    return shards
+
+
+def _copy_rows(rows: np.ndarray) -> np.ndarray:
+    """A copy of a record range: one memcpy for a contiguous structured array (numpy's structured copy goes field by
+    field, several times slower on the reference's records dtype)."""
+    if rows.flags.c_contiguous and rows.ndim == 1 and rows.dtype.itemsize and len(rows):
+        return rows.view(np.uint8).copy().view(rows.dtype)
+    return rows.copy()
+
+
+class ShardError(RuntimeError):
+    """A shard's worker raised; `device_id` and `shard` name where, `__cause__` is the worker's exception."""
+
+    def __init__(self, message: str, device_id: int, shard: int):
+        super().__init__(message)
+        self.device_id = device_id
+        self.shard = shard
+
+
+def _default_factory(device_id: int):
+    from .device import DeviceSession
+
+    return DeviceSession(device_id)
+
+
+class ShardedRun:
+    """One session and one worker thread per entry of `device_ids` (an id may repeat: several sessions on one GPU).
+
+    Every call to a session happens on its worker thread.  Residency follows `DeviceSession.ensure_pool`: a shard's
+    upload is skipped while its session still holds the slice of the very same pool array OBJECT (strong reference,
+    compared with `is`) with the same bounds."""
+
+    def __init__(self, device_ids: Sequence[int], session_factory: Callable | None = None):
+        ids = [int(d) for d in device_ids]
+        if not ids:
+            raise ValueError("ShardedRun needs at least one device id")
+        self.device_ids = ids
+        self._factory = session_factory or _default_factory
+        self.sessions: list = []
+        self._workers = [ThreadPoolExecutor(max_workers=1, thread_name_prefix=f"wfa-shard{k}") for k in range(len(ids))]
+        self._resident: list[tuple | None] = [None] * len(ids)  # (pool, lo, hi, view) the session holds
+        self._lock = threading.Lock()  # one run at a time: the sessions hold one run's rows
+        self.closed = False
+        futures = [w.submit(self._factory, d) for w, d in zip(self._workers, ids)]
+        made, error = [], None
+        for fut in futures:
+            try:
+                made.append(fut.result())
+            except BaseException as exc:  # noqa: BLE001  (re-raised below once every worker is done)
+                made.append(None)
+                error = error or exc
+        self.sessions = made
+        if error is not None:
+            self.close()
+            raise error
+
+    @property
+    def n_shards(self) -> int:
+        return len(self.device_ids)
+
+    # -- workers ---------------------------------------------------------------------------------------------------
+    def _on_all(self, fn: Callable[[int], object], shards: Sequence[int] | None = None) -> list:
+        """fn(k) on worker k for every k; every worker finishes before a failure is reported.  A failed shard's session
+        is closed and replaced (its device state is not trusted, as DevicePool.drop_session), then the first failure
+        (in shard order) is raised with its device id."""
+        ks = range(self.n_shards) if shards is None else shards
+        futures = {k: self._workers[k].submit(fn, k) for k in ks}
+        results, failed = [None] * self.n_shards, []
+        for k, fut in futures.items():
+            try:
+                results[k] = fut.result()
+            except BaseException as exc:  # noqa: BLE001  (re-raised below once every worker is done)
+                failed.append((k, exc))
+        if not failed:
+            return results
+        for k, _exc in failed:
+            self._replace_session(k)
+        k, exc = failed[0]
+        raise ShardError(f"shard {k} on device {self.device_ids[k]} failed: {type(exc).__name__}: {exc}",
+                         self.device_ids[k], k) from exc
+
+    def _replace_session(self, k: int) -> None:
+        self._resident[k] = None
+        old = self.sessions[k]
+
+        def swap():
+            try:
+                old.close()
+            except Exception:  # noqa: BLE001  (a broken context may not close cleanly; the new one is what counts)
+                pass
+            return self._factory(self.device_ids[k])
+
+        try:
+            self.sessions[k] = self._workers[k].submit(swap).result()
+        except BaseException:  # noqa: BLE001  (no new context on that device: this run is done, the next call starts anew)
+            self.sessions[k] = None
+            self.close()
+
+    def _ensure_slice(self, k: int, sess, pool: np.ndarray, lo: int, hi: int, cacheable: bool) -> None:
+        tag = self._resident[k]
+        if cacheable and tag is not None and tag[0] is pool and tag[1] == lo and tag[2] == hi:
+            view = tag[3]  # the object the session remembers: its own `is` test decides
+        else:
+            view = pool[lo:hi]
+        sess.ensure_pool(view, cacheable=cacheable)
+        self._resident[k] = (pool, lo, hi, view) if cacheable else None
+
+    # -- a run -----------------------------------------------------------------------------------------------------
+    def run(self, records: np.ndarray, pool: np.ndarray, row_dtype, task: Callable, *, fetch: Callable | None = None,
+            per_record: Sequence = (), cacheable: bool = True, record_index_field: str | None = None) -> np.ndarray:
+        """The run's table, shards placed one after another in shard order.
+
+        task(sess, records_k, *per_record_k, out=...) runs on worker k after the shard's pool slice is resident, with
+        records_k = records[r0:r1] (wave_offset shifted to the slice) and every per-record array of `per_record` sliced
+        the same way (scalars, 0-d arrays and None go through as they are).
+          * fetch=None: one row per record.  `out` is the shard's slice of the table; task writes it.
+            record_index_field: a field that holds the record index; the shard's r0 is added to it.
+          * fetch given: task(..., out=None) runs the pass and returns the shard's row count, rows left on the device;
+            then fetch(sess, out_k) downloads them into the shard's slice of the table.
+        A failure raises ShardError and returns no table."""
+        if self.closed:
+            raise RuntimeError("ShardedRun is closed")
+        row_dtype = np.dtype(row_dtype)
+        n = len(records)
+        shards = split_records(records, self.n_shards)
+        args = [a if isinstance(a, np.ndarray) and a.ndim == 1 and len(a) == n else None for a in per_record]
+
+        def shard_inputs(k):
+            sh = shards[k]
+            lo = sh.span_start - sh.span_start % POOL_ALIGN
+            rec = _copy_rows(records[sh.r0:sh.r1])
+            if lo:
+                rec["wave_offset"] -= lo
+            extra = [a[sh.r0:sh.r1] if s is not None else a for a, s in zip(per_record, args)]
+            return sh, lo, rec, extra
+
+        with self._lock:
+            busy = [k for k in range(self.n_shards) if shards[k].n_records > 0]
+            if fetch is None:
+                out = np.zeros(n, dtype=row_dtype)
+
+                def one_pass(k):
+                    sh, lo, rec, extra = shard_inputs(k)
+                    sess = self.sessions[k]
+                    self._ensure_slice(k, sess, pool, lo, sh.span_end, cacheable)
+                    part = out[sh.r0:sh.r1]
+                    task(sess, rec, *extra, out=part)
+                    if record_index_field is not None and sh.r0:
+                        part[record_index_field] += sh.r0
+
+                self._on_all(one_pass, busy)
+                return out
+
+            def count(k):
+                sh, lo, rec, extra = shard_inputs(k)
+                sess = self.sessions[k]
+                self._ensure_slice(k, sess, pool, lo, sh.span_end, cacheable)
+                return int(task(sess, rec, *extra, out=None))
+
+            counts = self._on_all(count, busy)
+            rows = np.array([c or 0 for c in counts], dtype=np.int64)
+            first = np.zeros(self.n_shards + 1, dtype=np.int64)
+            np.cumsum(rows, out=first[1:])
+            out = np.empty(int(first[-1]), dtype=row_dtype)
+            self._on_all(lambda k: fetch(self.sessions[k], out[first[k]:first[k + 1]]),
+                         [k for k in busy if rows[k] > 0])
+            return out
+
+    # -- lifetime --------------------------------------------------------------------------------------------------
+    def release_scratch(self) -> None:
+        """DeviceSession.release_scratch on every session (the plugins' cleanup hook)."""
+        self._on_all(lambda k: self.sessions[k].release_scratch())
+
+    def close(self) -> None:
+        """Close every session and stop the workers."""
+        if self.closed:
+            return
+        self.closed = True
+        self._resident = [None] * self.n_shards
+        for k, w in enumerate(self._workers):
+            s = self.sessions[k] if k < len(self.sessions) else None
+            try:
+                if s is not None:
+                    w.submit(s.close).result()
+            finally:
+                w.shutdown(wait=True)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def resolve_devices(devices) -> tuple[int, ...] | None:
+    """The `devices` plugin option: None (single-device route), "all" (every visible device) or a list of ids."""
+    if devices is None:
+        return None
+    if isinstance(devices, str):
+        if devices.strip().lower() != "all":
+            raise ValueError(f"devices must be None, 'all' or a list of device ids, got {devices!r}")
+        from .device import device_count
+
+        n = device_count()
+        if n < 1:
+            raise RuntimeError("devices='all': no HIP device visible")
+        return tuple(range(n))
+    ids = tuple(int(d) for d in devices)
+    if not ids:
+        raise ValueError("devices must name at least one device")
+    return ids
+
+
+_runs: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()  # context -> {device tuple: ShardedRun}
+_shared: dict = {}  # the same for contexts that take no weak reference
+_runs_lock = threading.Lock()
+
+
+def _cache(context, create: bool) -> dict | None:
+    try:
+        cache = _runs.get(context)
+        if cache is None and create:
+            cache = _runs[context] = {}
+        return cache
+    except TypeError:
+        return _shared
+
+
+def sharded_run(context, devices) -> ShardedRun:
+    """The ShardedRun of (context, device tuple), created on first use.  A context may name the session factory its
+    sessions come from (`context.wfa_session_factory`, as `context.wfa_device_pool` names the single-device pool)."""
+    ids = resolve_devices(devices)
+    with _runs_lock:
+        cache = _cache(context, create=True)
+        run = cache.get(ids)
+        if run is None or run.closed:
+            run = cache[ids] = ShardedRun(ids, session_factory=getattr(context, "wfa_session_factory", None))
+    return run
+
+
+def peek_sharded_runs(context) -> list[ShardedRun]:
+    """Every live ShardedRun of `context` (never creates one)."""
+    with _runs_lock:
+        cache = _cache(context, create=False) or {}
+        return [r for r in cache.values() if not r.closed]
+
+
+def close_sharded_runs(context) -> None:
+    """Close and forget every ShardedRun of `context`."""
+    with _runs_lock:
+        cache = _cache(context, create=False) or {}
+        runs = list(cache.values())
+        cache.clear()
+    for r in runs:
+        r.close()
+
+
+__all__ = ["POOL_ALIGN", "RecordShard", "ShardError", "ShardedRun", "split_records", "resolve_devices", "sharded_run",
+           "peek_sharded_runs", "close_sharded_runs"]

@@ -16,6 +16,7 @@ import numpy as np
 
 from .. import _lib
 from ..channel_config import per_record_option, resolve_channel_values, scatter_per_record
+from .. import multidevice
 from ..device import DeviceSession, default_pool
 from ..plugin_api import Plugin
 
@@ -213,6 +214,18 @@ def invalidate_residency(context: Any = None) -> None:
         sess.forget_resident()
 
 
+# ---- several devices from one process: the `devices` option of the per-record plugins -------------------------------
+DEVICES_HELP = ("None: one device (the calling thread's session); a list of device ids (repeats allowed) or 'all': the "
+                "records route runs on those devices, one contiguous record range each, output identical.  The dense "
+                "routes (st_waveforms / filtered_waveforms) stay on one device whatever this says.")
+
+
+def sharded_run(context: Any, devices) -> "multidevice.ShardedRun":
+    """The ShardedRun of this context and device tuple (multidevice.sharded_run): one session and one worker thread per
+    device, kept between calls so a pool stays resident on every shard."""
+    return multidevice.sharded_run(context, devices)
+
+
 SRC_RAW, SRC_F32, SRC_SG_FUSED = _lib.SRC_RAW, _lib.SRC_F32, _lib.SRC_SG_FUSED
 
 
@@ -322,7 +335,8 @@ class HipPlugin(Plugin):
       PluginStatsCollector, the kernels of this compute() are timed with HIP events and published
       (`publish_device_report`);
     * cleanup(context) (core/plugins/core/base.py:608-613, always called after compute()): the device scratch the
-      next call rebuilds by itself is freed (`wfa_release_scratch`), the resident pool / records / rows stay; after a
+      next call rebuilds by itself is freed (`wfa_release_scratch`) on the thread's session and on the sessions of the
+      context's ShardedRuns, the resident pool / records / rows stay; after a
       failed compute() (`on_error`, base.py:602-606) the thread's session is closed: its device state is not trusted.
     algorithmic_bytes = (per sample, per record, per output row) of the plugin's device pass."""
 
@@ -340,6 +354,9 @@ class HipPlugin(Plugin):
     def cleanup(self, context: Any) -> None:
         from .. import device as _device
 
+        for run in multidevice.peek_sharded_runs(context):  # a failed shard's session was replaced by the run itself
+            if not run.closed:
+                run.release_scratch()
         pool_obj = getattr(context, "wfa_device_pool", None) or _device._default_pool  # never creates a pool here
         peek = getattr(pool_obj, "peek_session", None)
         sess = peek() if peek is not None else None

@@ -33,6 +33,7 @@ class HipBasicFeaturesPlugin(K.HipPlugin):
                               help="auto|records|st_waveforms|filtered_waveforms"),
         "fixed_baseline": Option(default=None, type=dict, help="deprecated; use channel_config"),
         "channel_config": Option(default=None, type=dict, help="per (board, channel) fixed_baseline"),
+        "devices": Option(default=None, track=False, help=K.DEVICES_HELP),
     }
 
     def resolve_depends_on(self, context: Any, run_id: str | None = None) -> list[str]:
@@ -60,9 +61,15 @@ class HipBasicFeaturesPlugin(K.HipPlugin):
             source = K.SRC_RAW
         else:
             raise ValueError(f"wave pool must be uint16 or float32, got {pool.dtype}")
+        devices = context.get_config(self, "devices")
+        if devices is not None:
+            def task(sess, rec_k, fixed_k, out):
+                records_pass(sess, rec_k, source, height_range, area_range, fixed_k, out=out)
+
+            return K.sharded_run(context, devices).run(records, pool, BASIC_FEATURES_DTYPE, task, per_record=(fixed,),
+                                                       record_index_field="event_index")
         sess = K.resident_session(context, pool)
-        sess.upload_records(records)
-        return sess.basic_features(source, height_range, area_range, fixed)
+        return records_pass(sess, records, source, height_range, area_range, fixed)
 
     def _compute_dense(self, context, run_id, data_name, channel_config, height_range, area_range) -> np.ndarray:
         """basic_features.py:197-278: whole rows, wave-based formulas, sign from the literal "positive"."""
@@ -79,3 +86,12 @@ class HipBasicFeaturesPlugin(K.HipPlugin):
         sess = K.resident_session(context, pool, cacheable=False)  # temporary of the dense `wave` field
         sess.upload_records(records, polarity=dense.dense_polarity_wave_rule(data))
         return sess.basic_features(source, height_range, area_range, fixed)
+
+
+def records_pass(sess, records: np.ndarray, source: int, height_range, area_range, fixed, out=None) -> np.ndarray:
+    """The per-session part of the records route, on a session whose pool is resident: one row per record (written into
+    `out` when given); event_index counts the session's records from 0."""
+    sess.upload_records(records)
+    if out is None:
+        return sess.basic_features(source, height_range, area_range, fixed)
+    return sess.basic_features(source, height_range, area_range, fixed, out=out)

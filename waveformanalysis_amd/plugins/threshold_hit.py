@@ -42,6 +42,7 @@ class HipThresholdHitPlugin(K.HipPlugin):
         "right_extension": Option(default=2, type=int, help="samples added right of a hit"),
         "dt": Option(default=None, type=int, help="sample interval (ns) when records lack dt"),
         "channel_config": Option(default=None, type=dict, help="per (board, channel) threshold"),
+        "devices": Option(default=None, track=False, help=K.DEVICES_HELP),
     }
 
     def resolve_depends_on(self, context: Any, run_id: str | None = None) -> list[str]:
@@ -76,28 +77,37 @@ class HipThresholdHitPlugin(K.HipPlugin):
         if "dt" not in (records.dtype.names or ()):
             rec = _with_dt(records, dt_values)
 
+        cacheable = True
         if use_filtered and not fused:
             converted = pool.dtype != np.float32
             if converted:
                 pool = np.asarray(pool, dtype=np.float32)
-            sess = K.resident_session(context, pool, cacheable=not converted)
+            cacheable = not converted
             source = K.SRC_F32
         else:
             if pool.dtype != np.uint16:
                 raise ValueError(f"wave_pool must be uint16, got {pool.dtype}")
-            sess = K.resident_session(context, pool)
             source = K.SRC_SG_FUSED if fused else K.SRC_RAW
-        sess.upload_records(rec, thresholds)
+        sg = None
         if fused:
             fplugin = context.get_plugin("wave_pool_filtered") if "wave_pool_filtered" in getattr(context, "_plugins", {}) else None
             w = context.get_config(fplugin, "sg_window_size") if fplugin else 11
             p = context.get_config(fplugin, "sg_poly_order") if fplugin else 2
-            sess.set_sg_plan(*normalize_window(w, p))
-        if fused and fuse_baseline is not None:
-            return sess.fused_baseline_filter_hits(tuple(fuse_baseline), le, re)
-        if fuse_baseline is not None:
-            sess.baseline_mean(int(fuse_baseline[0]), int(fuse_baseline[1]), update_records=True)
-        return sess.threshold_hits(source, le, re)
+            sg = normalize_window(w, p)
+        devices = context.get_config(self, "devices")
+        if devices is not None:
+            # the run's padded width on every shard (hit_finder.py:354-370), not the shard's own
+            max_len = int(np.max(rec["event_length"]))
+
+            def task(sess, rec_k, thr_k, out=None):
+                return records_pass(sess, rec_k, thr_k, source, sg, fuse_baseline, le, re, max_len=max_len,
+                                    download=False)
+
+            run = K.sharded_run(context, devices)
+            return run.run(rec, pool, THRESHOLD_HIT_DTYPE, task, fetch=lambda sess, out: sess.download_hits(out),
+                           per_record=(thresholds,), cacheable=cacheable)
+        sess = K.resident_session(context, pool, cacheable=cacheable)
+        return records_pass(sess, rec, thresholds, source, sg, fuse_baseline, le, re)
 
     def _compute_dense(self, context, run_id, data_name, threshold, le, re, explicit_dt, channel_config) -> np.ndarray:
         """hit_finder.py:179-255: the whole row is searched; the records/wave_pool length of the same record_id
@@ -131,6 +141,22 @@ class HipThresholdHitPlugin(K.HipPlugin):
             hits["edge_start"], hits["edge_end"] = edge_start, edge_end
             hits["width"] = (edge_end - edge_start).astype(np.float32)
         return hits
+
+
+def records_pass(sess, records: np.ndarray, thresholds, source: int, sg: tuple[int, int] | None, fuse_baseline,
+                 le: int, re: int, max_len: int = 0, download: bool = True):
+    """The per-session part of the records route, on a session whose pool is resident: records in, hit pass run ->
+    THRESHOLD_HIT_DTYPE rows, or their count with download=False (rows left on the device).  sg: the Savitzky-Golay
+    (window, order) of the fused filter, None for the raw / materialised sources.  max_len: the padded width (0 = the
+    longest uploaded record)."""
+    sess.upload_records(records, thresholds)
+    if sg is not None:
+        sess.set_sg_plan(*sg)
+    if sg is not None and fuse_baseline is not None:
+        return sess.fused_baseline_filter_hits(tuple(fuse_baseline), le, re, max_len=max_len, download=download)
+    if fuse_baseline is not None:
+        sess.baseline_mean(int(fuse_baseline[0]), int(fuse_baseline[1]), update_records=True)
+    return sess.threshold_hits(source, le, re, max_len=max_len, download=download)
 
 
 def _lengths_from_records(context: Any, run_id: str, record_ids: np.ndarray, source_lengths: np.ndarray) -> np.ndarray:

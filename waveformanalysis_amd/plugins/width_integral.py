@@ -31,6 +31,7 @@ class HipWaveformWidthIntegralPlugin(K.HipPlugin):
                               help="auto|records|st_waveforms|filtered_waveforms"),
         "sampling_rate": Option(default=0.5, type=float, help="GHz, used when dt is None"),
         "dt": Option(default=None, type=float, help="sample interval (ns), wins over sampling_rate"),
+        "devices": Option(default=None, track=False, help=K.DEVICES_HELP),
     }
 
     def resolve_depends_on(self, context: Any, run_id: str | None = None) -> list[str]:
@@ -74,6 +75,21 @@ class HipWaveformWidthIntegralPlugin(K.HipPlugin):
             source = K.SRC_RAW
         else:
             raise ValueError(f"wave pool must be uint16 or float32, got {pool.dtype}")
+        devices = context.get_config(self, "devices")
+        if devices is not None:
+            def task(sess, rec_k, out):
+                records_pass(sess, rec_k, source, q_low, q_high, float(dt), out=out)
+
+            return K.sharded_run(context, devices).run(records, pool, WAVEFORM_WIDTH_INTEGRAL_DTYPE, task,
+                                                       record_index_field="event_index")
         sess = K.resident_session(context, pool)
-        sess.upload_records(records)
-        return sess.width_integral(source, q_low, q_high, float(dt))
+        return records_pass(sess, records, source, q_low, q_high, float(dt))
+
+
+def records_pass(sess, records: np.ndarray, source: int, q_low: float, q_high: float, dt: float, out=None) -> np.ndarray:
+    """The per-session part of the records route, on a session whose pool is resident: one row per record (written into
+    `out` when given); event_index counts the session's records from 0."""
+    sess.upload_records(records)
+    if out is None:
+        return sess.width_integral(source, q_low, q_high, dt)
+    return sess.width_integral(source, q_low, q_high, dt, out=out)
