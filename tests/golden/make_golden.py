@@ -790,6 +790,30 @@ def main():
     pool = np.array([100, 100, 80, 80, 80, 80, 100, 100], dtype=np.uint16)
     run_case("kat_records_view", records, pool, hit_cfg={"left_extension": 0, "right_extension": 0})
 
+    # threshold boundary (tests/boundary_util.py): each record's target sample exactly on  +-(b - y) >= thr  or one
+    # float64 step to either side -- in the baseline (raw samples, one global threshold) or in a per-channel threshold
+    # (Savitzky-Golay (7, 3) output, positive polarity, NaN / inf / negative thresholds on a few channels)
+    from tests import boundary_util as BU
+
+    bs = BU.make_set(192, 64, source="raw", threshold=10.3, seed=101, specials=False)
+    run_case("boundary_baseline_raw", bs.records, bs.pool, hit_cfg={"threshold": 10.3})
+    # (seed 103: no record-edge sample whose exact filter value is 0 -- that case is sgedge_zero below)
+    bs = BU.make_set(96, 128, source="sg", plan=(7, 3), mode="threshold", positive=True, seed=103)
+    run_case("boundary_threshold_sg7_3", bs.records, bs.pool, filter_cfg={"sg_window_size": 7, "sg_poly_order": 3},
+             hit_cfg={"threshold": 10.0, "channel_config": bs.channel_config()})
+
+    # a record-edge sample whose exact Savitzky-Golay (7, 3) value is 0 (last samples 0 56 0 56 0 0 0 of record 45 of
+    # the seed-102 set): scipy's least-squares edge fit returns rounding noise there (~1e-13, its value depends on the
+    # BLAS kernel), the threshold of that record sits exactly on it
+    bs = BU.make_set(96, 128, source="sg", plan=(7, 3), mode="threshold", positive=True, seed=102)
+    rec = bs.records[40:48].copy()
+    rec["wave_offset"] -= rec["wave_offset"][0]
+    pool = bs.pool[40 * 128:48 * 128].copy()
+    cc = {f"{int(b)}:{int(c)}": {"threshold": float(t)} for b, c, t in zip(rec["board"], rec["channel"], bs.thresholds[40:48])}
+    cc[f"{int(rec['board'][5])}:{int(rec['channel'][5])}"] = {"threshold": float(bs.filtered[45 * 128 + 127]) - 0.0}
+    run_case("sgedge_zero", rec, pool, filter_cfg={"sg_window_size": 7, "sg_poly_order": 3},
+             hit_cfg={"threshold": 10.0, "channel_config": cc}, want=("filtered", "hits_filt"))
+
     # per-channel thresholds + fixed baseline overrides
     rec, pool = synth.make_run(48, "v1725", cfg=3)
     run_case("v1725_channel_cfg", rec, pool,

@@ -209,7 +209,10 @@ __global__ __launch_bounds__(kRunsBlock, kRunsOcc) void k_sg_runs32(RunsArgs a) 
             const bool f_above = fd > v, f_pos = (u >> 31) == 0;
             const uint32_t u_lo = f_above ? (f_pos ? u - 1u : u + 1u) : u;   // one float32 towards -inf
             const uint32_t u_hi = f_above ? u : (f_pos ? u + 1u : u - 1u);   // one float32 towards +inf
-            const double zt = ((double)__uint_as_float(u_lo) + (double)__uint_as_float(u_hi)) * (0.5 * den);
+            // v = +inf (thr = -inf, or an infinite baseline on the hit side): every sample hits, as sig >= -inf does in
+            // the reference; u_hi would step past +inf into a NaN there
+            const double zt = v == __builtin_huge_val() ? v
+                                                        : ((double)__uint_as_float(u_lo) + (double)__uint_as_float(u_hi)) * (0.5 * den);
             double zl = floor(zt - delta), zh = ceil(zt + delta);
             // v = fl(+-b - thr) stands for the real number +-b - thr.  If it lies (almost) on a float32 value the
             // rounding of that subtraction decides the side: unless the subtraction was exact, take a band of one
@@ -224,7 +227,7 @@ __global__ __launch_bounds__(kRunsBlock, kRunsOcc) void k_sg_runs32(RunsArgs a) 
                     zh = ceil(v * den + w);
                 }
             }
-            zh = fmin(fmax(zh + shift, -1073741824.0), 1073741824.0);  // NaN / -inf (no hits) -> -2^30
+            zh = fmin(fmax(zh + shift, -1073741824.0), 1073741824.0);  // -inf (no hits) -> -2^30, +inf (all hit) -> 2^30
             zl = fmin(fmax(zl + shift, -1073741825.0), 1073741823.0);
             const int zhi = (int)zh;
             const int nb_l = zhi - 1 - (int)zl;  // integers strictly between zl and zh (0 almost always)
