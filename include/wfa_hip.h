@@ -43,6 +43,8 @@ extern "C" {
  * indexes samples with 32-bit integers and sums them in 64 bits. */
 #define WFA_MAX_RECORD_SAMPLES 130432
 #define WFA_MAX_SG_WINDOW 63
+/* wfa_sosfiltfilt: second-order sections per filter (a Butterworth band-pass of order N has N sections) */
+#define WFA_MAX_SOS_SECTIONS 32
 
 /* wave source of a consumer (reference: cpu/_wave_source.py:119-165, records branch) */
 #define WFA_SRC_RAW 0        /* wave_pool (uint16)                                        */
@@ -138,7 +140,7 @@ int wfa_upload_records_packed(wfa_ctx* ctx, const void* rows, int64_t n_records,
  *   tab: n_tables * (window + 2*(window/2)*window) doubles:
  *        [ fw[window] | E_left[window/2][window] | E_right[window/2][window] ] per table
  *        fw = correlation weights (savgol_coeffs reversed), E = polynomial edge projection.
- *   symmetric[t]: 1 if ndimage.correlate1d takes its symmetric branch for fw.
+ *   symmetric[t]: the branch ndimage.correlate1d takes for fw: 1 symmetric, 2 anti-symmetric, 0 general.
  *   Integer plan for the full window (exact rational arithmetic):
  *        itab: [ n[window] | NL[window/2][window] | NR[window/2][window] ] int32,
  *        y = n.x / den (interior), edges N.x / den_edge; guard_* = |numerator| below which
@@ -172,7 +174,7 @@ int wfa_savgol(wfa_ctx* ctx, float* out);
  * float32 result (reference: filtering.py:84-101,198-224).  sos = n_sections x 6 coefficients from
  * scipy.signal.butter(..., output="sos"), zi = n_sections x 2 from scipy.signal.sosfilt_zi, padlen =
  * the reference's _estimate_sosfiltfilt_padlen; records with length <= padlen are copied.  The result
- * stays resident as the WFA_SRC_F32 pool; out may be NULL.  n_sections <= 8. */
+ * stays resident as the WFA_SRC_F32 pool; out may be NULL.  1 <= n_sections <= WFA_MAX_SOS_SECTIONS. */
 int wfa_sosfiltfilt(wfa_ctx* ctx, int n_sections, const double* sos, const double* zi, int32_t padlen,
                     float* out);
 

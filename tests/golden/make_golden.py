@@ -162,6 +162,28 @@ def ragged_case(seed=7):
     return records, pool
 
 
+def with_short_records(records, pool, lengths, seed):
+    """records + one record per entry of `lengths`, cut from the first record's pulse region (short records shrink the
+    Savitzky-Golay window, filtering.py:181-195, or are copied by the Butterworth branch when not longer than padlen)."""
+    rng = np.random.default_rng(seed)
+    src = pool[int(records["wave_offset"][0]) : int(records["wave_offset"][0]) + int(records["event_length"][0])]
+    peak = int(np.argmin(src))
+    extra = np.zeros(len(lengths), dtype=records.dtype)
+    chunks, cursor = [pool], len(pool)
+    for k, L in enumerate(lengths):
+        s = int(np.clip(peak - L // 2 + rng.integers(-3, 4), 0, len(src) - L))
+        chunks.append(src[s : s + L].copy())
+        extra[k] = records[0]
+        extra["wave_offset"][k] = cursor
+        extra["event_length"][k] = L
+        extra["baseline"][k] = float(np.mean(src[s : s + min(40, L)].astype(float)))
+        cursor += L
+    extra["record_id"] = records["record_id"].max() + 1 + np.arange(len(lengths))
+    extra["timestamp"] = records["timestamp"].max() + 10**6 * (1 + np.arange(len(lengths)))
+    extra["channel"] = np.arange(len(lengths)) % 8
+    return np.concatenate([records, extra]), np.concatenate(chunks).astype(np.uint16)
+
+
 def peaks_case(name, records, pool, filtered, configs):
     """Reference HitFinderPlugin (core/plugins/builtin/cpu/peak_finding.py:49-614, records source)."""
     if not name.startswith(ONLY):
@@ -813,6 +835,21 @@ def main():
     cc[f"{int(rec['board'][5])}:{int(rec['channel'][5])}"] = {"threshold": float(bs.filtered[45 * 128 + 127]) - 0.0}
     run_case("sgedge_zero", rec, pool, filter_cfg={"sg_window_size": 7, "sg_poly_order": 3},
              hit_cfg={"threshold": 10.0, "channel_config": cc}, want=("filtered", "hits_filt"))
+
+    # high-order Savitzky-Golay (edges above the parity set of tests/sg_reference.py) and Butterworth orders above 8,
+    # each also on records short enough to shrink the window / to be copied (prefix sgbw_: not in the bit-exact sets)
+    for W, P, cfg in [(15, 13, 60), (21, 16, 61), (63, 12, 62)]:
+        rec, pool = synth.make_run(12, "v1725", cfg=cfg)
+        rec, pool = with_short_records(rec, pool, [P + 1, P + 2, W - 1, W, W + 1, 2 * W + 3], seed=cfg)
+        run_case(f"sgbw_sg{W}_{P}", rec, pool, filter_cfg={"sg_window_size": W, "sg_poly_order": P},
+                 hit_cfg={"threshold": 10.0}, want=("filtered", "hits_filt"))
+    for order, cfg in [(1, 63), (9, 64), (12, 65)]:
+        rec, pool = synth.make_run(12, "v1725", cfg=cfg)
+        padlen = 3 * (2 * order + 1)
+        rec, pool = with_short_records(rec, pool, [padlen - 1, padlen, padlen + 1, padlen + 2, 4 * padlen], seed=cfg)
+        run_case(f"sgbw_bw{order}", rec, pool,
+                 filter_cfg={"filter_type": "BW", "lowcut": 0.01, "highcut": 0.2, "fs": 0.5, "filter_order": order},
+                 hit_cfg={"threshold": 10.0}, want=("filtered", "hits_filt"))
 
     # per-channel thresholds + fixed baseline overrides
     rec, pool = synth.make_run(48, "v1725", cfg=3)

@@ -1129,7 +1129,8 @@ int wfa_sosfiltfilt(wfa_ctx* c, int n_sections, const double* sos, const double*
     int rc = use_device(c);
     if (rc) return rc;
     if ((rc = need_source(c, WFA_SRC_RAW))) return rc;
-    if (n_sections < 1 || n_sections > 8) return fail(WFA_E_INVALID, "n_sections must be in [1, 8], got %d", n_sections);
+    if (n_sections < 1 || n_sections > WFA_MAX_SOS_SECTIONS)
+        return fail(WFA_E_INVALID, "n_sections must be in [1, %d], got %d", WFA_MAX_SOS_SECTIONS, n_sections);
     if (!sos || !zi || padlen < 0) return fail(WFA_E_INVALID, "bad sosfiltfilt arguments");
     if ((rc = c->pool_f32.ensure((size_t)c->pool_n * sizeof(float)))) return rc;
     if (!c->filter_keep) WFA_HIP_CHECK(hipMemsetAsync(c->pool_f32.ptr, 0, (size_t)c->pool_n * sizeof(float), c->stream));

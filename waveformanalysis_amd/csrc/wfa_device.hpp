@@ -63,15 +63,17 @@ __device__ __forceinline__ void wave_argmax(double& v, int& idx) {
 
 // ---- Savitzky-Golay, literal float64 evaluation ---------------------------------------------
 // Interior: scipy.ndimage.correlate1d as called by savgol_filter(mode="interp") (reference call
-// site cpu/filtering.py:234-240).  Symmetric branch:  tmp = x[c]*fw[h];
-// for jj=-h..-1: tmp += (x[c+jj] + x[c-jj]) * fw[h+jj];  general branch: tmp = x[c+h]*fw[w-1];
+// site cpu/filtering.py:234-240).  Symmetric branch (sym == 1):  tmp = x[c]*fw[h];
+// for jj=-h..-1: tmp += (x[c+jj] + x[c-jj]) * fw[h+jj];  anti-symmetric branch (sym == 2, taken by scipy for weights
+// that are antisymmetric but not symmetric to within DBL_EPSILON, e.g. the near-identity SG(5,4) and SG(9,8)): the same
+// with (x[c+jj] - x[c-jj]);  general branch (sym == 0): tmp = x[c+h]*fw[w-1];
 // for jj=-h..h-1: tmp += x[c+jj]*fw[h+jj].  Edges: the degree-P least-squares polynomial of the
 // first / last w samples evaluated at the edge positions (scipy _fit_edges_polyfit), here as a
 // precomputed projection row.  Result rounded to float32 like scipy's float32 output array.
 struct SgView {
     int w;         // effective window (0 = copy)
     int h;         // w / 2
-    int sym;       // correlate1d symmetric branch?
+    int sym;       // correlate1d branch: 1 symmetric, 2 anti-symmetric, 0 general
     const double* fw;
     const double* el;  // [h][W] rows
     const double* er;
@@ -112,10 +114,14 @@ __device__ __forceinline__ float sg_value_f64(const uint16_t* __restrict__ x, in
     }
     const double* fw = v.fw;
     double tmp;
-    if (v.sym) {
+    if (v.sym == 1) {
         tmp = (double)x[i] * fw[h];
         for (int jj = -h; jj < 0; ++jj)
             tmp += ((double)x[i + jj] + (double)x[i - jj]) * fw[h + jj];
+    } else if (v.sym == 2) {
+        tmp = (double)x[i] * fw[h];
+        for (int jj = -h; jj < 0; ++jj)
+            tmp += ((double)x[i + jj] - (double)x[i - jj]) * fw[h + jj];
     } else {
         tmp = (double)x[i + h] * fw[w - 1];
         for (int jj = -h; jj < h; ++jj) tmp += (double)x[i + jj] * fw[h + jj];

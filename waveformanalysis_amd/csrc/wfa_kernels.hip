@@ -2979,16 +2979,19 @@ __global__ __launch_bounds__(kPeakBlock) void k_peak_rows(PoolView pool, RecView
 //   bwd  = sosfilt(sos, reverse(fwd), zi = zi0 * fwd[-1]) ; result = reverse(bwd)[edge:-edge] -> float32
 // The forward output lives in a float64 scratch laid out [sample][record-in-batch] so the 64 lanes of a
 // wave read and write consecutive addresses.  Records with L <= padlen are copied (filtering.py:221-222).
-constexpr int kMaxSections = 8;
-
+// The section loops are unrolled over a compile-time bound NS, so the per-section state stays in registers: one instance
+// per bucket of section counts (8 covers orders 1..8, the common case; 16 and 32 the higher orders up to
+// WFA_MAX_SOS_SECTIONS).
+template <int NS>
 struct SosParams {
     int n_sections;
     int edge;                       // padlen
-    double sos[kMaxSections][6];
-    double zi[kMaxSections][2];
+    double sos[NS][6];
+    double zi[NS][2];
 };
 
-__global__ __launch_bounds__(kBlock) void k_sosfiltfilt(PoolView pool, RecView rec, SosParams sp, int64_t r_begin,
+template <int NS>
+__global__ __launch_bounds__(kBlock) void k_sosfiltfilt(PoolView pool, RecView rec, SosParams<NS> sp, int64_t r_begin,
                                                         int64_t r_end, double* __restrict__ scratch,
                                                         int64_t batch_stride, float* __restrict__ out) {
     const int64_t r = r_begin + (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -3011,10 +3014,10 @@ __global__ __launch_bounds__(kBlock) void k_sosfiltfilt(PoolView pool, RecView r
         if (n < edge + L) return (double)(float)x[n - edge];
         return (double)(2.0f * (float)x[L - 1] - (float)x[L - 2 - (n - edge - L)]);
     };
-    double z0[kMaxSections], z1[kMaxSections];
+    double z0[NS], z1[NS];
     const double x0 = ext_at(0);
 #pragma unroll
-    for (int s = 0; s < kMaxSections; ++s) {
+    for (int s = 0; s < NS; ++s) {
         z0[s] = s < sp.n_sections ? sp.zi[s][0] * x0 : 0.0;
         z1[s] = s < sp.n_sections ? sp.zi[s][1] * x0 : 0.0;
     }
@@ -3022,7 +3025,7 @@ __global__ __launch_bounds__(kBlock) void k_sosfiltfilt(PoolView pool, RecView r
     for (int n = 0; n < n_ext; ++n) {
         double xc = ext_at(n);
 #pragma unroll
-        for (int s = 0; s < kMaxSections; ++s) {
+        for (int s = 0; s < NS; ++s) {
             if (s < sp.n_sections) {
                 const double xn = sp.sos[s][0] * xc + z0[s];
                 z0[s] = sp.sos[s][1] * xc - sp.sos[s][4] * xn + z1[s];
@@ -3034,14 +3037,14 @@ __global__ __launch_bounds__(kBlock) void k_sosfiltfilt(PoolView pool, RecView r
         last = xc;
     }
 #pragma unroll
-    for (int s = 0; s < kMaxSections; ++s) {
+    for (int s = 0; s < NS; ++s) {
         z0[s] = s < sp.n_sections ? sp.zi[s][0] * last : 0.0;
         z1[s] = s < sp.n_sections ? sp.zi[s][1] * last : 0.0;
     }
     for (int n = n_ext - 1; n >= 0; --n) {
         double xc = col[(int64_t)n * batch_stride];
 #pragma unroll
-        for (int s = 0; s < kMaxSections; ++s) {
+        for (int s = 0; s < NS; ++s) {
             if (s < sp.n_sections) {
                 const double xn = sp.sos[s][0] * xc + z0[s];
                 z0[s] = sp.sos[s][1] * xc - sp.sos[s][4] * xn + z1[s];
@@ -3145,10 +3148,11 @@ hipError_t launch_width_integral(hipStream_t st, int source, const PoolView& poo
     return hipGetLastError();
 }
 
-hipError_t launch_sosfiltfilt(hipStream_t st, const PoolView& pool, const RecView& rec, int n_sections,
-                              const double* sos, const double* zi, int edge, int64_t r_begin, int64_t r_end,
-                              double* scratch, int64_t batch_stride, float* out) {
-    SosParams sp{};
+template <int NS>
+static hipError_t launch_sosfiltfilt_ns(hipStream_t st, const PoolView& pool, const RecView& rec, int n_sections,
+                                       const double* sos, const double* zi, int edge, int64_t r_begin, int64_t r_end,
+                                       double* scratch, int64_t batch_stride, float* out) {
+    SosParams<NS> sp{};
     sp.n_sections = n_sections;
     sp.edge = edge;
     for (int s = 0; s < n_sections; ++s) {
@@ -3159,9 +3163,21 @@ hipError_t launch_sosfiltfilt(hipStream_t st, const PoolView& pool, const RecVie
     const int64_t n = r_end - r_begin;
     if (n <= 0) return hipSuccess;
     const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_sosfiltfilt, dim3(grid), dim3(kBlock), 0, st, pool, rec, sp, r_begin, r_end, scratch,
+    hipLaunchKernelGGL((k_sosfiltfilt<NS>), dim3(grid), dim3(kBlock), 0, st, pool, rec, sp, r_begin, r_end, scratch,
                        batch_stride, out);
     return hipGetLastError();
+}
+
+hipError_t launch_sosfiltfilt(hipStream_t st, const PoolView& pool, const RecView& rec, int n_sections,
+                              const double* sos, const double* zi, int edge, int64_t r_begin, int64_t r_end,
+                              double* scratch, int64_t batch_stride, float* out) {
+    static_assert(WFA_MAX_SOS_SECTIONS == 32, "one k_sosfiltfilt bucket per power of two up to the maximum");
+    if (n_sections < 1 || n_sections > WFA_MAX_SOS_SECTIONS) return hipErrorInvalidValue;
+    if (n_sections <= 8)
+        return launch_sosfiltfilt_ns<8>(st, pool, rec, n_sections, sos, zi, edge, r_begin, r_end, scratch, batch_stride, out);
+    if (n_sections <= 16)
+        return launch_sosfiltfilt_ns<16>(st, pool, rec, n_sections, sos, zi, edge, r_begin, r_end, scratch, batch_stride, out);
+    return launch_sosfiltfilt_ns<32>(st, pool, rec, n_sections, sos, zi, edge, r_begin, r_end, scratch, batch_stride, out);
 }
 
 hipError_t launch_find_hits_legacy(hipStream_t st, int source, bool fill, const PoolView& pool, int64_t n_rows, int32_t L,

@@ -15,6 +15,9 @@ import numpy as np
 
 from .channel_config import per_record_option
 
+# WFA_MAX_SOS_SECTIONS: the device filters at most this many second-order sections, i.e. band-pass orders up to it
+MAX_BW_ORDER = 32
+
 FILTER_OPTION_NAMES = ("filter_type", "lowcut", "highcut", "fs", "filter_order", "sg_window_size", "sg_poly_order")
 
 
@@ -34,6 +37,8 @@ def design_bw(lowcut, highcut, fs, order):
         raise ValueError(f"lowcut ({lowcut}) 必须小于 highcut ({highcut})")
     if highcut >= fs / 2:
         raise ValueError(f"highcut ({highcut}) 必须小于奈奎斯特频率 ({fs / 2})")
+    if order > MAX_BW_ORDER:  # the reference designs any order; the device kernel stops here
+        raise ValueError(f"Butterworth filter_order {order} exceeds the supported maximum {MAX_BW_ORDER}")
     sos = butter(order, [lowcut, highcut], btype="band", output="sos", fs=fs)
     n_sections = int(sos.shape[0])
     padlen = 3 * (2 * n_sections + 1 - min(int((sos[:, 2] == 0).sum()), int((sos[:, 5] == 0).sum())))

@@ -6,7 +6,7 @@ builtin/cpu/filtering.py:226-240), where W is clamped to the record length and m
 (filtering.py:181-195).  The kernels need, for every effective window w = 1, 3, ..., W:
 
 * ``fw``      the float64 correlation weights scipy convolves with (``savgol_coeffs`` reversed),
-              plus whether ``ndimage.correlate1d`` takes its symmetric branch for them;
+              plus which branch ``ndimage.correlate1d`` takes for them (symmetric, anti-symmetric, general);
 * ``E_left / E_right``  the rows of the least-squares projection ("hat") matrix that scipy's
               ``_fit_edges_polyfit`` evaluates for the first / last w//2 samples;
 * for the full window, an *integer* plan: the hat matrix is rational, H = N / den with integer
@@ -94,12 +94,23 @@ def _is_symmetric(fw: np.ndarray) -> bool:
     return all(abs(fw[c + i] - fw[c - i]) <= DBL_EPSILON for i in range(1, c + 1))
 
 
+def _correlate_branch(fw: np.ndarray) -> int:
+    """NI_Correlate1D's branch: 1 symmetric, else 2 if |fw[c+i] + fw[c-i]| <= DBL_EPSILON for all i, else 0."""
+    if _is_symmetric(fw):
+        return 1
+    w = len(fw)
+    c = w // 2
+    if w % 2 == 1 and all(abs(fw[c + i] + fw[c - i]) <= DBL_EPSILON for i in range(1, c + 1)):
+        return 2
+    return 0
+
+
 @dataclass(frozen=True)
 class SgPlan:
     window: int
     polyorder: int
     tab: np.ndarray        # float64 [n_tables * stride]
-    symmetric: np.ndarray  # uint8 [n_tables]
+    symmetric: np.ndarray  # uint8 [n_tables]: correlate1d branch, 1 symmetric, 2 anti-symmetric, 0 general
     int_ok: bool
     itab: np.ndarray       # int32 [stride]
     den: int
@@ -141,7 +152,7 @@ def build_plan(sg_window_size: int = 11, sg_poly_order: int = 2) -> SgPlan:
         fw = coeffs[::-1].copy()  # convolve1d correlates with the reversed kernel
         base = t * stride
         tab[base : base + w] = fw
-        sym[t] = 1 if _is_symmetric(fw) else 0
+        sym[t] = _correlate_branch(fw)
         for i in range(h):
             tab[base + W + i * W : base + W + i * W + w] = [float(v) for v in hat[i]]
             tab[base + W + H * W + i * W : base + W + H * W + i * W + w] = [float(v) for v in hat[w - h + i]]
