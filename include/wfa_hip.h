@@ -70,7 +70,8 @@ int wfa_ctx_create(int device_id, wfa_ctx** out);
 void wfa_ctx_destroy(wfa_ctx* ctx);
 int wfa_sync(wfa_ctx* ctx);
 /* Free the device scratch a later call rebuilds by itself (hit bitmap, run-event buffer, padded shadow pool, candidate
- * and sort buffers, filter scratch); the resident pools, the records, the plan and the rows of the last passes stay.
+ * and sort buffers, filter scratch, the samples of the last wfa_csv_decode_fill); the resident pools, the records, the
+ * plan, the rows of the last passes and the CSV sample arena stay.
  * This is what Plugin.cleanup(context) of the HIP plugins calls (core/plugins/core/base.py:608-613: "releasing
  * resources" after compute()).  freed_bytes (nullable) receives the capacity given back. */
 int wfa_release_scratch(wfa_ctx* ctx, int64_t* freed_bytes);
@@ -332,6 +333,24 @@ int wfa_csv_decode_count(wfa_ctx* ctx, const uint8_t* text, int64_t n_bytes, int
 int wfa_csv_decode_fill(wfa_ctx* ctx, int64_t n_rows, int32_t n_meta, const int32_t* meta_cols, int64_t* meta,
                         int64_t* row_offset, int32_t* n_fields, int64_t* sample_offset, uint16_t* samples,
                         int64_t n_samples);
+
+/* K15 over a run of several parts (texts < 2^31 bytes each, cut after a '\n'): the decoded samples of every part go
+ * to one context-owned sample arena, and one gather packs the run's wave_pool from it.
+ * _reserve makes room for n_samples; keep_filled = 0 empties the arena (a new run), 1 keeps what is filled (growth).
+ * _count is wfa_csv_decode_count with the text sent through the pinned staging ring.
+ * _fill is wfa_csv_decode_fill writing part samples to arena[sample_base + sample_offset[r] ...]; sample_offset comes
+ * back shifted by sample_base.  sample_base must lie in [0, filled] and sample_base + n_samples within the reserve
+ * (checked before any launch); the filled extent grows to sample_base + n_samples.
+ * _gather is wfa_pool_gather with the arena's filled extent as the source pool.
+ * _filled reports the filled extent and the capacity (samples).  wfa_release_scratch keeps the arena. */
+int wfa_csv_arena_reserve(wfa_ctx* ctx, int64_t n_samples, int keep_filled);
+int wfa_csv_arena_count(wfa_ctx* ctx, const uint8_t* text, int64_t n_bytes, int delimiter, int32_t samples_start,
+                        int64_t* n_rows, int64_t* n_samples);
+int wfa_csv_arena_fill(wfa_ctx* ctx, int64_t sample_base, int64_t n_rows, int32_t n_meta, const int32_t* meta_cols,
+                       int64_t* meta, int64_t* row_offset, int32_t* n_fields, int64_t* sample_offset, int64_t n_samples);
+int wfa_csv_arena_gather(wfa_ctx* ctx, int64_t n_records, const int64_t* src_offset, const int32_t* length,
+                         int64_t* out_offset, uint16_t* out_pool, int64_t out_samples);
+int wfa_csv_arena_filled(wfa_ctx* ctx, int64_t* filled, int64_t* capacity);
 
 /* Wave index of a CAEN V1725 DAW_DEMO binary stream held in host memory (reference: utils/formats/v1725.py:66-114
  * `V1725Reader.iter_waves`): 16-byte event header (channel mask in bytes 4 and 11), per set channel a 12-byte

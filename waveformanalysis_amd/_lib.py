@@ -58,6 +58,11 @@ SIGNATURES = {
     "wfa_find_peaks_fill": (_int, [_p, _p, _i64]),
     "wfa_csv_decode_count": (_int, [_p, _p, _i64, _int, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
     "wfa_csv_decode_fill": (_int, [_p, _i64, _i32, _p, _p, _p, _p, _p, _p, _i64]),
+    "wfa_csv_arena_reserve": (_int, [_p, _i64, _int]),
+    "wfa_csv_arena_count": (_int, [_p, _p, _i64, _int, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
+    "wfa_csv_arena_fill": (_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _i64]),
+    "wfa_csv_arena_gather": (_int, [_p, _i64, _p, _p, _p, _p, _i64]),
+    "wfa_csv_arena_filled": (_int, [_p, C.POINTER(_i64), C.POINTER(_i64)]),
     "wfa_find_hits_count": (_int, [_p, _int, _i64, _i32, _p, _f64, C.POINTER(_i64)]),
     "wfa_find_hits_fill": (_int, [_p, _i64, _p, _p]),
     "wfa_waveform_width": (_int, [_p, _int, _i64, _p, _p, _i64, _i32, _f64, _f64, _f64, _f64, _f64, _int, _p, _p]),

@@ -81,20 +81,28 @@ def resolve_channel_values(
     base_values: Mapping[str, Any] | None = None,
 ) -> dict[str, Any]:
     """Effective option values for one hardware channel (channel.py:412-431)."""
-    hw = (int(board), int(channel))
     resolved: dict[str, Any] = dict(base_values or {})
     if not isinstance(channel_config, Mapping):
         return resolved
     block = channel_config
     if isinstance(block.get(run_id), Mapping):  # {run_id: {...}} wrapper
         block = block[run_id]
+    resolved.update(_layer_values(block, (int(board), int(channel)), "config"))
+    return resolved
 
+
+def _layer_values(block: Mapping, hw: tuple[int, int], group_key: str) -> dict[str, Any]:
+    """defaults < matching groups < the channel entry of one layer (channel.py:268-313); a group's values sit under
+    `group_key`, with "config" as the fallback key."""
+    resolved: dict[str, Any] = {}
     defaults = block.get("defaults")
     if isinstance(defaults, Mapping):
         resolved.update(defaults)
     for grp in _groups(block):
         if _selects(grp.get("channels"), hw):
-            values = grp.get("config")
+            values = grp.get(group_key)
+            if values is None and group_key != "config":
+                values = grp.get("config")
             if isinstance(values, Mapping):
                 resolved.update(values)
 
@@ -117,6 +125,42 @@ def resolve_channel_values(
         resolved.update(values)
         break
     return resolved
+
+
+VALID_POLARITIES = ("positive", "negative")
+
+
+def channel_metadata_layers(context: Any, run_id: str) -> list[Mapping]:
+    """`channel_metadata` of the context config, then of the run config (channel.py:324-343)."""
+    config = getattr(context, "config", {})
+    base = config.get("channel_metadata") if isinstance(config, Mapping) else None
+    run_config: Any = {}
+    getter = getattr(context, "get_run_config", None)
+    if callable(getter):
+        try:
+            run_config = getter(run_id)
+        except Exception:
+            run_config = {}
+    override = run_config.get("channel_metadata") if isinstance(run_config, Mapping) else None
+    return [layer for layer in (base, override) if isinstance(layer, Mapping)]
+
+
+def metadata_polarity(layers: Sequence[Mapping], board: int, channel: int) -> str:
+    """Polarity of one hardware channel from the metadata layers, later layers winning; anything but "positive" /
+    "negative" is "unknown" (channel.py:192-210, 536-548)."""
+    resolved: dict[str, Any] = {}
+    for layer in layers:
+        resolved.update(_layer_values(layer, (int(board), int(channel)), "metadata"))
+    polarity = resolved.get("polarity", "unknown")
+    return polarity if isinstance(polarity, str) and polarity in VALID_POLARITIES else "unknown"
+
+
+def polarity_lookup(layers: Sequence[Mapping], boards: np.ndarray, channels: np.ndarray) -> dict[tuple[int, int], str]:
+    """{(board, channel): polarity} over the distinct channels present (waveforms.py:293-314)."""
+    if not layers or len(boards) == 0:
+        return {}
+    keys = np.unique(np.stack([np.asarray(boards, dtype=np.int64), np.asarray(channels, dtype=np.int64)], axis=1), axis=0)
+    return {(int(b), int(c)): metadata_polarity(layers, int(b), int(c)) for b, c in keys}
 
 
 def per_record_option(
@@ -155,4 +199,7 @@ __all__ = [
     "resolve_channel_values",
     "per_record_option",
     "scatter_per_record",
+    "channel_metadata_layers",
+    "metadata_polarity",
+    "polarity_lookup",
 ]

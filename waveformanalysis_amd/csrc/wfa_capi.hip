@@ -86,6 +86,12 @@ static int h2d_staged(wfa_ctx* c, void* dst, const void* src, size_t bytes) {
     return WFA_OK;
 }
 
+int h2d_copy(wfa_ctx* c, void* dst, const void* src, size_t bytes) {
+    if (bytes >= kStageMin) return h2d_staged(c, dst, src, bytes);
+    if (bytes) WFA_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+    return WFA_OK;
+}
+
 static int h2d(wfa_ctx* c, DevBuf& b, const void* src, size_t bytes) {
     int rc = b.ensure(bytes);
     if (rc) return rc;
@@ -717,7 +723,7 @@ void wfa_ctx_destroy(wfa_ctx* c) {
                       &c->sg.itab, &c->sg.sym, &c->hit_tmp, &c->cursor, &c->rec_tmp_start,
                       &c->rec_nhits, &c->rec_out_start, &c->scan_blocks, &c->hit_out, &c->out_rows, &c->out_rows2,
                       &c->gathered, &c->pw_plan, &c->fw_ties, &c->run_ev, &c->run_span_off, &c->run_span_cnt, &c->run_span_row0, &c->run_scan_blocks, &c->run_ctrl, &c->run_groups, &c->run_lit,
-                      &c->shadow_pool, &c->shadow_off};
+                      &c->shadow_pool, &c->shadow_off, &c->csv_arena};
     for (DevBuf* b : bufs) b->release();
     for (DevBuf& b : c->ht) b.release();
     if (c->h_total) (void)hipHostFree(c->h_total);
@@ -740,7 +746,9 @@ int wfa_release_scratch(wfa_ctx* c, int64_t* freed_bytes) {
     if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
     // what a later call rebuilds by itself.  Kept: the resident pools, the records columns, the filter plan, the rows of the
     // last passes (hit_out / hit_desc / peak_out / out_rows / gathered: *_fill and the resident hit-table stages read them),
-    // the decoded CSV samples (source of wfa_pool_gather), the pinned staging ring and the small control blocks.
+    // the CSV sample arena (source of wfa_csv_arena_gather), the pinned staging ring and the small control blocks.  The
+    // samples of the last wfa_csv_decode_fill live in a scratch slot: they go, and wfa_pool_gather(src_pool = NULL) refuses
+    // until the next decode.
     DevBuf* bufs[] = {&c->bitmap, &c->hit_tmp, &c->bw_scratch, &c->peak_cand_n, &c->peak_cand_pos, &c->peak_cand_val,
                       &c->peak_slot_pos, &c->peak_slot_val, &c->peak_cand_state, &c->peak_cand_rec, &c->peak_accept,
                       &c->peak_ips, &c->peak_row_start, &c->wh_pos, &c->wh_row, &c->wh_valid, &c->fw_ties, &c->run_ev,
@@ -750,6 +758,9 @@ int wfa_release_scratch(wfa_ctx* c, int64_t* freed_bytes) {
     for (DevBuf& b : c->ht) { freed += (int64_t)b.cap; b.release(); }  // (a count pass without its fill is void after this)
     c->ht_n = -1;
     c->ht_perm = nullptr;
+    c->csv_rows = -1;
+    c->csv_samples = -1;
+    c->csv_filled = false;
     c->bitmap_clean = false;
     c->shadow_valid = false;
     c->hit_tmp_rows = 0;

@@ -19,6 +19,9 @@ extern thread_local std::string g_last_error;
 
 int fail(int code, const char* fmt, ...);
 
+// host -> device on the context's stream: the pinned staging ring from 4 MiB on, a plain async copy below (wfa_capi.hip)
+int h2d_copy(wfa_ctx* c, void* dst, const void* src, size_t bytes);
+
 #define WFA_HIP_CHECK(expr)                                                                  \
     do {                                                                                     \
         hipError_t _e = (expr);                                                              \
@@ -165,6 +168,10 @@ struct wfa_ctx {
     int32_t csv_samples_start = 0;
     int csv_delim = ';';
     bool csv_filled = false;
+    // sample arena of a run decoded in several parts (wfa_csv_arena_*): part k's samples land at [base_k, base_k + n_k);
+    // [0, arena_filled) has been written.  Not scratch: wfa_release_scratch keeps it, wfa_ctx_destroy frees it
+    wfa::DevBuf csv_arena;
+    int64_t arena_filled = 0;
     wfa::DevBuf bw_scratch;  // float64 forward pass of sosfiltfilt, [sample][record-in-batch]
 
     // profiling: HIP events around every launch on the context's stream.  The pairs are only recorded while the

@@ -1055,16 +1055,11 @@ int wfa_records_sort(wfa_ctx* c, int64_t n, const int64_t* timestamp, const int3
     return WFA_OK;
 }
 
-int wfa_pool_gather(wfa_ctx* c, int64_t n, const int64_t* src_offset, const int32_t* length, const uint16_t* src_pool,
-                    int64_t src_samples, int64_t* out_offset, uint16_t* out_pool, int64_t out_samples) {
-    int rc = use_device_ht(c);
-    if (rc) return rc;
-    if (n < 0 || src_samples < 0 || out_samples < 0) return fail(WFA_E_INVALID, "negative size");
-    if (n > 0 && (!src_offset || !length || !out_offset)) return fail(WFA_E_INVALID, "null argument");
-    const bool from_csv = !src_pool && src_samples > 0;  // the samples the last wfa_csv_decode_fill left on the device
-    if (from_csv && (!c->csv_filled || c->csv_samples != src_samples))
-        return fail(WFA_E_INVALID, "src_pool is null and no decoded CSV samples of that size are resident");
-    // every slice is checked before a kernel indexes with it; offsets of the packed pool are the running sum
+}  // extern "C"
+
+// every slice is checked before a kernel indexes with it; offsets of the packed pool are the running sum
+static int gather_offsets(int64_t n, const int64_t* src_offset, const int32_t* length, int64_t src_samples,
+                          int64_t* out_offset, int64_t out_samples) {
     int64_t cursor = 0;
     for (int64_t r = 0; r < n; ++r) {
         const int64_t len = length[r] > 0 ? length[r] : 0;
@@ -1076,13 +1071,17 @@ int wfa_pool_gather(wfa_ctx* c, int64_t n, const int64_t* src_offset, const int3
     }
     if (cursor != out_samples)
         return fail(WFA_E_INVALID, "lengths add up to %lld samples, caller expects %lld", (long long)cursor, (long long)out_samples);
-    uint16_t* d_src;
+    return WFA_OK;
+}
+
+// k_pool_gather from the device samples d_src into the resident pool (slices already checked by gather_offsets)
+static int gather_run(wfa_ctx* c, int64_t n, const int64_t* src_offset, const int32_t* length, const uint16_t* d_src,
+                      const int64_t* out_offset, uint16_t* out_pool, int64_t out_samples) {
+    int rc;
     int64_t *d_so, *d_do;
     int32_t* d_len;
-    if (from_csv) d_src = c->ht[S_CSV].as<uint16_t>();
-    else if ((rc = upload(c, S_F0, src_pool, src_samples, &d_src))) return rc;
     if ((rc = upload(c, S_K0, src_offset, n, &d_so)) ||
-        (rc = upload(c, S_K1, (const int64_t*)out_offset, n, &d_do)) || (rc = upload(c, S_K2, length, n, &d_len)))
+        (rc = upload(c, S_K1, out_offset, n, &d_do)) || (rc = upload(c, S_K2, length, n, &d_len)))
         return rc;
     if ((rc = c->pool_u16.ensure((size_t)(out_samples > 0 ? out_samples : 1) * sizeof(uint16_t)))) return rc;
     {
@@ -1107,6 +1106,34 @@ int wfa_pool_gather(wfa_ctx* c, int64_t n, const int64_t* src_offset, const int3
     return WFA_OK;
 }
 
+extern "C" {
+
+int wfa_pool_gather(wfa_ctx* c, int64_t n, const int64_t* src_offset, const int32_t* length, const uint16_t* src_pool,
+                    int64_t src_samples, int64_t* out_offset, uint16_t* out_pool, int64_t out_samples) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (n < 0 || src_samples < 0 || out_samples < 0) return fail(WFA_E_INVALID, "negative size");
+    if (n > 0 && (!src_offset || !length || !out_offset)) return fail(WFA_E_INVALID, "null argument");
+    const bool from_csv = !src_pool && src_samples > 0;  // the samples the last wfa_csv_decode_fill left on the device
+    if (from_csv && (!c->csv_filled || c->csv_samples != src_samples))
+        return fail(WFA_E_INVALID, "src_pool is null and no decoded CSV samples of that size are resident");
+    if ((rc = gather_offsets(n, src_offset, length, src_samples, out_offset, out_samples))) return rc;
+    uint16_t* d_src;
+    if (from_csv) d_src = c->ht[S_CSV].as<uint16_t>();
+    else if ((rc = upload(c, S_F0, src_pool, src_samples, &d_src))) return rc;
+    return gather_run(c, n, src_offset, length, d_src, out_offset, out_pool, out_samples);
+}
+
+int wfa_csv_arena_gather(wfa_ctx* c, int64_t n, const int64_t* src_offset, const int32_t* length, int64_t* out_offset,
+                         uint16_t* out_pool, int64_t out_samples) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (n < 0 || out_samples < 0) return fail(WFA_E_INVALID, "negative size");
+    if (n > 0 && (!src_offset || !length || !out_offset)) return fail(WFA_E_INVALID, "null argument");
+    if ((rc = gather_offsets(n, src_offset, length, c->arena_filled, out_offset, out_samples))) return rc;
+    return gather_run(c, n, src_offset, length, c->csv_arena.as<uint16_t>(), out_offset, out_pool, out_samples);
+}
+
 // Host-only: header walk of a CAEN V1725 DAW_DEMO binary stream (utils/formats/v1725.py:66-114).  The stream is a
 // chain of variable-length events, so the walk is sequential; it touches 16 + 12 bytes per wave and leaves the
 // payloads where they are -- wfa_pool_gather moves them on the GPU.
@@ -1122,9 +1149,11 @@ int wfa_v1725_index(const uint8_t* buf, int64_t n_bytes, int64_t capacity, int16
     return WFA_OK;
 }
 
-// K15 entry points: see include/wfa_hip.h
-int wfa_csv_decode_count(wfa_ctx* c, const uint8_t* text, int64_t n_bytes, int delimiter, int32_t samples_start,
-                         int64_t* n_rows, int64_t* n_samples) {
+}  // extern "C"
+
+// K15 count pass; staged: the text goes up through the pinned staging ring (arena parts) instead of one pageable copy
+static int csv_count(wfa_ctx* c, const uint8_t* text, int64_t n_bytes, int delimiter, int32_t samples_start, bool staged,
+                     int64_t* n_rows, int64_t* n_samples) {
     int rc = use_device_ht(c);
     if (rc) return rc;
     if (n_bytes < 0 || !n_rows || !n_samples) return fail(WFA_E_INVALID, "bad arguments");
@@ -1139,7 +1168,11 @@ int wfa_csv_decode_count(wfa_ctx* c, const uint8_t* text, int64_t n_bytes, int d
     if (n_bytes == 0) { c->csv_rows = 0; c->csv_samples = 0; c->csv_bytes = 0; return WFA_OK; }
     uint8_t* d_text;
     if ((rc = slot<uint8_t>(c, S_ABS0, n_bytes + 2 * kCsvTile, &d_text))) return rc;
-    WFA_HIP_CHECK(hipMemcpyAsync(d_text, text, (size_t)n_bytes, hipMemcpyHostToDevice, c->stream));
+    if (staged) {
+        if ((rc = h2d_copy(c, d_text, text, (size_t)n_bytes))) return rc;
+    } else {
+        WFA_HIP_CHECK(hipMemcpyAsync(d_text, text, (size_t)n_bytes, hipMemcpyHostToDevice, c->stream));
+    }
     WFA_HIP_CHECK(hipMemsetAsync(d_text + n_bytes, 0, 2 * kCsvTile, c->stream));  // tiles read past the last row
     const int64_t nb = (n_bytes + kCsvNlBlock * 16 - 1) / (kCsvNlBlock * 16);
     int64_t *d_bc, *d_bs;
@@ -1191,14 +1224,21 @@ int wfa_csv_decode_count(wfa_ctx* c, const uint8_t* text, int64_t n_bytes, int d
     return WFA_OK;
 }
 
-int wfa_csv_decode_fill(wfa_ctx* c, int64_t n_rows, int32_t n_meta, const int32_t* meta_cols, int64_t* meta,
-                        int64_t* row_offset, int32_t* n_fields, int64_t* sample_offset, uint16_t* samples,
-                        int64_t n_samples) {
+// K15 fill pass.  arena: the samples go to csv_arena[sample_base + sample_offset[r] ...] (range checked by the caller)
+// instead of the S_CSV slot, and sample_offset comes back shifted by sample_base
+static int csv_fill(wfa_ctx* c, int64_t n_rows, int32_t n_meta, const int32_t* meta_cols, int64_t* meta, int64_t* row_offset,
+                    int32_t* n_fields, int64_t* sample_offset, uint16_t* samples, int64_t n_samples, bool arena,
+                    int64_t sample_base) {
     int rc = use_device_ht(c);
     if (rc) return rc;
     if (c->csv_rows < 0) return fail(WFA_E_STATE, "no wfa_csv_decode_count pass has been run");
     if (n_rows != c->csv_rows || n_samples != c->csv_samples)
         return fail(WFA_E_INVALID, "the count pass found %lld rows / %lld samples", (long long)c->csv_rows, (long long)c->csv_samples);
+    if (arena && (sample_base < 0 || sample_base > c->arena_filled ||
+                  sample_base + n_samples > (int64_t)(c->csv_arena.cap / sizeof(uint16_t))))
+        return fail(WFA_E_INVALID, "arena part [%lld, %lld) outside the reserved %lld samples or past the filled %lld",
+                    (long long)sample_base, (long long)(sample_base + n_samples),
+                    (long long)(c->csv_arena.cap / sizeof(uint16_t)), (long long)c->arena_filled);
     if (n_meta < 0 || n_meta > kCsvMaxMeta) return fail(WFA_E_INVALID, "n_meta must be 0..%d", kCsvMaxMeta);
     if (n_meta > 0 && (!meta_cols || !meta)) return fail(WFA_E_INVALID, "null meta arguments");
     CsvCols cols{};
@@ -1208,12 +1248,13 @@ int wfa_csv_decode_fill(wfa_ctx* c, int64_t n_rows, int32_t n_meta, const int32_
             return fail(WFA_E_INVALID, "meta column %d is not before samples_start = %d", meta_cols[j], c->csv_samples_start);
         cols.col[j] = meta_cols[j];
     }
-    if (n_rows == 0) { c->csv_filled = true; return WFA_OK; }
+    if (n_rows == 0) { c->csv_filled = !arena; return WFA_OK; }
     int64_t* d_meta;
-    uint16_t* d_samples;
+    uint16_t* d_samples = arena ? c->csv_arena.as<uint16_t>() + sample_base : nullptr;
     unsigned long long* d_err;
     if ((rc = slot<int64_t>(c, S_OUT1, n_rows * (n_meta > 0 ? n_meta : 1), &d_meta)) ||
-        (rc = slot<uint16_t>(c, S_CSV, n_samples, &d_samples)) || (rc = slot<unsigned long long>(c, S_FLAG, 1, &d_err)))
+        (!arena && (rc = slot<uint16_t>(c, S_CSV, n_samples, &d_samples))) ||
+        (rc = slot<unsigned long long>(c, S_FLAG, 1, &d_err)))
         return rc;
     WFA_HIP_CHECK(hipMemsetAsync(d_err, 0xff, 8, c->stream));
     WFA_HIP_CHECK(hipMemsetAsync(d_meta, 0, (size_t)n_rows * (n_meta > 0 ? n_meta : 1) * 8, c->stream));
@@ -1240,7 +1281,69 @@ int wfa_csv_decode_fill(wfa_ctx* c, int64_t n_rows, int32_t n_meta, const int32_
             return fail(WFA_E_INVALID, "row %lld field %lld: sample outside the uint16 range", row, field);
         return fail(WFA_E_INVALID, "row %lld field %lld: not a decimal integer", row, field);
     }
-    c->csv_filled = true;
+    if (!arena) {
+        c->csv_filled = true;
+        return WFA_OK;
+    }
+    if (sample_offset)
+        for (int64_t r = 0; r < n_rows; ++r) sample_offset[r] += sample_base;
+    c->arena_filled = std::max(c->arena_filled, sample_base + n_samples);
+    return WFA_OK;
+}
+
+extern "C" {
+
+// K15 entry points: see include/wfa_hip.h
+int wfa_csv_decode_count(wfa_ctx* c, const uint8_t* text, int64_t n_bytes, int delimiter, int32_t samples_start,
+                         int64_t* n_rows, int64_t* n_samples) {
+    return csv_count(c, text, n_bytes, delimiter, samples_start, false, n_rows, n_samples);
+}
+
+int wfa_csv_decode_fill(wfa_ctx* c, int64_t n_rows, int32_t n_meta, const int32_t* meta_cols, int64_t* meta,
+                        int64_t* row_offset, int32_t* n_fields, int64_t* sample_offset, uint16_t* samples,
+                        int64_t n_samples) {
+    return csv_fill(c, n_rows, n_meta, meta_cols, meta, row_offset, n_fields, sample_offset, samples, n_samples, false, 0);
+}
+
+int wfa_csv_arena_reserve(wfa_ctx* c, int64_t n_samples, int keep_filled) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (n_samples < 0) return fail(WFA_E_INVALID, "negative size");
+    const size_t bytes = (size_t)(n_samples > 0 ? n_samples : 1) * sizeof(uint16_t);
+    if (!keep_filled) c->arena_filled = 0;
+    if (bytes <= c->csv_arena.cap) return WFA_OK;
+    if (c->arena_filled == 0) return c->csv_arena.ensure(bytes);
+    // grow, keeping [0, arena_filled): new buffer, device copy, swap (DevBuf::ensure drops the contents)
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes + 256);
+    if (e != hipSuccess) return fail(WFA_E_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+    e = hipMemcpyAsync(p, c->csv_arena.ptr, (size_t)c->arena_filled * sizeof(uint16_t), hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return fail(WFA_E_HIP, "arena growth copy failed: %s", hipGetErrorString(e));
+    }
+    c->csv_arena.release();
+    c->csv_arena.ptr = p;
+    c->csv_arena.cap = bytes;
+    return WFA_OK;
+}
+
+int wfa_csv_arena_count(wfa_ctx* c, const uint8_t* text, int64_t n_bytes, int delimiter, int32_t samples_start,
+                        int64_t* n_rows, int64_t* n_samples) {
+    return csv_count(c, text, n_bytes, delimiter, samples_start, true, n_rows, n_samples);
+}
+
+int wfa_csv_arena_fill(wfa_ctx* c, int64_t sample_base, int64_t n_rows, int32_t n_meta, const int32_t* meta_cols,
+                       int64_t* meta, int64_t* row_offset, int32_t* n_fields, int64_t* sample_offset, int64_t n_samples) {
+    return csv_fill(c, n_rows, n_meta, meta_cols, meta, row_offset, n_fields, sample_offset, nullptr, n_samples, true,
+                    sample_base);
+}
+
+int wfa_csv_arena_filled(wfa_ctx* c, int64_t* filled, int64_t* capacity) {
+    if (!c) return fail(WFA_E_INVALID, "ctx is null");
+    if (filled) *filled = c->arena_filled;
+    if (capacity) *capacity = (int64_t)(c->csv_arena.cap / sizeof(uint16_t));
     return WFA_OK;
 }
 

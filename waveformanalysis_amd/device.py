@@ -414,10 +414,60 @@ class DeviceSession:
                                                  _ptr(out["sample_offset"]), _ptr(out["samples"]), ns))
         return out
 
+    # ---- CSV sample arena: a run decoded in several parts, packed by one gather --------------------------------
+    def csv_arena_reserve(self, n_samples: int, keep_filled: bool = False) -> None:
+        """Room for n_samples decoded samples; keep_filled=False starts a new run (filled extent 0), True grows the
+        arena keeping what is filled."""
+        _lib.check(self._lib.wfa_csv_arena_reserve(self._h, int(n_samples), int(bool(keep_filled))))
+
+    def csv_arena_filled(self) -> tuple[int, int]:
+        """(filled extent, capacity) of the arena in samples."""
+        filled, cap = C.c_int64(0), C.c_int64(0)
+        _lib.check(self._lib.wfa_csv_arena_filled(self._h, C.byref(filled), C.byref(cap)))
+        return int(filled.value), int(cap.value)
+
+    def csv_decode_part(self, text, sample_base: int, delimiter: str = ";", samples_start: int = 7,
+                        meta_cols=(0, 1, 2)) -> dict:
+        """csv_decode of one part of a run (text < 2^31 bytes, sent through the pinned staging ring); its samples land
+        in the arena at sample_base.  The arena grows (keeping what is filled) when the part does not fit.  Returns
+        the csv_decode tables with sample_offset relative to the arena."""
+        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else \
+            np.ascontiguousarray(text, dtype=np.uint8)
+        n_rows, n_samples = C.c_int64(0), C.c_int64(0)
+        _lib.check(self._lib.wfa_csv_arena_count(self._h, _ptr(buf), buf.size, ord(delimiter), int(samples_start),
+                                                 C.byref(n_rows), C.byref(n_samples)))
+        n, ns = int(n_rows.value), int(n_samples.value)
+        _filled, cap = self.csv_arena_filled()
+        if sample_base + ns > cap:
+            self.csv_arena_reserve(max(sample_base + ns, cap + cap // 2), keep_filled=True)
+        cols = np.ascontiguousarray(meta_cols, dtype=np.int32)
+        out = {"meta": np.zeros((n, len(cols)), dtype=np.int64), "row_offset": np.zeros(n, dtype=np.int64),
+               "n_fields": np.zeros(n, dtype=np.int32), "sample_offset": np.zeros(n, dtype=np.int64), "n_samples": ns}
+        _lib.check(self._lib.wfa_csv_arena_fill(self._h, int(sample_base), n, len(cols), _ptr(cols), _ptr(out["meta"]),
+                                                _ptr(out["row_offset"]), _ptr(out["n_fields"]),
+                                                _ptr(out["sample_offset"]), ns))
+        return out
+
+    def csv_arena_gather(self, src_offset, length, download: bool = True):
+        """pool_gather with the arena's filled extent as the source.  The downloaded pool is then remembered as the
+        resident wave_pool: ensure_pool(that very array) skips the upload."""
+        so = np.ascontiguousarray(src_offset, dtype=np.int64)
+        ln = np.ascontiguousarray(length, dtype=np.int32)
+        total = int(np.maximum(ln, 0).astype(np.int64).sum())
+        out_off = np.empty(len(so), dtype=np.int64)
+        out = np.empty(total, dtype=np.uint16) if download else None
+        self.forget_resident()
+        _lib.check(self._lib.wfa_csv_arena_gather(self._h, len(so), _ptr(so), _ptr(ln), _ptr(out_off), _ptr(out), total))
+        self.n_samples = total
+        self.n_records = 0
+        self._res_pool = out
+        return out_off, out
+
     def pool_gather(self, src_offset, length, src_pool: np.ndarray | None, download: bool = True,
-                    src_samples: int = 0):
+                    src_samples: int = 0, resident: bool = False):
         """Pack wave slices (given in output order) into the resident wave_pool -> (out_offset, pool | None).
-        src_pool=None with src_samples=n: the source is the samples the last csv_decode left on the device."""
+        src_pool=None with src_samples=n: the source is the samples the last csv_decode left on the device.
+        resident=True: remember the downloaded pool as the device pool's content (ensure_pool skips that array)."""
         so = np.ascontiguousarray(src_offset, dtype=np.int64)
         ln = np.ascontiguousarray(length, dtype=np.int32)
         total = int(np.maximum(ln, 0).astype(np.int64).sum())
@@ -429,6 +479,8 @@ class DeviceSession:
                                                  _ptr(out_off), _ptr(out), total))
             self.n_samples = total
             self.n_records = 0
+            if resident:
+                self._res_pool = out
             return out_off, out
         src = np.ascontiguousarray(src_pool)
         if src.dtype == np.int16:
@@ -439,6 +491,8 @@ class DeviceSession:
                                              _ptr(out), total))
         self.n_samples = total
         self.n_records = 0
+        if resident:
+            self._res_pool = out
         return out_off, out
 
     # ---- hit-table stages (device sort + scans) ------------------------------------------------------------

@@ -3,6 +3,7 @@
 ``hip_default()`` is the packaging the reference uses for backends: a profile function
 returning plugin instances (waveform_analysis/core/plugins/profiles.py:20-62); register them
 with ``ctx.register(p, allow_override=True)`` to replace the CPU plugins of the same name.
+``hip_with_records()`` adds the records / wave_pool builders (raw files -> bundle on the GPU).
 """
 
 from .basic_features import HipBasicFeaturesPlugin
@@ -10,6 +11,7 @@ from .filtered_waveforms import HipFilteredWaveformsPlugin
 from .hit_finder import HipHitFinderPlugin
 from .hit_grouped import HipHitGroupedPlugin
 from .hit_merge import HipHitMergeClustersPlugin, HipHitMergedComponentsPlugin, HipHitMergePlugin
+from .records import HipRecordsPlugin, HipWavePoolPlugin
 from .s1_s2 import HipS1S2ClassifierPlugin
 from .signal_peaks import HipSignalPeaksStreamPlugin
 from .threshold_hit import HipThresholdHitPlugin
@@ -26,7 +28,14 @@ def hip_default():
             HipSignalPeaksStreamPlugin()]
 
 
+def hip_with_records():
+    """hip_default() plus records / wave_pool built from raw_files on the GPU (the pool then stays resident for the
+    records-route plugins of the same thread)."""
+    return hip_default() + [HipRecordsPlugin(), HipWavePoolPlugin()]
+
+
 __all__ = ["HipWavePoolFilteredPlugin", "HipThresholdHitPlugin", "HipBasicFeaturesPlugin",
            "HipWaveformWidthIntegralPlugin", "HipHitGroupedPlugin", "HipHitFinderPlugin", "HipFilteredWaveformsPlugin",
            "HipWaveformWidthPlugin", "HipS1S2ClassifierPlugin", "HipHitMergeClustersPlugin",
-           "HipHitMergePlugin", "HipHitMergedComponentsPlugin", "HipSignalPeaksStreamPlugin", "hip_default"]
+           "HipHitMergePlugin", "HipHitMergedComponentsPlugin", "HipSignalPeaksStreamPlugin", "HipRecordsPlugin", "HipWavePoolPlugin",
+           "hip_default", "hip_with_records"]

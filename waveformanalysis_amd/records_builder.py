@@ -144,7 +144,7 @@ def merge_records_parts(parts: Sequence[RecordsBundle], session=None) -> Records
     if np.any(bad):
         i = int(np.flatnonzero(bad)[0])
         raise ValueError(f"could not broadcast input array: record {i} wave slice outside its part's wave_pool")
-    out_off, pool = sess.pool_gather(src_offset[order], lengths, src_pool)
+    out_off, pool = sess.pool_gather(src_offset[order], lengths, src_pool, resident=True)
     out["wave_offset"] = out_off
     record_ids = out["record_id"].astype(np.int64, copy=False)
     if len(np.unique(record_ids)) != len(record_ids):
@@ -205,7 +205,8 @@ def build_records_from_v1725_blob(blob: np.ndarray, board: int, dt_ns: int, sess
     buf = np.ascontiguousarray(blob, dtype=np.uint8)
     if buf.size % 2:
         buf = np.concatenate([buf, np.zeros(1, dtype=np.uint8)])
-    out_off, pool = sess.pool_gather(idx["payload_offset"][order] // 2, rec["event_length"], buf.view(np.uint16))
+    out_off, pool = sess.pool_gather(idx["payload_offset"][order] // 2, rec["event_length"], buf.view(np.uint16),
+                                     resident=True)
     rec["wave_offset"] = out_off
     rec["record_id"] = np.arange(n, dtype=np.int64)
     return RecordsBundle(records=rec, wave_pool=pool)
@@ -268,6 +269,15 @@ def _strip_rows(data: bytes, n: int) -> bytes:
     return data[pos:]
 
 
+def vx2730_body(data: bytes, is_first_file: bool) -> bytes:
+    """A file's rows as the decoder takes them: header rows cut off (vx2730_skiprows), ending with '\n' (b"" when
+    nothing is left)."""
+    body = _strip_rows(data, vx2730_skiprows(data, is_first_file))
+    if body and not body.endswith(b"\n"):
+        body += b"\n"
+    return body
+
+
 def _baseline_window(baseline_samples, samples_start: int, baseline_start: int, baseline_end: int) -> tuple[int, int]:
     """records_builder.py:53-105: None -> the adapter's columns; int n -> the first n samples; (s, e) -> samples[s:e]
     (same validation messages)."""
@@ -296,16 +306,89 @@ def _baseline_window(baseline_samples, samples_start: int, baseline_start: int, 
                     f"got {type(baseline_samples).__name__}")
 
 
+MAX_PART_BYTES = 2**31 - 1   # one device decode call takes < 2^31 bytes of text
+
+
+def vx2730_parts(bodies: Sequence[bytes], part_bytes: int) -> list[list[tuple[int, int, int]]]:
+    """Cut file bodies (header rows removed, each ending with '\n') into parts of at most `part_bytes` bytes:
+    part = list of (file index, start, end) slices, in file order, that concatenate to the bodies.
+
+    Files are packed whole while they fit; a file longer than the room left is cut only after a '\n', so no row is
+    ever split.  A single row longer than the budget makes a part of its own."""
+    part_bytes = int(part_bytes)
+    if part_bytes < 1:
+        raise ValueError(f"part_bytes must be >= 1, got {part_bytes}")
+    parts: list[list[tuple[int, int, int]]] = []
+    cur: list[tuple[int, int, int]] = []
+    used = 0
+    for f, body in enumerate(bodies):
+        n, pos = len(body), 0
+        while pos < n:
+            room = part_bytes - used
+            if n - pos <= room:
+                cur.append((f, pos, n))
+                used += n - pos
+                break
+            cut = body.rfind(b"\n", pos, pos + room) + 1   # 0: no line end inside the room
+            if cut <= pos and cur:                           # close this part, the next one has the whole budget
+                parts.append(cur)
+                cur, used = [], 0
+                continue
+            if cut <= pos:                                   # one row longer than the budget: a part of its own
+                nl = body.find(b"\n", pos)
+                cut = n if nl < 0 else nl + 1
+            cur.append((f, pos, cut))
+            parts.append(cur)
+            cur, used = [], 0
+            pos = cut
+    if cur:
+        parts.append(cur)
+    return parts
+
+
+def _part_text(bodies: Sequence[bytes], part: list[tuple[int, int, int]]) -> bytes:
+    if len(part) == 1:
+        f, a, b = part[0]
+        if a == 0 and b == len(bodies[f]):
+            return bodies[f]
+    return b"".join(bodies[f][a:b] for f, a, b in part)
+
+
+def _decode_parts(sess, bodies: Sequence[bytes], part_bytes: int) -> dict:
+    """Every part decoded into the session's sample arena; the tables of all parts concatenated, row_offset and
+    sample_offset relative to the whole run (the bytes of all bodies in order / the arena)."""
+    plan = vx2730_parts(bodies, min(int(part_bytes), MAX_PART_BYTES))
+    total_bytes = sum(len(b) for b in bodies)
+    sess.csv_arena_reserve(total_bytes // 4 + 1, keep_filled=False)   # grown by csv_decode_part when short
+    tables = []
+    sample_base = byte_base = 0
+    for part in plan:
+        text = _part_text(bodies, part)
+        d = sess.csv_decode_part(text, sample_base, VX2730_DELIMITER, VX2730_SAMPLES_START, (0, 1, 2))
+        d["row_offset"] += byte_base      # part row -> byte of the run -> file (per-part base)
+        tables.append(d)
+        byte_base += len(text)
+        sample_base += d["n_samples"]
+    out = {k: np.concatenate([d[k] for d in tables]) for k in ("meta", "row_offset", "n_fields", "sample_offset")}
+    out["n_samples"] = sample_base
+    return out
+
+
 def build_records_from_vx2730_files(raw_files, default_dt_ns: int = 1, baseline_samples=None, epoch_ns=None,
-                                    session=None) -> RecordsBundle:
+                                    session=None, part_bytes: int | None = None) -> RecordsBundle:
     """`build_records_from_raw_files(raw_files, adapter_name="vx2730", ...)` (records_builder.py:524-642, 834-867;
     per file `_build_records_part_from_raw_array` 212-302): raw_files is a list of per-channel file lists.
 
-    The text of all files goes to the GPU in one piece (header rows cut off on the host), is decoded there
-    (wfa_csv_decode_*), the records are ordered with the device sort and the decoded samples are packed into the
-    final wave_pool without leaving the device; the baselines are means over the packed pool.  The reference sorts
-    every file's part and heap-merges the parts with (part, row) as tie-break, which is the stable sort of all rows
-    in (channel list, file, row) order -- one sort here."""
+    The text of the files (header rows cut off on the host) is decoded on the GPU (wfa_csv_decode_*), the records are
+    ordered with the device sort and the decoded samples are packed into the final wave_pool without leaving the
+    device; the baselines are means over the packed pool.  The reference sorts every file's part and heap-merges the
+    parts with (part, row) as tie-break, which is the stable sort of all rows in (channel list, file, row) order -- one
+    sort here.
+
+    part_bytes=None: all text in one decode call (< 2^31 bytes).  part_bytes=n: the text is cut into parts of at most
+    n bytes (vx2730_parts: at file ends or after a '\n'), each decoded into the session's sample arena, then one sort
+    over all rows and one gather from the arena; the result is the same.  The gathered pool is then the session's
+    resident wave_pool."""
     import os
 
     b0, b1 = _baseline_window(baseline_samples, VX2730_SAMPLES_START, *VX2730_BASELINE_COLUMNS)
@@ -316,23 +399,23 @@ def build_records_from_vx2730_files(raw_files, default_dt_ns: int = 1, baseline_
             if not os.path.exists(path) or os.path.getsize(path) == 0:   # the reader skips both
                 continue
             with open(path, "rb") as fh:
-                data = fh.read()
-            body = _strip_rows(data, vx2730_skiprows(data, is_first_file=(k == 0)))
+                body = vx2730_body(fh.read(), is_first_file=(k == 0))
             if not body:
                 continue
-            if not body.endswith(b"\n"):
-                body += b"\n"
             chunks.append(body)
             file_rows_base.append(total)
             file_channel.append(channel_idx)
             total += len(body)
     if not chunks:
         return _empty()
-    if total >= 2**31:
-        raise ValueError(f"{total} bytes of CSV text; one device decode call takes < 2^31 bytes -- build the run in "
-                         "several calls and merge_records_parts the results")
     sess = _session(session)
-    dec = sess.csv_decode(b"".join(chunks), VX2730_DELIMITER, VX2730_SAMPLES_START, (0, 1, 2))
+    if part_bytes is None:
+        if total >= 2**31:
+            raise ValueError(f"{total} bytes of CSV text; one device decode call takes < 2^31 bytes -- build the run "
+                             "in several calls and merge_records_parts the results, or pass part_bytes")
+        dec = sess.csv_decode(b"".join(chunks), VX2730_DELIMITER, VX2730_SAMPLES_START, (0, 1, 2))
+    else:
+        dec = _decode_parts(sess, chunks, part_bytes)
     keep = dec["n_fields"] > 0            # blank lines
     file_of = np.searchsorted(np.asarray(file_rows_base, dtype=np.int64), dec["row_offset"], side="right") - 1
     nf = dec["n_fields"]
@@ -361,8 +444,11 @@ def build_records_from_vx2730_files(raw_files, default_dt_ns: int = 1, baseline_
     rec["time"] = rec["timestamp"] // 1000 if epoch_ns is None else np.int64(epoch_ns) + rec["timestamp"] // 1000
     order = records_sort_order(rec, sess)
     rec = rec[order]
-    out_off, pool = sess.pool_gather(dec["sample_offset"][rows][order], rec["event_length"], None,
-                                     src_samples=dec["n_samples"])
+    if part_bytes is None:
+        out_off, pool = sess.pool_gather(dec["sample_offset"][rows][order], rec["event_length"], None,
+                                         src_samples=dec["n_samples"])
+    else:
+        out_off, pool = sess.csv_arena_gather(dec["sample_offset"][rows][order], rec["event_length"])
     rec["wave_offset"] = out_off
     rec["record_id"] = np.arange(n, dtype=np.int64)
     sess.upload_records(rec)
@@ -372,4 +458,4 @@ def build_records_from_vx2730_files(raw_files, default_dt_ns: int = 1, baseline_
 
 __all__ = ["RecordsBundle", "records_sort_order", "build_records_from_st_waveforms", "merge_records_parts",
            "v1725_index", "build_records_from_v1725_blob", "build_records_from_v1725_files",
-           "build_records_from_vx2730_files", "vx2730_skiprows"]
+           "build_records_from_vx2730_files", "vx2730_skiprows", "vx2730_body", "vx2730_parts"]
