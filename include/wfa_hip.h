@@ -316,6 +316,29 @@ int wfa_pool_gather(wfa_ctx* ctx, int64_t n_records, const int64_t* src_offset, 
                     const uint16_t* src_pool, int64_t src_samples, int64_t* out_offset, uint16_t* out_pool,
                     int64_t out_samples);
 
+/* K16 st_waveforms rows: n rows of numpy's packed create_record_dtype(wave_length) layout (reference:
+ * processing/dtypes.py:36-64 ST_WAVEFORM_DTYPE; filled by core/plugins/builtin/cpu/waveforms.py:640-734
+ * `WaveformStruct._structure_waveform`, :384-450 the streaming structurizer, :233-290 `_convert_v1725_to_st_waveforms`).
+ * Row stride 76 + 2 * wave_length bytes: baseline f64 @0, baseline_upstream f64 @8, polarity 8 x UCS-4 @16,
+ * timestamp i64 @48, record_id i64 @56, dt i32 @64, event_length i32 @68, board i16 @72, channel i16 @74,
+ * wave i16[wave_length] @76 = the first min(src_len[r], wave_length) samples of the row's source slice, zeros after.
+ * The samples come from `source`: WFA_ST_SRC_HOST = src_pool (src_samples samples, uploaded through the staging
+ * ring), _CSV = the samples of the last wfa_csv_decode_fill, _ARENA = the CSV arena (src_samples = its filled
+ * extent), _POOL = the resident wave_pool (e.g. left by wfa_pool_gather).  polarity[r] indexes polarity_table:
+ * n_polarity (1..8) strings of 8 UCS-4 code points each, zero padded.  Rows are built on the device in batches of at
+ * most batch_bytes (>= one row, <= 1 GiB) in two buffers, each batch copied into `out` (n x stride bytes, caller
+ * owned) through the pinned staging ring while the next one is packed.  Slices and codes are checked before any
+ * launch (WFA_E_INVALID). */
+#define WFA_ST_SRC_HOST 0
+#define WFA_ST_SRC_CSV 1
+#define WFA_ST_SRC_ARENA 2
+#define WFA_ST_SRC_POOL 3
+int wfa_st_pack(wfa_ctx* ctx, int64_t n, int source, const uint16_t* src_pool, int64_t src_samples,
+                const int64_t* src_offset, const int32_t* src_len, int32_t wave_length, const double* baseline,
+                const double* baseline_upstream, const int64_t* timestamp, const int64_t* record_id, const int32_t* dt,
+                const int32_t* event_length, const int16_t* board, const int16_t* channel, const uint8_t* polarity,
+                const uint32_t* polarity_table, int32_t n_polarity, int64_t batch_bytes, uint8_t* out);
+
 /* K15 CAEN VX2730 CSV text -> integers on the device (reference: utils/formats/vx2730.py:78-110 column layout,
  * :193-340 `VX2730Reader.read_file` -- its polars / pyarrow / pandas backends all yield these integers; consumer
  * processing/records_builder.py:212-302).  text = the bytes of one or more files after their header rows: rows end

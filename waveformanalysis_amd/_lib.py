@@ -22,6 +22,7 @@ WFA_E_LIMIT = -6
 
 SRC_RAW, SRC_F32, SRC_SG_FUSED = 0, 1, 2
 POL_UNKNOWN, POL_NEGATIVE, POL_POSITIVE, POL_POSITIVE_WAVE = 0, 1, 2, 3
+ST_SRC_HOST, ST_SRC_CSV, ST_SRC_ARENA, ST_SRC_POOL = 0, 1, 2, 3
 ABI_VERSION = 1
 
 _p = C.c_void_p
@@ -76,6 +77,7 @@ SIGNATURES = {
     "wfa_v1725_index": (_int, [_p, _i64, _i64, _p, _p, _p, _p, _p, _p, C.POINTER(_i64)]),
     "wfa_records_sort": (_int, [_p, _i64, _p, _p, _p, _p, _p]),
     "wfa_pool_gather": (_int, [_p, _i64, _p, _p, _p, _i64, _p, _p, _i64]),
+    "wfa_st_pack": (_int, [_p, _i64, _int, _p, _i64, _p, _p, _i32] + [_p] * 10 + [_i32, _i64, _p]),
     "wfa_basic_features": (_int, [_p, _int, _i64, _i64, _int, _i64, _i64, _int, _p, _p]),
     "wfa_width_integral": (_int, [_p, _int, _f64, _f64, _f64, _p]),
     "wfa_features_both": (_int, [_p, _i64, _i64, _int, _i64, _i64, _int, _f64, _f64, _f64, _p, _p]),

@@ -92,6 +92,36 @@ int h2d_copy(wfa_ctx* c, void* dst, const void* src, size_t bytes) {
     return WFA_OK;
 }
 
+int d2h_staged(wfa_ctx* c, void* dst, const void* src, size_t bytes, int (*queued)(void*), void* arg) {
+    if (!c->stage[0]) {
+        for (int b = 0; b < 2; ++b) {
+            WFA_HIP_CHECK(hipHostMalloc(&c->stage[b], kStageBytes, hipHostMallocDefault));
+            WFA_HIP_CHECK(hipEventCreateWithFlags(&c->stage_ev[b], hipEventDisableTiming));
+        }
+        c->stage_bytes = kStageBytes;
+    }
+    size_t prev_off = 0, prev_n = 0;
+    int b = 0;
+    for (size_t off = 0; off < bytes || prev_n; off += kStageBytes, b ^= 1) {
+        const size_t n = off < bytes ? std::min(bytes - off, kStageBytes) : 0;
+        if (n) {  // stage[b] is free: its last chunk was copied out one iteration ago
+            WFA_HIP_CHECK(hipMemcpyAsync(c->stage[b], (const char*)src + off, n, hipMemcpyDeviceToHost, c->stream));
+            WFA_HIP_CHECK(hipEventRecord(c->stage_ev[b], c->stream));
+            if (off == 0 && queued)
+                if (int rc = queued(arg)) return rc;
+        }
+        if (prev_n) {
+            WFA_HIP_CHECK(hipEventSynchronize(c->stage_ev[b ^ 1]));
+            host::parallel_memcpy((char*)dst + prev_off, c->stage[b ^ 1], prev_n);
+        }
+        prev_off = off;
+        prev_n = n;
+    }
+    if (bytes == 0 && queued)
+        if (int rc = queued(arg)) return rc;
+    return WFA_OK;
+}
+
 static int h2d(wfa_ctx* c, DevBuf& b, const void* src, size_t bytes) {
     int rc = b.ensure(bytes);
     if (rc) return rc;

@@ -21,6 +21,10 @@ int fail(int code, const char* fmt, ...);
 
 // host -> device on the context's stream: the pinned staging ring from 4 MiB on, a plain async copy below (wfa_capi.hip)
 int h2d_copy(wfa_ctx* c, void* dst, const void* src, size_t bytes);
+// device -> host through the same pinned ring: chunk k+1 is on the wire while the host copies chunk k out.  `queued`
+// (may be null) runs once, right after the first chunk's copy is queued: work it enqueues overlaps the host's draining.
+// Returns when every byte has reached dst (wfa_capi.hip)
+int d2h_staged(wfa_ctx* c, void* dst, const void* src, size_t bytes, int (*queued)(void*), void* arg);
 
 #define WFA_HIP_CHECK(expr)                                                                  \
     do {                                                                                     \

@@ -532,6 +532,121 @@ __global__ __launch_bounds__(128) void k_pool_gather(int64_t n, const int64_t* _
 }
 
 
+// ---- st_waveforms rows: numpy's packed create_record_dtype(L) layout written on the device ---------------------------
+// (reference: processing/dtypes.py:36-64; waveforms.py:640-734 / :233-290 fill the same rows with a strided host pass)
+// Output-stationary: a lane owns 16 bytes of the batch's byte stream, finds its (row, byte-in-row) with a reciprocal
+// multiply, composes the eight halfwords (header bytes, or samples realigned from two aligned dwords by a funnel shift,
+// zero past the row's length) and stores them with one dwordx4 store.  The stride 76 + 2L is even, so a lane's first
+// byte is always even and every halfword lies in one field; stores never straddle a lane.
+constexpr uint32_t kStHeader = 76;   // baseline 0, baseline_upstream 8, polarity 16 (8 UCS-4), timestamp 48,
+                                     // record_id 56, dt 64, event_length 68, board 72, channel 74, wave 76
+constexpr int kStBlock = 256;
+constexpr int kStMaxPol = 8;
+
+struct StPackArgs {
+    const uint16_t* src;         // device samples (4-byte aligned base)
+    const int64_t* src_off;      // per row, samples
+    const int32_t* src_len;
+    const double* baseline;
+    const double* baseline_up;
+    const int64_t* ts;
+    const int64_t* rid;
+    const int32_t* dt;
+    const int32_t* ev_len;
+    const int16_t* board;
+    const int16_t* chan;
+    const uint8_t* pol;          // index into pol_tab
+    const uint32_t* pol_tab;     // kStMaxPol x 8 UCS-4 code points
+    int64_t row0;                // first row of this batch
+    int64_t n_rows;              // rows in this batch
+    uint32_t n_chunks;           // 16-byte chunks of this batch (the buffer is padded to a whole chunk)
+    uint32_t stride;             // bytes per row
+    uint32_t magic;              // floor((2^32 - 1) / stride)
+    int32_t L;
+};
+
+// halfword h (0..37) of row r's header
+__device__ __forceinline__ uint32_t st_header_half(const StPackArgs& a, int64_t r, uint32_t h) {
+    uint64_t v;
+    uint32_t k;
+    if (h < 4) { v = (uint64_t)__double_as_longlong(a.baseline[r]); k = h; }
+    else if (h < 8) { v = (uint64_t)__double_as_longlong(a.baseline_up[r]); k = h - 4; }
+    else if (h < 24) { v = a.pol_tab[a.pol[r] * 8 + ((h - 8) >> 1)]; k = (h - 8) & 1; }
+    else if (h < 28) { v = (uint64_t)a.ts[r]; k = h - 24; }
+    else if (h < 32) { v = (uint64_t)a.rid[r]; k = h - 28; }
+    else if (h < 34) { v = (uint32_t)a.dt[r]; k = h - 32; }
+    else if (h < 36) { v = (uint32_t)a.ev_len[r]; k = h - 34; }
+    else if (h == 36) { v = (uint16_t)a.board[r]; k = 0; }
+    else { v = (uint16_t)a.chan[r]; k = 0; }
+    return (uint32_t)(v >> (16 * k)) & 0xffffu;
+}
+
+__device__ __forceinline__ int32_t st_len(const StPackArgs& a, int64_t r) {
+    const int32_t n = a.src_len[r];
+    return n <= 0 ? 0 : (n < a.L ? n : a.L);
+}
+
+__global__ __launch_bounds__(kStBlock) void k_st_pack(StPackArgs a, uint8_t* __restrict__ out) {
+    const uint32_t g = blockIdx.x * kStBlock + threadIdx.x;
+    if (g >= a.n_chunks) return;
+    const uint32_t b = g * 16u;
+    uint32_t r = __umulhi(b, a.magic);  // floor(b / stride) or up to two less
+    uint32_t p = b - r * a.stride;
+    if (p >= a.stride) { ++r; p -= a.stride; }
+    if (p >= a.stride) { ++r; p -= a.stride; }
+    uint32_t w[4];
+    if (p >= kStHeader && p + 16 <= a.stride) {
+        // eight samples of one row: s0 .. s0 + 7
+        const int64_t gr = a.row0 + r;
+        const int64_t off = a.src_off[gr];
+        const int32_t len = st_len(a, gr);
+        const int32_t s0 = (int32_t)((p - kStHeader) >> 1);
+        const int64_t at = off + s0, lim = off + len;   // sample indices into src; [.., lim) is this row's to write
+        const int64_t ab = at >> 1;
+        const bool odd = at & 1;
+        const uint32_t* src32 = reinterpret_cast<const uint32_t*>(a.src);
+        const bool any = s0 < len;   // (a row of length 0 may carry any offset: nothing of it is read)
+        uint32_t d[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i)  // only dwords holding a sample of this row are read
+            d[i] = (any && (i < 4 || odd) && 2 * (ab + i) < lim) ? src32[ab + i] : 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            uint32_t v = odd ? __builtin_amdgcn_alignbit(d[j + 1], d[j], 16) : d[j];
+            const int32_t s = s0 + 2 * j;
+            if (s >= len) v = 0;
+            else if (s + 1 >= len) v &= 0xffffu;
+            w[j] = v;
+        }
+    } else {
+        // header bytes, a row boundary or the padding after the last row: halfword by halfword
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                uint32_t q = p + 4 * j + 2 * k;
+                uint32_t rr = r;
+                if (q >= a.stride) { q -= a.stride; ++rr; }
+                uint32_t hw = 0;
+                if (rr < a.n_rows) {
+                    const int64_t gr = a.row0 + rr;
+                    if (q < kStHeader) {
+                        hw = st_header_half(a, gr, q >> 1);
+                    } else {
+                        const int32_t s = (int32_t)((q - kStHeader) >> 1);
+                        if (s < st_len(a, gr)) hw = a.src[a.src_off[gr] + s];
+                    }
+                }
+                v |= hw << (16 * k);
+            }
+            w[j] = v;
+        }
+    }
+    *reinterpret_cast<uint4*>(out + b) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+
 // ---- K15: delimiter-separated integer text -> int64 columns + uint16 samples (CAEN VX2730 CSV) ------------------
 // (utils/formats/vx2730.py:193-340: every reader backend yields the same integers; records_builder.py:212-302 then
 // uses columns board / channel / timestamp and the samples from `samples_start` to the end of the row.)
@@ -1344,6 +1459,131 @@ int wfa_csv_arena_filled(wfa_ctx* c, int64_t* filled, int64_t* capacity) {
     if (!c) return fail(WFA_E_INVALID, "ctx is null");
     if (filled) *filled = c->arena_filled;
     if (capacity) *capacity = (int64_t)(c->csv_arena.cap / sizeof(uint16_t));
+    return WFA_OK;
+}
+
+}  // extern "C"
+
+
+// ---- st_waveforms rows (k_st_pack) ----------------------------------------------------------------------------------
+namespace {
+struct StPackLoop {
+    wfa_ctx* c;
+    StPackArgs a;
+    uint8_t* buf[2];
+    int64_t rows_per_batch, n, next;  // next: first row of the batch to pack next
+    int launch() {  // pack the batch starting at row `next` into buf[(next / rows_per_batch) & 1]
+        if (next >= n) return WFA_OK;
+        const int64_t k = next / rows_per_batch;
+        a.row0 = next;
+        a.n_rows = std::min(rows_per_batch, n - next);
+        const uint64_t bytes = (uint64_t)a.n_rows * a.stride;
+        a.n_chunks = (uint32_t)((bytes + 15) / 16);
+        LaunchTimer t(c, true);
+        hipLaunchKernelGGL(k_st_pack, dim3((a.n_chunks + kStBlock - 1) / kStBlock), dim3(kStBlock), 0, c->stream, a,
+                           buf[k & 1]);
+        WFA_HIP_CHECK(hipGetLastError());
+        next += a.n_rows;
+        return t.end("k_st_pack");
+    }
+    static int launch_cb(void* self) { return static_cast<StPackLoop*>(self)->launch(); }
+};
+}  // namespace
+
+extern "C" {
+
+int wfa_st_pack(wfa_ctx* c, int64_t n, int source, const uint16_t* src_pool, int64_t src_samples,
+                const int64_t* src_offset, const int32_t* src_len, int32_t wave_length, const double* baseline,
+                const double* baseline_upstream, const int64_t* timestamp, const int64_t* record_id, const int32_t* dt,
+                const int32_t* event_length, const int16_t* board, const int16_t* channel, const uint8_t* polarity,
+                const uint32_t* polarity_table, int32_t n_polarity, int64_t batch_bytes, uint8_t* out) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (n < 0 || src_samples < 0) return fail(WFA_E_INVALID, "negative size");
+    if (wave_length < 0 || wave_length > (1 << 28)) return fail(WFA_E_INVALID, "wave_length %d out of range", wave_length);
+    if (n_polarity < 1 || n_polarity > kStMaxPol) return fail(WFA_E_INVALID, "1..%d polarity strings", kStMaxPol);
+    if (!polarity_table) return fail(WFA_E_INVALID, "null polarity table");
+    if (n == 0) return WFA_OK;
+    if (!src_offset || !src_len || !baseline || !baseline_upstream || !timestamp || !record_id || !dt || !event_length ||
+        !board || !channel || !polarity || !out)
+        return fail(WFA_E_INVALID, "null argument");
+    const uint16_t* d_src = nullptr;
+    switch (source) {
+    case WFA_ST_SRC_HOST:
+        if (src_samples > 0 && !src_pool) return fail(WFA_E_INVALID, "src_pool is null");
+        break;
+    case WFA_ST_SRC_CSV:
+        if (!c->csv_filled || c->csv_samples != src_samples)
+            return fail(WFA_E_INVALID, "no decoded CSV samples of that size are resident");
+        d_src = c->ht[S_CSV].as<uint16_t>();
+        break;
+    case WFA_ST_SRC_ARENA:
+        if (src_samples != c->arena_filled)
+            return fail(WFA_E_INVALID, "the arena holds %lld samples, not %lld", (long long)c->arena_filled, (long long)src_samples);
+        d_src = c->csv_arena.as<uint16_t>();
+        break;
+    case WFA_ST_SRC_POOL:
+        if (!c->have_u16 || c->pool_n != src_samples)
+            return fail(WFA_E_INVALID, "the resident wave_pool holds %lld samples, not %lld",
+                        (long long)(c->have_u16 ? c->pool_n : 0), (long long)src_samples);
+        d_src = c->pool_u16.as<uint16_t>();
+        break;
+    default:
+        return fail(WFA_E_INVALID, "unknown sample source %d", source);
+    }
+    // every slice a lane may read, and every polarity code, is checked before the launch
+    for (int64_t r = 0; r < n; ++r) {
+        const int64_t len = std::min<int64_t>(std::max<int32_t>(src_len[r], 0), wave_length);
+        if (len > 0 && (src_offset[r] < 0 || src_offset[r] + len > src_samples))
+            return fail(WFA_E_INVALID, "row %lld: slice [%lld, %lld) outside the source of %lld samples", (long long)r,
+                        (long long)src_offset[r], (long long)(src_offset[r] + len), (long long)src_samples);
+        if (polarity[r] >= n_polarity)
+            return fail(WFA_E_INVALID, "row %lld: polarity code %d, table has %d strings", (long long)r, polarity[r], n_polarity);
+    }
+    const uint64_t stride = kStHeader + 2ull * (uint64_t)wave_length;
+    const int64_t cap = std::min<int64_t>(std::max<int64_t>(batch_bytes, 1), 1ll << 30);
+    const int64_t rows_per_batch = std::min<int64_t>(n, std::max<int64_t>(1, cap / (int64_t)stride));
+    const uint64_t buf_bytes = ((uint64_t)rows_per_batch * stride + 15) / 16 * 16;
+    if (buf_bytes >= (1ull << 31)) return fail(WFA_E_LIMIT, "row of %llu bytes too long", (unsigned long long)stride);
+
+    StPackArgs a{};
+    if (source == WFA_ST_SRC_HOST) {
+        uint16_t* d;
+        if ((rc = slot<uint16_t>(c, S_F0, src_samples, &d))) return rc;
+        if ((rc = h2d_copy(c, d, src_pool, (size_t)src_samples * sizeof(uint16_t)))) return rc;
+        d_src = d;
+    }
+    int64_t *d_off, *d_ts, *d_rid;
+    int32_t *d_len, *d_dt, *d_ev;
+    double *d_bl, *d_blu;
+    int16_t *d_b, *d_ch;
+    uint8_t *d_pol, *d_out0, *d_out1;
+    uint32_t* d_tab;
+    if ((rc = upload(c, S_K0, src_offset, n, &d_off)) || (rc = upload(c, S_K1, src_len, n, &d_len)) ||
+        (rc = upload(c, S_HEIGHT, baseline, n, &d_bl)) || (rc = upload(c, S_INTEGRAL, baseline_upstream, n, &d_blu)) ||
+        (rc = upload(c, S_TS, timestamp, n, &d_ts)) || (rc = upload(c, S_RID, record_id, n, &d_rid)) ||
+        (rc = upload(c, S_DT, dt, n, &d_dt)) || (rc = upload(c, S_K2, event_length, n, &d_ev)) ||
+        (rc = upload(c, S_BOARD, board, n, &d_b)) || (rc = upload(c, S_CHAN, channel, n, &d_ch)) ||
+        (rc = upload(c, S_ID, polarity, n, &d_pol)) || (rc = upload(c, S_CNT2, polarity_table, (int64_t)n_polarity * 8, &d_tab)) ||
+        (rc = slot<uint8_t>(c, S_OUT2, (int64_t)buf_bytes, &d_out0)) ||
+        (rc = slot<uint8_t>(c, S_OUT3, n > rows_per_batch ? (int64_t)buf_bytes : 1, &d_out1)))
+        return rc;
+    a.src = d_src; a.src_off = d_off; a.src_len = d_len; a.baseline = d_bl; a.baseline_up = d_blu; a.ts = d_ts;
+    a.rid = d_rid; a.dt = d_dt; a.ev_len = d_ev; a.board = d_b; a.chan = d_ch; a.pol = d_pol; a.pol_tab = d_tab;
+    a.stride = (uint32_t)stride;
+    a.magic = (uint32_t)(0xffffffffu / (uint32_t)stride);
+    a.L = wave_length;
+    StPackLoop loop{c, a, {d_out0, d_out1}, rows_per_batch, n, 0};
+    if ((rc = loop.launch())) return rc;
+    // batch k goes down through the staging ring; batch k + 1 is packed into the other buffer meanwhile
+    for (int64_t row = 0; row < n; row += rows_per_batch) {
+        const int64_t k = row / rows_per_batch;
+        const int64_t rows = std::min(rows_per_batch, n - row);
+        if ((rc = d2h_staged(c, out + (uint64_t)row * stride, loop.buf[k & 1], (size_t)((uint64_t)rows * stride),
+                             &StPackLoop::launch_cb, &loop)))
+            return rc;
+    }
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return WFA_OK;
 }
 

@@ -495,6 +495,53 @@ class DeviceSession:
             self._res_pool = out
         return out_off, out
 
+    # ---- st_waveforms rows (wfa_st_pack) ----------------------------------------------------------------------
+    ST_SOURCES = {"host": _lib.ST_SRC_HOST, "csv": _lib.ST_SRC_CSV, "arena": _lib.ST_SRC_ARENA, "pool": _lib.ST_SRC_POOL}
+
+    def st_pack(self, wave_length: int, src_offset, src_len, columns: dict, polarity_code, polarity_table,
+                source: str = "host", src_pool: np.ndarray | None = None, src_samples: int = 0,
+                batch_bytes: int = 512 << 20) -> np.ndarray:
+        """Rows of create_record_dtype(wave_length) written on the device (wfa_st_pack).
+
+        Row r's wave = the first min(src_len[r], wave_length) samples at src_offset[r] of the source, zeros after.
+        source: "host" (src_pool, uploaded), "csv" (the samples of the last csv_decode), "arena" (the CSV arena,
+        src_samples = its filled extent) or "pool" (the resident wave_pool of src_samples samples).  columns: baseline,
+        baseline_upstream, timestamp, record_id, dt, event_length, board, channel (one value per row);
+        polarity_table: up to 8 strings, polarity_code[r] indexes it.  The rows are built in batches of at most
+        batch_bytes and copied down through the pinned staging ring."""
+        from .dtypes import create_record_dtype
+
+        L = int(wave_length)
+        dtype = create_record_dtype(L)
+        so = np.ascontiguousarray(src_offset, dtype=np.int64)
+        n = len(so)
+        out = np.zeros(n, dtype=dtype)
+        if n == 0:
+            return out
+        ln = np.ascontiguousarray(src_len, dtype=np.int32)
+        kinds = {"baseline": np.float64, "baseline_upstream": np.float64, "timestamp": np.int64, "record_id": np.int64,
+                 "dt": np.int32, "event_length": np.int32, "board": np.int16, "channel": np.int16}
+        cols = {k: np.ascontiguousarray(np.broadcast_to(np.asarray(columns[k]).astype(t, copy=False), (n,)))
+                for k, t in kinds.items()}
+        code = np.ascontiguousarray(polarity_code, dtype=np.uint8)
+        table = np.ascontiguousarray(np.asarray(list(polarity_table), dtype="U8").view(np.uint32))
+        if ln.shape != (n,) or code.shape != (n,):
+            raise ValueError("src_len and polarity_code must hold one value per row")
+        pool = None
+        if source == "host":
+            pool = np.ascontiguousarray(src_pool if src_pool is not None else np.zeros(0, np.uint16))
+            if pool.dtype == np.int16:
+                pool = pool.view(np.uint16)
+            if pool.dtype != np.uint16 or pool.ndim != 1:
+                raise ValueError("src_pool must be a flat uint16 / int16 array")
+            src_samples = pool.size
+        elif source not in self.ST_SOURCES:
+            raise ValueError(f"unknown st_pack source {source!r}")
+        _lib.check(self._lib.wfa_st_pack(
+            self._h, n, self.ST_SOURCES[source], _ptr(pool), int(src_samples), _ptr(so), _ptr(ln), L,
+            *[_ptr(cols[k]) for k in kinds], _ptr(code), _ptr(table), len(table) // 8, int(batch_bytes), _ptr(out)))
+        return out
+
     # ---- hit-table stages (device sort + scans) ------------------------------------------------------------
     @staticmethod
     def _hit_cols(timestamp, position, start, end, dt, board, channel, record_id):

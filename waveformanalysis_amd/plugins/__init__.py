@@ -3,7 +3,8 @@
 ``hip_default()`` is the packaging the reference uses for backends: a profile function
 returning plugin instances (waveform_analysis/core/plugins/profiles.py:20-62); register them
 with ``ctx.register(p, allow_override=True)`` to replace the CPU plugins of the same name.
-``hip_with_records()`` adds the records / wave_pool builders (raw files -> bundle on the GPU).
+``hip_with_records()`` adds the records / wave_pool builders (raw files -> bundle on the GPU);
+``hip_from_raw_files()`` adds st_waveforms built from the raw files on the GPU as well.
 """
 
 from .basic_features import HipBasicFeaturesPlugin
@@ -17,6 +18,7 @@ from .signal_peaks import HipSignalPeaksStreamPlugin
 from .threshold_hit import HipThresholdHitPlugin
 from .wave_pool_filtered import HipWavePoolFilteredPlugin
 from .waveform_width import HipWaveformWidthPlugin
+from .waveforms import HipWaveformsPlugin
 from .width_integral import HipWaveformWidthIntegralPlugin
 
 
@@ -34,8 +36,14 @@ def hip_with_records():
     return hip_default() + [HipRecordsPlugin(), HipWavePoolPlugin()]
 
 
+def hip_from_raw_files():
+    """hip_with_records() plus st_waveforms built from raw_files on the GPU (the root of the dense chain
+    st_waveforms -> filtered_waveforms -> hit -> waveform_width -> s1_s2)."""
+    return hip_with_records() + [HipWaveformsPlugin()]
+
+
 __all__ = ["HipWavePoolFilteredPlugin", "HipThresholdHitPlugin", "HipBasicFeaturesPlugin",
            "HipWaveformWidthIntegralPlugin", "HipHitGroupedPlugin", "HipHitFinderPlugin", "HipFilteredWaveformsPlugin",
            "HipWaveformWidthPlugin", "HipS1S2ClassifierPlugin", "HipHitMergeClustersPlugin",
            "HipHitMergePlugin", "HipHitMergedComponentsPlugin", "HipSignalPeaksStreamPlugin", "HipRecordsPlugin", "HipWavePoolPlugin",
-           "hip_default", "hip_with_records"]
+           "HipWaveformsPlugin", "hip_default", "hip_with_records", "hip_from_raw_files"]
