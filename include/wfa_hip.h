@@ -166,6 +166,10 @@ int wfa_filter_keep_output(wfa_ctx* ctx, int keep);
 /* Copy the resident float32 pool (wave_pool_filtered as built or uploaded) to the host; n_samples must match. */
 int wfa_download_pool_f32(wfa_ctx* ctx, float* out, int64_t n_samples);
 
+/* Copy samples [start, start + n) of the resident float32 pool to the host (one shard's part of a run's
+ * wave_pool_filtered, or the samples of some of its records).  0 <= start, 0 <= n, start + n <= the pool's samples. */
+int wfa_download_pool_f32_range(wfa_ctx* ctx, float* out, int64_t start, int64_t n);
+
 /* K2 wave_pool_filtered: float32 pool aligned to wave_pool, gaps 0.0
  * (reference: records.py:368-438, filtering.py:377-407).  The result stays resident as the
  * WFA_SRC_F32 pool; out may be NULL. */

@@ -48,6 +48,7 @@ SIGNATURES = {
     "wfa_baseline_mean": (_int, [_p, _i32, _i32, _int, _p]),
     "wfa_filter_keep_output": (_int, [_p, _int]),
     "wfa_download_pool_f32": (_int, [_p, _p, _i64]),
+    "wfa_download_pool_f32_range": (_int, [_p, _p, _i64, _i64]),
     "wfa_savgol": (_int, [_p, _p]),
     "wfa_sosfiltfilt": (_int, [_p, _int, _p, _p, _i32, _p]),
     "wfa_threshold_hits_count": (_int, [_p, _int, _i32, _i32, _i32, C.POINTER(_i64)]),

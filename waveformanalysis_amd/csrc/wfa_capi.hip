@@ -1122,6 +1122,21 @@ int wfa_download_pool_f32(wfa_ctx* c, float* out, int64_t n) {
     return WFA_OK;
 }
 
+int wfa_download_pool_f32_range(wfa_ctx* c, float* out, int64_t start, int64_t n) {
+    int rc = use_device(c);
+    if (rc) return rc;
+    if (!c->have_f32) return fail(WFA_E_STATE, "no float32 pool is resident");
+    if (start < 0 || n < 0 || start > c->pool_n || n > c->pool_n - start)
+        return fail(WFA_E_INVALID, "samples [%lld, %lld + %lld) are outside the pool of %lld", (long long)start,
+                    (long long)start, (long long)n, (long long)c->pool_n);
+    if (n == 0) return WFA_OK;
+    if (!out) return fail(WFA_E_INVALID, "out is null");
+    WFA_HIP_CHECK(hipMemcpyAsync(out, c->pool_f32.as<float>() + start, (size_t)n * sizeof(float),
+                                 hipMemcpyDeviceToHost, c->stream));
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return WFA_OK;
+}
+
 int wfa_savgol(wfa_ctx* c, float* out) {
     int rc = use_device(c);
     if (rc) return rc;

@@ -124,6 +124,16 @@ class DeviceSession:
             self._res_filtered = pool_f32
         return True
 
+    def note_filtered(self, pool_f32: np.ndarray) -> None:
+        """The device float32 pool, just written by this session's filters, is what the host array `pool_f32` holds (a
+        shard's slice of the wave_pool_filtered it returned): ensure_filtered_pool(pool_f32) uploads nothing from now on
+        until a call replaces a device pool."""
+        self._res_filtered = pool_f32
+
+    def holds_filtered(self, pool_f32: np.ndarray) -> bool:
+        """True while the device float32 pool still holds this very array object (the `is` test of ensure_filtered_pool)."""
+        return self._res_filtered is pool_f32
+
     def __enter__(self):
         return self
 
@@ -267,10 +277,19 @@ class DeviceSession:
         """keep=True: the next savgol/sosfiltfilt calls write only their records' slices into the output."""
         _lib.check(self._lib.wfa_filter_keep_output(self._h, int(bool(keep))))
 
-    def download_filtered(self) -> np.ndarray:
-        """The resident float32 pool (after one or more filter calls)."""
-        out = np.empty(self.n_samples, dtype=np.float32)
-        _lib.check(self._lib.wfa_download_pool_f32(self._h, _ptr(out), out.size))
+    def download_filtered(self, out: np.ndarray | None = None, start: int = 0) -> np.ndarray:
+        """The resident float32 pool (after one or more filter calls).  With `out` (a writeable contiguous float32 array,
+        e.g. a slice of a run's wave_pool_filtered) or start > 0: samples [start, start + len(out)) of it, into `out`
+        (a new array of the samples from `start` to the end when out is None)."""
+        start = int(start)
+        if out is None and start == 0:
+            out = np.empty(self.n_samples, dtype=np.float32)
+            _lib.check(self._lib.wfa_download_pool_f32(self._h, _ptr(out), out.size))
+            return out
+        if out is None:
+            out = np.empty(max(self.n_samples - start, 0), dtype=np.float32)
+        _check_out(out, np.dtype(np.float32), len(out) if isinstance(out, np.ndarray) and out.ndim == 1 else -1)
+        _lib.check(self._lib.wfa_download_pool_f32_range(self._h, _ptr(out), start, len(out)))
         return out
 
     def savgol(self, download: bool = True) -> np.ndarray | None:
@@ -332,10 +351,11 @@ class DeviceSession:
     def find_peaks(self, source: int = _lib.SRC_F32, use_derivative: bool = True, height: float = 30.0,
                    distance: int = 2, prominence: float = 0.7, width: float = 4, threshold: float | None = None,
                    height_method: str = "minmax", height_window_extension: int = 4,
-                   dense_rows: bool | int = False) -> np.ndarray:
+                   dense_rows: bool | int = False, download: bool = True) -> np.ndarray | int:
         """find_peaks-based hit detector (HitFinderPlugin) -> HIT_DTYPE rows.  dense_rows: True / 1 = the dense branch
         (WFA_PEAK_SIGNAL_ROWS), the uploaded records describe the rows of an st_waveforms / filtered_waveforms array;
-        2 = the streaming detector's float64 rows (WFA_PEAK_SIGNAL_ROWS_F64)."""
+        2 = the streaming detector's float64 rows (WFA_PEAK_SIGNAL_ROWS_F64).  download=False: the row count, rows left
+        on the device for download_peaks(out)."""
         if height_method not in ("minmax", "diff"):
             raise ValueError(f"不支持的峰高计算方法: {height_method}")  # peak_finding.py:612
         n = C.c_int64(0)
@@ -344,9 +364,17 @@ class DeviceSession:
             int(threshold is not None),
             float(threshold or 0.0), int(distance), float(prominence), float(width),
             1 if height_method == "diff" else 0, int(height_window_extension), C.byref(n)))
+        if not download:
+            return int(n.value)
         out = np.empty(int(n.value), dtype=HIT_DTYPE)
         _lib.check(self._lib.wfa_find_peaks_fill(self._h, _ptr(out), int(n.value)))
         return out
+
+    def download_peaks(self, out: np.ndarray) -> None:
+        """Rows of the last find_peaks pass (run with download=False) straight into `out`: a contiguous HIT_DTYPE array of
+        exactly the pass's row count, e.g. one shard's slice of a run's table."""
+        _check_out(out, HIT_DTYPE, len(out))
+        _lib.check(self._lib.wfa_find_peaks_fill(self._h, _ptr(out), len(out)))
 
     def find_hits_legacy(self, source: int, n_rows: int, row_length: int, baselines: np.ndarray,
                          threshold: float) -> tuple[np.ndarray, np.ndarray]:

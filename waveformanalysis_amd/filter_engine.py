@@ -82,8 +82,10 @@ def plan_filter_groups(context: Any, plugin: Any, run_id: str, boards: np.ndarra
     return list(by_key.items())
 
 
-def run_filter_groups(sess, records: np.ndarray, groups) -> np.ndarray:
-    """Filter every group into the session's float32 pool and return it (host copy)."""
+def run_filter_groups(sess, records: np.ndarray, groups, download: bool = True) -> np.ndarray | None:
+    """Filter every group into the session's float32 pool and return it (host copy; download=False: left on the
+    device, None returned).  Groups run in list order: where records of two groups share samples the later group's
+    values stay."""
     sess.filter_keep_output(False)
     try:
         for k, (key, mask) in enumerate(groups):
@@ -96,6 +98,6 @@ def run_filter_groups(sess, records: np.ndarray, groups) -> np.ndarray:
             else:
                 sess.set_sg_plan(key[1], key[2])
                 sess.savgol(download=False)
-        return sess.download_filtered()
+        return sess.download_filtered() if download else None
     finally:
         sess.filter_keep_output(False)

@@ -96,6 +96,52 @@ def _copy_rows(rows: np.ndarray) -> np.ndarray:
     return rows.copy()
 
 
+def _shard_inputs(records: np.ndarray, shards: Sequence[RecordShard], per_record: Sequence) -> Callable:
+    """k -> (shard, slice start, records_k with wave_offset shifted to the slice, per-record arguments of shard k)."""
+    n = len(records)
+    sliced = [isinstance(a, np.ndarray) and a.ndim == 1 and len(a) == n for a in per_record]
+
+    def inputs(k):
+        sh = shards[k]
+        lo = sh.span_start - sh.span_start % POOL_ALIGN
+        rec = _copy_rows(records[sh.r0:sh.r1])
+        if lo:
+            rec["wave_offset"] -= lo
+        extra = [a[sh.r0:sh.r1] if s else a for a, s in zip(per_record, sliced)]
+        return sh, lo, rec, extra
+
+    return inputs
+
+
+def _own_samples(records: np.ndarray, shards: Sequence[RecordShard]) -> tuple[list, bool]:
+    """([(starts, ends)] per shard: the samples of its records as sorted disjoint runs [start, end), adjacent records
+    joined), and whether a sample belongs to records of two shards."""
+    off = np.ascontiguousarray(records["wave_offset"]).astype(np.int64, copy=False) if len(records) else np.zeros(0, np.int64)
+    ln = np.ascontiguousarray(records["event_length"]).astype(np.int64, copy=False) if len(records) else np.zeros(0, np.int64)
+    runs = []
+    for sh in shards:
+        o, n_k = off[sh.r0:sh.r1], ln[sh.r0:sh.r1]
+        has = n_k > 0
+        if not has.all():
+            o, n_k = o[has], n_k[has]
+        if len(o) > 1 and np.any(o[1:] < o[:-1]):
+            order = np.argsort(o, kind="stable")
+            o, n_k = o[order], n_k[order]
+        e = o + n_k
+        if len(o) == 0:
+            runs.append((o, e))
+            continue
+        reach = np.maximum.accumulate(e)
+        first = np.flatnonzero(np.concatenate(([True], o[1:] > reach[:-1])))  # a run starts after a gap
+        runs.append((o[first], np.maximum.reduceat(e, first)))
+    starts = np.concatenate([r[0] for r in runs]) if runs else np.zeros(0, np.int64)
+    ends = np.concatenate([r[1] for r in runs]) if runs else np.zeros(0, np.int64)
+    order = np.argsort(starts, kind="stable")
+    starts, ends = starts[order], ends[order]
+    shared = len(starts) > 1 and bool(np.any(starts[1:] < np.maximum.accumulate(ends)[:-1]))
+    return runs, shared
+
+
 class ShardError(RuntimeError):
     """A shard's worker raised; `device_id` and `shard` name where, `__cause__` is the worker's exception."""
 
@@ -127,6 +173,7 @@ class ShardedRun:
         self.sessions: list = []
         self._workers = [ThreadPoolExecutor(max_workers=1, thread_name_prefix=f"wfa-shard{k}") for k in range(len(ids))]
         self._resident: list[tuple | None] = [None] * len(ids)  # (pool, lo, hi, view) the session holds
+        self._filtered: list[tuple | None] = [None] * len(ids)  # (output, lo, hi, view) its filters wrote (run_pool)
         self._lock = threading.Lock()  # one run at a time: the sessions hold one run's rows
         self.closed = False
         futures = [w.submit(self._factory, d) for w, d in zip(self._workers, ids)]
@@ -168,7 +215,7 @@ class ShardedRun:
                          self.device_ids[k], k) from exc
 
     def _replace_session(self, k: int) -> None:
-        self._resident[k] = None
+        self._resident[k] = self._filtered[k] = None
         old = self.sessions[k]
 
         def swap():
@@ -185,6 +232,10 @@ class ShardedRun:
             self.close()
 
     def _ensure_slice(self, k: int, sess, pool: np.ndarray, lo: int, hi: int, cacheable: bool) -> None:
+        f32 = self._filtered[k]
+        if cacheable and f32 is not None and f32[0] is pool and f32[1] == lo and f32[2] == hi \
+                and sess.holds_filtered(f32[3]):
+            return  # the slice of a run_pool output its own filters left on the device: the float32 source reads it
         tag = self._resident[k]
         if cacheable and tag is not None and tag[0] is pool and tag[1] == lo and tag[2] == hi:
             view = tag[3]  # the object the session remembers: its own `is` test decides
@@ -211,16 +262,7 @@ class ShardedRun:
         row_dtype = np.dtype(row_dtype)
         n = len(records)
         shards = split_records(records, self.n_shards)
-        args = [a if isinstance(a, np.ndarray) and a.ndim == 1 and len(a) == n else None for a in per_record]
-
-        def shard_inputs(k):
-            sh = shards[k]
-            lo = sh.span_start - sh.span_start % POOL_ALIGN
-            rec = _copy_rows(records[sh.r0:sh.r1])
-            if lo:
-                rec["wave_offset"] -= lo
-            extra = [a[sh.r0:sh.r1] if s is not None else a for a, s in zip(per_record, args)]
-            return sh, lo, rec, extra
+        shard_inputs = _shard_inputs(records, shards, per_record)
 
         with self._lock:
             busy = [k for k in range(self.n_shards) if shards[k].n_records > 0]
@@ -254,6 +296,71 @@ class ShardedRun:
                          [k for k in busy if rows[k] > 0])
             return out
 
+    def run_pool(self, records: np.ndarray, pool: np.ndarray, task: Callable, *, per_record: Sequence = (),
+                 cacheable: bool = True) -> np.ndarray:
+        """A float32 array of len(pool) samples (wave_pool_filtered): 0.0 except the samples of the records, each written
+        by the shard that holds its record.
+
+        task(sess, records_k, *per_record_k) runs on worker k after the shard's pool slice is resident (records and
+        per-record arrays sliced and shifted as in run()) and leaves the shard's float32 pool on the device, 0.0 outside
+        its records.  The worker then downloads the samples of its OWN records into the output: its whole span in one
+        copy when no other shard's record lies inside it (the builders' layout), else one copy per run of its records'
+        samples.  A sample two shards' records share (hand-made layouts: overlapping records) has one value for the
+        order the writes happen in, so when any sample is shared the whole call runs on the first shard alone, pool
+        and records as they are -- what one device computes.
+
+        With cacheable, each shard's float32 slice stays tagged as resident, keyed on the returned array object and the
+        slice bounds: a later run() on that array with the same records (same split) uploads nothing.  Of that slice the
+        device holds the samples of the shard's own records (0.0 elsewhere); a per-record pass reads no others.
+        A failure raises ShardError and returns no table."""
+        if self.closed:
+            raise RuntimeError("ShardedRun is closed")
+        out = np.zeros(len(pool), dtype=np.float32)
+        shards = split_records(records, self.n_shards)
+        runs, shared = _own_samples(records, shards)
+        with self._lock:
+            self._filtered = [None] * self.n_shards
+
+            def keep(k, sess, lo, hi):
+                if cacheable:
+                    view = out[lo:hi]
+                    sess.note_filtered(view)
+                    self._filtered[k] = (out, lo, hi, view)
+
+            if shared:
+                def alone(k):
+                    sess = self.sessions[k]
+                    self._ensure_slice(k, sess, pool, 0, len(pool), cacheable)
+                    task(sess, records, *per_record)
+                    sess.download_filtered(out)
+                    keep(k, sess, 0, len(pool))
+
+                self._on_all(alone, [0])
+                return out
+
+            shard_inputs = _shard_inputs(records, shards, per_record)
+            starts = np.concatenate([r[0] for r in runs])
+            ends = np.concatenate([r[1] for r in runs])
+            order = np.argsort(starts, kind="stable")
+            starts, ends = starts[order], ends[order]  # disjoint: sorted by start is sorted by end
+
+            def one(k):
+                sh, lo, rec, extra = shard_inputs(k)
+                sess = self.sessions[k]
+                self._ensure_slice(k, sess, pool, lo, sh.span_end, cacheable)
+                task(sess, rec, *extra)
+                own0, own1 = runs[k]
+                inside = int(np.searchsorted(starts, sh.span_end, "left") - np.searchsorted(ends, sh.span_start, "right"))
+                if inside == len(own0):  # nothing of another shard in the span: its gaps are 0.0 on the device too
+                    sess.download_filtered(out[sh.span_start:sh.span_end], start=sh.span_start - lo)
+                else:
+                    for a, b in zip(own0.tolist(), own1.tolist()):
+                        sess.download_filtered(out[a:b], start=a - lo)
+                keep(k, sess, lo, sh.span_end)
+
+            self._on_all(one, [k for k in range(self.n_shards) if shards[k].n_records > 0])
+            return out
+
     # -- lifetime --------------------------------------------------------------------------------------------------
     def release_scratch(self) -> None:
         """DeviceSession.release_scratch on every session (the plugins' cleanup hook)."""
@@ -265,6 +372,7 @@ class ShardedRun:
             return
         self.closed = True
         self._resident = [None] * self.n_shards
+        self._filtered = [None] * self.n_shards
         for k, w in enumerate(self._workers):
             s = self.sessions[k] if k < len(self.sessions) else None
             try:

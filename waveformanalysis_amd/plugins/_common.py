@@ -216,8 +216,10 @@ def invalidate_residency(context: Any = None) -> None:
 
 # ---- several devices from one process: the `devices` option of the per-record plugins -------------------------------
 DEVICES_HELP = ("None: one device (the calling thread's session); a list of device ids (repeats allowed) or 'all': the "
-                "records route runs on those devices, one contiguous record range each, output identical.  The dense "
-                "routes (st_waveforms / filtered_waveforms) stay on one device whatever this says.")
+                "records route runs on those devices, one contiguous record range each, output identical "
+                "(wave_pool_filtered: each device fills the samples of its records, and its slice stays resident for "
+                "the use_filtered plugins and hit).  The dense routes (st_waveforms / filtered_waveforms) stay on one "
+                "device whatever this says.")
 
 
 def sharded_run(context: Any, devices) -> "multidevice.ShardedRun":

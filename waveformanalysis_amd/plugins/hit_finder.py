@@ -48,6 +48,7 @@ class HipHitFinderPlugin(K.HipPlugin):
         "n_workers": Option(default=0, type=int, help="ignored"),
         "chunk_size": Option(default=1024, type=int, help="ignored"),
         "parallel_min_events": Option(default=20480, type=int, help="ignored"),
+        "devices": Option(default=None, track=False, help=K.DEVICES_HELP),
     }
 
     def resolve_depends_on(self, context: Any, run_id: str | None = None) -> list[str]:
@@ -100,6 +101,16 @@ class HipHitFinderPlugin(K.HipPlugin):
             if pool.dtype != np.uint16:
                 raise ValueError(f"wave_pool must be uint16, got {pool.dtype}")
             source = K.SRC_RAW
+        devices = context.get_config(self, "devices")
+        if devices is not None:
+            def task(sess, rec_k, out=None):
+                sess.upload_records(rec_k, np.zeros(len(rec_k), dtype=np.float64))
+                return sess.find_peaks(source, download=False, **peak_kw)
+
+            # rows carry record_id and timestamp, no record index: nothing to shift; shards in order = record order
+            return K.sharded_run(context, devices).run(rec, pool, HIT_DTYPE, task,
+                                                       fetch=lambda sess, out: sess.download_peaks(out),
+                                                       cacheable=not converted)
         sess = K.resident_session(context, pool, cacheable=not converted)
         sess.upload_records(rec, np.zeros(len(rec), dtype=np.float64))
         return sess.find_peaks(source, **peak_kw)

@@ -33,6 +33,7 @@ class HipWavePoolFilteredPlugin(K.HipPlugin):
         "max_workers": Option(default=None, type=int, help="ignored by the HIP backend", track=False),
         "batch_size": Option(default=0, type=int, help="ignored by the HIP backend (must be >= 0)"),
         "channel_config": Option(default=None, type=dict, help="per (board, channel) overrides"),
+        "devices": Option(default=None, track=False, help=K.DEVICES_HELP),
     }
 
     def compute(self, context: Any, run_id: str, **kwargs) -> np.ndarray:
@@ -66,10 +67,41 @@ class HipWavePoolFilteredPlugin(K.HipPlugin):
             i = int(np.flatnonzero(bad)[0])
             raise ValueError("wave_pool_filtered found out-of-bounds wave slice "
                              f"(offset={int(off[i])}, length={int(length[i])}, wave_pool_size={len(wave_pool)})")
+        devices = context.get_config(self, "devices")
+        if devices is not None:
+            return _sharded(context, devices, records, wave_pool, groups)
         sess = K.resident_session(context, wave_pool if isinstance(wave_pool, np.ndarray) else np.asarray(wave_pool),
                                   cacheable=isinstance(wave_pool, np.ndarray))
         out = run_filter_groups(sess, _view_records(records), groups)  # (the filters drop the float32 tag themselves)
         return out
+
+
+def _sharded(context: Any, devices, records: np.ndarray, wave_pool: np.ndarray, groups) -> np.ndarray:
+    """The `devices` route: ShardedRun.run_pool.  Every shard uploads its raw slice, runs the filter groups on its own
+    records in the order one device runs them (SG, Butterworth, per-channel channel_config groups) and downloads the
+    samples of its own records into its part of the one zero-filled output; gaps stay 0.0 (records.py:382).  Where
+    records of two shards share samples (hand-made layouts), the later write wins on one device (records.py:434-436)
+    and the outcome depends on the order of the writes: run_pool then runs the whole call on the first device, so the
+    output equals devices=None for every sample.  The shards' float32 slices stay resident, keyed on the returned array:
+    hit_threshold / basic_features / waveform_width_integral (use_filtered=True) and hit on it with the same devices
+    upload no pool."""
+    rec = _view_records(records)
+    group_of = np.full(len(rec), -1, dtype=np.int32)
+    for g, (_key, mask) in enumerate(groups):
+        group_of[mask] = g
+    length = rec["event_length"].astype(np.int64)
+    off = rec["wave_offset"].astype(np.int64)
+    idle = (length <= 0) & ((off < 0) | (off > len(wave_pool)))  # write nothing; their offsets would widen a shard's span
+    if np.any(idle):
+        rec, group_of = rec[~idle], group_of[~idle]
+    keys = [key for key, _mask in groups]
+
+    def task(sess, rec_k, group_k):
+        mine = [(key, group_k == g) for g, key in enumerate(keys)]
+        mine = [(key, m) for key, m in mine if m.any()] or [(keys[0], np.zeros(len(rec_k), dtype=bool))]
+        run_filter_groups(sess, rec_k, mine, download=False)
+
+    return K.sharded_run(context, devices).run_pool(rec, wave_pool, task, per_record=(group_of,))
 
 
 def _view_records(records: np.ndarray) -> np.ndarray:
