@@ -75,6 +75,9 @@ int wfa_sync(wfa_ctx* ctx);
  * This is what Plugin.cleanup(context) of the HIP plugins calls (core/plugins/core/base.py:608-613: "releasing
  * resources" after compute()).  freed_bytes (nullable) receives the capacity given back. */
 int wfa_release_scratch(wfa_ctx* ctx, int64_t* freed_bytes);
+/* Capacity (bytes) of that same scratch as it stands: what wfa_release_scratch would give back now.  Read only; it
+ * bounds the device memory a pass holds beyond its inputs and outputs (e.g. the hit-table slots of a grouping pass). */
+int wfa_scratch_bytes(wfa_ctx* ctx, int64_t* bytes);
 /* Choice between code paths that produce identical results (no counterpart in the reference: its plugins have one
  * code path).  For tests, which compare the paths with each other, and for measurement; a caller never needs it.
  * Names (any other name: WFA_E_INVALID):

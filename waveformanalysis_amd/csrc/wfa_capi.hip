@@ -770,6 +770,24 @@ void wfa_ctx_destroy(wfa_ctx* c) {
     delete c;
 }
 
+// the buffers wfa_release_scratch gives back: the hit-table slots and the per-pass scratch
+static std::vector<DevBuf*> scratch_bufs(wfa_ctx* c) {
+    std::vector<DevBuf*> bufs = {&c->bitmap, &c->hit_tmp, &c->bw_scratch, &c->peak_cand_n, &c->peak_cand_pos, &c->peak_cand_val,
+                                 &c->peak_slot_pos, &c->peak_slot_val, &c->peak_cand_state, &c->peak_cand_rec, &c->peak_accept,
+                                 &c->peak_ips, &c->peak_row_start, &c->wh_pos, &c->wh_row, &c->wh_valid, &c->fw_ties, &c->run_ev,
+                                 &c->shadow_pool, &c->shadow_off};
+    for (DevBuf& b : c->ht) bufs.push_back(&b);
+    return bufs;
+}
+
+int wfa_scratch_bytes(wfa_ctx* c, int64_t* bytes) {
+    if (!c || !bytes) return fail(WFA_E_INVALID, "null argument");
+    int64_t held = 0;
+    for (DevBuf* b : scratch_bufs(c)) held += (int64_t)b->cap;
+    *bytes = held;
+    return WFA_OK;
+}
+
 int wfa_release_scratch(wfa_ctx* c, int64_t* freed_bytes) {
     if (!c) return fail(WFA_E_INVALID, "null context");
     WFA_HIP_CHECK(hipSetDevice(c->device));
@@ -779,13 +797,8 @@ int wfa_release_scratch(wfa_ctx* c, int64_t* freed_bytes) {
     // the CSV sample arena (source of wfa_csv_arena_gather), the pinned staging ring and the small control blocks.  The
     // samples of the last wfa_csv_decode_fill live in a scratch slot: they go, and wfa_pool_gather(src_pool = NULL) refuses
     // until the next decode.
-    DevBuf* bufs[] = {&c->bitmap, &c->hit_tmp, &c->bw_scratch, &c->peak_cand_n, &c->peak_cand_pos, &c->peak_cand_val,
-                      &c->peak_slot_pos, &c->peak_slot_val, &c->peak_cand_state, &c->peak_cand_rec, &c->peak_accept,
-                      &c->peak_ips, &c->peak_row_start, &c->wh_pos, &c->wh_row, &c->wh_valid, &c->fw_ties, &c->run_ev,
-                      &c->shadow_pool, &c->shadow_off};
     int64_t freed = 0;
-    for (DevBuf* b : bufs) { freed += (int64_t)b->cap; b->release(); }
-    for (DevBuf& b : c->ht) { freed += (int64_t)b.cap; b.release(); }  // (a count pass without its fill is void after this)
+    for (DevBuf* b : scratch_bufs(c)) { freed += (int64_t)b->cap; b->release(); }  // (a count pass without its fill is void after this)
     c->ht_n = -1;
     c->ht_perm = nullptr;
     c->csv_rows = -1;

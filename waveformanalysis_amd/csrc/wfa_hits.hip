@@ -327,8 +327,10 @@ __global__ void k_event_minmax(int64_t n_events, const int64_t* __restrict__ eve
 // ---- legacy fixed-window grouping (group_multi_channel_hits, event_grouping.py:98-283, 475-525) ----------------------
 // After a stable sort by timestamp a cluster takes every hit within `window` of its FIRST hit: the boundaries are the
 // chain 0 -> next[0] -> next[next[0]] -> ... with next[i] = upper_bound(ts, ts[i] + window), compared in float64 like
-// numpy's searchsorted of an int64 column against a float64 needle.  The chain is marked by pointer jumping: with
-// J_k = next^(2^k), after the levels K-1 .. k the marks are { next^m(0) : 2^k | m }; a level is one launch over all hits.
+// numpy's searchsorted of an int64 column against a float64 needle.  The chain is marked by pointer jumping, bottom up:
+// with J_k = next^(2^k) and the marks {next^m(0) : m < 2^k} before level k, marking J_k of every marked hit gives
+// {next^m(0) : m < 2^(k+1)}.  A level reads J_k and writes J_(k+1) in the same launch, so two (n+1)-entry levels are all
+// the jump storage there is, whatever n; once J_k[0] == n every chain hit is marked and the later launches return at once.
 __global__ void k_mc_keys(int64_t n, const int64_t* __restrict__ ts, const int64_t* __restrict__ ch,
                           uint64_t* __restrict__ k_ts, uint64_t* __restrict__ k_ch) {
     const int64_t i = (int64_t)blockIdx.x * kTB + threadIdx.x;
@@ -352,16 +354,17 @@ __global__ void k_mc_next(int64_t n, const double* __restrict__ ts_f, double win
     }
     nxt[i] = (int32_t)lo;
 }
-__global__ void k_mc_jump(int64_t n, const int32_t* __restrict__ j_in, int32_t* __restrict__ j_out) {
+__global__ void k_mc_mark_jump(int64_t n, const int32_t* __restrict__ j_in, int32_t* __restrict__ j_out,
+                               int64_t* __restrict__ mark) {
     const int64_t i = (int64_t)blockIdx.x * kTB + threadIdx.x;
-    if (i <= n) j_out[i] = j_in[j_in[i]];
-}
-__global__ void k_mc_mark(int64_t n, const int32_t* __restrict__ j_k, int64_t* __restrict__ mark) {
-    const int64_t i = (int64_t)blockIdx.x * kTB + threadIdx.x;
-    if (i < n && mark[i]) {
-        const int32_t t = j_k[i];
-        if (t < n) mark[t] = 1;  // (a mark set during this launch belongs to the level's result as well)
+    if (i > n) return;
+    if (j_in[0] == n) {  // the chain from hit 0 ends within 2^k steps: marked already; pass the end on to the next level
+        if (i == 0) j_out[0] = (int32_t)n;
+        return;
     }
+    const int32_t t = j_in[i];  // <= n, and j_in[n] == n
+    j_out[i] = j_in[t];
+    if (i < n && t < n && mark[i]) mark[t] = 1;  // (a mark set during this launch is a chain hit as well)
 }
 __global__ void k_mc_bounds(int64_t n, const int64_t* __restrict__ mark, const int64_t* __restrict__ incl, int64_t n_events,
                             int64_t* __restrict__ bounds) {
@@ -949,11 +952,11 @@ int wfa_group_multi_channel_count(wfa_ctx* c, int64_t n, const int64_t* timestam
     int64_t *ts, *ch, *mark, *incl;
     uint64_t *k_ts, *k_ch, *k_ev;
     double* ts_f;
-    int32_t* jump;
+    int32_t* jump;  // two levels, J_k and J_(k+1), used in turn
     if ((rc = upload(c, S_TS, timestamp, n, &ts)) || (rc = upload(c, S_POS, channel, n, &ch)) ||
         (rc = slot(c, S_K0, n, &k_ts)) || (rc = slot(c, S_K1, n, &k_ch)) || (rc = slot(c, S_K2, n, &k_ev)) ||
         (rc = slot(c, S_ABS0, n, &ts_f)) || (rc = slot(c, S_FLAG, n, &mark)) || (rc = slot(c, S_ID, n, &incl)) ||
-        (rc = slot(c, S_OUT3, (int64_t)levels * (n + 1), &jump)))
+        (rc = slot(c, S_OUT3, 2 * (n + 1), &jump)))
         return rc;
     LaunchTimer t(c);
     hipLaunchKernelGGL(k_mc_keys, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, ts, ch, k_ts, k_ch);
@@ -964,14 +967,12 @@ int wfa_group_multi_channel_count(wfa_ctx* c, int64_t n, const int64_t* timestam
     }
     hipLaunchKernelGGL(k_mc_sorted_ts, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, ts, perm, ts_f);
     hipLaunchKernelGGL(k_mc_next, dim3(blocks_for(n + 1)), dim3(kTB), 0, c->stream, n, ts_f, time_window_ps, jump);
-    for (int k = 1; k < levels; ++k)
-        hipLaunchKernelGGL(k_mc_jump, dim3(blocks_for(n + 1)), dim3(kTB), 0, c->stream, n, jump + (int64_t)(k - 1) * (n + 1),
-                           jump + (int64_t)k * (n + 1));
     WFA_HIP_CHECK(hipMemsetAsync(mark, 0, (size_t)n * sizeof(int64_t), c->stream));
     const int64_t one = 1;
     WFA_HIP_CHECK(hipMemcpyAsync(mark, &one, sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    for (int k = levels - 1; k >= 0; --k)
-        hipLaunchKernelGGL(k_mc_mark, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, jump + (int64_t)k * (n + 1), mark);
+    for (int k = 0; k < levels; ++k)
+        hipLaunchKernelGGL(k_mc_mark_jump, dim3(blocks_for(n + 1)), dim3(kTB), 0, c->stream, n, jump + (int64_t)(k & 1) * (n + 1),
+                           jump + (int64_t)((k + 1) & 1) * (n + 1), mark);
     size_t tb = 0;
     WFA_HIP_CHECK(rocprim::inclusive_scan(nullptr, tb, mark, incl, (size_t)n, rocprim::plus<int64_t>(), c->stream));
     if ((rc = c->ht[S_CUB].ensure(tb))) return rc;

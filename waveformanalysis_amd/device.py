@@ -723,6 +723,12 @@ class DeviceSession:
         _lib.check(self._lib.wfa_release_scratch(self._h, C.byref(freed)))
         return int(freed.value)
 
+    def scratch_bytes(self) -> int:
+        """Bytes release_scratch() would give back now (wfa_scratch_bytes); nothing is freed."""
+        held = C.c_int64(0)
+        _lib.check(self._lib.wfa_scratch_bytes(self._h, C.byref(held)))
+        return int(held.value)
+
     def last_h2d_rate(self) -> float:
         """GB/s of the last large upload through the pinned staging ring."""
         v = C.c_double(0.0)

@@ -215,30 +215,12 @@ def group_multi_channel_hits(df, time_window_ns: float, use_numba: bool = True, 
     (`_group_multi_channel_order_host`), which is also what the device result is tested against."""
     import pandas as pd
 
-    if not time_window_ns >= 0:  # (the reference's boundary loop does not terminate for a negative window)
-        raise ValueError("time_window_ns must be >= 0")
-    time_window_ps = time_window_ns * 1e3
-    area_col = "area" if "area" in df.columns else "charge"
-    height_col = "height" if "height" in df.columns else "peak"
-    if area_col not in df.columns or height_col not in df.columns:
-        raise KeyError("df must contain area/height (or charge/peak) columns")
-    n = len(df)
-    if n == 0:
+    grouped = group_multi_channel_order(df, time_window_ns, session)
+    if grouped is None:
         return pd.DataFrame(columns=MULTI_CHANNEL_COLUMNS)
-    ts_in = df["timestamp"].to_numpy()
-    ch_in = df["channel"].to_numpy()
-    on_device = session is not False and ts_in.dtype.kind in "iu" and ch_in.dtype.kind in "iu" and \
-        ts_in.dtype != np.uint64 and ch_in.dtype != np.uint64
-    if on_device:
-        if session is None:
-            from .device import default_pool
-
-            session = default_pool().session()
-        order, bounds = session.group_multi_channel(ts_in, ch_in, float(time_window_ps))
-    else:
-        order, bounds = _group_multi_channel_order_host(ts_in, ch_in, time_window_ps)
+    order, bounds, ts_in, ch_in, area_in, height_in = grouped
     ts_o, ch_o = ts_in[order], ch_in[order]
-    ar_o, he_o = df[area_col].to_numpy()[order], df[height_col].to_numpy()[order]
+    ar_o, he_o = area_in[order], height_in[order]
     n_events = len(bounds) - 1
     starts, ends = bounds[:-1], bounds[1:]
     t_min = ts_o[starts].astype(np.int64)       # the reference takes the first / last row AFTER the channel sort
@@ -257,6 +239,35 @@ def group_multi_channel_hits(df, time_window_ns: float, use_numba: bool = True, 
     })
 
 
+def group_multi_channel_order(df, time_window_ns: float, session=None):
+    """The grouping of group_multi_channel_hits without the frame: (order, bounds, timestamp, channel, area, height)
+    with the four input columns as numpy arrays and event e = input rows order[bounds[e]:bounds[e + 1]]; None for an
+    empty df.  Same rules for the device and the host route (`session=False`) as group_multi_channel_hits."""
+    if not time_window_ns >= 0:  # (the reference's boundary loop does not terminate for a negative window)
+        raise ValueError("time_window_ns must be >= 0")
+    time_window_ps = time_window_ns * 1e3
+    area_col = "area" if "area" in df.columns else "charge"
+    height_col = "height" if "height" in df.columns else "peak"
+    if area_col not in df.columns or height_col not in df.columns:
+        raise KeyError("df must contain area/height (or charge/peak) columns")
+    n = len(df)
+    if n == 0:
+        return None
+    ts_in = df["timestamp"].to_numpy()
+    ch_in = df["channel"].to_numpy()
+    on_device = session is not False and ts_in.dtype.kind in "iu" and ch_in.dtype.kind in "iu" and \
+        ts_in.dtype != np.uint64 and ch_in.dtype != np.uint64
+    if on_device:
+        if session is None:
+            from .device import default_pool
+
+            session = default_pool().session()
+        order, bounds = session.group_multi_channel(ts_in, ch_in, float(time_window_ps))
+    else:
+        order, bounds = _group_multi_channel_order_host(ts_in, ch_in, time_window_ps)
+    return order, bounds, ts_in, ch_in, df[area_col].to_numpy(), df[height_col].to_numpy()
+
+
 def _group_multi_channel_order_host(ts_in: np.ndarray, ch_in: np.ndarray, time_window_ps: float):
     """(order, bounds) of group_multi_channel_hits with numpy: stable sort by timestamp, window chain, stable sort by
     (event, channel)."""
@@ -271,4 +282,5 @@ def _group_multi_channel_order_host(ts_in: np.ndarray, ch_in: np.ndarray, time_w
 
 
 __all__ = ["group_hit_windows", "group_hit_windows_flat", "EVENT_COLUMNS", "find_hits", "find_cluster_boundaries",
-           "group_multi_channel_hits", "MULTI_CHANNEL_COLUMNS"]
+           "group_multi_channel_hits", "group_multi_channel_order",
+           "MULTI_CHANNEL_COLUMNS"]

@@ -4,10 +4,14 @@
 returning plugin instances (waveform_analysis/core/plugins/profiles.py:20-62); register them
 with ``ctx.register(p, allow_override=True)`` to replace the CPU plugins of the same name.
 ``hip_with_records()`` adds the records / wave_pool builders (raw files -> bundle on the GPU);
-``hip_from_raw_files()`` adds st_waveforms built from the raw files on the GPU as well.
+``hip_from_raw_files()`` adds st_waveforms built from the raw files on the GPU as well;
+``hip_full()`` adds the tabular and event stages (df, df_events, df_paired) on top, the counterpart of the
+reference's ``cpu_default()``.
 """
 
 from .basic_features import HipBasicFeaturesPlugin
+from .dataframe import HipDataFramePlugin
+from .event_analysis import HipGroupedEventsPlugin, HipPairedEventsPlugin
 from .filtered_waveforms import HipFilteredWaveformsPlugin
 from .hit_finder import HipHitFinderPlugin
 from .hit_grouped import HipHitGroupedPlugin
@@ -42,8 +46,15 @@ def hip_from_raw_files():
     return hip_with_records() + [HipWaveformsPlugin()]
 
 
+def hip_full():
+    """hip_from_raw_files() plus df, df_events (grouped on the GPU) and df_paired: every product of the reference's
+    cpu_default() profile (io + waveform + peaks + basic_features + tabular + events)."""
+    return hip_from_raw_files() + [HipDataFramePlugin(), HipGroupedEventsPlugin(), HipPairedEventsPlugin()]
+
+
 __all__ = ["HipWavePoolFilteredPlugin", "HipThresholdHitPlugin", "HipBasicFeaturesPlugin",
            "HipWaveformWidthIntegralPlugin", "HipHitGroupedPlugin", "HipHitFinderPlugin", "HipFilteredWaveformsPlugin",
            "HipWaveformWidthPlugin", "HipS1S2ClassifierPlugin", "HipHitMergeClustersPlugin",
            "HipHitMergePlugin", "HipHitMergedComponentsPlugin", "HipSignalPeaksStreamPlugin", "HipRecordsPlugin", "HipWavePoolPlugin",
-           "HipWaveformsPlugin", "hip_default", "hip_with_records", "hip_from_raw_files"]
+           "HipWaveformsPlugin", "HipDataFramePlugin", "HipGroupedEventsPlugin", "HipPairedEventsPlugin", "hip_default",
+           "hip_with_records", "hip_from_raw_files", "hip_full"]
