@@ -346,6 +346,33 @@ int wfa_st_pack(wfa_ctx* ctx, int64_t n, int source, const uint16_t* src_pool, i
                 const int32_t* event_length, const int16_t* board, const int16_t* channel, const uint8_t* polarity,
                 const uint32_t* polarity_table, int32_t n_polarity, int64_t batch_bytes, uint8_t* out);
 
+/* K17 padded waves / signals matrix of a list of records (reference: core/data/records_view.py:216-330
+ * `RecordsView._waves_many` / `_signals_many`, one slice + cast + subtraction + two row assignments per record there).
+ * Row r shows record rec_index[r] of the resident records table (0 <= rec_index[r] < n_records), L = its length:
+ * end = min(sample_end < 0 ? L : sample_end, L), start = min(max(sample_start, 0), end); columns [0, end - start) hold
+ * the transformed samples pool[offset + start ...], columns up to pad_len hold +0 (all bits zero), and mask (n_rows x
+ * pad_len bytes, 0 / 1, may be NULL) marks the first.  Rows are pad_len * itemsize bytes, C order, no row padding.
+ * source: WFA_SRC_RAW (resident uint16 pool) or WFA_SRC_F32 (resident float32 pool).
+ * mode: _WAVES = cast only; _WAVES_BASELINE = x - b; _SIGNALS = x - b with the sign bit flipped iff the record's
+ * polarity code is WFA_POL_POSITIVE (-0.0 where x == b, as numpy's unary minus gives).  b = baseline_override[r] when
+ * baseline_override is not NULL (n_rows values), else the record's baseline.
+ * out_dtype: _U16 (a copy; WFA_SRC_RAW in _WAVES mode only), _F32: float(x) - (float)b with b rounded to float once
+ * (round to nearest even); _F64: (double)x - b.  One IEEE operation per sample.
+ * rec_index outside the table, pad_len below a row's window length, negative n_rows / pad_len or another
+ * mode / source / dtype combination: WFA_E_INVALID before any launch.  A request whose every window is empty (or
+ * pad_len == 0) fills out / mask with zeros without a launch.  The matrix is built on the device in batches of at most
+ * batch_bytes (>= one row, <= 1 GiB) in two buffers, each batch copied into out / mask (caller owned) through the
+ * pinned staging ring while the next one is built. */
+#define WFA_VIEW_WAVES 0
+#define WFA_VIEW_WAVES_BASELINE 1
+#define WFA_VIEW_SIGNALS 2
+#define WFA_VIEW_U16 0
+#define WFA_VIEW_F32 1
+#define WFA_VIEW_F64 2
+int wfa_view_gather(wfa_ctx* ctx, int64_t n_rows, const int64_t* rec_index, int32_t sample_start, int32_t sample_end,
+                    int32_t pad_len, int mode, int source, int out_dtype, const double* baseline_override,
+                    int64_t batch_bytes, void* out, uint8_t* mask);
+
 /* K15 CAEN VX2730 CSV text -> integers on the device (reference: utils/formats/vx2730.py:78-110 column layout,
  * :193-340 `VX2730Reader.read_file` -- its polars / pyarrow / pandas backends all yield these integers; consumer
  * processing/records_builder.py:212-302).  text = the bytes of one or more files after their header rows: rows end

@@ -23,6 +23,8 @@ WFA_E_LIMIT = -6
 SRC_RAW, SRC_F32, SRC_SG_FUSED = 0, 1, 2
 POL_UNKNOWN, POL_NEGATIVE, POL_POSITIVE, POL_POSITIVE_WAVE = 0, 1, 2, 3
 ST_SRC_HOST, ST_SRC_CSV, ST_SRC_ARENA, ST_SRC_POOL = 0, 1, 2, 3
+VIEW_WAVES, VIEW_WAVES_BASELINE, VIEW_SIGNALS = 0, 1, 2
+VIEW_U16, VIEW_F32, VIEW_F64 = 0, 1, 2
 ABI_VERSION = 1
 
 _p = C.c_void_p
@@ -80,6 +82,7 @@ SIGNATURES = {
     "wfa_records_sort": (_int, [_p, _i64, _p, _p, _p, _p, _p]),
     "wfa_pool_gather": (_int, [_p, _i64, _p, _p, _p, _i64, _p, _p, _i64]),
     "wfa_st_pack": (_int, [_p, _i64, _int, _p, _i64, _p, _p, _i32] + [_p] * 10 + [_i32, _i64, _p]),
+    "wfa_view_gather": (_int, [_p, _i64, _p, _i32, _i32, _i32, _int, _int, _int, _p, _i64, _p, _p]),
     "wfa_basic_features": (_int, [_p, _int, _i64, _i64, _int, _i64, _i64, _int, _p, _p]),
     "wfa_width_integral": (_int, [_p, _int, _f64, _f64, _f64, _p]),
     "wfa_features_both": (_int, [_p, _i64, _i64, _int, _i64, _i64, _int, _f64, _f64, _f64, _p, _p]),

@@ -947,6 +947,7 @@ int wfa_upload_records_soa(wfa_ctx* c, int64_t R, const int64_t* off, const int3
     c->pw_plan_n = -1;
     c->no_runs32 = false;
     c->have_records = true;
+    c->len_host_valid = false;
     c->n_hits = -1;
     return WFA_OK;
 }
@@ -1051,6 +1052,7 @@ int wfa_upload_records_packed(wfa_ctx* c, const void* rows, int64_t R, int32_t r
     c->pw_plan_n = -1;
     c->no_runs32 = false;
     c->have_records = true;
+    c->len_host_valid = false;
     c->n_hits = -1;
     if (max_len_out) *max_len_out = max_len;
     if (record_ids_increasing) *record_ids_increasing = increasing ? 1 : 0;

@@ -87,6 +87,10 @@ struct wfa_ctx {
     int32_t max_len = 0;
     bool have_records = false;
     wfa::DevBuf off, len, baseline, pol, thr, ts, dt, board, chan, rid, fixed_bl, bm_off;
+    // host copy of `len`, fetched by the first wfa_view_gather after a records upload (it sizes and checks the rows
+    // of a request before any launch)
+    std::vector<int32_t> len_host;
+    bool len_host_valid = false;
     int64_t bitmap_bytes = 0;  // mask bits of all records (k_sg_mask -> k_hit_runs)
     // span mode eligibility (uniform length, contiguous, aligned; see SpanParams)
     bool span_ok = false;

@@ -1589,3 +1589,278 @@ int wfa_st_pack(wfa_ctx* c, int64_t n, int source, const uint16_t* src_pool, int
 }
 
 }  // extern "C"
+
+
+// ---- RecordsView matrices (k_view_gather) ---------------------------------------------------------------------------
+// (reference: core/data/records_view.py:216-330 `_waves_many` / `_signals_many`.)  Output-stationary like k_st_pack: a
+// lane owns eight consecutive samples of the batch's flat n_rows x pad_len matrix, finds its (row, column) with a
+// reciprocal multiply, reads the eight source samples (uint16: aligned dwords realigned by a funnel shift, only dwords
+// holding a sample of this row's window; float32: two 16-byte loads when aligned), applies the row's cast / baseline
+// subtraction / sign flip and stores 16-byte vectors; the eight mask bytes go out as one 8-byte store.
+namespace {
+constexpr int kViewBlock = 256;
+constexpr uint32_t kViewRun = 8;  // output samples per lane
+
+struct ViewArgs {
+    const void* pool;           // uint16 or float samples of the resident pool
+    const int64_t* off;         // resident records columns
+    const int32_t* len;
+    const double* baseline;
+    const int8_t* pol;
+    const int64_t* rec_index;   // per row of the whole request
+    const double* bl_override;  // per row of the whole request, or null
+    int64_t row0;               // first row of this batch
+    uint32_t n_rows;            // rows of this batch
+    uint32_t n_chunks;          // runs of kViewRun samples in this batch (the buffers are padded to a whole run)
+    uint32_t pad_len;
+    uint32_t magic;             // floor((2^32 - 1) / pad_len)
+    int32_t sample_start, sample_end, mode;
+};
+
+struct ViewRow {
+    int64_t at;   // first source sample of the window
+    int32_t n;    // window length
+    double b;
+    bool flip;
+};
+
+__device__ __forceinline__ ViewRow view_row(const ViewArgs& a, uint32_t r) {
+    const int64_t gr = a.row0 + r;
+    const int64_t ri = a.rec_index[gr];
+    const int32_t L = a.len[ri];
+    const int32_t end = min(a.sample_end < 0 ? L : a.sample_end, L);
+    const int32_t start = min(max(a.sample_start, 0), end);
+    ViewRow v;
+    v.at = a.off[ri] + start;
+    v.n = end - start;
+    v.b = a.bl_override ? a.bl_override[gr] : a.baseline[ri];
+    v.flip = a.mode == WFA_VIEW_SIGNALS && a.pol[ri] == WFA_POL_POSITIVE;
+    return v;
+}
+
+// one output sample: a cast, at most one subtraction, and the sign BIT flipped (0.0 -> -0.0, like numpy's unary minus)
+template <typename O>
+struct ViewOp {
+    O b;
+    bool sub, flip;
+    __device__ __forceinline__ ViewOp(const ViewRow& row, int mode) : b((O)row.b), sub(mode != WFA_VIEW_WAVES), flip(row.flip) {}
+    template <typename S>
+    __device__ __forceinline__ O operator()(S x) const {
+        if constexpr (sizeof(O) == 2) {
+            return (O)x;
+        } else if constexpr (sizeof(O) == 4) {
+            float v = (float)x;
+            if (sub) v = v - b;
+            return flip ? __uint_as_float(__float_as_uint(v) ^ 0x80000000u) : v;
+        } else {
+            double v = (double)x;
+            if (sub) v = v - b;
+            return flip ? __longlong_as_double(__double_as_longlong(v) ^ (long long)0x8000000000000000ull) : v;
+        }
+    }
+};
+
+// samples [at, at + nv) of the pool into x[0 .. nv); the rest of x is unspecified
+__device__ __forceinline__ void view_load8(const uint16_t* pool, int64_t at, int nv, uint16_t (&x)[8]) {
+    const uint32_t* p32 = reinterpret_cast<const uint32_t*>(pool);
+    const int64_t ab = at >> 1, lim = at + nv;
+    const bool odd = at & 1;
+    uint32_t d[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i)  // only dwords holding a sample of this window are read
+        d[i] = (nv > 0 && (i < 4 || odd) && 2 * (ab + i) < lim) ? p32[ab + i] : 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t w = odd ? __builtin_amdgcn_alignbit(d[j + 1], d[j], 16) : d[j];
+        x[2 * j] = (uint16_t)(w & 0xffffu);
+        x[2 * j + 1] = (uint16_t)(w >> 16);
+    }
+}
+
+__device__ __forceinline__ void view_load8(const float* pool, int64_t at, int nv, float (&x)[8]) {
+    if (nv == 8 && (at & 3) == 0) {
+        const float4 lo = *reinterpret_cast<const float4*>(pool + at), hi = *reinterpret_cast<const float4*>(pool + at + 4);
+        x[0] = lo.x; x[1] = lo.y; x[2] = lo.z; x[3] = lo.w;
+        x[4] = hi.x; x[5] = hi.y; x[6] = hi.z; x[7] = hi.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = j < nv ? pool[at + j] : 0.f;
+    }
+}
+
+template <typename S, typename O>
+__global__ __launch_bounds__(kViewBlock) void k_view_gather(ViewArgs a, O* __restrict__ out, uint8_t* __restrict__ mask) {
+    const uint32_t g = blockIdx.x * kViewBlock + threadIdx.x;
+    if (g >= a.n_chunks) return;
+    const uint32_t s = g * kViewRun;  // flat sample index in the batch (< 2^31)
+    uint32_t r = __umulhi(s, a.magic);  // floor(s / pad_len) or up to two less
+    uint32_t p = s - r * a.pad_len;
+    if (p >= a.pad_len) { ++r; p -= a.pad_len; }
+    if (p >= a.pad_len) { ++r; p -= a.pad_len; }
+    const S* pool = static_cast<const S*>(a.pool);
+    union {
+        O v[kViewRun];
+        uint4 q[kViewRun * sizeof(O) / 16];
+    } u;
+    uint32_t valid = 0;  // bit j: sample j of the run lies in its row's window
+    if (p + kViewRun <= a.pad_len) {
+        // eight columns of one row (s < n_rows * pad_len, so the row exists)
+        const ViewRow row = view_row(a, r);
+        const int nv = max(0, min((int)kViewRun, row.n - (int)p));
+        S x[kViewRun];
+        view_load8(pool, row.at + p, nv, x);
+        const ViewOp<O> op(row, a.mode);
+#pragma unroll
+        for (int j = 0; j < (int)kViewRun; ++j) u.v[j] = j < nv ? op(x[j]) : (O)0;
+        valid = (1u << nv) - 1u;
+    } else {
+        // a row boundary (or several: pad_len < 8) or the padding after the last row: sample by sample
+#pragma unroll
+        for (int j = 0; j < (int)kViewRun; ++j) {
+            O v = (O)0;
+            if (r < a.n_rows) {
+                const ViewRow row = view_row(a, r);
+                if ((int)p < row.n) {
+                    v = ViewOp<O>(row, a.mode)(pool[row.at + p]);
+                    valid |= 1u << j;
+                }
+            }
+            u.v[j] = v;
+            if (++p == a.pad_len) { p = 0; ++r; }
+        }
+    }
+    uint4* o = reinterpret_cast<uint4*>(out + s);
+#pragma unroll
+    for (int k = 0; k < (int)(kViewRun * sizeof(O) / 16); ++k) o[k] = u.q[k];
+    if (mask) {
+        // bit i of a nibble -> byte i of a dword (the four partial products never meet, so nothing carries)
+        const uint32_t lo = ((valid & 0xfu) * 0x00204081u) & 0x01010101u;
+        const uint32_t hi = ((valid >> 4) * 0x00204081u) & 0x01010101u;
+        *reinterpret_cast<uint2*>(mask + s) = make_uint2(lo, hi);
+    }
+}
+
+struct ViewLoop {
+    wfa_ctx* c;
+    ViewArgs a;
+    int source, out_dtype;
+    void* buf[2];
+    uint8_t* mbuf[2];  // null without a mask
+    int64_t rows_per_batch, n, next;  // next: first row of the batch to build next
+    template <typename S, typename O>
+    void run(int k) {
+        hipLaunchKernelGGL((k_view_gather<S, O>), dim3((a.n_chunks + kViewBlock - 1) / kViewBlock), dim3(kViewBlock), 0,
+                           c->stream, a, static_cast<O*>(buf[k]), mbuf[k]);
+    }
+    int launch() {  // build the batch starting at row `next` into buffer (next / rows_per_batch) & 1
+        if (next >= n) return WFA_OK;
+        const int k = (int)((next / rows_per_batch) & 1);
+        a.row0 = next;
+        a.n_rows = (uint32_t)std::min(rows_per_batch, n - next);
+        a.n_chunks = (uint32_t)(((uint64_t)a.n_rows * a.pad_len + kViewRun - 1) / kViewRun);
+        LaunchTimer t(c, true);
+        if (source == WFA_SRC_RAW) {
+            if (out_dtype == WFA_VIEW_U16) run<uint16_t, uint16_t>(k);
+            else if (out_dtype == WFA_VIEW_F32) run<uint16_t, float>(k);
+            else run<uint16_t, double>(k);
+        } else {
+            if (out_dtype == WFA_VIEW_F32) run<float, float>(k);
+            else run<float, double>(k);
+        }
+        WFA_HIP_CHECK(hipGetLastError());
+        next += a.n_rows;
+        return t.end("k_view_gather");
+    }
+    static int launch_cb(void* self) { return static_cast<ViewLoop*>(self)->launch(); }
+};
+}  // namespace
+
+extern "C" {
+
+int wfa_view_gather(wfa_ctx* c, int64_t n_rows, const int64_t* rec_index, int32_t sample_start, int32_t sample_end,
+                    int32_t pad_len, int mode, int source, int out_dtype, const double* baseline_override,
+                    int64_t batch_bytes, void* out, uint8_t* mask) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (n_rows < 0) return fail(WFA_E_INVALID, "negative row count %lld", (long long)n_rows);
+    if (pad_len < 0) return fail(WFA_E_INVALID, "negative pad_len %d", pad_len);
+    if (mode != WFA_VIEW_WAVES && mode != WFA_VIEW_WAVES_BASELINE && mode != WFA_VIEW_SIGNALS)
+        return fail(WFA_E_INVALID, "unknown view mode %d", mode);
+    if (source != WFA_SRC_RAW && source != WFA_SRC_F32) return fail(WFA_E_INVALID, "unknown view source %d", source);
+    if (out_dtype != WFA_VIEW_U16 && out_dtype != WFA_VIEW_F32 && out_dtype != WFA_VIEW_F64)
+        return fail(WFA_E_INVALID, "unknown view output type %d", out_dtype);
+    if (out_dtype == WFA_VIEW_U16 && (source != WFA_SRC_RAW || mode != WFA_VIEW_WAVES))
+        return fail(WFA_E_INVALID, "uint16 output is a copy: only plain waves of the uint16 pool have it");
+    if (!c->have_records) return fail(WFA_E_STATE, "records not uploaded");
+    if (source == WFA_SRC_RAW ? !c->have_u16 : !c->have_f32)
+        return fail(WFA_E_STATE, source == WFA_SRC_RAW ? "wave_pool (uint16) not uploaded" : "float32 pool not resident");
+    if (n_rows > 0 && !rec_index) return fail(WFA_E_INVALID, "rec_index is null");
+    const size_t itemsize = out_dtype == WFA_VIEW_U16 ? 2 : out_dtype == WFA_VIEW_F32 ? 4 : 8;
+    if (n_rows > 0 && pad_len > 0 && !out) return fail(WFA_E_INVALID, "out is null");
+    // the lengths of the resident table, fetched once per records upload: every row is sized and checked on the host
+    if (!c->len_host_valid) {
+        c->len_host.resize((size_t)c->R);
+        if (c->R > 0)
+            WFA_HIP_CHECK(hipMemcpyAsync(c->len_host.data(), c->len.ptr, (size_t)c->R * 4, hipMemcpyDeviceToHost, c->stream));
+        WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+        c->len_host_valid = true;
+    }
+    int64_t max_window = 0;
+    for (int64_t r = 0; r < n_rows; ++r) {
+        if (rec_index[r] < 0 || rec_index[r] >= c->R)
+            return fail(WFA_E_INVALID, "row %lld: record index %lld outside the resident table of %lld records", (long long)r,
+                        (long long)rec_index[r], (long long)c->R);
+        const int32_t L = c->len_host[(size_t)rec_index[r]];
+        const int32_t end = std::min(sample_end < 0 ? L : sample_end, L);
+        const int32_t start = std::min(std::max<int32_t>(sample_start, 0), end);
+        max_window = std::max<int64_t>(max_window, end - start);
+    }
+    if (pad_len < max_window) return fail(WFA_E_INVALID, "pad_len (%d) < max length (%lld)", pad_len, (long long)max_window);
+    if (n_rows == 0 || pad_len == 0) return WFA_OK;
+    const uint64_t row_bytes = (uint64_t)pad_len * itemsize;
+    if (max_window == 0) {  // nothing to gather
+        std::memset(out, 0, (size_t)((uint64_t)n_rows * row_bytes));
+        if (mask) std::memset(mask, 0, (size_t)((uint64_t)n_rows * (uint64_t)pad_len));
+        return WFA_OK;
+    }
+    const int64_t cap = std::min<int64_t>(std::max<int64_t>(batch_bytes, 1), 1ll << 30);
+    const int64_t rows_per_batch = std::min<int64_t>(n_rows, std::max<int64_t>(1, cap / (int64_t)row_bytes));
+    const uint64_t buf_samples = ((uint64_t)rows_per_batch * (uint64_t)pad_len + kViewRun - 1) / kViewRun * kViewRun;
+    if (buf_samples >= (1ull << 31)) return fail(WFA_E_LIMIT, "row of %d samples too long", pad_len);
+
+    int64_t* d_idx;
+    double* d_bl = nullptr;
+    uint8_t *d_out0, *d_out1, *d_m0 = nullptr, *d_m1 = nullptr;
+    const bool two = n_rows > rows_per_batch;
+    if ((rc = upload(c, S_K0, rec_index, n_rows, &d_idx)) ||
+        (baseline_override && (rc = upload(c, S_HEIGHT, baseline_override, n_rows, &d_bl))) ||
+        (rc = slot<uint8_t>(c, S_OUT2, (int64_t)(buf_samples * itemsize), &d_out0)) ||
+        (rc = slot<uint8_t>(c, S_OUT3, two ? (int64_t)(buf_samples * itemsize) : 1, &d_out1)) ||
+        (mask && ((rc = slot<uint8_t>(c, S_OUT4, (int64_t)buf_samples, &d_m0)) ||
+                  (rc = slot<uint8_t>(c, S_OUT5, two ? (int64_t)buf_samples : 1, &d_m1)))))
+        return rc;
+    ViewArgs a{};
+    a.pool = source == WFA_SRC_RAW ? c->pool_u16.ptr : c->pool_f32.ptr;
+    a.off = c->off.as<int64_t>(); a.len = c->len.as<int32_t>(); a.baseline = c->baseline.as<double>(); a.pol = c->pol.as<int8_t>();
+    a.rec_index = d_idx; a.bl_override = d_bl;
+    a.pad_len = (uint32_t)pad_len;
+    a.magic = 0xffffffffu / (uint32_t)pad_len;
+    a.sample_start = sample_start; a.sample_end = sample_end; a.mode = mode;
+    ViewLoop loop{c, a, source, out_dtype, {d_out0, d_out1}, {d_m0, d_m1}, rows_per_batch, n_rows, 0};
+    if ((rc = loop.launch())) return rc;
+    // batch k goes down through the staging ring; batch k + 1 is built into the other buffers meanwhile
+    for (int64_t row = 0; row < n_rows; row += rows_per_batch) {
+        const int k = (int)((row / rows_per_batch) & 1);
+        const uint64_t rows = (uint64_t)std::min(rows_per_batch, n_rows - row);
+        if ((rc = d2h_staged(c, static_cast<uint8_t*>(out) + (uint64_t)row * row_bytes, loop.buf[k], (size_t)(rows * row_bytes),
+                             &ViewLoop::launch_cb, &loop)))
+            return rc;
+        if (mask && (rc = d2h_staged(c, mask + (uint64_t)row * (uint64_t)pad_len, loop.mbuf[k], (size_t)(rows * (uint64_t)pad_len),
+                                     nullptr, nullptr)))
+            return rc;
+    }
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return WFA_OK;
+}
+
+}  // extern "C"

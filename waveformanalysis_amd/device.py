@@ -84,6 +84,9 @@ class DeviceSession:
         self._res_pool: np.ndarray | None = None
         self._res_filtered: np.ndarray | None = None
         self.uploads = 0  # pool uploads performed (tests, measurement)
+        # who uploaded the resident records table last (note_records), while the device columns still hold what it
+        # uploaded: every records upload, pool replacement and baseline-writing pass resets it
+        self._res_records = None
 
     # -- lifetime -------------------------------------------------------------------------------
     def close(self) -> None:
@@ -96,6 +99,7 @@ class DeviceSession:
         """The device pools no longer mirror any host array the session knows of."""
         self._res_pool = None
         self._res_filtered = None
+        self._res_records = None
 
     def _drop_f32_tags(self) -> None:
         """The device float32 buffer is about to be overwritten: forget every host array remembered as its content (the
@@ -129,6 +133,18 @@ class DeviceSession:
         shard's slice of the wave_pool_filtered it returned): ensure_filtered_pool(pool_f32) uploads nothing from now on
         until a call replaces a device pool."""
         self._res_filtered = pool_f32
+
+    def holds_pool(self, wave_pool: np.ndarray) -> bool:
+        """True while the device pool still holds this very array object (the `is` test of ensure_pool)."""
+        return self._res_pool is wave_pool
+
+    def note_records(self, owner) -> None:
+        """`owner` (any object) has just called upload_records: holds_records(owner) stays True until another records
+        upload, a pool replacement or a pass that writes the device baselines."""
+        self._res_records = owner
+
+    def holds_records(self, owner) -> bool:
+        return owner is not None and self._res_records is owner
 
     def holds_filtered(self, pool_f32: np.ndarray) -> bool:
         """True while the device float32 pool still holds this very array object (the `is` test of ensure_filtered_pool)."""
@@ -169,6 +185,7 @@ class DeviceSession:
         if self.n_samples and arr.size != self.n_samples:
             raise ValueError(f"wave_pool_filtered has {arr.size} samples, wave_pool has {self.n_samples}")
         self._drop_f32_tags()
+        self._res_records = None  # (the library drops the records when the float32 pool stands alone)
         _lib.check(self._lib.wfa_upload_pool_f32(self._h, _ptr(arr), arr.size))
         self.uploads += 1
 
@@ -211,6 +228,7 @@ class DeviceSession:
         missing = [n for n in REQUIRED_RECORD_FIELDS if n not in records.dtype.names]
         if missing:
             raise ValueError(f"records missing required fields: {missing}")
+        self._res_records = None
         n = len(records)
         layout = self._packed_layout(records) if self.packed_records else None
         if layout is not None:
@@ -270,6 +288,8 @@ class DeviceSession:
     # -- kernels --------------------------------------------------------------------------------
     def baseline_mean(self, start: int, end: int, update_records: bool = False) -> np.ndarray:
         out = np.empty(self.n_records, dtype=np.float64)
+        if update_records:
+            self._res_records = None
         _lib.check(self._lib.wfa_baseline_mean(self._h, int(start), int(end), int(update_records), _ptr(out)))
         return out
 
@@ -332,6 +352,7 @@ class DeviceSession:
                                    right_extension: int = 2, max_len: int = 0,
                                    download: bool = True) -> np.ndarray | int:
         n = C.c_int64(0)
+        self._res_records = None  # the pass may write the device baselines
         _lib.check(self._lib.wfa_fused_baseline_filter_hits(
             self._h, int(baseline_window[0]), int(baseline_window[1]), int(left_extension),
             int(right_extension), int(max_len), C.byref(n)))
@@ -340,6 +361,7 @@ class DeviceSession:
     def hits_enqueue(self, source: int = _lib.SRC_SG_FUSED, baseline_window: tuple[int, int] = (0, 0),
                      left_extension: int = 2, right_extension: int = 2, max_len: int = 0) -> None:
         """Queue a hit pass without waiting for it (see wfa_hits_enqueue); hits_wait() / _fill_hits deliver."""
+        self._res_records = None  # the pass may write the device baselines
         _lib.check(self._lib.wfa_hits_enqueue(self._h, int(source), int(baseline_window[0]), int(baseline_window[1]),
                                               int(left_extension), int(right_extension), int(max_len)))
 
@@ -569,6 +591,57 @@ class DeviceSession:
             self._h, n, self.ST_SOURCES[source], _ptr(pool), int(src_samples), _ptr(so), _ptr(ln), L,
             *[_ptr(cols[k]) for k in kinds], _ptr(code), _ptr(table), len(table) // 8, int(batch_bytes), _ptr(out)))
         return out
+
+    # ---- RecordsView matrices ------------------------------------------------------------------------------
+    VIEW_MODES = {"waves": _lib.VIEW_WAVES, "waves_baseline": _lib.VIEW_WAVES_BASELINE, "signals": _lib.VIEW_SIGNALS}
+    VIEW_SOURCES = {"u16": _lib.SRC_RAW, "f32": _lib.SRC_F32}
+    VIEW_DTYPES = {np.dtype(np.uint16): _lib.VIEW_U16, np.dtype(np.float32): _lib.VIEW_F32,
+                   np.dtype(np.float64): _lib.VIEW_F64}
+
+    def view_gather(self, rec_index, *, mode: str, source: str, out_dtype, pad_len: int, sample_start: int = 0,
+                    sample_end: int | None = None, mask: bool = False, baseline_override=None,
+                    out: np.ndarray | None = None, batch_bytes: int = 256 << 20):
+        """The padded (len(rec_index), pad_len) matrix of RecordsView.waves / .signals, gathered from the resident pool
+        (wfa_view_gather); with mask=True also the uint8 matrix marking each row's window.
+
+        rec_index: rows of the records table uploaded last.  mode: "waves" (cast), "waves_baseline" (x - baseline) or
+        "signals" (x - baseline, sign flipped for polarity "positive"); source: "u16" (the resident wave_pool) or "f32"
+        (the resident float32 pool); out_dtype: float32 / float64, or uint16 for plain waves of the u16 pool.  Row r
+        holds samples [start, end) of its record, start = min(max(sample_start, 0), end), end = min(sample_end, length)
+        (None: the record's end; negative: 0), zeros after.  baseline_override: one value per row instead of the records'
+        baselines.  Nothing is uploaded here but the index list; pool and records are the session's resident ones."""
+        if mode not in self.VIEW_MODES:
+            raise ValueError(f"unknown view mode {mode!r}")
+        if source not in self.VIEW_SOURCES:
+            raise ValueError(f"unknown view source {source!r}")
+        dtype = np.dtype(out_dtype)
+        if dtype not in self.VIEW_DTYPES:
+            raise ValueError(f"unsupported view dtype {dtype}")
+        idx = np.ascontiguousarray(rec_index, dtype=np.int64)
+        if idx.ndim != 1:
+            raise ValueError("rec_index must be 1-D")
+        n, pad = len(idx), int(pad_len)
+        if pad > 2**31 - 1:
+            raise ValueError(f"pad_len {pad} too long")
+        end = -1 if sample_end is None else max(int(sample_end), 0)
+        start = min(max(int(sample_start), 0), 2**31 - 1)
+        end = min(end, 2**31 - 1)
+        bl = None
+        if baseline_override is not None:
+            bl = np.ascontiguousarray(baseline_override, dtype=np.float64)
+            if bl.shape != (n,):
+                raise ValueError("baseline_override must hold one value per row")
+        shape = (n, max(pad, 0))
+        if out is None:
+            out = np.empty(shape, dtype=dtype)
+        elif not isinstance(out, np.ndarray) or out.dtype != dtype or out.shape != shape or not out.flags.c_contiguous \
+                or not out.flags.writeable:
+            raise ValueError(f"out must be a writeable contiguous array of shape {shape} of {dtype}")
+        m = np.empty(shape, dtype=np.uint8) if mask else None
+        _lib.check(self._lib.wfa_view_gather(
+            self._h, n, _ptr(idx), start, end, pad, self.VIEW_MODES[mode], self.VIEW_SOURCES[source],
+            self.VIEW_DTYPES[dtype], _ptr(bl), int(batch_bytes), _ptr(out), _ptr(m)))
+        return (out, m) if mask else out
 
     # ---- hit-table stages (device sort + scans) ------------------------------------------------------------
     @staticmethod

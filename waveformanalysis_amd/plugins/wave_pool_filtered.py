@@ -73,6 +73,8 @@ class HipWavePoolFilteredPlugin(K.HipPlugin):
         sess = K.resident_session(context, wave_pool if isinstance(wave_pool, np.ndarray) else np.asarray(wave_pool),
                                   cacheable=isinstance(wave_pool, np.ndarray))
         out = run_filter_groups(sess, _view_records(records), groups)  # (the filters drop the float32 tag themselves)
+        if isinstance(wave_pool, np.ndarray):
+            sess.note_filtered(out)  # the device float32 pool is what `out` was just copied from: no upload for its readers
         return out
 
 
