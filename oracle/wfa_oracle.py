@@ -357,9 +357,10 @@ def width_integral(records: np.ndarray, wave_pool: np.ndarray, *, q_low=0.10, q_
 
 
 # --- a15: event grouping ----------------------------------------------------------------------
-def group_hit_windows_literal(hits: np.ndarray, time_window_ns: float):
+def group_hit_windows_literal(hits: np.ndarray, time_window_ns: float, abs_start_fix=None, abs_end_fix=None):
     """event_grouping.py:286-471, literal gap-chain loop; returns a list of events
-    (t_min, t_max, member hit indices in the reference's per-event order)."""
+    (t_min, t_max, member hit indices in the reference's per-event order).  abs_start_fix / abs_end_fix: float64 per
+    hit, a non-NaN entry replaces the hit's absolute window (what :369-416 does for merged hits that span records)."""
     names = set(hits.dtype.names or ())
     s_name, e_name = ("sample_start", "sample_end") if {"sample_start", "sample_end"} <= names else ("edge_start", "edge_end")
     ts = np.asarray(hits["timestamp"], dtype=np.int64)
@@ -373,6 +374,10 @@ def group_hit_windows_literal(hits: np.ndarray, time_window_ns: float):
     dt_ps = dt.astype(np.float64) * 1e3
     a_s = ts.astype(np.float64) + (s_rel - pos) * dt_ps
     a_e = ts.astype(np.float64) + (e_rel - pos) * dt_ps
+    if abs_start_fix is not None:
+        f0, f1 = np.asarray(abs_start_fix, dtype=np.float64), np.asarray(abs_end_fix, dtype=np.float64)
+        a_s = np.where(np.isnan(f0), a_s, f0)
+        a_e = np.where(np.isnan(f1), a_e, f1)
     if len(hits) == 0:
         return []
     order = np.lexsort((rid, ts, dt, a_s))

@@ -168,8 +168,8 @@ struct HitCols {
 // Sort keys.  The window starts are float64 in the reference, but they are integers (picoseconds) whenever timestamps and
 // dt are: then the key is that integer -- lexsort sorts (key - min) over the bits the range needs, 44 bits for 12 s of data
 // where the float64 bit pattern needs 56 -- and the timestamp key, which only ever breaks ties between EQUAL starts, is
-// (timestamp - start): a few thousand samples of range instead of the run's.  A start that is not an integer below 2^62
-// raises *inexact: the caller rewrites the two keys in their float64 / plain forms (k_float_keys).
+// (timestamp - start): a few thousand samples of range instead of the run's.  A start that is not an integer of magnitude
+// below 4.0e18 raises *inexact: the caller rewrites the two keys in their float64 / plain forms (k_float_keys).
 __global__ void k_hit_prep(int64_t n, HitCols h, const double* __restrict__ fix0, const double* __restrict__ fix1,
                            double* __restrict__ abs0, double* __restrict__ abs1,
                            uint64_t* __restrict__ k_abs0, uint64_t* __restrict__ k_dt, uint64_t* __restrict__ k_ts,
@@ -199,7 +199,10 @@ __global__ void k_float_keys(int64_t n, const double* __restrict__ abs0, const i
                              uint64_t* __restrict__ k_abs0, uint64_t* __restrict__ k_ts) {
     const int64_t i = (int64_t)blockIdx.x * kTB + threadIdx.x;
     if (i >= n) return;
-    k_abs0[i] = ord_f64(abs0[i]);
+    // np.lexsort compares float64 values: -0.0 == +0.0 is a tie the later keys decide, while the bit patterns differ
+    // (a start of -0.0 can only come in through abs_start_fix).  The key is canonical; abs0 itself stays as given.
+    const double v = abs0[i];
+    k_abs0[i] = ord_f64(v == 0.0 ? 0.0 : v);
     if (k_ts) k_ts[i] = ord_i64(ts[i]);
 }
 
