@@ -309,6 +309,115 @@ def test_devices_none_constructs_no_sharded_run(monkeypatch):
     assert MD.peek_sharded_runs(ctx) == []
 
 
+# what a traced call keeps of its arguments (by parameter name); everything else about a call is its name and its place
+PINNED_ARGS = {"ensure_pool": ("cacheable",), "upload_pool": (), "upload_records": ("thresholds",),
+               "threshold_hits": ("download", "max_len"), "download_hits": (), "basic_features": ("out",),
+               "width_integral": ("out",), "ensure_filtered_pool": ("cacheable",), "upload_filtered_pool": (),
+               "filter_keep_output": ("keep",), "set_sg_plan": ("sg_window_size", "sg_poly_order"),
+               "savgol": ("download",), "sosfiltfilt": ("download",), "download_filtered": ("out", "start"),
+               "note_filtered": (), "find_peaks": ("download",), "download_peaks": ()}
+
+
+def traced(base):
+    """`base` (an OracleSession class) whose instances list their device calls in `calls`: (name, {pinned argument:
+    value}), defaults filled in.  An array argument is pinned as "given" / None, `out` as its length; `records_seen`
+    keeps the records objects that were uploaded."""
+    import functools
+    import inspect
+
+    class Traced(base):
+        def __init__(self, device_id=0):
+            super().__init__(device_id)
+            self.calls, self.records_seen = [], []
+
+    def wrap(name, fn):
+        sig = inspect.signature(fn)
+
+        @functools.wraps(fn)
+        def method(self, *a, **k):
+            bound = sig.bind(self, *a, **k)
+            explicit = set(bound.arguments)
+            bound.apply_defaults()
+            pinned = {}
+            for arg in PINNED_ARGS[name]:
+                v = bound.arguments[arg]
+                if arg == "out":
+                    v = None if v is None else len(v)
+                elif arg == "thresholds":
+                    v = "given" if arg in explicit else None
+                pinned[arg] = v
+            if name == "upload_records":
+                self.records_seen.append(bound.arguments["records"])
+            self.calls.append((name, pinned))
+            return fn(self, *a, **k)
+
+        return method
+
+    for name in PINNED_ARGS:
+        if hasattr(base, name):
+            setattr(Traced, name, wrap(name, getattr(base, name)))
+    return Traced
+
+
+def pinned_calls(plugin_cls, ctx, devices, session_cls):
+    """The device calls of one compute() on `ctx`: [calls] of the calling thread's session for devices=None, else one
+    list per shard session; and the records objects those sessions were given."""
+    ctx.config["devices"] = devices
+    ctx.wfa_session_factory = session_cls
+    ctx.wfa_device_pool.s = session_cls()
+    try:
+        plugin_cls().compute(ctx, "run")
+        sessions = [ctx.wfa_device_pool.s] if devices is None else MD.sharded_run(ctx, devices).sessions
+        assert devices is not None or MD.peek_sharded_runs(ctx) == []
+        if devices is not None:
+            assert ctx.wfa_device_pool.s.calls == []         # the calling thread's session stays out of a sharded run
+        return [s.calls for s in sessions], [r for s in sessions for r in s.records_seen]
+    finally:
+        MD.close_sharded_runs(ctx)
+
+
+POOL_UP = [("ensure_pool", {"cacheable": True}), ("upload_pool", {})]
+RECORDS_UP = ("upload_records", {"thresholds": None})
+
+
+def test_each_route_does_the_parent_commits_device_work():
+    """The ordered session calls of the three per-record plugins on `ragged_mixed`, as recorded before the records route
+    became one function: devices=None on the calling thread's session (download inside the pass, padded width 0 = the
+    longest uploaded record, the context's records object uploaded as it is), devices=[0, 1] on each shard's session
+    (the run's padded width 1500, rows fetched / written into the shard's slice of the table)."""
+    case = G.load_case("ragged_mixed")
+    rec, pool = case["records"], case["wave_pool"]
+    Traced = traced(OracleSession)
+    rows = [sh.n_records for sh in MD.split_records(rec, 2)]
+    assert min(rows) > 0 and int(rec["event_length"].max()) == 1500
+
+    one = {
+        HipThresholdHitPlugin: POOL_UP + [("upload_records", {"thresholds": "given"}),
+                                          ("threshold_hits", {"download": True, "max_len": 0})],
+        HipBasicFeaturesPlugin: POOL_UP + [RECORDS_UP, ("basic_features", None)],
+        HipWaveformWidthIntegralPlugin: POOL_UP + [RECORDS_UP, ("width_integral", None)],
+    }
+    for cls, want in one.items():
+        (calls,), seen = pinned_calls(cls, _ctx(rec, pool), None, Traced)
+        # the feature passes: `out` of a fresh zeroed table or None is the same device work, only name and place count
+        got = [(n, None if n in ("basic_features", "width_integral") else a) for n, a in calls]
+        assert got == want, cls.provides
+        assert len(seen) == 1 and seen[0] is rec, f"{cls.provides}: records copied on the way to the session"
+
+    def two(k):
+        return {
+            HipThresholdHitPlugin: POOL_UP + [("upload_records", {"thresholds": "given"}),
+                                              ("threshold_hits", {"download": False, "max_len": 1500}),
+                                              ("download_hits", {})],
+            HipBasicFeaturesPlugin: POOL_UP + [RECORDS_UP, ("basic_features", {"out": rows[k]})],
+            HipWaveformWidthIntegralPlugin: POOL_UP + [RECORDS_UP, ("width_integral", {"out": rows[k]})],
+        }
+
+    for cls in one:
+        per_session, _seen = pinned_calls(cls, _ctx(rec, pool), [0, 1], Traced)
+        assert per_session == [two(0)[cls], two(1)[cls]], cls.provides
+
+
 def test_devices_option_is_untracked_and_resolves():
     for cls in (HipThresholdHitPlugin, HipBasicFeaturesPlugin, HipWaveformWidthIntegralPlugin):
         opt = cls.options["devices"]

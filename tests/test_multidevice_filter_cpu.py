@@ -8,7 +8,7 @@ import pytest
 
 from oracle import wfa_oracle as O
 from tests import golden_util as G
-from tests.test_multidevice_cpu import OracleSession
+from tests.test_multidevice_cpu import OracleSession, pinned_calls, traced
 from waveformanalysis_amd import _lib, multidevice as MD
 from waveformanalysis_amd import device as D
 from waveformanalysis_amd.dtypes import HIT_DTYPE, RECORDS_DTYPE
@@ -251,7 +251,7 @@ def test_the_hand_made_layouts_take_the_routes_they_are_meant_for():
         rec, _pool = _hand_made(layout)
         for n_shards in (2, 3):
             shards = MD.split_records(rec, n_shards)
-            runs, got_shared = MD._own_samples(rec, shards)
+            runs, _merged, got_shared = MD._own_samples(rec, shards)
             assert got_shared == shared, (layout, n_shards)
             if layout == "interleaved":                        # some span holds another shard's samples
                 assert any(r[0].size and (r[0][0] > sh.span_start or r[1][-1] < sh.span_end or r[0].size > 1)
@@ -401,6 +401,57 @@ def test_devices_none_constructs_no_sharded_run(monkeypatch):
     f = ctx.get_data("run", "wave_pool_filtered")
     h = ctx.get_data("run", "hit")
     assert len(f) == len(pool) and len(h) and MD.peek_sharded_runs(ctx) == []
+
+
+def _sg(window, order):
+    return [("set_sg_plan", {"sg_window_size": window, "sg_poly_order": order}), ("savgol", {"download": False})]
+
+
+def test_each_route_does_the_parent_commits_device_work():
+    """The ordered session calls of wave_pool_filtered and hit, as recorded before the records route became one function
+    (tests/test_multidevice_cpu.py has the three other plugins): devices=None filters on the calling thread's session
+    and downloads the whole float32 pool, devices=[0, 1] leaves each shard's output on its device and downloads the
+    span of its own records; the filter groups of `v1725_channel_cfg` run in the order one device runs them, a shard
+    skipping the groups none of its records belong to."""
+    pool_up = [("ensure_pool", {"cacheable": True}), ("upload_pool", {})]
+    records_up = ("upload_records", {"thresholds": None})
+    off, on = ("filter_keep_output", {"keep": False}), ("filter_keep_output", {"keep": True})
+    whole = [("download_filtered", {"out": None, "start": 0}), off, ("note_filtered", {})]
+    bw = ("sosfiltfilt", {"download": False})
+    Traced = traced(FilterOracleSession)
+
+    def part(n, start):
+        return [off, ("download_filtered", {"out": n, "start": start}), ("note_filtered", {})]
+
+    def calls(plugin_cls, name, devices, **data):
+        rec, pool, cfg = _inputs(name)
+        ctx = _ctx(rec, pool, **cfg)
+        ctx._data.update(data)
+        got, seen = pinned_calls(plugin_cls, ctx, devices, Traced)
+        return got, seen, rec
+
+    # ragged_mixed: one Savitzky-Golay group; records [0, 6) on samples [4, 2339), records [6, 20) on [2340, 3756)
+    one_group = pool_up + [off, records_up] + _sg(11, 2)
+    got, seen, rec = calls(HipWavePoolFilteredPlugin, "ragged_mixed", None)
+    assert got == [one_group + whole] and len(seen) == 1 and seen[0] is rec
+    got, _seen, _rec = calls(HipWavePoolFilteredPlugin, "ragged_mixed", [0, 1])
+    assert got == [one_group + part(2335, 4), one_group + part(1416, 4)]
+
+    # v1725_channel_cfg: SG(11, 2), BW, SG(21, 4), BW in that order; the second half of the records has no first BW group
+    groups = [off, records_up] + _sg(11, 2) + [records_up, on, bw, records_up] + _sg(21, 4) + [records_up, bw]
+    got, _seen, _rec = calls(HipWavePoolFilteredPlugin, "v1725_channel_cfg", None)
+    assert got == [pool_up + groups + whole]
+    got, _seen, _rec = calls(HipWavePoolFilteredPlugin, "v1725_channel_cfg", [0, 1])
+    second = [off, records_up] + _sg(11, 2) + [records_up, on] + _sg(21, 4) + [records_up, bw]
+    assert got == [pool_up + groups + part(19200, 0), pool_up + second + part(19200, 0)]
+
+    # hit on a ready-made wave_pool_filtered
+    filtered = G.load_case("ragged_mixed")["wave_pool_filtered"]
+    find = pool_up + [("upload_records", {"thresholds": "given"})]
+    got, seen, rec = calls(HipHitFinderPlugin, "ragged_mixed", None, wave_pool_filtered=filtered)
+    assert got == [find + [("find_peaks", {"download": True})]] and len(seen) == 1 and seen[0] is rec
+    got, _seen, _rec = calls(HipHitFinderPlugin, "ragged_mixed", [0, 1], wave_pool_filtered=filtered)
+    assert got == [find + [("find_peaks", {"download": False}), ("download_peaks", {})]] * 2
 
 
 def test_devices_option_on_the_two_plugins():

@@ -5,11 +5,18 @@ passed to every shard explicitly, hit_finder.py:354-370), so a run splits into c
 between devices.  Each shard's rows are the rows of its records in record order; placing the shards' tables one after
 another in shard order is the reference's order (record index, then start sample) with no sort and no gather.
 
-`ShardedRun` keeps one `DeviceSession` and one long-lived worker thread per entry of `device_ids`.  A run is:
-  1. every worker puts its shard's pool slice on its device (skipped when it is still resident),
-  2. uploads its records (wave_offset shifted to the slice) and runs the pass, rows left on the device,
-  3. the caller allocates the run's table once,
-  4. every worker downloads its rows straight into its slice of that table.
+The plugins come here through one function, plugins/_common.py::records_route, which reads their `devices` option:
+None stays on the calling thread's session, anything else takes the context's `ShardedRun` (sharded_run) and hands it
+the plugin's pass.  `ShardedRun` keeps one `DeviceSession` and one long-lived worker thread per entry of `device_ids`.
+Every run starts the same way (`_plan`: split, lock, and per shard its inputs, its session and its pool slice); the
+three kinds of run differ in what follows:
+  * run, one row per record: the caller allocates the table, every worker runs the pass into its slice of it;
+  * run with `fetch`, any number of rows: every worker runs the pass, rows left on the device, and reports its count;
+    the caller allocates the run's table once; every worker downloads its rows straight into its slice of it;
+  * run_pool, a float32 pool (wave_pool_filtered): every worker filters its records and downloads their samples into
+    the one output, and its slice stays resident for the passes that read it.
+A worker's first step is always to put its shard's pool slice on its device (skipped when it is still resident) and to
+take its records with wave_offset shifted to the slice.
 The uploads and downloads are ctypes calls, which release the GIL: the links of different devices work at once.
 
 This is the in-process path.  `bench.py --gpus N` keeps its multi-process route (one rank per GPU, channel shards, hit
@@ -21,6 +28,7 @@ from __future__ import annotations
 import threading
 import weakref
 from concurrent.futures import ThreadPoolExecutor
+from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import Callable, Sequence
 
@@ -46,6 +54,14 @@ class RecordShard:
         return self.r1 - self.r0
 
 
+def _columns(records: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """(wave_offset, event_length), contiguous: one strided read per column (the records rows are ~100 B wide),
+    everything after it on contiguous arrays."""
+    if not len(records):
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    return np.ascontiguousarray(records["wave_offset"]), np.ascontiguousarray(records["event_length"])
+
+
 def split_records(records: np.ndarray, n_shards: int) -> list[RecordShard]:
     """Contiguous record ranges balanced by sample count (cumulative event_length), one per shard.
 
@@ -53,13 +69,14 @@ def split_records(records: np.ndarray, n_shards: int) -> list[RecordShard]:
     builders' layout (offsets non-decreasing and disjoint), wider than needed for anything else (offsets out of order,
     gaps, overlaps) but always holding every sample of its records.  With fewer records than shards, or samples that
     cannot be balanced, some shards are empty (r0 == r1, span (0, 0))."""
+    return _split(*_columns(records), n_shards)
+
+
+def _split(offsets: np.ndarray, lengths: np.ndarray, n_shards: int) -> list[RecordShard]:
     n_shards = int(n_shards)
     if n_shards < 1:
         raise ValueError("n_shards must be >= 1")
-    n = len(records)
-    # one strided read per column (the records rows are ~100 B wide), everything after it on contiguous arrays
-    lengths = np.ascontiguousarray(records["event_length"]) if n else np.zeros(0, np.int64)
-    offsets = np.ascontiguousarray(records["wave_offset"]) if n else np.zeros(0, np.int64)
+    n = len(lengths)
     if n and int(lengths.min()) < 0:  # negative lengths hold no samples
         lengths = np.maximum(lengths, 0)
     cum = np.zeros(n + 1, dtype=np.int64)
@@ -96,28 +113,26 @@ def _copy_rows(rows: np.ndarray) -> np.ndarray:
     return rows.copy()
 
 
-def _shard_inputs(records: np.ndarray, shards: Sequence[RecordShard], per_record: Sequence) -> Callable:
-    """k -> (shard, slice start, records_k with wave_offset shifted to the slice, per-record arguments of shard k)."""
-    n = len(records)
-    sliced = [isinstance(a, np.ndarray) and a.ndim == 1 and len(a) == n for a in per_record]
-
-    def inputs(k):
-        sh = shards[k]
-        lo = sh.span_start - sh.span_start % POOL_ALIGN
-        rec = _copy_rows(records[sh.r0:sh.r1])
-        if lo:
-            rec["wave_offset"] -= lo
-        extra = [a[sh.r0:sh.r1] if s else a for a, s in zip(per_record, sliced)]
-        return sh, lo, rec, extra
-
-    return inputs
+def _per_record(per_record: Sequence, n: int, rows) -> list:
+    """`per_record` with every 1-d array of n entries cut to `rows` (a slice or a mask); scalars, 0-d arrays and None go
+    through as they are."""
+    return [a[rows] if isinstance(a, np.ndarray) and a.ndim == 1 and len(a) == n else a for a in per_record]
 
 
-def _own_samples(records: np.ndarray, shards: Sequence[RecordShard]) -> tuple[list, bool]:
+def _shard_inputs(records: np.ndarray, sh: RecordShard, per_record: Sequence) -> tuple:
+    """(slice start, records of the shard with wave_offset shifted to the slice, its per-record arguments)."""
+    lo = sh.span_start - sh.span_start % POOL_ALIGN
+    rec = _copy_rows(records[sh.r0:sh.r1])
+    if lo:
+        rec["wave_offset"] -= lo
+    return lo, rec, _per_record(per_record, len(records), slice(sh.r0, sh.r1))
+
+
+def _own_samples(records: np.ndarray, shards: Sequence[RecordShard]) -> tuple[list, tuple, bool]:
     """([(starts, ends)] per shard: the samples of its records as sorted disjoint runs [start, end), adjacent records
-    joined), and whether a sample belongs to records of two shards."""
-    off = np.ascontiguousarray(records["wave_offset"]).astype(np.int64, copy=False) if len(records) else np.zeros(0, np.int64)
-    ln = np.ascontiguousarray(records["event_length"]).astype(np.int64, copy=False) if len(records) else np.zeros(0, np.int64)
+    joined; (starts, ends) of every shard's runs merged and sorted by start; whether a sample belongs to records of two
+    shards -- if none does the merged runs are disjoint, so sorted by end as well)."""
+    off, ln = (c.astype(np.int64, copy=False) for c in _columns(records))
     runs = []
     for sh in shards:
         o, n_k = off[sh.r0:sh.r1], ln[sh.r0:sh.r1]
@@ -139,7 +154,7 @@ def _own_samples(records: np.ndarray, shards: Sequence[RecordShard]) -> tuple[li
     order = np.argsort(starts, kind="stable")
     starts, ends = starts[order], ends[order]
     shared = len(starts) > 1 and bool(np.any(starts[1:] < np.maximum.accumulate(ends)[:-1]))
-    return runs, shared
+    return runs, (starts, ends), shared
 
 
 class ShardError(RuntimeError):
@@ -245,8 +260,28 @@ class ShardedRun:
         self._resident[k] = (pool, lo, hi, view) if cacheable else None
 
     # -- a run -----------------------------------------------------------------------------------------------------
+    @contextmanager
+    def _plan(self, records: np.ndarray, pool: np.ndarray, per_record: Sequence, cacheable: bool):
+        """What every run starts with, the run's lock held inside: (shards, the shards that have records, ready, the
+        run's longest event_length).  ready(k), on worker k, puts the shard's pool slice on its device and returns
+        (session, shard, slice start, records_k, per-record arguments of shard k)."""
+        if self.closed:
+            raise RuntimeError("ShardedRun is closed")
+        offsets, lengths = _columns(records)
+        shards = _split(offsets, lengths, self.n_shards)
+
+        def ready(k):
+            sh, sess = shards[k], self.sessions[k]
+            lo, rec, extra = _shard_inputs(records, sh, per_record)
+            self._ensure_slice(k, sess, pool, lo, sh.span_end, cacheable)
+            return sess, sh, lo, rec, extra
+
+        with self._lock:
+            yield shards, [k for k, sh in enumerate(shards) if sh.n_records > 0], ready, int(lengths.max(initial=0))
+
     def run(self, records: np.ndarray, pool: np.ndarray, row_dtype, task: Callable, *, fetch: Callable | None = None,
-            per_record: Sequence = (), cacheable: bool = True, record_index_field: str | None = None) -> np.ndarray:
+            per_record: Sequence = (), cacheable: bool = True, record_index_field: str | None = None,
+            width_arg: str | None = None) -> np.ndarray:
         """The run's table, shards placed one after another in shard order.
 
         task(sess, records_k, *per_record_k, out=...) runs on worker k after the shard's pool slice is resident, with
@@ -256,23 +291,16 @@ class ShardedRun:
             record_index_field: a field that holds the record index; the shard's r0 is added to it.
           * fetch given: task(..., out=None) runs the pass and returns the shard's row count, rows left on the device;
             then fetch(sess, out_k) downloads them into the shard's slice of the table.
+            width_arg: a keyword under which task also gets the run's longest event_length (the hit pass pads every
+            shard to the run's width, hit_finder.py:354-370, not to the shard's own).
         A failure raises ShardError and returns no table."""
-        if self.closed:
-            raise RuntimeError("ShardedRun is closed")
         row_dtype = np.dtype(row_dtype)
-        n = len(records)
-        shards = split_records(records, self.n_shards)
-        shard_inputs = _shard_inputs(records, shards, per_record)
-
-        with self._lock:
-            busy = [k for k in range(self.n_shards) if shards[k].n_records > 0]
+        with self._plan(records, pool, per_record, cacheable) as (_shards, busy, ready, width):
             if fetch is None:
-                out = np.zeros(n, dtype=row_dtype)
+                out = np.zeros(len(records), dtype=row_dtype)
 
                 def one_pass(k):
-                    sh, lo, rec, extra = shard_inputs(k)
-                    sess = self.sessions[k]
-                    self._ensure_slice(k, sess, pool, lo, sh.span_end, cacheable)
+                    sess, sh, _lo, rec, extra = ready(k)
                     part = out[sh.r0:sh.r1]
                     task(sess, rec, *extra, out=part)
                     if record_index_field is not None and sh.r0:
@@ -281,11 +309,11 @@ class ShardedRun:
                 self._on_all(one_pass, busy)
                 return out
 
+            run_width = {width_arg: width} if width_arg else {}
+
             def count(k):
-                sh, lo, rec, extra = shard_inputs(k)
-                sess = self.sessions[k]
-                self._ensure_slice(k, sess, pool, lo, sh.span_end, cacheable)
-                return int(task(sess, rec, *extra, out=None))
+                sess, _sh, _lo, rec, extra = ready(k)
+                return int(task(sess, rec, *extra, out=None, **run_width))
 
             counts = self._on_all(count, busy)
             rows = np.array([c or 0 for c in counts], dtype=np.int64)
@@ -307,18 +335,20 @@ class ShardedRun:
         copy when no other shard's record lies inside it (the builders' layout), else one copy per run of its records'
         samples.  A sample two shards' records share (hand-made layouts: overlapping records) has one value for the
         order the writes happen in, so when any sample is shared the whole call runs on the first shard alone, pool
-        and records as they are -- what one device computes.
+        and records as they are -- what one device computes.  Records that hold no sample and point outside the pool
+        are left out of the run: they write nothing, and their offsets would widen a shard's span.
 
         With cacheable, each shard's float32 slice stays tagged as resident, keyed on the returned array object and the
         slice bounds: a later run() on that array with the same records (same split) uploads nothing.  Of that slice the
         device holds the samples of the shard's own records (0.0 elsewhere); a per-record pass reads no others.
         A failure raises ShardError and returns no table."""
-        if self.closed:
-            raise RuntimeError("ShardedRun is closed")
+        off, ln = _columns(records)
+        idle = (ln <= 0) & ((off < 0) | (off > len(pool)))
+        if np.any(idle):
+            records, per_record = records[~idle], _per_record(per_record, len(records), ~idle)
         out = np.zeros(len(pool), dtype=np.float32)
-        shards = split_records(records, self.n_shards)
-        runs, shared = _own_samples(records, shards)
-        with self._lock:
+        with self._plan(records, pool, per_record, cacheable) as (shards, busy, ready, _width):
+            runs, (starts, ends), shared = _own_samples(records, shards)
             self._filtered = [None] * self.n_shards
 
             def keep(k, sess, lo, hi):
@@ -327,27 +357,15 @@ class ShardedRun:
                     sess.note_filtered(view)
                     self._filtered[k] = (out, lo, hi, view)
 
-            if shared:
-                def alone(k):
-                    sess = self.sessions[k]
-                    self._ensure_slice(k, sess, pool, 0, len(pool), cacheable)
-                    task(sess, records, *per_record)
-                    sess.download_filtered(out)
-                    keep(k, sess, 0, len(pool))
-
-                self._on_all(alone, [0])
-                return out
-
-            shard_inputs = _shard_inputs(records, shards, per_record)
-            starts = np.concatenate([r[0] for r in runs])
-            ends = np.concatenate([r[1] for r in runs])
-            order = np.argsort(starts, kind="stable")
-            starts, ends = starts[order], ends[order]  # disjoint: sorted by start is sorted by end
+            def alone(k):
+                sess = self.sessions[k]
+                self._ensure_slice(k, sess, pool, 0, len(pool), cacheable)
+                task(sess, records, *per_record)
+                sess.download_filtered(out)
+                keep(k, sess, 0, len(pool))
 
             def one(k):
-                sh, lo, rec, extra = shard_inputs(k)
-                sess = self.sessions[k]
-                self._ensure_slice(k, sess, pool, lo, sh.span_end, cacheable)
+                sess, sh, lo, rec, extra = ready(k)
                 task(sess, rec, *extra)
                 own0, own1 = runs[k]
                 inside = int(np.searchsorted(starts, sh.span_end, "left") - np.searchsorted(ends, sh.span_start, "right"))
@@ -358,7 +376,10 @@ class ShardedRun:
                         sess.download_filtered(out[a:b], start=a - lo)
                 keep(k, sess, lo, sh.span_end)
 
-            self._on_all(one, [k for k in range(self.n_shards) if shards[k].n_records > 0])
+            if shared:
+                self._on_all(alone, [0])
+            else:
+                self._on_all(one, busy)
             return out
 
     # -- lifetime --------------------------------------------------------------------------------------------------

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import threading
 import warnings
+from functools import partial
 from typing import Any
 
 import numpy as np
@@ -22,7 +23,9 @@ from ..plugin_api import Plugin
 
 WAVE_SOURCE_AUTO = "auto"
 WAVE_SOURCE_RECORDS = "records"
-WAVE_SOURCES = {"auto", "records", "st_waveforms", "filtered_waveforms"}
+WAVE_SOURCE_ST = "st_waveforms"
+WAVE_SOURCE_FILTERED = "filtered_waveforms"
+WAVE_SOURCES = {WAVE_SOURCE_AUTO, WAVE_SOURCE_RECORDS, WAVE_SOURCE_ST, WAVE_SOURCE_FILTERED}
 
 
 def _cfg(context: Any, plugin: Any, name: str):
@@ -61,10 +64,6 @@ def records_dependencies(context: Any, plugin: Any) -> tuple[list[str], str]:
     if use_filtered and not fused:
         return ["records", "wave_pool_filtered"], "wave_pool_filtered"
     return ["records", "wave_pool"], "wave_pool"
-
-
-WAVE_SOURCE_ST = "st_waveforms"
-WAVE_SOURCE_FILTERED = "filtered_waveforms"
 
 
 def resolve_wave_input(context: Any, plugin: Any) -> tuple[str, list[str], str]:
@@ -186,7 +185,49 @@ def per_record_channel_option(records: np.ndarray, channel_config: Any, run_id: 
     return values[inverse.reshape(-1)]
 
 
+def fixed_baseline_per_record(records: np.ndarray, channel_config: Any, run_id: str) -> np.ndarray | None:
+    """The `fixed_baseline` of channel_config per record (NaN where a channel has none); None when no record has one."""
+    if not channel_config:
+        return None
+    fixed = per_record_channel_option(records, channel_config, run_id, "fixed_baseline", None, np.nan)
+    return None if np.all(np.isnan(fixed)) else fixed
+
+
+def records_with_dt(records: np.ndarray, dt_values: np.ndarray) -> np.ndarray:
+    """A copy of records that lack the `dt` column, with it appended (the device reads dt from the records)."""
+    out = np.zeros(len(records), dtype=np.dtype(records.dtype.descr + [("dt", "i4")]))
+    for n in records.dtype.names:
+        out[n] = records[n]
+    out["dt"] = dt_values
+    return out
+
+
+SRC_RAW, SRC_F32, SRC_SG_FUSED = _lib.SRC_RAW, _lib.SRC_F32, _lib.SRC_SG_FUSED
+
+
+def pool_source(pool: np.ndarray, raw_only: bool = False) -> int:
+    """SRC_RAW for a uint16 pool, SRC_F32 for a float32 one; raw_only: the caller reads wave_pool itself."""
+    if pool.dtype == np.uint16:
+        return SRC_RAW
+    if raw_only:
+        raise ValueError(f"wave_pool must be uint16, got {pool.dtype}")
+    if pool.dtype == np.float32:
+        return SRC_F32
+    raise ValueError(f"wave pool must be uint16 or float32, got {pool.dtype}")
+
+
+def float32_pool(pool: np.ndarray) -> tuple[np.ndarray, bool]:
+    """(wave_pool_filtered as float32, cacheable): an array of another type is converted, and the copy is a temporary."""
+    if pool.dtype == np.float32:
+        return pool, True
+    return np.asarray(pool, dtype=np.float32), False
+
+
 # ---- residency: keep the pool of a run on the GPU between plugin calls -----------------------------
+def _device_pool(context: Any):
+    return getattr(context, "wfa_device_pool", None) or default_pool()
+
+
 def resident_session(context: Any, pool: np.ndarray, pool_filtered: np.ndarray | None = None, *,
                      cacheable: bool = True) -> DeviceSession:
     """Session of this thread with `pool` on the device.
@@ -195,26 +236,14 @@ def resident_session(context: Any, pool: np.ndarray, pool_filtered: np.ndarray |
     strong reference, compared with `is`, dropped by every call that replaces a device pool -- upload_pool,
     pool_gather, the filters, close).  Pass cacheable=False for temporaries: dense `wave` fields, astype / asarray
     copies.  Arrays handed out by a Context (`get_data` memoises its results) are the cacheable case."""
-    pool_obj = getattr(context, "wfa_device_pool", None) or default_pool()
-    sess = note_session(pool_obj.session())
+    sess = note_session(_device_pool(context).session())
     sess.ensure_pool(pool, cacheable=cacheable)
     if pool_filtered is not None:
         sess.ensure_filtered_pool(pool_filtered, cacheable=cacheable)
     return sess
 
 
-def invalidate_residency(context: Any = None) -> None:
-    """Drop what this thread's session believes to be resident (kept for callers that replace a pool through
-    the session's own methods -- those reset the tags themselves)."""
-    from .. import device as _device
-
-    pool_obj = (getattr(context, "wfa_device_pool", None) if context is not None else None) or _device._default_pool
-    sess = getattr(pool_obj._local, "session", None) if pool_obj is not None else None
-    if sess is not None:
-        sess.forget_resident()
-
-
-# ---- several devices from one process: the `devices` option of the per-record plugins -------------------------------
+# ---- the records route of the per-record plugins, on one device or on several ---------------------------------------
 DEVICES_HELP = ("None: one device (the calling thread's session); a list of device ids (repeats allowed) or 'all': the "
                 "records route runs on those devices, one contiguous record range each, output identical "
                 "(wave_pool_filtered: each device fills the samples of its records, and its slice stays resident for "
@@ -222,20 +251,42 @@ DEVICES_HELP = ("None: one device (the calling thread's session); a list of devi
                 "device whatever this says.")
 
 
-def sharded_run(context: Any, devices) -> "multidevice.ShardedRun":
-    """The ShardedRun of this context and device tuple (multidevice.sharded_run): one session and one worker thread per
-    device, kept between calls so a pool stays resident on every shard."""
-    return multidevice.sharded_run(context, devices)
+def records_route(context: Any, plugin: Any, records: np.ndarray, pool: np.ndarray, row_dtype, run_pass,
+                  per_record=(), *, cacheable: bool = True, download=None, record_index_field: str | None = None):
+    """A plugin's pass over records + pool, on the devices its `devices` option names (read here and nowhere else).
 
+    run_pass(sess, records, *per_record, ...) is the pass on a session whose pool is resident: it uploads the records
+    it is given and runs the kernels.  `per_record`: arguments with one entry per record (or scalars, 0-d arrays,
+    None).  What else run_pass takes follows from what the plugin provides:
+      * one row per record (`download` None): out=None -> the rows, written into `out` when given.
+        record_index_field: a field of the rows that counts the records of a pass from 0 (`event_index`).
+      * any number of rows (`download` given): max_len=0, download=True -> the rows, or with download=False their
+        count, the rows left on the device for download(sess, out) (`download_hits` / `download_peaks`).  max_len is
+        the padded width of the hit pass, 0 = the longest uploaded record.
+      * a float32 pool (row_dtype None, wave_pool_filtered): download=True -> the filtered pool, or with
+        download=False None, the pool left on the device.
 
-SRC_RAW, SRC_F32, SRC_SG_FUSED = _lib.SRC_RAW, _lib.SRC_F32, _lib.SRC_SG_FUSED
+    devices=None: run_pass runs once on the calling thread's session (resident_session -- the session the other plugins
+    of the thread share) with `records` as they are; nothing per record happens on the host.  Otherwise the
+    context's ShardedRun of those devices splits the records into one contiguous range per device and calls run_pass
+    on each shard's worker: with its slice of the table as `out`, or with download=False and the run's padded width,
+    the rows then fetched into the run's one table (multidevice.ShardedRun.run / run_pool)."""
+    devices = context.get_config(plugin, "devices")
+    if devices is None:
+        return run_pass(resident_session(context, pool, cacheable=cacheable), records, *per_record)
+    run = multidevice.sharded_run(context, devices)
+    if row_dtype is None:
+        return run.run_pool(records, pool, partial(run_pass, download=False), per_record=per_record,
+                            cacheable=cacheable)
+    if download is None:
+        return run.run(records, pool, row_dtype, run_pass, per_record=per_record, cacheable=cacheable,
+                       record_index_field=record_index_field)
+    return run.run(records, pool, row_dtype,
+                   lambda sess, rec, *args, out, max_len: run_pass(sess, rec, *args, max_len=max_len, download=False),
+                   fetch=download, per_record=per_record, cacheable=cacheable, width_arg="max_len")
 
 
 # ---- the reference's profiling / statistics / cleanup hooks (SURVEY section 5) --------------------------------------
-def _device_pool(context: Any):
-    return getattr(context, "wfa_device_pool", None) or default_pool()
-
-
 def _hooks(context: Any):
     """(profiler, stats collector) of a reference Context when they are switched on
     (core/context_execution.py:140-149, core/foundation/utils.py:92-207, core/plugins/core/stats.py:103-520)."""

@@ -50,26 +50,15 @@ class HipBasicFeaturesPlugin(K.HipPlugin):
         records, pool = K.load_records_input(context, self, run_id, data_name)
         if len(records) == 0:
             return np.zeros(0, dtype=BASIC_FEATURES_DTYPE)
-        fixed = None
-        if channel_config:
-            fixed = K.per_record_channel_option(records, channel_config, run_id, "fixed_baseline", None, np.nan)
-            if np.all(np.isnan(fixed)):
-                fixed = None
-        if pool.dtype == np.float32:
-            source = K.SRC_F32
-        elif pool.dtype == np.uint16:
-            source = K.SRC_RAW
-        else:
-            raise ValueError(f"wave pool must be uint16 or float32, got {pool.dtype}")
-        devices = context.get_config(self, "devices")
-        if devices is not None:
-            def task(sess, rec_k, fixed_k, out):
-                records_pass(sess, rec_k, source, height_range, area_range, fixed_k, out=out)
+        fixed = K.fixed_baseline_per_record(records, channel_config, run_id)
+        source = K.pool_source(pool)
 
-            return K.sharded_run(context, devices).run(records, pool, BASIC_FEATURES_DTYPE, task, per_record=(fixed,),
-                                                       record_index_field="event_index")
-        sess = K.resident_session(context, pool)
-        return records_pass(sess, records, source, height_range, area_range, fixed)
+        def features(sess, rec, fixed_k, out=None):
+            sess.upload_records(rec)
+            return sess.basic_features(source, height_range, area_range, fixed_k, out=out)
+
+        return K.records_route(context, self, records, pool, BASIC_FEATURES_DTYPE, features, (fixed,),
+                               record_index_field="event_index")
 
     def _compute_dense(self, context, run_id, data_name, channel_config, height_range, area_range) -> np.ndarray:
         """basic_features.py:197-278: whole rows, wave-based formulas, sign from the literal "positive"."""
@@ -78,20 +67,7 @@ class HipBasicFeaturesPlugin(K.HipPlugin):
             return np.zeros(0, dtype=BASIC_FEATURES_DTYPE)
         pool, source, L = dense.dense_pool(data, data_name)
         records = dense.dense_records(data, L)
-        fixed = None
-        if channel_config:
-            fixed = K.per_record_channel_option(records, channel_config, run_id, "fixed_baseline", None, np.nan)
-            if np.all(np.isnan(fixed)):
-                fixed = None
+        fixed = K.fixed_baseline_per_record(records, channel_config, run_id)
         sess = K.resident_session(context, pool, cacheable=False)  # temporary of the dense `wave` field
         sess.upload_records(records, polarity=dense.dense_polarity_wave_rule(data))
         return sess.basic_features(source, height_range, area_range, fixed)
-
-
-def records_pass(sess, records: np.ndarray, source: int, height_range, area_range, fixed, out=None) -> np.ndarray:
-    """The per-session part of the records route, on a session whose pool is resident: one row per record (written into
-    `out` when given); event_index counts the session's records from 0."""
-    sess.upload_records(records)
-    if out is None:
-        return sess.basic_features(source, height_range, area_range, fixed)
-    return sess.basic_features(source, height_range, area_range, fixed, out=out)

@@ -107,8 +107,7 @@ class HipGroupedEventsPlugin(K.HipPlugin):
         tw = context.get_config(self, "time_window_ns")
         if tw is None:  # EventAnalyzer keeps its 100 ns
             tw = 100.0
-        pool_obj = getattr(context, "wfa_device_pool", None) or K.default_pool()
-        grouped = group_multi_channel_order(df, tw, session=K.note_session(pool_obj.session()))
+        grouped = group_multi_channel_order(df, tw, session=K.note_session(K._device_pool(context).session()))
         if grouped is None:
             return pd.DataFrame(columns=MULTI_CHANNEL_COLUMNS)
         frame, flat = build_events_frame(*grouped)

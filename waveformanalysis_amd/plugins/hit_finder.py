@@ -79,41 +79,21 @@ class HipHitFinderPlugin(K.HipPlugin):
         if height_method not in ("minmax", "diff"):
             raise ValueError(f"不支持的峰高计算方法: {height_method}")  # peak_finding.py:612
 
-        names = records.dtype.names or ()
-        if "dt" in names:
-            dt_values = np.asarray(records["dt"], dtype=np.int64)
-            if np.any(dt_values <= 0):
-                raise ValueError("[hit] dt must be > 0")  # peak_finding.py:542
-            if np.any(dt_values > np.iinfo(np.int32).max):
-                raise ValueError(f"[hit] dt exceeds int32 range: {int(dt_values.max())}")
-        elif explicit_dt is None:
-            raise ValueError("[hit] records is missing required field 'dt'; provide explicit config 'dt'.")
-        else:
-            dt_values = K.require_dt_array(records, explicit_dt=explicit_dt, plugin_name="hit", data_name="records")
-
-        rec = _records_for_upload(records, dt_values)
-        converted = False
+        rec = _records_for_upload(records, _dt_values(records, explicit_dt, "records"))
+        cacheable = True
         if pool_name == "wave_pool_filtered":
-            if pool.dtype != np.float32:
-                pool, converted = np.asarray(pool, dtype=np.float32), True
+            pool, cacheable = K.float32_pool(pool)
             source = K.SRC_F32
         else:
-            if pool.dtype != np.uint16:
-                raise ValueError(f"wave_pool must be uint16, got {pool.dtype}")
-            source = K.SRC_RAW
-        devices = context.get_config(self, "devices")
-        if devices is not None:
-            def task(sess, rec_k, out=None):
-                sess.upload_records(rec_k, np.zeros(len(rec_k), dtype=np.float64))
-                return sess.find_peaks(source, download=False, **peak_kw)
+            source = K.pool_source(pool, raw_only=True)
 
-            # rows carry record_id and timestamp, no record index: nothing to shift; shards in order = record order
-            return K.sharded_run(context, devices).run(rec, pool, HIT_DTYPE, task,
-                                                       fetch=lambda sess, out: sess.download_peaks(out),
-                                                       cacheable=not converted)
-        sess = K.resident_session(context, pool, cacheable=not converted)
-        sess.upload_records(rec, np.zeros(len(rec), dtype=np.float64))
-        return sess.find_peaks(source, **peak_kw)
+        def peaks(sess, rec_k, max_len=0, download=True):  # (find_peaks pads nothing: the run's width is not used)
+            sess.upload_records(rec_k, np.zeros(len(rec_k), dtype=np.float64))
+            return sess.find_peaks(source, download=download, **peak_kw)
+
+        # rows carry record_id and timestamp, no record index: nothing to shift; shards in order = record order
+        return K.records_route(context, self, rec, pool, HIT_DTYPE, peaks, cacheable=cacheable,
+                               download=lambda sess, out: sess.download_peaks(out))
 
     def _compute_dense(self, context, run_id, data_name, explicit_dt, peak_kw) -> np.ndarray:
         """peak_finding.py:316-378: the row (cut at event_length) is the waveform, pulses are negative-going."""
@@ -122,15 +102,8 @@ class HipHitFinderPlugin(K.HipPlugin):
             return np.zeros(0, dtype=HIT_DTYPE)
         if peak_kw["height_method"] not in ("minmax", "diff"):
             raise ValueError(f"不支持的峰高计算方法: {peak_kw['height_method']}")
-        names = data.dtype.names or ()
-        if "dt" not in names and explicit_dt is None:
-            raise ValueError("[hit] st_waveforms is missing required field 'dt'; provide explicit config 'dt'.")
-        dt_values = np.asarray(data["dt"], dtype=np.int64) if "dt" in names else np.full(len(data), int(explicit_dt), np.int64)
-        if np.any(dt_values <= 0):
-            raise ValueError("[hit] dt must be > 0")
-        if np.any(dt_values > np.iinfo(np.int32).max):
-            raise ValueError(f"[hit] dt exceeds int32 range: {int(dt_values.max())}")
-        if "baseline" not in names and not peak_kw["use_derivative"]:
+        dt_values = _dt_values(data, explicit_dt, "st_waveforms")  # the reference's text, whatever data_name is
+        if "baseline" not in (data.dtype.names or ()) and not peak_kw["use_derivative"]:
             raise ValueError(f"hit (HIP backend) needs a 'baseline' field on {data_name} when use_derivative=False")
         pool, source, L = dense.dense_pool(data, data_name)
         rec = dense.dense_records(data, L, keep_record_id=True, truncate_to_event_length=True)
@@ -138,6 +111,22 @@ class HipHitFinderPlugin(K.HipPlugin):
         sess = K.resident_session(context, pool, cacheable=False)  # `pool` is a temporary of the dense `wave` field
         sess.upload_records(rec, np.zeros(len(rec), dtype=np.float64))
         return sess.find_peaks(source, dense_rows=True, **peak_kw)
+
+
+def _dt_values(data: np.ndarray, explicit_dt, data_name: str) -> np.ndarray:
+    """dt per row (int64): the `dt` field, else the explicit option; positive and within int32
+    (peak_finding.py:535-545, its messages)."""
+    if "dt" in (data.dtype.names or ()):
+        dt_values = np.asarray(data["dt"], dtype=np.int64)
+    elif explicit_dt is None:
+        raise ValueError(f"[hit] {data_name} is missing required field 'dt'; provide explicit config 'dt'.")
+    else:
+        dt_values = np.full(len(data), int(explicit_dt), dtype=np.int64)
+    if np.any(dt_values <= 0):
+        raise ValueError("[hit] dt must be > 0")  # peak_finding.py:542
+    if np.any(dt_values > np.iinfo(np.int32).max):
+        raise ValueError(f"[hit] dt exceeds int32 range: {int(dt_values.max())}")
+    return dt_values
 
 
 def _records_for_upload(records: np.ndarray, dt_values: np.ndarray) -> np.ndarray:
@@ -148,21 +137,16 @@ def _records_for_upload(records: np.ndarray, dt_values: np.ndarray) -> np.ndarra
     two coincide; otherwise the waveform fields are taken from the row record_id points at.
     """
     names = records.dtype.names or ()
-    need_dt = "dt" not in names
-    descr = records.dtype.descr + ([("dt", "i4")] if need_dt else [])
     n = len(records)
     rid = np.asarray(records["record_id"], dtype=np.int64) if "record_id" in names else np.arange(n, dtype=np.int64)
-    if not need_dt and np.array_equal(rid, np.arange(n, dtype=np.int64)):
-        return records
-    out = np.zeros(n, dtype=np.dtype(descr))
-    for name in names:
-        out[name] = records[name]
-    if need_dt:
-        out["dt"] = dt_values
-    if not np.array_equal(rid, np.arange(n, dtype=np.int64)):
-        if np.any(rid < -n) or np.any(rid >= n):
-            raise IndexError(f"index {int(rid[(rid < -n) | (rid >= n)][0])} is out of bounds for axis 0 with size {n}")
-        for name in ("wave_offset", "event_length", "baseline", "polarity"):
-            if name in names:
-                out[name] = records[name][rid]
+    out = records if "dt" in names else K.records_with_dt(records, dt_values)
+    if np.array_equal(rid, np.arange(n, dtype=np.int64)):
+        return out
+    if np.any(rid < -n) or np.any(rid >= n):
+        raise IndexError(f"index {int(rid[(rid < -n) | (rid >= n)][0])} is out of bounds for axis 0 with size {n}")
+    if out is records:
+        out = records.copy()
+    for name in ("wave_offset", "event_length", "baseline", "polarity"):
+        if name in names:
+            out[name] = records[name][rid]
     return out

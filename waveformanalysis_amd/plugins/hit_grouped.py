@@ -47,7 +47,6 @@ class HipHitGroupedPlugin(K.HipPlugin):
         if source == "hit_merged":
             component_rows = context.get_data(run_id, "hit_merged_components")
             component_hits = context.get_data(run_id, "hit_threshold")
-        pool_obj = getattr(context, "wfa_device_pool", None) or K.default_pool()
         return group_hit_windows(hits, time_window_ns=time_window_ns, dt_values=dt_values,
                                  component_rows=component_rows, component_hits=component_hits,
-                                 session=K.note_session(pool_obj.session()))
+                                 session=K.note_session(K._device_pool(context).session()))

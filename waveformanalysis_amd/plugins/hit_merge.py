@@ -20,8 +20,7 @@ MERGE_OPTIONS = {
 
 
 def _session(context):
-    pool_obj = getattr(context, "wfa_device_pool", None) or K.default_pool()
-    return K.note_session(pool_obj.session())
+    return K.note_session(K._device_pool(context).session())
 
 
 def _clusters_or_compute(context, run_id, hits, cfg_plugin):

@@ -3,6 +3,7 @@
 
 from __future__ import annotations
 
+from functools import partial
 from typing import Any
 
 import numpy as np
@@ -75,39 +76,25 @@ class HipThresholdHitPlugin(K.HipPlugin):
                                                  threshold, threshold)
         rec = records
         if "dt" not in (records.dtype.names or ()):
-            rec = _with_dt(records, dt_values)
+            rec = K.records_with_dt(records, dt_values)
 
         cacheable = True
         if use_filtered and not fused:
-            converted = pool.dtype != np.float32
-            if converted:
-                pool = np.asarray(pool, dtype=np.float32)
-            cacheable = not converted
+            pool, cacheable = K.float32_pool(pool)
             source = K.SRC_F32
         else:
-            if pool.dtype != np.uint16:
-                raise ValueError(f"wave_pool must be uint16, got {pool.dtype}")
-            source = K.SRC_SG_FUSED if fused else K.SRC_RAW
+            source = K.pool_source(pool, raw_only=True)
+            if fused:
+                source = K.SRC_SG_FUSED
         sg = None
         if fused:
             fplugin = context.get_plugin("wave_pool_filtered") if "wave_pool_filtered" in getattr(context, "_plugins", {}) else None
             w = context.get_config(fplugin, "sg_window_size") if fplugin else 11
             p = context.get_config(fplugin, "sg_poly_order") if fplugin else 2
             sg = normalize_window(w, p)
-        devices = context.get_config(self, "devices")
-        if devices is not None:
-            # the run's padded width on every shard (hit_finder.py:354-370), not the shard's own
-            max_len = int(np.max(rec["event_length"]))
-
-            def task(sess, rec_k, thr_k, out=None):
-                return records_pass(sess, rec_k, thr_k, source, sg, fuse_baseline, le, re, max_len=max_len,
-                                    download=False)
-
-            run = K.sharded_run(context, devices)
-            return run.run(rec, pool, THRESHOLD_HIT_DTYPE, task, fetch=lambda sess, out: sess.download_hits(out),
-                           per_record=(thresholds,), cacheable=cacheable)
-        sess = K.resident_session(context, pool, cacheable=cacheable)
-        return records_pass(sess, rec, thresholds, source, sg, fuse_baseline, le, re)
+        return K.records_route(context, self, rec, pool, THRESHOLD_HIT_DTYPE,
+                               partial(records_pass, source=source, sg=sg, fuse_baseline=fuse_baseline, le=le, re=re),
+                               (thresholds,), cacheable=cacheable, download=lambda sess, out: sess.download_hits(out))
 
     def _compute_dense(self, context, run_id, data_name, threshold, le, re, explicit_dt, channel_config) -> np.ndarray:
         """hit_finder.py:179-255: the whole row is searched; the records/wave_pool length of the same record_id
@@ -143,12 +130,12 @@ class HipThresholdHitPlugin(K.HipPlugin):
         return hits
 
 
-def records_pass(sess, records: np.ndarray, thresholds, source: int, sg: tuple[int, int] | None, fuse_baseline,
+def records_pass(sess, records: np.ndarray, thresholds, *, source: int, sg: tuple[int, int] | None, fuse_baseline,
                  le: int, re: int, max_len: int = 0, download: bool = True):
-    """The per-session part of the records route, on a session whose pool is resident: records in, hit pass run ->
+    """The pass K.records_route runs, on a session whose pool is resident: records in, hit pass run ->
     THRESHOLD_HIT_DTYPE rows, or their count with download=False (rows left on the device).  sg: the Savitzky-Golay
     (window, order) of the fused filter, None for the raw / materialised sources.  max_len: the padded width (0 = the
-    longest uploaded record)."""
+    longest uploaded record; a shard gets the run's width, hit_finder.py:354-370, not its own)."""
     sess.upload_records(records, thresholds)
     if sg is not None:
         sess.set_sg_plan(*sg)
@@ -180,11 +167,3 @@ def _lengths_from_records(context: Any, run_id: str, record_ids: np.ndarray, sou
         raise ValueError("hit_threshold waveform source length does not match records/wave_pool length for "
                          f"record_id={int(record_ids[i])}: source={int(source_lengths[i])}, records={int(lengths[i])}")
     return lengths
-
-
-def _with_dt(records: np.ndarray, dt_values: np.ndarray) -> np.ndarray:
-    out = np.zeros(len(records), dtype=np.dtype(records.dtype.descr + [("dt", "i4")]))
-    for n in records.dtype.names:
-        out[n] = records[n]
-    out["dt"] = dt_values
-    return out

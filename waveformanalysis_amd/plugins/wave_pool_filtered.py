@@ -67,43 +67,24 @@ class HipWavePoolFilteredPlugin(K.HipPlugin):
             i = int(np.flatnonzero(bad)[0])
             raise ValueError("wave_pool_filtered found out-of-bounds wave slice "
                              f"(offset={int(off[i])}, length={int(length[i])}, wave_pool_size={len(wave_pool)})")
-        devices = context.get_config(self, "devices")
-        if devices is not None:
-            return _sharded(context, devices, records, wave_pool, groups)
-        sess = K.resident_session(context, wave_pool if isinstance(wave_pool, np.ndarray) else np.asarray(wave_pool),
-                                  cacheable=isinstance(wave_pool, np.ndarray))
-        out = run_filter_groups(sess, _view_records(records), groups)  # (the filters drop the float32 tag themselves)
-        if isinstance(wave_pool, np.ndarray):
-            sess.note_filtered(out)  # the device float32 pool is what `out` was just copied from: no upload for its readers
-        return out
+        keys, masks = zip(*groups)
 
+        def filters(sess, rec, *masks_k, download=True):
+            # the groups in the order one device runs them (SG, Butterworth, per-channel channel_config groups); of a
+            # shard's records, the groups that have any (one empty group where none has: the output is still zeroed)
+            mine = [(key, m) for key, m in zip(keys, masks_k) if m.any()] or [(keys[0], masks_k[0])]
+            out = run_filter_groups(sess, rec, mine, download=download)  # (the filters drop the float32 tag themselves)
+            if download:
+                sess.note_filtered(out)  # the device float32 pool is what `out` was just copied from: no upload for its readers
+            return out
 
-def _sharded(context: Any, devices, records: np.ndarray, wave_pool: np.ndarray, groups) -> np.ndarray:
-    """The `devices` route: ShardedRun.run_pool.  Every shard uploads its raw slice, runs the filter groups on its own
-    records in the order one device runs them (SG, Butterworth, per-channel channel_config groups) and downloads the
-    samples of its own records into its part of the one zero-filled output; gaps stay 0.0 (records.py:382).  Where
-    records of two shards share samples (hand-made layouts), the later write wins on one device (records.py:434-436)
-    and the outcome depends on the order of the writes: run_pool then runs the whole call on the first device, so the
-    output equals devices=None for every sample.  The shards' float32 slices stay resident, keyed on the returned array:
-    hit_threshold / basic_features / waveform_width_integral (use_filtered=True) and hit on it with the same devices
-    upload no pool."""
-    rec = _view_records(records)
-    group_of = np.full(len(rec), -1, dtype=np.int32)
-    for g, (_key, mask) in enumerate(groups):
-        group_of[mask] = g
-    length = rec["event_length"].astype(np.int64)
-    off = rec["wave_offset"].astype(np.int64)
-    idle = (length <= 0) & ((off < 0) | (off > len(wave_pool)))  # write nothing; their offsets would widen a shard's span
-    if np.any(idle):
-        rec, group_of = rec[~idle], group_of[~idle]
-    keys = [key for key, _mask in groups]
-
-    def task(sess, rec_k, group_k):
-        mine = [(key, group_k == g) for g, key in enumerate(keys)]
-        mine = [(key, m) for key, m in mine if m.any()] or [(keys[0], np.zeros(len(rec_k), dtype=bool))]
-        run_filter_groups(sess, rec_k, mine, download=False)
-
-    return K.sharded_run(context, devices).run_pool(rec, wave_pool, task, per_record=(group_of,))
+        # devices: every shard uploads its raw slice, filters its own records and downloads their samples into its part of
+        # the one zero-filled output, gaps stay 0.0 (records.py:382); records of two shards that share samples (hand-made
+        # layouts: the later write wins, records.py:434-436) send the whole call to the first device, so the output
+        # equals devices=None for every sample.  The shards' float32 slices stay resident, keyed on the returned array:
+        # hit_threshold / basic_features / waveform_width_integral (use_filtered=True) and hit on it with the same
+        # devices upload no pool (multidevice.ShardedRun.run_pool).
+        return K.records_route(context, self, _view_records(records), wave_pool, None, filters, masks)
 
 
 def _view_records(records: np.ndarray) -> np.ndarray:

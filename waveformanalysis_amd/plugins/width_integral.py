@@ -69,27 +69,11 @@ class HipWaveformWidthIntegralPlugin(K.HipPlugin):
             return sess.width_integral(source, q_low, q_high, float(dt))
         if len(records) == 0:
             return np.zeros(0, dtype=WAVEFORM_WIDTH_INTEGRAL_DTYPE)
-        if pool.dtype == np.float32:
-            source = K.SRC_F32
-        elif pool.dtype == np.uint16:
-            source = K.SRC_RAW
-        else:
-            raise ValueError(f"wave pool must be uint16 or float32, got {pool.dtype}")
-        devices = context.get_config(self, "devices")
-        if devices is not None:
-            def task(sess, rec_k, out):
-                records_pass(sess, rec_k, source, q_low, q_high, float(dt), out=out)
+        source = K.pool_source(pool)
 
-            return K.sharded_run(context, devices).run(records, pool, WAVEFORM_WIDTH_INTEGRAL_DTYPE, task,
-                                                       record_index_field="event_index")
-        sess = K.resident_session(context, pool)
-        return records_pass(sess, records, source, q_low, q_high, float(dt))
+        def widths(sess, rec, out=None):
+            sess.upload_records(rec)
+            return sess.width_integral(source, q_low, q_high, float(dt), out=out)
 
-
-def records_pass(sess, records: np.ndarray, source: int, q_low: float, q_high: float, dt: float, out=None) -> np.ndarray:
-    """The per-session part of the records route, on a session whose pool is resident: one row per record (written into
-    `out` when given); event_index counts the session's records from 0."""
-    sess.upload_records(records)
-    if out is None:
-        return sess.width_integral(source, q_low, q_high, dt)
-    return sess.width_integral(source, q_low, q_high, dt, out=out)
+        return K.records_route(context, self, records, pool, WAVEFORM_WIDTH_INTEGRAL_DTYPE, widths,
+                               record_index_field="event_index")
