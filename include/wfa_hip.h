@@ -384,7 +384,13 @@ int wfa_view_gather(wfa_ctx* ctx, int64_t n_rows, const int64_t* rec_index, int3
  * offset of row r in text (maps rows back to files), n_fields[r] = its field count.  Any output pointer but meta may
  * be NULL.  The samples stay resident: wfa_pool_gather with src_pool = NULL, src_samples = n_samples packs them
  * without a host round trip.  A requested field that is not a decimal integer, or a sample outside 0..65535, fails
- * with WFA_E_INVALID naming the row and field; other columns (ENERGY, FLAGS as hex, ...) are never parsed. */
+ * with WFA_E_INVALID naming the row and field; other columns (ENERGY, FLAGS as hex, ...) are never parsed.
+ * A decimal integer is [+-]?[0-9]{1,19} with a magnitude <= 2^63 - 1, and nothing else (no blanks, no empty field):
+ *   - a field of 20 or more digits is refused even when its value is small (leading zeros count);
+ *   - -9223372036854775808 is refused (the magnitude is tested before the sign is applied);
+ *   - a meta column a row does not have reads 0; a column listed twice in meta_cols is filled twice.
+ * Of several bad fields the one with the smallest (row, field) is named; "not a decimal integer" wins over the range
+ * message for the same field.  After a failed _fill no decoded samples are resident. */
 int wfa_csv_decode_count(wfa_ctx* ctx, const uint8_t* text, int64_t n_bytes, int delimiter, int32_t samples_start,
                          int64_t* n_rows, int64_t* n_samples);
 int wfa_csv_decode_fill(wfa_ctx* ctx, int64_t n_rows, int32_t n_meta, const int32_t* meta_cols, int64_t* meta,

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from tests import golden_util as G
+from tests import ingest_edges_util as U
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "waveformanalysis_amd", "csrc")
@@ -49,6 +50,19 @@ def test_v1725_header_walk_under_sanitizers(host_check, tmp_path):
     # the product's entry point runs the same function (wfa_hits.hip includes wfa_host.hpp)
     assert "host::v1725_index" in open(os.path.join(CSRC, "wfa_hits.hip")).read()
     assert "host::staged_copy" in open(os.path.join(CSRC, "wfa_capi.hip")).read()
+
+
+def test_v1725_walk_of_every_prefix_under_sanitizers(host_check, tmp_path):
+    """Every prefix 0..n of the crafted stream of tests/ingest_edges_util.py as an exact-size heap copy: the guards of
+    the walk (short event header, short channel header, short payload) each meet a buffer that ends exactly there.  The
+    digest over every column of every wave of every prefix is recomputed from the plain-Python walk."""
+    blob = U.v1725_prefix_stream()
+    path = tmp_path / "prefixes.bin"
+    path.write_bytes(blob)
+    got = run(host_check, "v1725-prefixes", path)
+    want = U.prefix_sweep_digest(blob)
+    assert want["waves"] > 5000 and want["prefixes"] == len(blob) + 1
+    assert got == want
 
 
 @pytest.mark.parametrize("nbytes,stage", [(50_000_000, 8 << 20), ((8 << 20) * 3, 8 << 20), (5, 4096), (1 << 20, 1 << 20),

@@ -4,6 +4,7 @@
 // in-order queue of asynchronous copies executed by one thread, with a completion stamp per staging buffer -- what the
 // HIP stream + events are to the real ring.
 //   host_check v1725 <blob file>     header walk over the whole stream and over every truncation of it
+//   host_check v1725-prefixes <blob file>  the walk over EVERY prefix 0..n of a small stream: wave total and a digest
 //   host_check ring <bytes> <stage>  staged copy of a pseudo-random buffer, compared byte for byte
 #include <atomic>
 #include <condition_variable>
@@ -106,6 +107,46 @@ int check_v1725(const char* path) {
     return 0;
 }
 
+// Every prefix length 0..n of the stream as an exactly-sized heap copy (a read behind it is a heap-buffer-overflow for
+// the sanitizer): count pass, fill pass, and one running digest over every column of every wave of every prefix, which
+// tests/test_host_sanitized.py recomputes from a plain-Python walk (tests/ingest_edges_util.py prefix_sweep_digest).
+int check_v1725_prefixes(const char* path) {
+    FILE* f = fopen(path, "rb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", path); return 2; }
+    std::vector<uint8_t> blob;
+    uint8_t tmp[4096];
+    size_t got;
+    while ((got = fread(tmp, 1, sizeof(tmp), f)) > 0) blob.insert(blob.end(), tmp, tmp + got);
+    fclose(f);
+    char err[160] = "";
+    uint64_t digest = 0, total = 0;
+    for (size_t cut = 0; cut <= blob.size(); ++cut) {
+        uint8_t* buf = (uint8_t*)malloc(cut ? cut : 1);  // cut == 0: one byte nobody may read
+        if (!buf) return 2;
+        if (cut) memcpy(buf, blob.data(), cut);
+        int64_t n = 0, n2 = 0;
+        int rc = wfa::host::v1725_index(buf, (int64_t)cut, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &n, err, sizeof(err));
+        std::vector<int16_t> ch((size_t)n);
+        std::vector<int64_t> ts((size_t)n), off((size_t)n);
+        std::vector<uint8_t> tr((size_t)n);
+        std::vector<uint16_t> bl((size_t)n);
+        std::vector<int32_t> ns((size_t)n);
+        if (!rc) rc = wfa::host::v1725_index(buf, (int64_t)cut, n, ch.data(), ts.data(), tr.data(), bl.data(), off.data(), ns.data(), &n2, err, sizeof(err));
+        free(buf);
+        if (rc || n2 != n) { fprintf(stderr, "prefix %zu: walk failed: %s\n", cut, err); return 1; }
+        for (int64_t k = 0; k < n; ++k) {
+            if (off[k] < 0 || off[k] + 2 * (int64_t)ns[k] > (int64_t)cut) { fprintf(stderr, "prefix %zu: wave %lld outside the prefix\n", cut, (long long)k); return 1; }
+            const uint64_t term = (uint64_t)ch[k] + 31ull * (uint64_t)ts[k] + 131ull * tr[k] + 8191ull * bl[k] +
+                                  65537ull * (uint64_t)off[k] + 1000033ull * (uint64_t)ns[k];
+            digest = digest * 1000003ull + term * (uint64_t)(k + 1);
+        }
+        total += (uint64_t)n;
+    }
+    printf("{\"prefixes\": %zu, \"waves\": %llu, \"digest\": %llu}\n", blob.size() + 1, (unsigned long long)total,
+           (unsigned long long)digest);
+    return 0;
+}
+
 int check_ring(size_t bytes, size_t stage_bytes) {
     std::vector<uint8_t> src(bytes), dst(bytes, 0);
     uint64_t s = 88172645463325252ull;
@@ -145,7 +186,8 @@ int check_ring(size_t bytes, size_t stage_bytes) {
 
 int main(int argc, char** argv) {
     if (argc == 3 && !strcmp(argv[1], "v1725")) return check_v1725(argv[2]);
+    if (argc == 3 && !strcmp(argv[1], "v1725-prefixes")) return check_v1725_prefixes(argv[2]);
     if (argc == 4 && !strcmp(argv[1], "ring")) return check_ring((size_t)atoll(argv[2]), (size_t)atoll(argv[3]));
-    fprintf(stderr, "usage: host_check v1725 <blob> | ring <bytes> <stage bytes>\n");
+    fprintf(stderr, "usage: host_check v1725 <blob> | v1725-prefixes <blob> | ring <bytes> <stage bytes>\n");
     return 2;
 }

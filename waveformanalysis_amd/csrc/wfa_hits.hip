@@ -788,10 +788,10 @@ __global__ __launch_bounds__(64) void k_csv_decode(int64_t n_rows, const uint8_t
             if (first) { q = lo; first = false; }
             else { const int b = __ffs(m) - 1; m &= m - 1; q = a + b + 1; ++f; }
             const int fidx = (q == lo) ? 0 : f;
-            int mj = -1;
-            for (int j = 0; j < cols.n_meta; ++j) if (cols.col[j] == fidx) mj = j;
+            bool is_meta = false;  // (a column may be requested more than once: every request is filled)
+            for (int j = 0; j < cols.n_meta; ++j) is_meta |= cols.col[j] == fidx;
             const bool is_sample = fidx >= samples_start;
-            if (mj < 0 && !is_sample) continue;
+            if (!is_meta && !is_sample) continue;
             int p = (int)(q - t0);
             const int p_end = (int)((hi - t0) < (int64_t)(kCsvTile + kCsvLook) ? (hi - t0) : (kCsvTile + kCsvLook));
             bool neg = false, any = false, bad = false;
@@ -810,7 +810,8 @@ __global__ __launch_bounds__(64) void k_csv_decode(int64_t n_rows, const uint8_t
                 continue;
             }
             const int64_t val = neg ? -(int64_t)v : (int64_t)v;
-            if (mj >= 0) meta[r * cols.n_meta + mj] = val;
+            for (int j = 0; j < cols.n_meta; ++j)
+                if (cols.col[j] == fidx) meta[r * cols.n_meta + j] = val;
             if (is_sample) {
                 if (val < 0 || val > 65535)
                     atomicMin(err, ((unsigned long long)r << 24) | ((unsigned long long)(fidx & 0x3fffff) << 2) | kCsvErrRange);
