@@ -71,3 +71,74 @@ def test_staging_ring_under_sanitizers(host_check, nbytes, stage):
     """Two staging buffers, asynchronous copies out of them: whole chunks, one byte over, less than a chunk, nothing."""
     got = run(host_check, "ring", nbytes, stage)
     assert got["bytes"] == nbytes and got["chunks"] == (nbytes + stage - 1) // stage
+
+
+def _layout_cases():
+    """Records tables (R, have_u16, off, len, pol) around every threshold of the uniform-layout rule."""
+    UNKNOWN, NEGATIVE, POSITIVE, POSITIVE_WAVE = 0, 1, 2, 3
+    cases = []
+
+    def table(R, L, off0, pol0):
+        r = np.arange(R, dtype=np.int64)
+        return off0 + r * L, np.full(R, L, np.int32), np.full(R, pol0, np.int8)
+
+    for R in (0, 1, 2, 130):
+        for L in (8, 16, 23, 24, 31, 32, 40, 44, 48, 64, 68, 88, 1500):
+            for off0 in (0, 3, 4, 8):
+                for pol0 in (UNKNOWN, POSITIVE):
+                    for have_u16 in (1, 0):
+                        cases.append((R, have_u16, *table(R, L, off0, pol0)))
+                if R < 2:
+                    continue
+                for at in (1, R - 1):   # uniformity broken at record 1 only / at the last record only
+                    off, ln, pol = table(R, L, off0, UNKNOWN)
+                    ln[at] += 8                              # length
+                    cases.append((R, 1, off, ln, pol))
+                    off, ln, pol = table(R, L, off0, UNKNOWN)
+                    off[at:] += 1                            # a one-sample gap in front of the record
+                    cases.append((R, 1, off, ln, pol))
+                    # polarity class: positive against everything else
+                    for pol0, other in ((UNKNOWN, POSITIVE), (POSITIVE, POSITIVE_WAVE), (POSITIVE, NEGATIVE),
+                                        (NEGATIVE, UNKNOWN), (UNKNOWN, POSITIVE_WAVE), (POSITIVE_WAVE, NEGATIVE)):
+                        off, ln, pol = table(R, L, off0, pol0)
+                        pol[at] = other
+                        cases.append((R, 1, off, ln, pol))
+    return cases
+
+
+def _layout_expected(R, have_u16, off, ln, pol):
+    """[uniform, span, pad, positive, L, S, off0] by the stated rule, in numpy."""
+    POSITIVE = 2
+    r = np.arange(R, dtype=np.int64)
+    uniform = R == 0 or bool(np.all(ln == ln[0]) and np.all(off == off[0] + r * int(ln[0]))
+                             and np.all((pol == POSITIVE) == (pol[0] == POSITIVE)))
+    if not uniform or R == 0:
+        return [int(uniform), 0, 0, 0, 0, 0, 0]
+    L, off0 = int(ln[0]), int(off[0])
+    span = L >= 24 and L % 8 == 0 and off0 % 8 == 0
+    pad = bool(have_u16) and L >= 32 and L % 16 != 0
+    if not span and not pad:
+        return [1, 0, 0, 0, 0, 0, 0]
+    return [1, int(span), int(pad), int(pol[0] == POSITIVE), L, (L + 15) // 16 * 16 if pad else L, off0]
+
+
+def test_uniform_layout_rule_under_sanitizers(host_check, tmp_path):
+    """Layout detection of a records upload (csrc/wfa_host.hpp records_uniform + uniform_layout, the one copy both upload
+    routes run): every table as exactly-sized heap columns, the expected layout recomputed here from the rule."""
+    cases = _layout_cases()
+    path = tmp_path / "layouts.bin"
+    with open(path, "wb") as f:
+        for R, have_u16, off, ln, pol in cases:
+            f.write(np.array([R, have_u16], np.int64).tobytes())
+            f.write(off.astype(np.int64).tobytes() + ln.astype(np.int32).tobytes() + pol.astype(np.int8).tobytes())
+    got = run(host_check, "layout", path)
+    want = [_layout_expected(*c) for c in cases]
+    assert got["cases"] == len(cases) > 1000
+    seen = {tuple(w[1:3]) for w in want}
+    assert seen == {(0, 0), (0, 1), (1, 0), (1, 1)}          # neither, padded only, span only, both
+    assert any(w[0] and not w[1] and not w[2] and c[0] > 0 for w, c in zip(want, cases))
+    for k, (g, w) in enumerate(zip(got["layouts"], want)):
+        assert g == w, (k, cases[k][0], cases[k][1], int(cases[k][3][0]) if cases[k][0] else None, g, w)
+    # both upload routes of the product run this copy
+    capi = open(os.path.join(CSRC, "wfa_capi.hip")).read()
+    assert capi.count("host::uniform_layout(") == 2 and capi.count("host::records_uniform(") == 1

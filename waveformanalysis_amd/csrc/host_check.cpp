@@ -6,6 +6,7 @@
 //   host_check v1725 <blob file>     header walk over the whole stream and over every truncation of it
 //   host_check v1725-prefixes <blob file>  the walk over EVERY prefix 0..n of a small stream: wave total and a digest
 //   host_check ring <bytes> <stage>  staged copy of a pseudo-random buffer, compared byte for byte
+//   host_check layout <cases file>   the uniform-record layout of every records table in the file
 #include <atomic>
 #include <condition_variable>
 #include <cstdlib>
@@ -182,12 +183,44 @@ int check_ring(size_t bytes, size_t stage_bytes) {
     return 0;
 }
 
+// File: cases back to back, each int64 R, int64 have_u16, then the columns off[R] (int64), len[R] (int32), pol[R] (int8).
+// Every column is an exactly-sized heap copy: a read past the last record is a heap-buffer-overflow for the sanitizer.
+int check_layout(const char* path) {
+    FILE* f = fopen(path, "rb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", path); return 2; }
+    printf("{\"layouts\": [");
+    int64_t head[2];
+    int n_cases = 0;
+    while (fread(head, sizeof(int64_t), 2, f) == 2) {
+        const size_t R = (size_t)head[0];
+        int64_t* off = (int64_t*)malloc(R ? R * sizeof(int64_t) : 1);  // R == 0: one byte nobody may read
+        int32_t* len = (int32_t*)malloc(R ? R * sizeof(int32_t) : 1);
+        int8_t* pol = (int8_t*)malloc(R ? R : 1);
+        if (!off || !len || !pol) return 2;
+        if (fread(off, sizeof(int64_t), R, f) != R || fread(len, sizeof(int32_t), R, f) != R || fread(pol, 1, R, f) != R) {
+            fprintf(stderr, "case %d is cut short\n", n_cases);
+            return 2;
+        }
+        const bool uniform = wfa::host::records_uniform((int64_t)R, off, len, pol);
+        const wfa::UniformLayout u = wfa::host::uniform_layout(uniform, (int64_t)R, R ? len[0] : 0, R ? off[0] : 0,
+                                                               R ? pol[0] : (int8_t)0, head[1] != 0);
+        printf("%s[%d, %d, %d, %d, %d, %d, %lld]", n_cases ? ", " : "", (int)uniform, (int)u.span, (int)u.pad, (int)u.positive,
+               (int)u.L, (int)u.S, (long long)u.off0);
+        free(off); free(len); free(pol);
+        ++n_cases;
+    }
+    fclose(f);
+    printf("], \"cases\": %d}\n", n_cases);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     if (argc == 3 && !strcmp(argv[1], "v1725")) return check_v1725(argv[2]);
     if (argc == 3 && !strcmp(argv[1], "v1725-prefixes")) return check_v1725_prefixes(argv[2]);
     if (argc == 4 && !strcmp(argv[1], "ring")) return check_ring((size_t)atoll(argv[2]), (size_t)atoll(argv[3]));
-    fprintf(stderr, "usage: host_check v1725 <blob> | v1725-prefixes <blob> | ring <bytes> <stage bytes>\n");
+    if (argc == 3 && !strcmp(argv[1], "layout")) return check_layout(argv[2]);
+    fprintf(stderr, "usage: host_check v1725 <blob> | v1725-prefixes <blob> | ring <bytes> <stage bytes> | layout <cases>\n");
     return 2;
 }

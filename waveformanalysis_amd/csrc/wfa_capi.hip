@@ -59,16 +59,21 @@ static int use_device(wfa_ctx* c) {
 constexpr size_t kStageBytes = 32u << 20;   // per staging buffer
 constexpr size_t kStageMin = 4u << 20;      // smaller copies go straight through hipMemcpyAsync
 
+// the pinned staging ring of the context, created by its first large copy in either direction
+static int ensure_stage(wfa_ctx* c) {
+    if (c->stage[0]) return WFA_OK;
+    for (int b = 0; b < 2; ++b) {
+        WFA_HIP_CHECK(hipHostMalloc(&c->stage[b], kStageBytes, hipHostMallocDefault));
+        WFA_HIP_CHECK(hipEventCreateWithFlags(&c->stage_ev[b], hipEventDisableTiming));
+    }
+    c->stage_bytes = kStageBytes;
+    return WFA_OK;
+}
+
 // host -> device through the context's pinned double buffer (see wfa_ctx::stage; the ring itself: wfa_host.hpp); returns
 // when the last chunk has landed
 static int h2d_staged(wfa_ctx* c, void* dst, const void* src, size_t bytes) {
-    if (!c->stage[0]) {
-        for (int b = 0; b < 2; ++b) {
-            WFA_HIP_CHECK(hipHostMalloc(&c->stage[b], kStageBytes, hipHostMallocDefault));
-            WFA_HIP_CHECK(hipEventCreateWithFlags(&c->stage_ev[b], hipEventDisableTiming));
-        }
-        c->stage_bytes = kStageBytes;
-    }
+    if (int rc = ensure_stage(c)) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     hipError_t err = hipSuccess;
     const int rc = host::staged_copy(
@@ -93,13 +98,7 @@ int h2d_copy(wfa_ctx* c, void* dst, const void* src, size_t bytes) {
 }
 
 int d2h_staged(wfa_ctx* c, void* dst, const void* src, size_t bytes, int (*queued)(void*), void* arg) {
-    if (!c->stage[0]) {
-        for (int b = 0; b < 2; ++b) {
-            WFA_HIP_CHECK(hipHostMalloc(&c->stage[b], kStageBytes, hipHostMallocDefault));
-            WFA_HIP_CHECK(hipEventCreateWithFlags(&c->stage_ev[b], hipEventDisableTiming));
-        }
-        c->stage_bytes = kStageBytes;
-    }
+    if (int rc = ensure_stage(c)) return rc;
     size_t prev_off = 0, prev_n = 0;
     int b = 0;
     for (size_t off = 0; off < bytes || prev_n; off += kStageBytes, b ^= 1) {
@@ -191,22 +190,51 @@ static int need_source(wfa_ctx* c, int source) {
     }
 }
 
-// padded shadow of the u16 pool (see wfa_ctx::pad_ok): built once per upload, on the device
+// padded shadow of the u16 pool (see wfa_ctx::layout): built once per upload, on the device
 static int ensure_shadow(wfa_ctx* c) {
     if (c->shadow_valid) return WFA_OK;
     int rc;
-    const size_t shadow_samples = (size_t)c->R * c->pad_S;
+    const UniformLayout& u = c->layout;
+    const size_t shadow_samples = (size_t)c->R * u.S;
     if ((rc = c->shadow_pool.ensure(shadow_samples * sizeof(uint16_t) + 256))) return rc;
     if ((rc = c->shadow_off.ensure((size_t)c->R * sizeof(int64_t)))) return rc;
     LaunchTimer t(c);
     WFA_HIP_CHECK(hipMemsetAsync(c->shadow_pool.as<uint8_t>() + shadow_samples * sizeof(uint16_t), 0, 256, c->stream));
-    WFA_HIP_CHECK(launch_pad_rows(c->stream, c->pool_u16.as<uint16_t>(), c->pad_off0, c->pad_L, c->pad_S, c->R,
+    WFA_HIP_CHECK(launch_pad_rows(c->stream, c->pool_u16.as<uint16_t>(), u.off0, u.L, u.S, c->R,
                                   c->shadow_pool.as<uint16_t>(), c->shadow_off.as<int64_t>()));
     if ((rc = t.end("k_pad_rows (once per upload)"))) return rc;
     c->shadow_valid = true;
     return WFA_OK;
 }
 
+// The pool, the records and the record geometry a pass over uniform records reads: in place, or (padded) through the
+// shadow, in which record r starts at sample r * S.  The one place that reads the shadow buffers; what of it a kernel's
+// parameter block takes, and in which convention, is the consumer's business.
+struct LayoutView {
+    PoolView pool;
+    RecView rec;        // (padded: `off` is the shadow's offsets column)
+    int32_t L, S;       // record length and stride; S == L in place
+    int64_t off0;       // first sample of record 0 in `pool`
+    int positive;
+};
+
+static int layout_view(wfa_ctx* c, bool padded, LayoutView* v) {
+    const UniformLayout& u = c->layout;
+    *v = LayoutView{pool_view(c), rec_view(c), u.L, u.L, u.off0, u.positive ? 1 : 0};
+    if (!padded) return WFA_OK;
+    if (int rc = ensure_shadow(c)) return rc;
+    v->pool.u16 = c->shadow_pool.as<uint16_t>();
+    v->pool.n = c->R * (int64_t)u.S;
+    v->rec.off = c->shadow_off.as<int64_t>();
+    v->S = u.S;
+    v->off0 = 0;
+    return WFA_OK;
+}
+
+// uniform records of the row stage (RowParams::uni_S: 0 = records back to back)
+static void row_layout(RowParams& rp, const LayoutView& v) {
+    rp.uni_L = v.L; rp.uni_S = v.S == v.L ? 0 : v.S; rp.uni_positive = v.positive; rp.uni_off0 = v.off0;
+}
 
 // ---- row stage of the fused hit pass (both routes) ----------------------------------------------------------------
 // Speculative launch: a pass usually finds about as many hits as the previous one on this context.  When the row buffers
@@ -313,18 +341,16 @@ static int run_hits_runs32(wfa_ctx* c, bool fused_bl, int32_t bl_start, int32_t 
     *done = false;
     if (c->no_runs32 || c->opt.no_runs32) return WFA_OK;
     const SgParams sp0 = sg_params(c);
-    SpanParams sp{};
-    bool padded = false;
-    if (c->span_ok && c->span_L % 32 == 0) {
-        sp.off0 = c->span_off0; sp.L = c->span_L; sp.S = c->span_L; sp.positive = c->span_positive;
-    } else if (c->pad_ok && c->pad_S % 32 == 0 && !c->opt.no_pad) {
-        padded = true;
-        sp.off0 = 0; sp.L = c->pad_L; sp.S = c->pad_S; sp.positive = c->pad_positive;
-    } else {
-        return WFA_OK;
-    }
-    if (!sg_runs32_supported(sp0, sp.L, sp.S, bl_start, bl_end, fused_bl)) return WFA_OK;
+    const UniformLayout& u = c->layout;
+    const bool in_place = u.span && u.L % 32 == 0;
+    const bool padded = !in_place && u.pad && u.S % 32 == 0 && !c->opt.no_pad;
+    if (!in_place && !padded) return WFA_OK;
+    if (!sg_runs32_supported(sp0, u.L, padded ? u.S : u.L, bl_start, bl_end, fused_bl)) return WFA_OK;
     int rc;
+    LayoutView v;
+    if ((rc = layout_view(c, padded, &v))) return rc;
+    SpanParams sp{};
+    sp.off0 = v.off0; sp.L = v.L; sp.S = v.S; sp.positive = v.positive;
     const int64_t R = c->R;
     int32_t g_wstride = 0, g_nseg = 0, g_segw = 0;
     sg_runs32_geometry(sp.S, &sp.rs, &g_wstride, &g_nseg, &g_segw);
@@ -345,16 +371,8 @@ static int run_hits_runs32(wfa_ctx* c, bool fused_bl, int32_t bl_start, int32_t 
     if (new_ctrl) c->run_cold_valid = false;
     if (new_ctrl || new_groups) c->run_dirty_groups = (int64_t)(c->run_groups.cap / sizeof(unsigned long long));
 
-    PoolView pvf = pool_view(c);
-    RecView rvf = rec_view(c);
-    if (padded) {
-        if ((rc = ensure_shadow(c))) return rc;
-        pvf.u16 = c->shadow_pool.as<uint16_t>();
-        pvf.n = c->R * (int64_t)c->pad_S;
-        rvf.off = c->shadow_off.as<int64_t>();
-    }
     RowParams rp{le, re, max_len, sp0.W / 2};
-    rp.uni_L = sp.L; rp.uni_S = sp.S == sp.L ? 0 : sp.S; rp.uni_positive = sp.positive ? 1 : 0; rp.uni_off0 = sp.off0;
+    row_layout(rp, v);
     int64_t* d_total = c->run_scan_blocks.as<int64_t>() + nb;
     auto* ctrl = c->run_ctrl.as<unsigned long long>();  // [0] event cursor, [1] flags, [2] hits listed for the literal kernel
     constexpr int kLitCap = 65536;
@@ -384,7 +402,7 @@ static int run_hits_runs32(wfa_ctx* c, bool fused_bl, int32_t bl_start, int32_t 
         c->run_dirty_groups = 0;
     }
     RunsArgs ra{};
-    ra.pool = pvf.u16; ra.thr = rvf.thr; ra.baseline = rvf.baseline_rw; ra.R = R;
+    ra.pool = v.pool.u16; ra.thr = v.rec.thr; ra.baseline = v.rec.baseline_rw; ra.R = R;
     ra.itab = sp0.itab; ra.den = sp0.den; ra.margin = sp0.margin;
     ra.den_edge = sp0.den_edge; ra.margin_edge = sp0.margin_edge;
     // sg_plan.py: guard = 8 eps den^2 2^24 + 1 with eps = bound on |scipy's float64 chain - exact rational|; here in
@@ -400,7 +418,7 @@ static int run_hits_runs32(wfa_ctx* c, bool fused_bl, int32_t bl_start, int32_t 
     ra.cold = reinterpret_cast<const RunsCold*>(ctrl + 32);  // 256 bytes behind the atomically updated words
     {
         // what the float64 reference paths read: a device copy next to the control words, refreshed when it changes
-        RunsCold cold{pvf, sp0};
+        RunsCold cold{v.pool, sp0};
         if (!c->run_cold_valid || memcmp(&cold, &c->run_cold_host, sizeof(cold)) != 0) {
             memcpy(c->h_cold, &cold, sizeof(cold));
             WFA_HIP_CHECK(hipMemcpyAsync(ctrl + 32, c->h_cold, sizeof(cold), hipMemcpyHostToDevice, c->stream));
@@ -426,7 +444,7 @@ static int run_hits_runs32(wfa_ctx* c, bool fused_bl, int32_t bl_start, int32_t 
                                   c->run_span_row0.as<int64_t>()));
         return t.end("k_scan(span hit counts)");
     };
-    return run_rows(c, pvf, rvf, sp0, rp, d_total, ctrl, rn.group_sum, desc, count,
+    return run_rows(c, v.pool, v.rec, sp0, rp, d_total, ctrl, rn.group_sum, desc, count,
                     {WFA_SRC_SG_FUSED, fused_bl, bl_start, bl_end, le, re, max_len, 0, true}, enqueue_only, n_hits, done);
 }
 
@@ -462,8 +480,6 @@ static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int
     if ((rc = c->scan_blocks.ensure((nb + 1) * sizeof(int64_t)))) return rc;
     if ((rc = c->cursor.ensure(sizeof(unsigned long long)))) return rc;
 
-    const PoolView pv0 = pool_view(c);
-    const RecView rv0 = rec_view(c);
     const SgParams sp0 = sg_params(c);
     if (source == WFA_SRC_SG_FUSED && sg_mask_supported(sp0) && !c->opt.no_fast) {
         {
@@ -483,37 +499,26 @@ static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int
         mp.bitmap = c->bitmap.as<uint8_t>();
         mp.rec_nhits = c->rec_nhits.as<int32_t>();
         // views the kernels of this pass read: the uploaded layout, or the padded shadow of it
-        PoolView pvf = pv0;
-        RecView rvf = rv0;
-        const bool padded = c->pad_ok && sg_mask_span16_padded_supported(sp0, c->pad_L) && !c->opt.no_pad &&
-                            !c->opt.no_span;
-        if (padded) {
-            if ((rc = ensure_shadow(c))) return rc;
-            pvf.u16 = c->shadow_pool.as<uint16_t>();
-            pvf.n = c->R * (int64_t)c->pad_S;
-            rvf.off = c->shadow_off.as<int64_t>();
-        }
-        if (padded || (c->span_ok && c->span_L >= sp0.W && !c->opt.no_span)) {
-            SpanParams sp{};
-            sp.off0 = c->span_off0; sp.L = c->span_L; sp.positive = c->span_positive;
-            if (padded) { sp.off0 = 0; sp.L = c->pad_L; sp.S = c->pad_S; sp.positive = c->pad_positive; }
-            const int32_t span_L = sp.L;
-            sp.rs = 64;
-            sp.n_spans = (R + sp.rs - 1) / sp.rs;
-            sp.bm_off0 = 0;
-            sp.bm_stride = ((int64_t)span_L + 7 + 63) / 64 * 8 + 8;
+        const UniformLayout& u = c->layout;
+        const bool padded = u.pad && sg_mask_span16_padded_supported(sp0, u.L) && !c->opt.no_pad && !c->opt.no_span;
+        LayoutView v;
+        if ((rc = layout_view(c, padded, &v))) return rc;
+        {
             LaunchTimer t(c, true);
-            if (padded || (sg_mask_span16_supported(sp0, span_L))) {
-                WFA_HIP_CHECK(launch_sg_mask_span16(c->stream, fused_bl, pvf, rvf, sp0, mp, sp));
+            if (padded || (u.span && u.L >= sp0.W && !c->opt.no_span && sg_mask_span16_supported(sp0, u.L))) {
+                SpanParams sp{};
+                sp.off0 = v.off0; sp.L = v.L; sp.positive = v.positive;
+                if (padded) sp.S = v.S;  // (in place: 0)
+                sp.rs = 64;
+                sp.n_spans = (R + sp.rs - 1) / sp.rs;
+                sp.bm_off0 = 0;
+                sp.bm_stride = ((int64_t)sp.L + 7 + 63) / 64 * 8 + 8;
+                WFA_HIP_CHECK(launch_sg_mask_span16(c->stream, fused_bl, v.pool, v.rec, sp0, mp, sp));
                 if ((rc = t.end(fused_bl ? "k_sg_mask_span16<baseline>" : "k_sg_mask_span16"))) return rc;
             } else {
-                WFA_HIP_CHECK(launch_sg_mask(c->stream, fused_bl, c->max_len, pvf, rvf, sp0, mp));
+                WFA_HIP_CHECK(launch_sg_mask(c->stream, fused_bl, c->max_len, v.pool, v.rec, sp0, mp));
                 if ((rc = t.end(fused_bl ? "k_sg_mask<baseline>" : "k_sg_mask"))) return rc;
             }
-        } else {
-            LaunchTimer t(c, true);
-            WFA_HIP_CHECK(launch_sg_mask(c->stream, fused_bl, c->max_len, pvf, rvf, sp0, mp));
-            if ((rc = t.end(fused_bl ? "k_sg_mask<baseline>" : "k_sg_mask"))) return rc;
         }
         {
             LaunchTimer t(c);
@@ -522,8 +527,7 @@ static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int
             if ((rc = t.end("k_scan(hit counts)"))) return rc;
         }
         RowParams rp{le, re, max_len, sp0.W / 2};
-        if (padded) { rp.uni_L = c->pad_L; rp.uni_S = c->pad_S; rp.uni_positive = c->pad_positive ? 1 : 0; rp.uni_off0 = 0; }
-        else if (c->span_ok) { rp.uni_L = c->span_L; rp.uni_positive = c->span_positive ? 1 : 0; rp.uni_off0 = c->span_off0; }
+        if (padded || u.span) row_layout(rp, v);
         {
             // mask bytes of one block's records (+16 for the aligned start), rounded up to 1 KiB
             const int64_t per_rec = ((int64_t)c->max_len + 7 + 63) / 64 * 8 + 8;
@@ -532,12 +536,12 @@ static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int
         }
         auto desc = [&](const RowParams& r) -> int {
             LaunchTimer t(c);
-            WFA_HIP_CHECK(launch_hit_runs(c->stream, rvf, c->bitmap.as<uint8_t>(), c->rec_nhits.as<int32_t>(),
+            WFA_HIP_CHECK(launch_hit_runs(c->stream, v.rec, c->bitmap.as<uint8_t>(), c->rec_nhits.as<int32_t>(),
                                           c->rec_out_start.as<int64_t>(), c->hit_desc.as<int4>(), r));
             return t.end("k_hit_runs");
         };
         bool done = false;  // (no event buffers on this route: always done)
-        return run_rows(c, pvf, rvf, sp0, rp, c->scan_blocks.as<int64_t>() + nb, nullptr, nullptr, desc, [] { return WFA_OK; },
+        return run_rows(c, v.pool, v.rec, sp0, rp, c->scan_blocks.as<int64_t>() + nb, nullptr, nullptr, desc, [] { return WFA_OK; },
                         {source, fused_bl, bl_start, bl_end, le, re, max_len, 0, false}, enqueue_only, n_hits, &done);
     }
 
@@ -746,16 +750,6 @@ void wfa_ctx_destroy(wfa_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->comm) (void)wfa_rccl_destroy(c);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    DevBuf* bufs[] = {&c->pool_u16, &c->pool_f32, &c->off, &c->len, &c->baseline, &c->pol, &c->thr,
-                      &c->ts, &c->dt, &c->board, &c->chan, &c->rid, &c->fixed_bl, &c->bm_off, &c->bitmap,
-                      &c->hit_desc, &c->bw_scratch, &c->peak_out, &c->peak_cand_n, &c->peak_cand_pos, &c->peak_cand_val, &c->peak_slot_pos, &c->peak_slot_val,
-                        &c->peak_cand_state, &c->peak_cand_rec, &c->peak_accept, &c->peak_ips, &c->peak_row_start, &c->wh_pos, &c->wh_row, &c->wh_valid, &c->sg.tab,
-                      &c->sg.itab, &c->sg.sym, &c->hit_tmp, &c->cursor, &c->rec_tmp_start,
-                      &c->rec_nhits, &c->rec_out_start, &c->scan_blocks, &c->hit_out, &c->out_rows, &c->out_rows2,
-                      &c->gathered, &c->pw_plan, &c->fw_ties, &c->run_ev, &c->run_span_off, &c->run_span_cnt, &c->run_span_row0, &c->run_scan_blocks, &c->run_ctrl, &c->run_groups, &c->run_lit,
-                      &c->shadow_pool, &c->shadow_off, &c->csv_arena};
-    for (DevBuf* b : bufs) b->release();
-    for (DevBuf& b : c->ht) b.release();
     if (c->h_total) (void)hipHostFree(c->h_total);
     for (int b = 0; b < 2; ++b) {
         if (c->stage[b]) (void)hipHostFree(c->stage[b]);
@@ -767,23 +761,13 @@ void wfa_ctx_destroy(wfa_ctx* c) {
     for (hipEvent_t e : c->prof_free) (void)hipEventDestroy(e);
     c->prof_free.clear();
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-}
-
-// the buffers wfa_release_scratch gives back: the hit-table slots and the per-pass scratch
-static std::vector<DevBuf*> scratch_bufs(wfa_ctx* c) {
-    std::vector<DevBuf*> bufs = {&c->bitmap, &c->hit_tmp, &c->bw_scratch, &c->peak_cand_n, &c->peak_cand_pos, &c->peak_cand_val,
-                                 &c->peak_slot_pos, &c->peak_slot_val, &c->peak_cand_state, &c->peak_cand_rec, &c->peak_accept,
-                                 &c->peak_ips, &c->peak_row_start, &c->wh_pos, &c->wh_row, &c->wh_valid, &c->fw_ties, &c->run_ev,
-                                 &c->shadow_pool, &c->shadow_off};
-    for (DevBuf& b : c->ht) bufs.push_back(&b);
-    return bufs;
+    delete c;  // every DevBuf frees its memory
 }
 
 int wfa_scratch_bytes(wfa_ctx* c, int64_t* bytes) {
     if (!c || !bytes) return fail(WFA_E_INVALID, "null argument");
     int64_t held = 0;
-    for (DevBuf* b : scratch_bufs(c)) held += (int64_t)b->cap;
+    for (DevBuf* b : c->scratch) held += (int64_t)b->cap;
     *bytes = held;
     return WFA_OK;
 }
@@ -798,14 +782,13 @@ int wfa_release_scratch(wfa_ctx* c, int64_t* freed_bytes) {
     // samples of the last wfa_csv_decode_fill live in a scratch slot: they go, and wfa_pool_gather(src_pool = NULL) refuses
     // until the next decode.
     int64_t freed = 0;
-    for (DevBuf* b : scratch_bufs(c)) { freed += (int64_t)b->cap; b->release(); }  // (a count pass without its fill is void after this)
+    for (DevBuf* b : c->scratch) { freed += (int64_t)b->cap; b->release(); }  // (a count pass without its fill is void after this)
     c->ht_n = -1;
     c->ht_perm = nullptr;
     c->csv_rows = -1;
     c->csv_samples = -1;
     c->csv_filled = false;
-    c->bitmap_clean = false;
-    c->shadow_valid = false;
+    pass_caches_dropped(c);
     c->hit_tmp_rows = 0;
     if (freed_bytes) *freed_bytes = freed;
     return WFA_OK;
@@ -847,13 +830,7 @@ int wfa_upload_pool_u16(wfa_ctx* c, const uint16_t* pool, int64_t n) {
     if (n < 0 || (n > 0 && !pool)) return fail(WFA_E_INVALID, "bad wave_pool argument");
     if ((rc = h2d(c, c->pool_u16, pool, (size_t)n * sizeof(uint16_t)))) return rc;
     WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    c->pool_n = n;
-    c->have_u16 = true;
-    c->have_f32 = false;  // a filtered pool belongs to the previous wave_pool
-    c->filter_keep = false;
-    c->have_records = false;
-    c->shadow_valid = false;
-    c->pad_ok = false;
+    pool_replaced(c, n, true);
     return WFA_OK;
 }
 
@@ -864,11 +841,7 @@ int wfa_upload_pool_f32(wfa_ctx* c, const float* pool, int64_t n) {
     if (c->have_u16 && n != c->pool_n) c->have_u16 = false;  // a different run: the resident wave_pool is stale
     if ((rc = h2d(c, c->pool_f32, pool, (size_t)n * sizeof(float)))) return rc;
     WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (!c->have_u16) {
-        c->pool_n = n;
-        c->have_records = false;
-    }
-    c->have_f32 = true;
+    pool_replaced(c, n, false);
     return WFA_OK;
 }
 
@@ -904,31 +877,8 @@ int wfa_upload_records_soa(wfa_ctx* c, int64_t R, const int64_t* off, const int3
         bm_off[(size_t)r] = bm_total;
         bm_total += ((int64_t)len[r] + 7 + 63) / 64 * 8 + 8;
     }
-    c->bitmap_bytes = bm_total + 64;
-    c->bitmap_clean = false;
-    // span mode: every record the same length (multiple of 8, >= 24), laid out back to back from a
-    // 16-byte aligned start, one polarity class
-    c->span_ok = R > 0 && len[0] >= 24 && (len[0] % 8) == 0 && (off[0] % 8) == 0;
-    for (int64_t r = 0; c->span_ok && r < R; ++r)
-        c->span_ok = len[r] == len[0] && off[r] == off[0] + r * (int64_t)len[0] &&
-                     (pol[r] == WFA_POL_POSITIVE) == (pol[0] == WFA_POL_POSITIVE);
-    if (c->span_ok) {
-        c->span_L = len[0];
-        c->span_off0 = off[0];
-        c->span_positive = pol[0] == WFA_POL_POSITIVE;
-    }
-    // padded shadow layout: uniform, back-to-back records whose length is not a multiple of 16 samples (VX2730: 1500)
-    c->shadow_valid = false;
-    c->pad_ok = R > 0 && c->have_u16 && len[0] >= 32 && (len[0] % 16) != 0;
-    for (int64_t r = 0; c->pad_ok && r < R; ++r)
-        c->pad_ok = len[r] == len[0] && off[r] == off[0] + r * (int64_t)len[0] &&
-                    (pol[r] == WFA_POL_POSITIVE) == (pol[0] == WFA_POL_POSITIVE);
-    if (c->pad_ok) {
-        c->pad_L = len[0];
-        c->pad_S = (len[0] + 15) / 16 * 16;
-        c->pad_off0 = off[0];
-        c->pad_positive = pol[0] == WFA_POL_POSITIVE;
-    }
+    const bool uniform = host::records_uniform(R, off, len, pol);
+    const UniformLayout layout = host::uniform_layout(uniform, R, R ? len[0] : 0, R ? off[0] : 0, R ? pol[0] : 0, c->have_u16);
     const size_t n = (size_t)R;
     if ((rc = h2d(c, c->bm_off, bm_off.data(), n * 8))) return rc;
     if ((rc = h2d(c, c->off, off, n * 8))) return rc;
@@ -942,13 +892,7 @@ int wfa_upload_records_soa(wfa_ctx* c, int64_t R, const int64_t* off, const int3
     if ((rc = h2d(c, c->chan, chan, n * 2))) return rc;
     if ((rc = h2d(c, c->rid, rid, n * 8))) return rc;
     WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    c->R = R;
-    c->max_len = max_len;
-    c->pw_plan_n = -1;
-    c->no_runs32 = false;
-    c->have_records = true;
-    c->len_host_valid = false;
-    c->n_hits = -1;
+    records_replaced(c, R, max_len, bm_total + 64, layout);
     return WFA_OK;
 }
 
@@ -979,13 +923,11 @@ int wfa_upload_records_packed(wfa_ctx* c, const void* rows, int64_t R, int32_t r
         (rc = c->thr.ensure(n * 8)) || (rc = c->ts.ensure(n * 8)) || (rc = c->dt.ensure(n * 4)) || (rc = c->board.ensure(n * 2)) ||
         (rc = c->chan.ensure(n * 2)) || (rc = c->rid.ensure(n * 8)) || (rc = c->bm_off.ensure(n * 8)))
         return rc;
-    c->have_records = false;
-    c->R = 0;
+    records_dropped(c);  // from here on a failure leaves the context without records
     int32_t max_len = 0;
     bool increasing = true;
-    c->span_ok = c->pad_ok = false;
-    c->shadow_valid = false;
-    c->bitmap_bytes = 64;
+    int64_t bitmap_bytes = 64;
+    UniformLayout layout;
     if (R > 0) {
         // scratch: the rows, per-record bitmap bytes, the optional per-record columns of the caller, the result block
         DevBuf d_rows, d_bm, d_thr, d_pol, d_res, d_blocks;
@@ -1013,12 +955,12 @@ int wfa_upload_records_packed(wfa_ctx* c, const void* rows, int64_t R, int32_t r
         }
         UnpackResult res{};
         int64_t bm_total = 0;
-        int64_t first[2] = {0, 0};
+        int64_t off0 = 0;
         int32_t len0 = 0;
         int8_t pol0 = 0;
         WFA_HIP_CHECK(hipMemcpyAsync(&res, d_res.ptr, sizeof(res), hipMemcpyDeviceToHost, c->stream));
         WFA_HIP_CHECK(hipMemcpyAsync(&bm_total, d_blocks.as<int64_t>() + nb, 8, hipMemcpyDeviceToHost, c->stream));
-        WFA_HIP_CHECK(hipMemcpyAsync(&first[0], c->off.ptr, 8, hipMemcpyDeviceToHost, c->stream));
+        WFA_HIP_CHECK(hipMemcpyAsync(&off0, c->off.ptr, 8, hipMemcpyDeviceToHost, c->stream));
         WFA_HIP_CHECK(hipMemcpyAsync(&len0, c->len.ptr, 4, hipMemcpyDeviceToHost, c->stream));
         WFA_HIP_CHECK(hipMemcpyAsync(&pol0, c->pol.ptr, 1, hipMemcpyDeviceToHost, c->stream));
         WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -1039,21 +981,10 @@ int wfa_upload_records_packed(wfa_ctx* c, const void* rows, int64_t R, int32_t r
         }
         max_len = res.max_len;
         increasing = res.rid_not_increasing == 0;
-        c->bitmap_bytes = bm_total + 64;
-        const bool uniform = res.nonuniform == 0;
-        c->span_ok = uniform && len0 >= 24 && (len0 % 8) == 0 && (first[0] % 8) == 0;
-        if (c->span_ok) { c->span_L = len0; c->span_off0 = first[0]; c->span_positive = pol0 == WFA_POL_POSITIVE; }
-        c->pad_ok = uniform && c->have_u16 && len0 >= 32 && (len0 % 16) != 0;
-        if (c->pad_ok) { c->pad_L = len0; c->pad_S = (len0 + 15) / 16 * 16; c->pad_off0 = first[0]; c->pad_positive = pol0 == WFA_POL_POSITIVE; }
+        bitmap_bytes = bm_total + 64;
+        layout = host::uniform_layout(res.nonuniform == 0, R, len0, off0, pol0, c->have_u16);
     }
-    c->bitmap_clean = false;
-    c->R = R;
-    c->max_len = max_len;
-    c->pw_plan_n = -1;
-    c->no_runs32 = false;
-    c->have_records = true;
-    c->len_host_valid = false;
-    c->n_hits = -1;
+    records_replaced(c, R, max_len, bitmap_bytes, layout);
     if (max_len_out) *max_len_out = max_len;
     if (record_ids_increasing) *record_ids_increasing = increasing ? 1 : 0;
     return WFA_OK;
@@ -1160,31 +1091,25 @@ int wfa_savgol(wfa_ctx* c, float* out) {
     // gaps between records stay 0.0 (records.py:382)
     if (!c->filter_keep) WFA_HIP_CHECK(hipMemsetAsync(c->pool_f32.ptr, 0, (size_t)c->pool_n * sizeof(float), c->stream));
     if (c->R > 0) {
-        PoolView pv = pool_view(c);
         const SgParams sp0 = sg_params(c);
-        const bool padded = c->pad_ok && c->pad_L >= sp0.W && sg_mask_supported(sp0) && !c->opt.no_fast &&
-                            !c->opt.no_pad;
-        if (padded && (rc = ensure_shadow(c))) return rc;
+        const UniformLayout& u = c->layout;
+        const bool fast = sg_mask_supported(sp0) && !c->opt.no_fast;
+        // uniform records, L % 16 != 0: the span kernel reads the padded shadow and writes the packed pool
+        const bool padded = u.pad && u.L >= sp0.W && fast && !c->opt.no_pad;
+        LayoutView v;
+        if ((rc = layout_view(c, padded, &v))) return rc;
         LaunchTimer t(c);
-        if (padded) {  // uniform records, L % 16 != 0: span kernel reading the padded shadow, writing the packed pool
+        if (padded || (u.span && u.L >= 16 && u.L >= sp0.W && fast)) {
             SpanParams sp{};
-            sp.off0 = 0; sp.L = c->pad_L; sp.S = c->pad_S; sp.out_off0 = c->pad_off0; sp.positive = 0;
+            sp.off0 = v.off0; sp.L = v.L; sp.positive = 0;
+            if (padded) { sp.S = v.S; sp.out_off0 = u.off0; }
             sp.rs = 64;
             sp.n_spans = (c->R + sp.rs - 1) / sp.rs;
-            pv.u16 = c->shadow_pool.as<uint16_t>();
-            pv.n = c->R * (int64_t)c->pad_S;
-            WFA_HIP_CHECK(launch_savgol_span(c->stream, pv, rec_view(c), sp0, sp, c->pool_f32.as<float>()));
-            if ((rc = t.end("k_savgol_span<padded>"))) return rc;
-        } else if (c->span_ok && c->span_L >= 16 && c->span_L >= sp0.W && sg_mask_supported(sp0) &&
-            !c->opt.no_fast) {
-            SpanParams sp{};
-            sp.off0 = c->span_off0; sp.L = c->span_L; sp.positive = 0;
-            sp.rs = 64;
-            sp.n_spans = (c->R + sp.rs - 1) / sp.rs;
-            WFA_HIP_CHECK(launch_savgol_span(c->stream, pv, rec_view(c), sp0, sp, c->pool_f32.as<float>()));
-            if ((rc = t.end("k_savgol_span"))) return rc;
+            // (the records as uploaded: their offsets address the output)
+            WFA_HIP_CHECK(launch_savgol_span(c->stream, v.pool, rec_view(c), sp0, sp, c->pool_f32.as<float>()));
+            if ((rc = t.end(padded ? "k_savgol_span<padded>" : "k_savgol_span"))) return rc;
         } else {
-            WFA_HIP_CHECK(launch_savgol(c->stream, pv, rec_view(c), sp0, c->pool_f32.as<float>()));
+            WFA_HIP_CHECK(launch_savgol(c->stream, v.pool, v.rec, sp0, c->pool_f32.as<float>()));
             if ((rc = t.end("k_savgol"))) return rc;
         }
     }
@@ -1343,12 +1268,12 @@ int wfa_find_peaks_count(wfa_ctx* c, int source, int signal_mode, int use_deriva
             // uniform records: the walk on LDS-staged groups (coalesced); any other layout: one lane per record
             // uniform records: LDS-staged groups (coalesced) -- the plateau machine only on the chunks that can hold a value
             // >= `height` (k_find_peaks_hot), or over every sample (k_find_peaks_staged)
-            const bool hot = c->span_ok && !c->opt.no_span && !c->opt.no_peak_hot &&
-                             launch_find_peaks_hot(c->stream, source, pv, rv, pp, c->span_off0, c->span_L, K, counts,
+            const bool hot = c->layout.span && !c->opt.no_span && !c->opt.no_peak_hot &&
+                             launch_find_peaks_hot(c->stream, source, pv, rv, pp, c->layout.off0, c->layout.L, K, counts,
                                                    c->peak_slot_pos.as<int32_t>(), c->peak_slot_val.as<double>(), overflow, &herr);
             WFA_HIP_CHECK(herr);
-            const bool staged = !hot && c->span_ok && !c->opt.no_span &&
-                                launch_find_peaks_staged(c->stream, source, pv, rv, pp, c->span_off0, c->span_L, K, counts,
+            const bool staged = !hot && c->layout.span && !c->opt.no_span &&
+                                launch_find_peaks_staged(c->stream, source, pv, rv, pp, c->layout.off0, c->layout.L, K, counts,
                                                          c->peak_slot_pos.as<int32_t>(), c->peak_slot_val.as<double>(), overflow, &herr);
             WFA_HIP_CHECK(herr);
             if (!staged && !hot)

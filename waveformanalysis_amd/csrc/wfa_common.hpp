@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "wfa_hip.h"
+#include "wfa_host.hpp"
 #include "wfa_kernels.hpp"
 
 namespace wfa {
@@ -39,9 +40,12 @@ struct DevBuf {
     void* ptr = nullptr;
     size_t cap = 0;
     DevBuf() = default;
+    // a scratch buffer lists itself in its owner's `scratch` (wfa_ctx declares the list above its buffers, lives on the
+    // heap and is never copied): what wfa_release_scratch gives back and wfa_scratch_bytes counts
+    explicit DevBuf(std::vector<DevBuf*>& scratch) { scratch.push_back(this); }
     DevBuf(const DevBuf&) = delete;             // owns device memory
     DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }                    // whatever wfa_ctx_destroy's list misses is still freed
+    ~DevBuf() { release(); }                    // (wfa_ctx_destroy: `delete c` frees every buffer of the context)
     int ensure(size_t bytes);  // keeps contents only if no growth is needed
     void release();
     template <typename T>
@@ -75,6 +79,8 @@ struct SgPlanDev {
 struct wfa_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
+    std::vector<wfa::DevBuf*> scratch;  // the buffers declared `{scratch}` below, and ht[]
+    wfa_ctx() { for (wfa::DevBuf& b : ht) scratch.push_back(&b); }
 
     // resident pool
     wfa::DevBuf pool_u16;
@@ -92,11 +98,12 @@ struct wfa_ctx {
     std::vector<int32_t> len_host;
     bool len_host_valid = false;
     int64_t bitmap_bytes = 0;  // mask bits of all records (k_sg_mask -> k_hit_runs)
-    // span mode eligibility (uniform length, contiguous, aligned; see SpanParams)
-    bool span_ok = false;
-    int32_t span_L = 0;
-    int64_t span_off0 = 0;
-    int span_positive = 0;
+    // what the records upload found about its layout (wfa_host.hpp), and whether the padded shadow of the u16 pool
+    // (layout.pad: records at stride layout.S, with the matching offsets column) has been built for it: on the device, the
+    // first time a pass needs it (layout_view, wfa_capi.hip)
+    wfa::UniformLayout layout;
+    bool shadow_valid = false;
+    wfa::DevBuf shadow_pool{scratch}, shadow_off{scratch};
     bool bitmap_clean = false;  // padding bytes of the bitmap are zero
 
     wfa::SgPlanDev sg;
@@ -104,7 +111,7 @@ struct wfa_ctx {
     bool filter_keep = false;  // wfa_filter_keep_output
 
     // hit scratch
-    wfa::DevBuf hit_tmp;        // 60 B rows in chunk order
+    wfa::DevBuf hit_tmp{scratch};  // 60 B rows in chunk order
     int64_t hit_tmp_rows = 0;
     wfa::DevBuf cursor;         // unsigned long long
     wfa::DevBuf rec_tmp_start;  // int64 per record
@@ -112,10 +119,10 @@ struct wfa_ctx {
     wfa::DevBuf rec_out_start;  // int64 per record
     wfa::DevBuf scan_blocks;    // int64 per scan block
     wfa::DevBuf hit_out;        // final rows
-    wfa::DevBuf bitmap;         // 1 bit per sample, per-record regions (bm_off)
+    wfa::DevBuf bitmap{scratch};  // 1 bit per sample, per-record regions (bm_off)
     wfa::DevBuf hit_desc;       // int4 (record, start, end, k) per hit
     // streaming pass on uniform records (k_sg_runs32): event buffer, per-span tables, control words
-    wfa::DevBuf run_ev, run_span_off, run_span_cnt, run_span_row0, run_scan_blocks, run_ctrl, run_groups, run_lit;
+    wfa::DevBuf run_ev{scratch}, run_span_off, run_span_cnt, run_span_row0, run_scan_blocks, run_ctrl, run_groups, run_lit;
     // host -> device staging: two pinned buffers; a chunk is copied in (a few host threads) while the previous one is on
     // the wire.  Pageable hipMemcpyAsync of a whole pool depends on the driver's own staging (5 GB/s on one box, 0.03
     // GB/s on another)
@@ -147,14 +154,14 @@ struct wfa_ctx {
     wfa::DevBuf out_rows2; // the second table of wfa_features_both (width rows)
     wfa::DevBuf pw_plan;   // numpy pairwise-sum plan of the wave-per-record feature kernels (wfa_features.hip)
     int pw_plan_n = -1;    // reduction length the device copy was built for
-    wfa::DevBuf fw_ties;   // width-integral records whose quantile positions are re-walked in numpy's order
+    wfa::DevBuf fw_ties{scratch};  // width-integral records whose quantile positions are re-walked in numpy's order
     wfa::DevBuf peak_out;  // HIT_DTYPE rows of the last find_peaks pass
     int64_t n_peaks = -1;
     int64_t n_legacy = -1;  // hits of the last wfa_find_hits_count pass
-    wfa::DevBuf peak_cand_n, peak_cand_pos, peak_cand_val, peak_cand_state;  // candidate lists of find_peaks
-    wfa::DevBuf peak_slot_pos, peak_slot_val;  // kPeakSlots candidates per record, written by the single walk
-    wfa::DevBuf peak_cand_rec, peak_accept, peak_ips, peak_row_start;
-    wfa::DevBuf wh_pos, wh_row, wh_valid;  // per-hit inputs of k_waveform_width
+    wfa::DevBuf peak_cand_n{scratch}, peak_cand_pos{scratch}, peak_cand_val{scratch}, peak_cand_state{scratch};  // candidate lists of find_peaks
+    wfa::DevBuf peak_slot_pos{scratch}, peak_slot_val{scratch};  // kPeakSlots candidates per record, written by the single walk
+    wfa::DevBuf peak_cand_rec{scratch}, peak_accept{scratch}, peak_ips{scratch}, peak_row_start{scratch};
+    wfa::DevBuf wh_pos{scratch}, wh_row{scratch}, wh_valid{scratch};  // per-hit inputs of k_waveform_width
     // hit-table stages (wfa_hits.hip): scratch slots and the state of the last count pass
     wfa::DevBuf ht[40];
     int ht_src = 1;            // wfa_hit_rows_source: 1 = rows of the last hit pass, 2 = rows of the last gather
@@ -164,13 +171,6 @@ struct wfa_ctx {
     int64_t ht_n = -1, ht_groups = 0;
     int ht_kind = 0;  // 1 = event grouping, 2 = hit merge, 3 = legacy multi-channel grouping
     int64_t* ht_perm = nullptr;
-    // padded device layout for uniform records whose length is not a multiple of 16 samples (the span16 kernels need
-    // every lane's 16-sample chunk inside one record): a shadow copy of the u16 pool with the records at stride
-    // pad_S = roundup16(L) and the matching offsets column, built on the device the first time a fused pass needs it
-    bool pad_ok = false, pad_positive = false, shadow_valid = false;
-    int32_t pad_L = 0, pad_S = 0;
-    int64_t pad_off0 = 0;
-    wfa::DevBuf shadow_pool, shadow_off;
     // CSV decode (wfa_hits.hip): rows / samples of the last wfa_csv_decode_count pass; the samples stay resident
     int64_t csv_rows = -1, csv_samples = -1, csv_bytes = 0;
     int32_t csv_samples_start = 0;
@@ -180,7 +180,7 @@ struct wfa_ctx {
     // [0, arena_filled) has been written.  Not scratch: wfa_release_scratch keeps it, wfa_ctx_destroy frees it
     wfa::DevBuf csv_arena;
     int64_t arena_filled = 0;
-    wfa::DevBuf bw_scratch;  // float64 forward pass of sosfiltfilt, [sample][record-in-batch]
+    wfa::DevBuf bw_scratch{scratch};  // float64 forward pass of sosfiltfilt, [sample][record-in-batch]
 
     // profiling: HIP events around every launch on the context's stream.  The pairs are only recorded while the
     // work runs and resolved (hipEventElapsedTime) when the report is read, so timing adds no host round trip
@@ -210,6 +210,41 @@ struct wfa_ctx {
 };
 
 namespace wfa {
+
+// ---- what an upload voids: every entry point that replaces the pool or the records says so here, and only here ----
+// what a pass builds in scratch for the resident records and keeps for the next one: gone with the records or the scratch
+inline void pass_caches_dropped(wfa_ctx* c) { c->shadow_valid = c->bitmap_clean = false; }
+
+// No records: the passes refuse until the next records upload, and what the old ones gave rise to goes with them.
+inline void records_dropped(wfa_ctx* c) {
+    c->have_records = false;
+    c->layout = {};
+    pass_caches_dropped(c);
+}
+
+// A records upload has landed: nothing cached for the previous table survives.
+inline void records_replaced(wfa_ctx* c, int64_t R, int32_t max_len, int64_t bitmap_bytes, const UniformLayout& layout) {
+    c->R = R; c->max_len = max_len; c->bitmap_bytes = bitmap_bytes; c->layout = layout;
+    c->have_records = true;
+    pass_caches_dropped(c);
+    c->len_host_valid = c->no_runs32 = false;
+    c->n_hits = c->pw_plan_n = -1;
+}
+
+// A pool of n samples has landed.  A wave_pool (u16) starts a new run: the filtered pool and the records belonged to the
+// previous one.  A float32 pool beside a wave_pool (of equal size: the caller has dropped any other) is its filtered
+// twin and the records stay; alone it is the run.
+inline void pool_replaced(wfa_ctx* c, int64_t n, bool u16) {
+    if (u16) {
+        c->have_u16 = true;
+        c->have_f32 = c->filter_keep = false;
+    } else {
+        c->have_f32 = true;
+        if (c->have_u16) return;
+    }
+    c->pool_n = n;
+    records_dropped(c);
+}
 
 // Launch timer: constructed before the launch(es), end(name) after them.
 struct LaunchTimer {

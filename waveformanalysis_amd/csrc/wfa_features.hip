@@ -719,12 +719,12 @@ __global__ __launch_bounds__(64) void k_width_ties(FwParams fw, RecView rec, uin
 
 }  // namespace
 
-// Uniform records (wfa_ctx::span_ok), uint16 pool, reduction length <= 8192: the lane-per-leaf kernels.  Returns
+// Uniform records (wfa_ctx::layout.span), uint16 pool, reduction length <= 8192: the lane-per-leaf kernels.  Returns
 // false when the layout is outside that (the caller launches the general lane-per-record kernel).
 static bool features_wave(wfa_ctx* c, int mode, const RecView& rec, FwParams fw, int n_sum, uint8_t* out, hipError_t* err,
                           uint8_t* out2 = nullptr) {
     *err = hipSuccess;
-    if (!c->span_ok || c->span_L < 8 || c->span_L > kFwGroupSamples || c->opt.no_span) return false;
+    if (!c->layout.span || c->layout.L < 8 || c->layout.L > kFwGroupSamples || c->opt.no_span) return false;
     if (fw.c0 % 8) return false;  // leaves start on 16-byte chunks of the staged record
     PwPlan plan;
     if (!pw_plan(plan, n_sum)) return false;
@@ -736,8 +736,8 @@ static bool features_wave(wfa_ctx* c, int mode, const RecView& rec, FwParams fw,
         c->pw_plan_n = n_sum;
     }
     fw.pool = c->pool_u16.as<uint16_t>();
-    fw.off0 = c->span_off0;
-    fw.L = c->span_L;
+    fw.off0 = c->layout.off0;
+    fw.L = c->layout.L;
     if (mode >= 1) {
         if (rec.R >= INT32_MAX || c->fw_ties.ensure(((size_t)rec.R + 1) * sizeof(int32_t)) != WFA_OK) return false;
         fw.ties = c->fw_ties.as<int32_t>();
@@ -786,8 +786,8 @@ static void resolve_slice(int64_t start, int64_t end, int has_end, int L, int& l
 
 bool launch_basic_features_wave(wfa_ctx* c, const RecView& rec, const FeatParams& fp, uint8_t* out, hipError_t* err) {
     FwParams fw{};
-    resolve_slice(fp.h0, fp.h1, fp.h_has_end, c->span_L, fw.p0, fw.p1);
-    resolve_slice(fp.a0, fp.a1, fp.a_has_end, c->span_L, fw.c0, fw.c1);
+    resolve_slice(fp.h0, fp.h1, fp.h_has_end, c->layout.L, fw.p0, fw.p1);
+    resolve_slice(fp.a0, fp.a1, fp.a_has_end, c->layout.L, fw.c0, fw.c1);
     fw.fixed_bl = fp.fixed_bl;
     return features_wave(c, 0, rec, fw, fw.c1 - fw.c0, out, err);
 }
@@ -797,17 +797,17 @@ bool launch_basic_features_wave(wfa_ctx* c, const RecView& rec, const FeatParams
 bool launch_features_both_wave(wfa_ctx* c, const RecView& rec, const FeatParams& fp, const WidthParams& wp, uint8_t* out_basic,
                                uint8_t* out_width, hipError_t* err) {
     FwParams fw{};
-    resolve_slice(fp.h0, fp.h1, fp.h_has_end, c->span_L, fw.p0, fw.p1);
-    resolve_slice(fp.a0, fp.a1, fp.a_has_end, c->span_L, fw.c0, fw.c1);
-    if (fp.fixed_bl || fw.c0 != 0 || fw.c1 != c->span_L) { *err = hipSuccess; return false; }
+    resolve_slice(fp.h0, fp.h1, fp.h_has_end, c->layout.L, fw.p0, fw.p1);
+    resolve_slice(fp.a0, fp.a1, fp.a_has_end, c->layout.L, fw.c0, fw.c1);
+    if (fp.fixed_bl || fw.c0 != 0 || fw.c1 != c->layout.L) { *err = hipSuccess; return false; }
     fw.q_low = wp.q_low; fw.q_high = wp.q_high; fw.dt = wp.dt;
-    return features_wave(c, 2, rec, fw, c->span_L, out_basic, err, out_width);
+    return features_wave(c, 2, rec, fw, c->layout.L, out_basic, err, out_width);
 }
 
 bool launch_width_integral_wave(wfa_ctx* c, const RecView& rec, const WidthParams& wp, uint8_t* out, hipError_t* err) {
     FwParams fw{};
     fw.q_low = wp.q_low; fw.q_high = wp.q_high; fw.dt = wp.dt;
-    return features_wave(c, 1, rec, fw, c->span_L, out, err);
+    return features_wave(c, 1, rec, fw, c->layout.L, out, err);
 }
 
 }  // namespace wfa

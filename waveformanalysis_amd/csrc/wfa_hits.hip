@@ -1216,13 +1216,7 @@ static int gather_run(wfa_ctx* c, int64_t n, const int64_t* src_offset, const in
         WFA_HIP_CHECK(hipMemcpyAsync(out_pool, c->pool_u16.ptr, (size_t)out_samples * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
     WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
     // the packed pool is now the resident wave_pool
-    c->pool_n = out_samples;
-    c->have_u16 = true;
-    c->have_f32 = false;
-    c->filter_keep = false;
-    c->have_records = false;
-    c->shadow_valid = false;
-    c->pad_ok = false;
+    pool_replaced(c, out_samples, true);
     return WFA_OK;
 }
 

@@ -3,7 +3,8 @@
 // stand-in for the device (csrc/host_check.cpp; SURVEY section 5: the reference has no sanitizer run of its own).
 //   * v1725_index: header walk of a CAEN V1725 DAW_DEMO binary stream (reference utils/formats/v1725.py:66-114);
 //   * staged_copy: host -> device through two pinned staging buffers, a few host threads filling one while the other is
-//     on the wire (the ring of wfa_upload_pool_u16 / wfa_upload_pool_f32).
+//     on the wire (the ring of wfa_upload_pool_u16 / wfa_upload_pool_f32);
+//   * records_uniform / uniform_layout: the uniform-record layout of a records upload (both upload routes).
 #pragma once
 
 #include <cstdint>
@@ -11,8 +12,44 @@
 #include <cstring>
 #include <thread>
 
+#include "wfa_hip.h"
+
 namespace wfa {
+
+// What a records upload found about its layout.  span: every record L samples (a multiple of 8, >= 24), back to back from
+// the 16-byte aligned sample off0, one polarity class -- the uniform-record kernels read the pool in place.  pad: uniform
+// records over a uint16 pool whose L >= 32 is no multiple of 16 -- the span16 kernels need every lane's 16-sample chunk
+// inside one record and read a shadow copy of the pool with the records at stride S = roundup16(L) (S = L without pad).
+struct UniformLayout {
+    bool span = false, pad = false, positive = false;
+    int32_t L = 0, S = 0;
+    int64_t off0 = 0;
+};
+
 namespace host {
+
+// every record as long as record 0, back to back behind it, in its polarity class (positive or not)
+inline bool records_uniform(int64_t R, const int64_t* off, const int32_t* len, const int8_t* pol) {
+    for (int64_t r = 0; r < R; ++r)
+        if (len[r] != len[0] || off[r] != off[0] + r * (int64_t)len[0] ||
+            (pol[r] == WFA_POL_POSITIVE) != (pol[0] == WFA_POL_POSITIVE))
+            return false;
+    return true;
+}
+
+// (len0, off0, pol0: record 0 of R records that are `uniform`)
+inline UniformLayout uniform_layout(bool uniform, int64_t R, int32_t len0, int64_t off0, int8_t pol0, bool have_u16) {
+    UniformLayout u;
+    if (!uniform || R <= 0) return u;
+    u.span = len0 >= 24 && len0 % 8 == 0 && off0 % 8 == 0;
+    u.pad = have_u16 && len0 >= 32 && len0 % 16 != 0;
+    if (!u.span && !u.pad) return u;
+    u.positive = pol0 == WFA_POL_POSITIVE;
+    u.L = len0;
+    u.S = u.pad ? (len0 + 15) / 16 * 16 : len0;
+    u.off0 = off0;
+    return u;
+}
 
 // Returns 0, or -1 with a message in err (the stream is malformed: a channel block shorter than its own header).
 // capacity = rows the output columns hold (0: count only); *n_waves = waves in the stream either way.
