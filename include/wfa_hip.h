@@ -262,6 +262,20 @@ int wfa_waveform_width(wfa_ctx* ctx, int source, int64_t n_hits, const int64_t* 
                        double rise_high, double fall_high, double fall_low, double sampling_rate,
                        int interpolation, void* out_rows, uint8_t* valid);
 
+/* K10 on the resident records: the same rows without a dense matrix (reference: cpu/waveform_width.py:205-374,
+ * `_calculate_width_from_peak` applied to waveform = pool[wave_offset[r] : wave_offset[r] + event_length[r]]).
+ * record_index[i] = r is an INDEX into the uploaded records table (as the `hit` records branch fetches its waveform,
+ * peak_finding.py:401-407), position[i] = p the sample inside that record.  valid[i] = 0 (hit dropped) when r is
+ * outside [0, n_records), p >= event_length[r] (so every hit of an empty record), p < 0, or the peak value is <= 0.
+ * The baseline is mean(first min(50, event_length[r]) samples of the record).  source: WFA_SRC_RAW (wave_pool, uint16:
+ * float64 arithmetic) or WFA_SRC_F32 (wave_pool_filtered: float32 arithmetic with numpy 2's weak-scalar rules); pulses
+ * are positive-going in stored counts, as in the reference.  Needs uploaded records and that source's pool
+ * (WFA_E_STATE otherwise); everything else as wfa_waveform_width, bit-exact float fields included. */
+int wfa_waveform_width_records(wfa_ctx* ctx, int source, int64_t n_hits, const int64_t* position,
+                               const int64_t* record_index, double rise_low, double rise_high, double fall_high,
+                               double fall_low, double sampling_rate, int interpolation, void* out_rows,
+                               uint8_t* valid);
+
 /* ---- hit-table stages (device sort + scans; host columns in, host index tables out) ----------------------
  * K11 hit merge (reference: cpu/hit_merge.py:115-181 `_build_merged_clusters`, 256-322 `_emit_cluster`).
  * Input: the columns of a hit table (THRESHOLD_HIT_DTYPE or its renamed variants).

@@ -71,6 +71,7 @@ SIGNATURES = {
     "wfa_find_hits_count": (_int, [_p, _int, _i64, _i32, _p, _f64, C.POINTER(_i64)]),
     "wfa_find_hits_fill": (_int, [_p, _i64, _p, _p]),
     "wfa_waveform_width": (_int, [_p, _int, _i64, _p, _p, _i64, _i32, _f64, _f64, _f64, _f64, _f64, _int, _p, _p]),
+    "wfa_waveform_width_records": (_int, [_p, _int, _i64, _p, _p, _f64, _f64, _f64, _f64, _f64, _int, _p, _p]),
     "wfa_hit_merge_count": (_int, [_p, _i64] + [_p] * 7 + [_f64, _f64, C.POINTER(_i64)]),
     "wfa_hit_merge_fill": (_int, [_p, _i64, _i64, _p, _p]),
     "wfa_hit_merge_emit": (_int, [_p, _i64] + [_p] * 6 + [_i64, _p, _i64, _p] + [_p] * 6),

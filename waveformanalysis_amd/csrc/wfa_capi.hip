@@ -1448,6 +1448,39 @@ int wfa_find_hits_fill(wfa_ctx* c, int64_t n_hits, int64_t* event_index, int64_t
     return WFA_OK;
 }
 
+}  // extern "C"
+
+// K10 on either addressing: the per-hit columns up, one launch (enqueued by `launch(position, index, rows, valid)` on
+// the context's stream, timed under `name`), rows and valid bytes down.
+template <class Launch>
+static int width_pass(wfa_ctx* c, int64_t n_hits, const int64_t* position, const int64_t* index, double sampling_rate,
+                      const char* name, void* out_rows, uint8_t* valid, Launch launch) {
+    if (n_hits == 0) return WFA_OK;
+    if (!position || !index || !out_rows || !valid) return fail(WFA_E_INVALID, "null argument");
+    if (!(sampling_rate == sampling_rate) || sampling_rate == 0.0) return fail(WFA_E_INVALID, "float division by zero");
+    int rc;
+    // scratch: positions, row indices, rows, valid bytes
+    const size_t b_idx = (size_t)n_hits * sizeof(int64_t);
+    if ((rc = c->wh_pos.ensure(b_idx))) return rc;
+    if ((rc = c->wh_row.ensure(b_idx))) return rc;
+    if ((rc = c->out_rows.ensure((size_t)n_hits * 56))) return rc;
+    if ((rc = c->wh_valid.ensure((size_t)n_hits))) return rc;
+    WFA_HIP_CHECK(hipMemcpyAsync(c->wh_pos.ptr, position, b_idx, hipMemcpyHostToDevice, c->stream));
+    WFA_HIP_CHECK(hipMemcpyAsync(c->wh_row.ptr, index, b_idx, hipMemcpyHostToDevice, c->stream));
+    {
+        LaunchTimer t(c);
+        WFA_HIP_CHECK(launch(c->wh_pos.as<int64_t>(), c->wh_row.as<int64_t>(), c->out_rows.as<uint8_t>(),
+                             c->wh_valid.as<uint8_t>()));
+        if ((rc = t.end(name))) return rc;
+    }
+    WFA_HIP_CHECK(hipMemcpyAsync(out_rows, c->out_rows.ptr, (size_t)n_hits * 56, hipMemcpyDeviceToHost, c->stream));
+    WFA_HIP_CHECK(hipMemcpyAsync(valid, c->wh_valid.ptr, (size_t)n_hits, hipMemcpyDeviceToHost, c->stream));
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return WFA_OK;
+}
+
+extern "C" {
+
 int wfa_waveform_width(wfa_ctx* c, int source, int64_t n_hits, const int64_t* position, const int64_t* row_index,
                        int64_t n_rows, int32_t row_length, double rise_low, double rise_high, double fall_high,
                        double fall_low, double sampling_rate, int interpolation, void* out_rows, uint8_t* valid) {
@@ -1460,29 +1493,29 @@ int wfa_waveform_width(wfa_ctx* c, int source, int64_t n_hits, const int64_t* po
     if (n_rows * (int64_t)row_length > c->pool_n)
         return fail(WFA_E_INVALID, "wave matrix %lld x %d exceeds the resident pool (%lld samples)", (long long)n_rows,
                     row_length, (long long)c->pool_n);
-    if (n_hits == 0) return WFA_OK;
-    if (!position || !row_index || !out_rows || !valid) return fail(WFA_E_INVALID, "null argument");
-    if (!(sampling_rate == sampling_rate) || sampling_rate == 0.0) return fail(WFA_E_INVALID, "float division by zero");
-    // scratch: positions, row indices, rows, valid bytes
-    const size_t b_idx = (size_t)n_hits * sizeof(int64_t);
-    if ((rc = c->wh_pos.ensure(b_idx))) return rc;
-    if ((rc = c->wh_row.ensure(b_idx))) return rc;
-    if ((rc = c->out_rows.ensure((size_t)n_hits * 56))) return rc;
-    if ((rc = c->wh_valid.ensure((size_t)n_hits))) return rc;
-    WFA_HIP_CHECK(hipMemcpyAsync(c->wh_pos.ptr, position, b_idx, hipMemcpyHostToDevice, c->stream));
-    WFA_HIP_CHECK(hipMemcpyAsync(c->wh_row.ptr, row_index, b_idx, hipMemcpyHostToDevice, c->stream));
-    {
-        LaunchTimer t(c);
-        WFA_HIP_CHECK(launch_waveform_width(c->stream, source, pool_view(c), n_hits, c->wh_pos.as<int64_t>(),
-                                            c->wh_row.as<int64_t>(), n_rows, row_length, rise_low, rise_high, fall_high,
-                                            fall_low, sampling_rate, interpolation, c->out_rows.as<uint8_t>(),
-                                            c->wh_valid.as<uint8_t>()));
-        if ((rc = t.end("k_waveform_width"))) return rc;
-    }
-    WFA_HIP_CHECK(hipMemcpyAsync(out_rows, c->out_rows.ptr, (size_t)n_hits * 56, hipMemcpyDeviceToHost, c->stream));
-    WFA_HIP_CHECK(hipMemcpyAsync(valid, c->wh_valid.ptr, (size_t)n_hits, hipMemcpyDeviceToHost, c->stream));
-    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return WFA_OK;
+    return width_pass(c, n_hits, position, row_index, sampling_rate, "k_waveform_width", out_rows, valid,
+                      [&](const int64_t* d_pos, const int64_t* d_row, uint8_t* d_out, uint8_t* d_valid) {
+                          return launch_waveform_width(c->stream, source, pool_view(c), n_hits, d_pos, d_row, n_rows,
+                                                       row_length, rise_low, rise_high, fall_high, fall_low,
+                                                       sampling_rate, interpolation, d_out, d_valid);
+                      });
+}
+
+int wfa_waveform_width_records(wfa_ctx* c, int source, int64_t n_hits, const int64_t* position,
+                               const int64_t* record_index, double rise_low, double rise_high, double fall_high,
+                               double fall_low, double sampling_rate, int interpolation, void* out_rows, uint8_t* valid) {
+    int rc = use_device(c);
+    if (rc) return rc;
+    if (source != WFA_SRC_RAW && source != WFA_SRC_F32)
+        return fail(WFA_E_INVALID, "waveform_width reads stored samples: source must be WFA_SRC_RAW or WFA_SRC_F32");
+    if ((rc = need_source(c, source))) return rc;  // records (their slices were checked against the pool) + this pool
+    if (n_hits < 0) return fail(WFA_E_INVALID, "negative size");
+    return width_pass(c, n_hits, position, record_index, sampling_rate, "k_waveform_width_rec", out_rows, valid,
+                      [&](const int64_t* d_pos, const int64_t* d_row, uint8_t* d_out, uint8_t* d_valid) {
+                          return launch_waveform_width_records(c->stream, source, pool_view(c), rec_view(c), n_hits, d_pos,
+                                                               d_row, rise_low, rise_high, fall_high, fall_low,
+                                                               sampling_rate, interpolation, d_out, d_valid);
+                      });
 }
 
 int wfa_width_integral(wfa_ctx* c, int source, double q_low, double q_high, double dt, void* out_rows) {

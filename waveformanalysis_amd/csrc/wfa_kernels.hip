@@ -1874,10 +1874,10 @@ __global__ __launch_bounds__(kBlock) void k_find_hits_legacy(PoolView pool, int6
 }
 
 // =============================================================================================
-// K10: rise / fall / total width per hit on dense rows  (waveform_width.py:205-374)
+// K10: rise / fall / total width per hit on dense rows or on records  (waveform_width.py:205-374)
 // =============================================================================================
-// One lane per hit.  T = double for int16 rows (numpy promotes int16 - float64 mean to float64), float for
-// float32 rows (mean, subtraction, thresholds, interpolation all stay float32 under numpy 2 promotion).
+// One lane per hit.  T = double for int16 / uint16 samples (numpy promotes integer - float64 mean to float64), float
+// for float32 samples (mean, subtraction, thresholds, interpolation all stay float32 under numpy 2 promotion).
 // numpy float32 pairwise_sum of x[0..n), n <= 128 (np.mean / np.sum of a short float32 slice)
 __device__ inline float np_pairwise_leaf_f32(const float* x, int n) {
     if (n < 8) {
@@ -1899,8 +1899,32 @@ __device__ inline float np_pairwise_leaf_f32(const float* x, int n) {
 struct WidthHitParams {
     double rise_low, rise_high, fall_high, fall_low, sampling_rate;
     int interpolation;
-    int32_t L;
+};
+
+// Where the waveform of a hit lies in the pool: locate(row, &base, &L) -> false when there is no such row.
+// Dense rows: row i of the (n_rows x L) matrix.  Records: the slice of record i of the resident table, whatever its
+// offset's alignment and its length (0 and 1 included; the upload checked off + len <= pool size).
+struct WidthDenseRows {
     int64_t n_rows;
+    int32_t L;
+    __device__ __forceinline__ bool locate(int64_t ri, int64_t* base, int* len) const {
+        if (ri < 0 || ri >= n_rows) return false;
+        *base = ri * L;
+        *len = L;
+        return true;
+    }
+};
+
+struct WidthRecordRows {
+    int64_t R;
+    const int64_t* __restrict__ off;
+    const int32_t* __restrict__ len_col;
+    __device__ __forceinline__ bool locate(int64_t ri, int64_t* base, int* len) const {
+        if (ri < 0 || ri >= R) return false;
+        *base = off[ri];
+        *len = len_col[ri];
+        return true;
+    }
 };
 
 // value that is either a python float / np.float64 (is32 = false) or an np.float32 (is32 = true)
@@ -1961,11 +1985,12 @@ __device__ __forceinline__ PyNum py_div(const PyNum& a, double python_float) {
     return r;
 }
 
-template <int SRC>
+template <int SRC, class Rows>
 __global__ __launch_bounds__(128) void k_waveform_width(PoolView pool, int64_t n_hits,
                                                         const int64_t* __restrict__ position,
-                                                        const int64_t* __restrict__ row_index, WidthHitParams wp,
-                                                        uint8_t* __restrict__ out, uint8_t* __restrict__ valid) {
+                                                        const int64_t* __restrict__ row_index, Rows rows,
+                                                        WidthHitParams wp, uint8_t* __restrict__ out,
+                                                        uint8_t* __restrict__ valid) {
     using T = typename std::conditional<SRC == WFA_SRC_RAW, double, float>::type;
     const int64_t h = (int64_t)blockIdx.x * 128 + threadIdx.x;
     if (h >= n_hits) return;
@@ -1975,12 +2000,13 @@ __global__ __launch_bounds__(128) void k_waveform_width(PoolView pool, int64_t n
     valid[h] = 0;
     const int64_t ri = row_index[h];
     const int64_t pos64 = position[h];
-    const int L = wp.L;
-    if (ri < 0 || ri >= wp.n_rows || L <= 0) return;
+    int64_t base;
+    int L;
+    if (!rows.locate(ri, &base, &L) || L <= 0) return;
     if (pos64 >= L || pos64 < 0) return;  // waveform_width.py:252
     const int peak = (int)pos64;
-    const uint16_t* xu = pool.u16 ? pool.u16 + ri * L : nullptr;
-    const float* xf = pool.f32 ? pool.f32 + ri * L : nullptr;
+    const uint16_t* xu = pool.u16 ? pool.u16 + base : nullptr;
+    const float* xf = pool.f32 ? pool.f32 + base : nullptr;
 
     // baseline = np.mean(waveform[:50])
     const int nb = L < 50 ? L : 50;
@@ -2003,7 +2029,6 @@ __global__ __launch_bounds__(128) void k_waveform_width(PoolView pool, int64_t n
     // python float options are weak: thresholds take the dtype of peak_value
     const T thr_rl = peak_value * (T)wp.rise_low, thr_rh = peak_value * (T)wp.rise_high;
     const T thr_fh = peak_value * (T)wp.fall_high, thr_fl = peak_value * (T)wp.fall_low;
-    const int64_t base = ri * L;
     const PyNum rise_lo = find_crossing<SRC, T>(pool, base, baseline, at, 0, peak, thr_rl, true, interp);
     const PyNum rise_hi = find_crossing<SRC, T>(pool, base, baseline, at, 0, peak, thr_rh, true, interp);
     PyNum fall_hi = find_crossing<SRC, T>(pool, base, baseline, at, peak, L, thr_fh, false, interp);
@@ -3194,20 +3219,37 @@ hipError_t launch_find_hits_legacy(hipStream_t st, int source, bool fill, const 
     return hipGetLastError();
 }
 
+template <class Rows>
+static hipError_t launch_width_rows(hipStream_t st, int source, const PoolView& pool, int64_t n_hits,
+                                    const int64_t* position, const int64_t* row_index, const Rows& rows,
+                                    const WidthHitParams& wp, uint8_t* out, uint8_t* valid) {
+    if (n_hits == 0) return hipSuccess;
+    const unsigned grid = (unsigned)((n_hits + 127) / 128);
+    if (source == WFA_SRC_RAW)
+        hipLaunchKernelGGL((k_waveform_width<WFA_SRC_RAW, Rows>), dim3(grid), dim3(128), 0, st, pool, n_hits, position, row_index, rows, wp, out, valid);
+    else if (source == WFA_SRC_F32)
+        hipLaunchKernelGGL((k_waveform_width<WFA_SRC_F32, Rows>), dim3(grid), dim3(128), 0, st, pool, n_hits, position, row_index, rows, wp, out, valid);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 hipError_t launch_waveform_width(hipStream_t st, int source, const PoolView& pool, int64_t n_hits,
                                  const int64_t* position, const int64_t* row_index, int64_t n_rows, int32_t L,
                                  double rise_low, double rise_high, double fall_high, double fall_low,
                                  double sampling_rate, int interpolation, uint8_t* out, uint8_t* valid) {
-    if (n_hits == 0) return hipSuccess;
-    WidthHitParams wp{rise_low, rise_high, fall_high, fall_low, sampling_rate, interpolation, L, n_rows};
-    const unsigned grid = (unsigned)((n_hits + 127) / 128);
-    if (source == WFA_SRC_RAW)
-        hipLaunchKernelGGL((k_waveform_width<WFA_SRC_RAW>), dim3(grid), dim3(128), 0, st, pool, n_hits, position, row_index, wp, out, valid);
-    else if (source == WFA_SRC_F32)
-        hipLaunchKernelGGL((k_waveform_width<WFA_SRC_F32>), dim3(grid), dim3(128), 0, st, pool, n_hits, position, row_index, wp, out, valid);
-    else
-        return hipErrorInvalidValue;
-    return hipGetLastError();
+    return launch_width_rows(st, source, pool, n_hits, position, row_index, WidthDenseRows{n_rows, L},
+                             WidthHitParams{rise_low, rise_high, fall_high, fall_low, sampling_rate, interpolation}, out,
+                             valid);
+}
+
+hipError_t launch_waveform_width_records(hipStream_t st, int source, const PoolView& pool, const RecView& rec,
+                                         int64_t n_hits, const int64_t* position, const int64_t* record_index,
+                                         double rise_low, double rise_high, double fall_high, double fall_low,
+                                         double sampling_rate, int interpolation, uint8_t* out, uint8_t* valid) {
+    return launch_width_rows(st, source, pool, n_hits, position, record_index, WidthRecordRows{rec.R, rec.off, rec.len},
+                             WidthHitParams{rise_low, rise_high, fall_high, fall_low, sampling_rate, interpolation}, out,
+                             valid);
 }
 
 hipError_t launch_find_peaks(hipStream_t st, int source, bool fill, const PoolView& pool, const RecView& rec,

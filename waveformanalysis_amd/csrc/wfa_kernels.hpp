@@ -197,6 +197,11 @@ hipError_t launch_waveform_width(hipStream_t st, int source, const PoolView& poo
                                  const int64_t* position, const int64_t* row_index, int64_t n_rows, int32_t L,
                                  double rise_low, double rise_high, double fall_high, double fall_low,
                                  double sampling_rate, int interpolation, uint8_t* out, uint8_t* valid);
+// the same kernel body on the slices of the resident records: record_index[h] indexes `rec`
+hipError_t launch_waveform_width_records(hipStream_t st, int source, const PoolView& pool, const RecView& rec,
+                                         int64_t n_hits, const int64_t* position, const int64_t* record_index,
+                                         double rise_low, double rise_high, double fall_high, double fall_low,
+                                         double sampling_rate, int interpolation, uint8_t* out, uint8_t* valid);
 // find_peaks: candidate scan per record (count / fill), distance selection per record, then per candidate
 hipError_t launch_find_peaks(hipStream_t st, int source, bool fill, const PoolView& pool, const RecView& rec,
                              const PeakParams& pp, int32_t* counts, const int64_t* out_start, int32_t* cand_pos,

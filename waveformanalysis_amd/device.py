@@ -431,6 +431,25 @@ class DeviceSession:
             _ptr(out), _ptr(valid)))
         return out, valid.astype(bool)
 
+    def waveform_width_records(self, source: int, position: np.ndarray, record_index: np.ndarray,
+                               rise_low: float = 0.1, rise_high: float = 0.9, fall_high: float = 0.9,
+                               fall_low: float = 0.1, sampling_rate: float = 0.5,
+                               interpolation: bool = True) -> tuple[np.ndarray, np.ndarray]:
+        """Rise/fall/total width per hit on the slices of the uploaded records (WaveformWidthPlugin's arithmetic on
+        pool[wave_offset[r] : wave_offset[r] + event_length[r]], r = record_index[i] an index into the records table).
+
+        Returns (rows, valid) like waveform_width."""
+        pos = np.ascontiguousarray(position, dtype=np.int64)
+        rec = np.ascontiguousarray(record_index, dtype=np.int64)
+        if pos.shape != rec.shape or pos.ndim != 1:
+            raise ValueError("position and record_index must be 1-D arrays of the same length")
+        out = np.zeros(len(pos), dtype=WAVEFORM_WIDTH_DTYPE)
+        valid = np.zeros(len(pos), dtype=np.uint8)
+        _lib.check(self._lib.wfa_waveform_width_records(
+            self._h, int(source), len(pos), _ptr(pos), _ptr(rec), float(rise_low), float(rise_high), float(fall_high),
+            float(fall_low), float(sampling_rate), int(bool(interpolation)), _ptr(out), _ptr(valid)))
+        return out, valid.astype(bool)
+
     # ---- records builder -----------------------------------------------------------------------------------------
     def records_sort_order(self, timestamp, pid, board, channel) -> np.ndarray:
         """np.lexsort((seq, channel, board, pid, timestamp)) on the device (records_builder.py:115-120)."""

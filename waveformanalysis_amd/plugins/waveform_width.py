@@ -5,6 +5,12 @@ Per `hit` row: baseline = mean of the first 50 samples of the waveform row the h
 crossings of the rise/fall fractions either side of the peak with linear interpolation, divided by the
 sampling rate.  One GPU lane per hit (k_waveform_width); the row lookup and the id columns are table
 work done here with numpy.
+
+wave_source="records" (no counterpart in the reference, whose plugin reads dense rows only): the same arithmetic on
+waveform = pool[wave_offset[r] : wave_offset[r] + event_length[r]] of the resident records + wave_pool /
+wave_pool_filtered, r = the hit's record_id taken as an index into `records` -- the way the `hit` records branch
+fetched the waveform the hit was found on (peak_finding.py:401-407).  No dense copy of the samples is built, and the
+pool the other records plugins left on the device is used as it is.
 """
 
 from __future__ import annotations
@@ -43,6 +49,8 @@ class HipWaveformWidthPlugin(K.HipPlugin):
 
     options = {
         "use_filtered": Option(default=False, type=bool, help="read filtered_waveforms instead of st_waveforms"),
+        "wave_source": Option(default=K.WAVE_SOURCE_AUTO, type=str,
+                              help="auto|records|st_waveforms|filtered_waveforms"),
         "sampling_rate": Option(default=None, type=float, help="sampling rate (GHz); 0.5 when unset"),
         "rise_low": Option(default=0.1, type=float, help="low fraction of the rise time"),
         "rise_high": Option(default=0.9, type=float, help="high fraction of the rise time"),
@@ -52,12 +60,11 @@ class HipWaveformWidthPlugin(K.HipPlugin):
     }
 
     def resolve_depends_on(self, context: Any, run_id: str | None = None) -> list[str]:
-        if context.get_config(self, "use_filtered"):
-            return ["hit", "filtered_waveforms"]
-        return ["hit", "st_waveforms"]
+        _kind, deps, _name = K.resolve_wave_input(context, self)
+        return ["hit"] + deps
 
     def compute(self, context: Any, run_id: str, **_kwargs) -> np.ndarray:
-        use_filtered = context.get_config(self, "use_filtered")
+        kind, _deps, data_name = K.resolve_wave_input(context, self)
         sampling_rate = context.get_config(self, "sampling_rate")
         if sampling_rate is None:
             sampling_rate = 0.5
@@ -69,7 +76,9 @@ class HipWaveformWidthPlugin(K.HipPlugin):
         interpolation = bool(context.get_config(self, "interpolation"))
 
         hits = context.get_data(run_id, "hit")
-        data_name = "filtered_waveforms" if use_filtered else "st_waveforms"
+        if kind == "records":
+            return self._compute_records(context, run_id, data_name, hits, rise_low, rise_high, fall_high, fall_low,
+                                         float(sampling_rate), interpolation)
         waveform_data = context.get_data(run_id, data_name)
         if not isinstance(hits, np.ndarray):
             raise ValueError("waveform_width expects hit as a single structured array")
@@ -78,11 +87,7 @@ class HipWaveformWidthPlugin(K.HipPlugin):
         if len(hits) == 0 or len(waveform_data) == 0:
             return np.zeros(0, dtype=WAVEFORM_WIDTH_DTYPE)
 
-        hit_names = hits.dtype.names or ()
-        record_id = np.asarray(hits["record_id"] if "record_id" in hit_names else hits["event_index"], dtype=np.int64)
-        position = np.asarray(hits["position"], dtype=np.int64)
-        if np.any(position < 0):
-            raise ValueError("waveform_width (HIP backend) requires hit positions >= 0")
+        record_id, position = _hit_columns(hits)
         if "record_id" in (waveform_data.dtype.names or ()):
             row = first_row_of_record_id(waveform_data["record_id"], record_id)
         else:
@@ -92,10 +97,49 @@ class HipWaveformWidthPlugin(K.HipPlugin):
         sess = K.resident_session(context, pool, cacheable=False)  # temporary of the dense `wave` field
         rows, valid = sess.waveform_width(source, position, row, len(waveform_data), L, rise_low, rise_high,
                                           fall_high, fall_low, float(sampling_rate), interpolation)
-        out = rows[valid]
-        sel = hits[valid]
-        out["timestamp"] = sel["timestamp"]
-        out["board"] = sel["board"] if "board" in hit_names else 0
-        out["channel"] = sel["channel"]
-        out["record_id"] = record_id[valid]
-        return out
+        return _kept_rows(rows, valid, hits, record_id)
+
+    def _compute_records(self, context, run_id, pool_name, hits, rise_low, rise_high, fall_high, fall_low, sampling_rate,
+                         interpolation) -> np.ndarray:
+        """The hit's record_id is an index into `records` (range-checked on the device); the session is the calling
+        thread's, its pool uploaded only if another array has taken its place since `hit` / `basic_features` ran."""
+        if not isinstance(hits, np.ndarray):
+            raise ValueError("waveform_width expects hit as a single structured array")
+        records, pool = K.load_records_input(context, self, run_id, pool_name)
+        if len(hits) == 0 or len(records) == 0:
+            return np.zeros(0, dtype=WAVEFORM_WIDTH_DTYPE)
+        record_id, position = _hit_columns(hits)
+        cacheable = True
+        if pool_name == "wave_pool_filtered":
+            pool, cacheable = K.float32_pool(pool)
+            source = K.SRC_F32
+        else:
+            source = K.pool_source(pool, raw_only=True)
+        sess = K.resident_session(context, pool, cacheable=cacheable)
+        if not sess.holds_records(records):  # (a pool upload above has dropped the note)
+            sess.upload_records(records)
+            sess.note_records(records)
+        rows, valid = sess.waveform_width_records(source, position, record_id, rise_low, rise_high, fall_high,
+                                                  fall_low, sampling_rate, interpolation)
+        return _kept_rows(rows, valid, hits, record_id)
+
+
+def _hit_columns(hits: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """(record_id, position) of a hit table as int64 columns (waveform_width.py:154-159)."""
+    hit_names = hits.dtype.names or ()
+    record_id = np.asarray(hits["record_id"] if "record_id" in hit_names else hits["event_index"], dtype=np.int64)
+    position = np.asarray(hits["position"], dtype=np.int64)
+    if np.any(position < 0):
+        raise ValueError("waveform_width (HIP backend) requires hit positions >= 0")
+    return record_id, position
+
+
+def _kept_rows(rows: np.ndarray, valid: np.ndarray, hits: np.ndarray, record_id: np.ndarray) -> np.ndarray:
+    """The rows of the hits the reference keeps, in hit order, id fields from the hit table."""
+    out = rows[valid]
+    sel = hits[valid]
+    out["timestamp"] = sel["timestamp"]
+    out["board"] = sel["board"] if "board" in (hits.dtype.names or ()) else 0
+    out["channel"] = sel["channel"]
+    out["record_id"] = record_id[valid]
+    return out
