@@ -1388,7 +1388,9 @@ __global__ __launch_bounds__(kWave) void k_hit_rows_flat(PoolView pool, RecView 
             const uint32_t u = ord ^ ((ord >> 31) ? 0x80000000u : 0xffffffffu);
             acc.best = sb - (double)__uint_as_float(u);
             acc.best_i = (int)(uint32_t)key;
-            acc.sum = (double)lds->npos[lane] * sb - (double)(long long)lds->tsum[lane] * (1.0 / 8388608.0);
+            // (no sample with signal > 0: the reference's sum is +0.0, 0 * sb with sb < 0 would be -0.0)
+            const uint32_t n_pos = lds->npos[lane];
+            acc.sum = n_pos ? (double)n_pos * sb - (double)(long long)lds->tsum[lane] * (1.0 / 8388608.0) : 0.0;
         }
     }
     // edge list: the samples [seg_start, min(seg_end, H)) and [max(seg_start, L - H), seg_end) of every hit that has any,
