@@ -155,8 +155,10 @@ int wfa_set_sg_plan(wfa_ctx* ctx, int window, int polyorder, const double* tab,
 
 /* ---- kernels ---------------------------------------------------------------------------- */
 
-/* K1 baseline estimate: mean of samples [start, end) of every record as float64, NaN when
- * the window is empty (reference: records_builder.py:243-257, waveforms.py:714-733).
+/* K1 baseline estimate: mean of samples [start, min(end, event_length)) of every record as
+ * float64, NaN when that range is empty (reference: records_builder.py:243-257,
+ * waveforms.py:714-733).  start >= 0, or WFA_E_INVALID; both ends are clamped to the longest
+ * uploaded record on the host, which changes no result (here and in the fused passes below).
  * Writes the device-resident baseline column when update_records != 0; out may be NULL. */
 int wfa_baseline_mean(wfa_ctx* ctx, int32_t start, int32_t end, int update_records, double* out);
 

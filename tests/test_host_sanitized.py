@@ -1,5 +1,5 @@
 """AddressSanitizer + UndefinedBehaviorSanitizer run of the host-only C++ of libwfa_hip.so (csrc/wfa_host.hpp: the V1725
-header walk and the pinned staging ring of the pool uploads) behind a stand-in device (csrc/host_check.cpp) -- SURVEY
+header walk, the pinned staging ring of the pool uploads, the uniform-layout rule, the baseline-window clamp) behind a stand-in device (csrc/host_check.cpp) -- SURVEY
 section 5 assigns this build to the backend (the reference has none); CPU box only, the GPU pool has no sanitizer.
 
 The V1725 streams are the reference-made fixture (tests/golden/v1725bin_files.npz: blobs written by the generator, index
@@ -142,3 +142,38 @@ def test_uniform_layout_rule_under_sanitizers(host_check, tmp_path):
     # both upload routes of the product run this copy
     capi = open(os.path.join(CSRC, "wfa_capi.hip")).read()
     assert capi.count("host::uniform_layout(") == 2 and capi.count("host::records_uniform(") == 1
+
+
+def _window_expected(start, end, max_len):
+    """The stated rule: start -> min(start, max_len), end -> min(end, max_len); empty for every record -> (max_len,
+    max_len)."""
+    s, e = min(start, max_len), min(end, max_len)
+    return (s, e) if s < e else (max_len, max_len)
+
+
+def test_baseline_window_clamp_under_sanitizers(host_check, tmp_path):
+    """csrc/wfa_host.hpp baseline_window, the clamp wfa_baseline_mean and the hit pass apply before any kernel sees a
+    window: starts up to INT32_MAX, where `start + lane` of the kernels' loops would overflow, never reach a kernel."""
+    i32max, limit = 2**31 - 1, 130_432                      # WFA_MAX_RECORD_SAMPLES
+    starts = (0, 1, 5, 39, 40, 63, 64, limit - 1, limit, limit + 1, i32max - 64, i32max - 63, i32max - 1, i32max)
+    ends = (0, 1, 8, 40, 41, 64, 65, limit - 1, limit, limit + 1, i32max - 63, i32max)
+    cases = [(s, e, m) for m in (0, 1, 24, 64, limit) for s in starts for e in ends]
+    path = tmp_path / "windows.bin"
+    path.write_bytes(np.array(cases, np.int32).tobytes())
+    got = run(host_check, "window", path)
+    assert got["cases"] == len(cases) > 800
+    assert {(i32max, i32max, m) for m in (0, 1, limit)} <= set(cases)
+    for (s, e, m), (gs, ge, last) in zip(cases, got["windows"]):
+        assert (gs, ge) == _window_expected(s, e, m), (s, e, m)
+        assert 0 <= gs <= ge <= m and last <= limit + 127, (s, e, m, gs, ge, last)
+        # the same records get the same baseline: for every length L <= max_len, [s, min(e, L)) is the same range or
+        # empty on both sides
+        for L in {L for L in (0, 1, m // 2, m - 1, m) if 0 <= L <= m}:
+            before = (s, min(e, L)) if min(e, L) > s else None
+            after = (gs, min(ge, L)) if min(ge, L) > gs else None
+            assert before == after, (s, e, m, L)
+    capi = open(os.path.join(CSRC, "wfa_capi.hip")).read()
+    assert capi.count("host::baseline_window(") == 2          # wfa_baseline_mean and run_hits
+    for fn in ("int wfa_baseline_mean(", "static int run_hits("):
+        body = capi[capi.index(fn):]
+        assert "host::baseline_window(" in body[:body.index("\n}\n")], fn

@@ -201,3 +201,89 @@ def test_fixture_v1725_equals_builder_fixture():
     want["polarity"] = fx["v1725_records"]["polarity"]
     G.assert_struct_equal(fx["v1725_records"], want)
     np.testing.assert_array_equal(fx["v1725_wave_pool"], z["wave_pool"])
+
+
+def test_fuse_baseline_is_validated_like_baseline_samples():
+    """HipThresholdHitPlugin's fuse_baseline: None, or two non-negative ints with start < end, with the messages of the
+    records builder's (start, end) rule.  An empty window is refused because the plugin's two routes would read it
+    differently (the fused pass skips the estimate, baseline_mean writes NaN)."""
+    from waveformanalysis_amd.plugins import threshold_hit as T
+
+    v = T.HipThresholdHitPlugin.options["fuse_baseline"].validate
+    assert T.fuse_baseline_window(None) is None and v(None)
+    for good in ((0, 40), [5, 29], (79, 2**31 - 1), (0, 2**31)):
+        assert T.fuse_baseline_window(good) == tuple(good) and v(good)
+    for bad, exc, msg in (((7, 7), ValueError, r"start must be less than end, got \(7, 7\)"),
+                          ((9, 3), ValueError, r"start must be less than end, got \(9, 3\)"),
+                          ((-1, 5), ValueError, r"indices must be non-negative, got \(-1, 5\)"),
+                          ((0, -5), ValueError, r"indices must be non-negative, got \(0, -5\)"),
+                          ((1, 2, 3), ValueError, "tuple must have 2 elements"),
+                          ((0.0, 40), TypeError, r"tuple elements must be int, got \(float, int\)"),
+                          (40, TypeError, "fuse_baseline must be None or a tuple"),
+                          (True, TypeError, "fuse_baseline must be None or a tuple"),
+                          ("0,40", TypeError, "fuse_baseline must be None or a tuple")):
+        assert not v(bad), bad
+        with pytest.raises(exc, match=msg):
+            T.fuse_baseline_window(bad)
+        # the same messages as the records builder, where it takes the value at all
+        if isinstance(bad, tuple):
+            with pytest.raises(exc, match=msg):
+                RB._baseline_window(bad, 0, 0, 1)
+    # compute() refuses the option before it reads any input
+    rec = np.zeros(1, dtype=RB.RECORDS_DTYPE)
+    ctx = SimpleContext({"wave_source": "records", "hit_threshold": {"fuse_baseline": (7, 7)}},
+                        {"records": rec, "wave_pool": np.zeros(0, np.uint16)}, [T.HipThresholdHitPlugin()])
+    with pytest.raises(RuntimeError, match=r"start must be less than end, got \(7, 7\)") as err:
+        ctx.get_data("run", "hit_threshold")
+    assert isinstance(err.value.__cause__, ValueError)
+
+
+class _WindowLib:
+    """Stand-in for libwfa_hip.so that records the window arguments as Python ints, before ctypes would narrow them."""
+
+    def __init__(self):
+        self.calls = []
+
+    def wfa_ctx_create(self, device_id, handle):
+        return 0
+
+    def wfa_baseline_mean(self, h, start, end, update, out):
+        self.calls.append((start, end))
+        return 0
+
+    def wfa_fused_baseline_filter_hits(self, h, start, end, le, re, max_len, n):
+        self.calls.append((start, end))
+        return 0
+
+    def wfa_hits_enqueue(self, h, source, start, end, le, re, max_len):
+        self.calls.append((start, end))
+        return 0
+
+    def wfa_threshold_hits_fill(self, h, out, n):
+        return 0
+
+
+def test_session_saturates_the_window_before_ctypes(monkeypatch):
+    """DeviceSession passes the window through int32 arguments, which ctypes narrows silently: 2**31 as "to the end"
+    would arrive as an empty window.  Both ends saturate at 2**31 - 1, a negative start is refused."""
+    from waveformanalysis_amd import _lib, device
+
+    lib = _WindowLib()
+    monkeypatch.setattr(_lib, "load", lambda: lib)
+    sess = device.DeviceSession(0)
+    i32max = 2**31 - 1
+    table = {(0, 40): (0, 40), (5, 2**31): (5, i32max), (5, 2**40): (5, i32max), (2**31, 2**33): (i32max, i32max),
+             (7, 7): (7, 7), (3, -2): (3, 0), (0, i32max): (0, i32max), (np.int64(2), np.int64(2**31)): (2, i32max)}
+    for window, want in table.items():
+        lib.calls.clear()
+        sess.baseline_mean(*window)
+        sess.fused_baseline_filter_hits(window, 2, 2)
+        sess.hits_enqueue(_lib.SRC_SG_FUSED, window, 2, 2)
+        assert lib.calls == [want] * 3, window
+        assert all(type(x) is int and 0 <= x <= i32max for call in lib.calls for x in call)
+    lib.calls.clear()
+    for call in (lambda: sess.baseline_mean(-1, 5), lambda: sess.fused_baseline_filter_hits((-1, 5)),
+                 lambda: sess.hits_enqueue(_lib.SRC_SG_FUSED, (-2**31, 5))):
+        with pytest.raises(ValueError, match="baseline window start must be >= 0"):
+            call()
+    assert lib.calls == []

@@ -7,6 +7,7 @@
 //   host_check v1725-prefixes <blob file>  the walk over EVERY prefix 0..n of a small stream: wave total and a digest
 //   host_check ring <bytes> <stage>  staged copy of a pseudo-random buffer, compared byte for byte
 //   host_check layout <cases file>   the uniform-record layout of every records table in the file
+//   host_check window <cases file>   the baseline window the kernels see for every (start, end, max_len) in the file
 #include <atomic>
 #include <condition_variable>
 #include <cstdlib>
@@ -214,6 +215,27 @@ int check_layout(const char* path) {
     return 0;
 }
 
+// File: int32 triples (start, end, max_len).  Prints the clamped window of each, and for each the largest sample index a
+// wave-strided kernel loop (`for (i = start + lane; i < e; i += 64)`, lane 0..63, e = min(end, L) for an L <= max_len)
+// computes, in 64 bits: the test asserts it fits an int32 with room to spare.
+int check_window(const char* path) {
+    FILE* f = fopen(path, "rb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", path); return 2; }
+    printf("{\"windows\": [");
+    int32_t t[3];
+    int n_cases = 0;
+    while (fread(t, sizeof(int32_t), 3, f) == 3) {
+        const wfa::host::BaselineWindow w = wfa::host::baseline_window(t[0], t[1], t[2]);
+        const int first = w.start + 63;                       // the addition the kernels do: int, under the sanitizer
+        const int64_t last = (int64_t)(w.end > first ? w.end : first) + 64;
+        printf("%s[%d, %d, %lld]", n_cases ? ", " : "", (int)w.start, (int)w.end, (long long)last);
+        ++n_cases;
+    }
+    fclose(f);
+    printf("], \"cases\": %d}\n", n_cases);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -221,6 +243,8 @@ int main(int argc, char** argv) {
     if (argc == 3 && !strcmp(argv[1], "v1725-prefixes")) return check_v1725_prefixes(argv[2]);
     if (argc == 4 && !strcmp(argv[1], "ring")) return check_ring((size_t)atoll(argv[2]), (size_t)atoll(argv[3]));
     if (argc == 3 && !strcmp(argv[1], "layout")) return check_layout(argv[2]);
-    fprintf(stderr, "usage: host_check v1725 <blob> | v1725-prefixes <blob> | ring <bytes> <stage bytes> | layout <cases>\n");
+    if (argc == 3 && !strcmp(argv[1], "window")) return check_window(argv[2]);
+    fprintf(stderr, "usage: host_check v1725 <blob> | v1725-prefixes <blob> | ring <bytes> <stage bytes> | layout <cases> | "
+                    "window <cases>\n");
     return 2;
 }

@@ -465,6 +465,10 @@ static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int
     if (max_len < c->max_len)
         return fail(WFA_E_INVALID, "max_len (%d) < longest uploaded record (%d)", max_len, c->max_len);
     if (fused_bl && bl_start < 0) return fail(WFA_E_INVALID, "baseline window start must be >= 0");
+    if (fused_bl) {  // (a queued pass that is redone comes back here with the clamped window: the clamp is idempotent)
+        const host::BaselineWindow w = host::baseline_window(bl_start, bl_end, c->max_len);
+        bl_start = w.start; bl_end = w.end;
+    }
     c->n_hits = -1;
     if (c->R == 0) {
         c->n_hits = 0;
@@ -1031,6 +1035,8 @@ int wfa_baseline_mean(wfa_ctx* c, int32_t start, int32_t end, int update_records
     if ((rc = need_source(c, WFA_SRC_RAW))) return rc;
     if (start < 0) return fail(WFA_E_INVALID, "baseline window start must be >= 0");
     if (c->R == 0) return WFA_OK;
+    const host::BaselineWindow w = host::baseline_window(start, end, c->max_len);
+    start = w.start; end = w.end;
     double* dst = c->baseline.as<double>();
     if (!update_records) {
         if ((rc = c->out_rows.ensure((size_t)c->R * sizeof(double)))) return rc;

@@ -4,7 +4,8 @@
 //   * v1725_index: header walk of a CAEN V1725 DAW_DEMO binary stream (reference utils/formats/v1725.py:66-114);
 //   * staged_copy: host -> device through two pinned staging buffers, a few host threads filling one while the other is
 //     on the wire (the ring of wfa_upload_pool_u16 / wfa_upload_pool_f32);
-//   * records_uniform / uniform_layout: the uniform-record layout of a records upload (both upload routes).
+//   * records_uniform / uniform_layout: the uniform-record layout of a records upload (both upload routes);
+//   * baseline_window: the clamp of a baseline window to the longest uploaded record (wfa_baseline_mean, the hit pass).
 #pragma once
 
 #include <cstdint>
@@ -49,6 +50,21 @@ inline UniformLayout uniform_layout(bool uniform, int64_t R, int32_t len0, int64
     u.S = u.pad ? (len0 + 15) / 16 * 16 : len0;
     u.off0 = off0;
     return u;
+}
+
+// The baseline window [start, end) as the kernels see it.  Every kernel clamps end to its record's length and takes a
+// window that is empty after that as NaN, so min(start, max_len) and min(end, max_len) give the same baselines
+// (max_len: the longest uploaded record); a window that is empty for every record becomes (max_len, max_len).  No kernel
+// then adds a lane number to a start above max_len <= WFA_MAX_RECORD_SAMPLES.  (Callers refuse start < 0; here it counts
+// as empty.)
+struct BaselineWindow {
+    int32_t start, end;
+};
+inline BaselineWindow baseline_window(int32_t start, int32_t end, int32_t max_len) {
+    if (max_len < 0) max_len = 0;
+    const int32_t e = end < max_len ? end : max_len;
+    if (start < 0 || e <= start) return {max_len, max_len};
+    return {start, e};
 }
 
 // Returns 0, or -1 with a message in err (the stream is malformed: a channel block shorter than its own header).

@@ -563,8 +563,9 @@ __device__ __attribute__((noinline)) void span_phase0(const PoolView& pool, cons
         thr = rec.thr[r];
         if (FUSED_BASELINE) {
             const int s0 = mp.bl_start, e0 = mp.bl_end < L ? mp.bl_end : L;
-            int tot = 0;
+            int64_t tot = 0;  // (an int holds one round's 32 samples, not 32 769 samples of 0xFFFF)
             for (int c = s0 >> 3; c * 8 < e0; c += 4) {  // 4 independent 16-byte loads per round
+                int part = 0;
                 uint4 v[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) v[k] = ((c + k) * 8 < e0) ? p[c + k] : make_uint4(0, 0, 0, 0);
@@ -575,9 +576,10 @@ __device__ __attribute__((noinline)) void span_phase0(const PoolView& pool, cons
                     for (int j = 0; j < 8; ++j) {
                         const int idx = (c + k) * 8 + j;
                         const int x = (int)((d[j >> 1] >> (16 * (j & 1))) & 0xffffu);
-                        tot += (idx >= s0 && idx < e0) ? x : 0;
+                        part += (idx >= s0 && idx < e0) ? x : 0;
                     }
                 }
+                tot += part;
             }
             baseline = (e0 <= s0) ? __longlong_as_double(0x7ff8000000000000LL) : (double)tot / (double)(e0 - s0);
             rec.baseline_rw[r] = baseline;

@@ -58,6 +58,20 @@ def _check_out(out: np.ndarray, dtype: np.dtype, n: int) -> None:
         raise ValueError(f"out must be a writeable contiguous array of {n} rows of {dtype}")
 
 
+_I32_MAX = 2**31 - 1
+
+
+def baseline_window_i32(start, end) -> tuple[int, int]:
+    """A baseline window [start, end) as the two int32 of the C ABI.  ctypes narrows silently (2**31 would arrive as
+    -2**31, "to the end" as an empty window), so: a negative start is refused here, with the library's message; both
+    ends saturate at 2**31 - 1, beyond every record length, which selects the same samples; a negative end, empty
+    either way, becomes 0."""
+    start, end = int(start), int(end)
+    if start < 0:
+        raise ValueError("baseline window start must be >= 0")
+    return min(start, _I32_MAX), min(max(end, 0), _I32_MAX)
+
+
 def device_count() -> int:
     n = C.c_int(0)
     _lib.check(_lib.load().wfa_device_count(C.byref(n)))
@@ -287,10 +301,11 @@ class DeviceSession:
 
     # -- kernels --------------------------------------------------------------------------------
     def baseline_mean(self, start: int, end: int, update_records: bool = False) -> np.ndarray:
+        start, end = baseline_window_i32(start, end)
         out = np.empty(self.n_records, dtype=np.float64)
         if update_records:
             self._res_records = None
-        _lib.check(self._lib.wfa_baseline_mean(self._h, int(start), int(end), int(update_records), _ptr(out)))
+        _lib.check(self._lib.wfa_baseline_mean(self._h, start, end, int(update_records), _ptr(out)))
         return out
 
     def filter_keep_output(self, keep: bool) -> None:
@@ -352,17 +367,19 @@ class DeviceSession:
                                    right_extension: int = 2, max_len: int = 0,
                                    download: bool = True) -> np.ndarray | int:
         n = C.c_int64(0)
+        start, end = baseline_window_i32(*baseline_window)
         self._res_records = None  # the pass may write the device baselines
         _lib.check(self._lib.wfa_fused_baseline_filter_hits(
-            self._h, int(baseline_window[0]), int(baseline_window[1]), int(left_extension),
+            self._h, start, end, int(left_extension),
             int(right_extension), int(max_len), C.byref(n)))
         return self._fill_hits(int(n.value)) if download else int(n.value)
 
     def hits_enqueue(self, source: int = _lib.SRC_SG_FUSED, baseline_window: tuple[int, int] = (0, 0),
                      left_extension: int = 2, right_extension: int = 2, max_len: int = 0) -> None:
         """Queue a hit pass without waiting for it (see wfa_hits_enqueue); hits_wait() / _fill_hits deliver."""
+        start, end = baseline_window_i32(*baseline_window)
         self._res_records = None  # the pass may write the device baselines
-        _lib.check(self._lib.wfa_hits_enqueue(self._h, int(source), int(baseline_window[0]), int(baseline_window[1]),
+        _lib.check(self._lib.wfa_hits_enqueue(self._h, int(source), start, end,
                                               int(left_extension), int(right_extension), int(max_len)))
 
     def hits_wait(self) -> int:

@@ -11,8 +11,29 @@ import numpy as np
 from .. import dense
 from ..dtypes import THRESHOLD_HIT_DTYPE
 from ..plugin_api import Option, Plugin
+from ..records_builder import _baseline_window
 from ..sg_plan import normalize_window
 from . import _common as K
+
+
+def fuse_baseline_window(value) -> tuple[int, int] | None:
+    """The fuse_baseline option as (start, end), validated like the (start, end) form of the records builder's
+    baseline_samples (same messages): None, or two non-negative ints with start < end.  An empty window is refused
+    because the two routes of the plugin would read it differently: the fused entry point of the library skips the
+    estimate for end <= start and keeps the uploaded baselines, baseline_mean gives NaN and with it no hits."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (tuple, list)):
+        raise TypeError(f"fuse_baseline must be None or a tuple (start, end), got {type(value).__name__}")
+    return _baseline_window(value, 0, 0, 1)
+
+
+def _valid_fuse_baseline(value) -> bool:
+    try:
+        fuse_baseline_window(value)
+    except (TypeError, ValueError):
+        return False
+    return True
 
 
 class HipThresholdHitPlugin(K.HipPlugin):
@@ -34,9 +55,10 @@ class HipThresholdHitPlugin(K.HipPlugin):
             help="with use_filtered: evaluate the Savitzky-Golay filter inside the hit kernel from "
                  "wave_pool instead of reading a materialised wave_pool_filtered (same result)"),
         "fuse_baseline": Option(
-            default=None,
-            help="None, or (start, end): re-estimate records.baseline as the mean of samples "
-                 "[start, end) inside the hit kernel (the records-builder rule)"),
+            default=None, validate=_valid_fuse_baseline,
+            help="None, or (start, end) with 0 <= start < end: re-estimate records.baseline as the mean of samples "
+                 "[start, min(end, event_length)) inside the hit kernel (the records-builder rule; NaN and no "
+                 "hits for a record that ends at or before start)"),
         "wave_source": Option(default=K.WAVE_SOURCE_AUTO, type=str,
                               help="auto|records|st_waveforms|filtered_waveforms"),
         "left_extension": Option(default=2, type=int, help="samples added left of a hit"),
@@ -61,7 +83,7 @@ class HipThresholdHitPlugin(K.HipPlugin):
         channel_config = context.get_config(self, "channel_config")
         use_filtered = bool(context.get_config(self, "use_filtered"))
         fused = use_filtered and bool(context.get_config(self, "fuse_filter"))
-        fuse_baseline = context.get_config(self, "fuse_baseline")
+        fuse_baseline = fuse_baseline_window(context.get_config(self, "fuse_baseline"))
         kind, _deps, data_name = K.resolve_wave_input(context, self)
         if kind == "dense":
             return self._compute_dense(context, run_id, data_name, threshold, le, re, explicit_dt, channel_config)
