@@ -12,7 +12,8 @@
  *   - plain C, caller-allocated host buffers, no callbacks;
  *   - every function returns 0 on success or a negative WFA_E_* code;
  *     wfa_last_error() returns the message of the calling thread's last failure;
- *   - one wfa_ctx per (GPU, host thread); a ctx owns one HIP stream and its device
+ *   - one wfa_ctx per (GPU, host thread); a ctx owns one HIP stream (plus a second one that
+ *     only wfa_upload_dense_rows uses, idle again when it returns) and its device
  *     buffers; calls on one ctx are serialised by the caller;
  *   - the pool and the records SoA stay resident in HBM between calls, so
  *     filter -> hits -> features read them without another host transfer.
@@ -27,7 +28,7 @@
 extern "C" {
 #endif
 
-#define WFA_ABI_VERSION 1
+#define WFA_ABI_VERSION 2
 
 #define WFA_OK 0
 #define WFA_E_INVALID (-1)   /* bad argument / malformed records (maps to ValueError) */
@@ -110,6 +111,28 @@ int wfa_upload_pool_u16(wfa_ctx* ctx, const uint16_t* pool, int64_t n_samples);
  * the resident wave_pool it becomes its float32 twin; with a different count it replaces the pool set (the
  * uint16 pool is dropped and records must be uploaded again). */
 int wfa_upload_pool_f32(wfa_ctx* ctx, const float* pool, int64_t n_samples);
+
+/* The samples of a dense array (st_waveforms / filtered_waveforms) as the resident pool, unpacked ON THE DEVICE
+ * (reference: cpu/_wave_source.py load_wave_input hands such an array to the dense branches hit_finder.py:179-255,
+ * peak_finding.py:336-343 and basic_features.py:197-278, which read data["wave"] row by row).  `rows` = the memory of a
+ * C-contiguous 1-D structured array: n_rows rows of row_bytes bytes, each with wave_length elements at byte wave_offset
+ * (ST_WAVEFORM_DTYPE, processing/dtypes.py:18-64: wave at byte 76, rows of 76 + 2 L bytes).  elem:
+ *   WFA_DENSE_I16  int16 samples read as uint16 ADC codes; a sample with the sign bit set is an error
+ *   WFA_DENSE_U16  uint16 samples
+ *   WFA_DENSE_F32  float32 samples, copied bit for bit (NaN payloads, -0.0, infinities)
+ * Whole rows go through the pinned staging ring in batches of at most batch_bytes (at least one row, at most 1 GiB)
+ * into two device buffers in turn; k_dense_unpack writes batch k into the pool in row-major order (sample j of row r at
+ * r * wave_length + j) on a second stream while batch k + 1 is copied.  Afterwards the context is in the state
+ * wfa_upload_pool_u16 (I16 / U16) or wfa_upload_pool_f32 (F32) of the n_rows * wave_length samples leaves.
+ * WFA_E_INVALID before any launch: a negative count, wave_offset or row_bytes no multiple of the element size,
+ * wave_offset + wave_length * itemsize > row_bytes.  n_rows == 0 or wave_length == 0: an empty pool, no launch.
+ * I16 with a negative sample: WFA_E_INVALID, *first_negative_row (nullable; -1 otherwise) = the smallest row that holds
+ * one, and the context is left without a pool and without records. */
+#define WFA_DENSE_I16 0
+#define WFA_DENSE_U16 1
+#define WFA_DENSE_F32 2
+int wfa_upload_dense_rows(wfa_ctx* ctx, const void* rows, int64_t n_rows, int64_t row_bytes, int32_t wave_offset,
+                          int32_t wave_length, int elem, int64_t batch_bytes, int64_t* first_negative_row);
 
 /* Records index table as structure-of-arrays (reference row layout: processing/dtypes.py:80-100;
  * the per-channel option lookups of hit_finder.py:288-327 are resolved by the caller into

@@ -6,9 +6,10 @@ kernel times are the HIP-event times of profile_report.  Prints the median, min 
 that both return the same rows.
 
 End-to-end leg (`--e2e-records`, default 625 000 x 800 = 5e8 samples, positive twin of the synthetic run, one hit per
-record at its maximum): wall time of HipWaveformWidthPlugin.compute on the dense route (st_waveforms: the dense copy is
-uploaded on every call and evicts the resident pool) and on the records route with the pool resident; median of 3
-after the call that uploads the pool, outputs compared.  `--e2e-records 0` skips it, `--rounds 0` the kernel leg.
+record at its maximum): wall time of HipWaveformWidthPlugin.compute on the dense route (st_waveforms: its rows are
+uploaded and unpacked on the device by the first call and stay resident) and on the records route with the pool
+resident; median of 3 after the call that uploads the samples, outputs compared.  `--e2e-records 0` skips it,
+`--rounds 0` the kernel leg.  (tools/dense_time.py times the dense route against its host-copy form.)
 
 One JSON line per leg.
 """

@@ -25,7 +25,8 @@ POL_UNKNOWN, POL_NEGATIVE, POL_POSITIVE, POL_POSITIVE_WAVE = 0, 1, 2, 3
 ST_SRC_HOST, ST_SRC_CSV, ST_SRC_ARENA, ST_SRC_POOL = 0, 1, 2, 3
 VIEW_WAVES, VIEW_WAVES_BASELINE, VIEW_SIGNALS = 0, 1, 2
 VIEW_U16, VIEW_F32, VIEW_F64 = 0, 1, 2
-ABI_VERSION = 1
+DENSE_I16, DENSE_U16, DENSE_F32 = 0, 1, 2
+ABI_VERSION = 2
 
 _p = C.c_void_p
 _i32, _i64, _f64, _int = C.c_int32, C.c_int64, C.c_double, C.c_int
@@ -45,6 +46,7 @@ SIGNATURES = {
     "wfa_hit_rows_source": (_int, [_p, _int]),
     "wfa_upload_pool_u16": (_int, [_p, _p, _i64]),
     "wfa_upload_pool_f32": (_int, [_p, _p, _i64]),
+    "wfa_upload_dense_rows": (_int, [_p, _p, _i64, _i64, _i32, _i32, _int, _i64, C.POINTER(_i64)]),
     "wfa_upload_records_soa": (_int, [_p, _i64] + [_p] * 10),
     "wfa_upload_records_packed": (_int, [_p, _p, _i64, _i32, _p, _i32, _f64, _p, _p, C.POINTER(_i32), C.POINTER(_int)]),
     "wfa_set_sg_plan": (_int, [_p, _int, _int, _p, _p, _int, _p, _i32, _i32, _i64, _i64]),

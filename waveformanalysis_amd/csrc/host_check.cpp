@@ -8,6 +8,7 @@
 //   host_check ring <bytes> <stage>  staged copy of a pseudo-random buffer, compared byte for byte
 //   host_check layout <cases file>   the uniform-record layout of every records table in the file
 //   host_check window <cases file>   the baseline window the kernels see for every (start, end, max_len) in the file
+//   host_check dense                 every lane of k_dense_unpack over exactly-sized batch buffers and pools
 #include <atomic>
 #include <condition_variable>
 #include <cstdlib>
@@ -236,9 +237,109 @@ int check_window(const char* path) {
     return 0;
 }
 
+// k_dense_unpack on the host: every lane of every batch of one upload, the way wfa_upload_dense_rows cuts it.  Each
+// batch is an exactly-sized, 16-byte aligned heap copy of its rows and the pool holds exactly n_rows * L elements: a
+// load outside the batch buffer or a store outside the pool is a heap-buffer-overflow, a load the alignment does not
+// allow a misaligned-address report.  Returns the elements that differ from rows[r].wave[j] (0 = pass); *negative = the
+// smallest row the lanes reported (-1: none).
+template <int ES, bool SIGNED>
+int64_t dense_upload(const std::vector<uint8_t>& rows, int64_t n_rows, int64_t row_bytes, int64_t wave_offset, int64_t L,
+                     int64_t batch_bytes, int64_t* negative, int64_t* lanes) {
+    namespace H = wfa::host;
+    const int W = H::dense_load_bytes(wave_offset, row_bytes, ES);
+    const size_t pool_bytes = (size_t)(n_rows * L) * ES;
+    uint8_t* pool = (uint8_t*)malloc(pool_bytes ? pool_bytes : 1);  // malloc: 16-byte aligned, exactly sized
+    if (!pool) return -1;
+    memset(pool, 0xa5, pool_bytes);
+    *negative = -1;
+    const int64_t rpb = n_rows && L ? H::dense_rows_per_batch(n_rows, row_bytes, batch_bytes) : 1;
+    for (int64_t row = 0; row < n_rows && L > 0; row += rpb) {
+        const int64_t nr = rpb < n_rows - row ? rpb : n_rows - row;
+        const size_t bytes = (size_t)(nr * row_bytes);
+        uint8_t* buf = (uint8_t*)malloc(bytes);
+        memcpy(buf, rows.data() + (size_t)(row * row_bytes), bytes);
+        H::DenseBatch b{};
+        b.out_begin = (uint64_t)(row * L);
+        b.out_end = (uint64_t)((row + nr) * L);
+        b.row0 = row;
+        b.L = (uint32_t)L;
+        b.row_elems = (uint32_t)(row_bytes / ES);
+        b.wave_elem = (uint32_t)(wave_offset / ES);
+        const uint64_t c0 = H::dense_first_chunk(b, ES), nc = H::dense_chunk_count(b, ES);
+        for (uint64_t g = 0; g < nc; ++g) {
+            int64_t neg = -1;
+            switch (W) {
+                case 2: if constexpr (ES == 2) neg = H::dense_unpack_lane<ES, 2, SIGNED>(buf, pool, b, c0 + g); break;
+                case 4: neg = H::dense_unpack_lane<ES, 4, SIGNED>(buf, pool, b, c0 + g); break;
+                case 8: neg = H::dense_unpack_lane<ES, 8, SIGNED>(buf, pool, b, c0 + g); break;
+                default: neg = H::dense_unpack_lane<ES, 16, SIGNED>(buf, pool, b, c0 + g); break;
+            }
+            if (neg >= 0 && (*negative < 0 || neg < *negative)) *negative = neg;
+        }
+        *lanes += (int64_t)nc;
+        free(buf);
+    }
+    int64_t bad = 0;
+    for (int64_t r = 0; r < n_rows; ++r)
+        for (int64_t j = 0; j < L; ++j)
+            bad += memcmp(pool + (size_t)(r * L + j) * ES, rows.data() + (size_t)(r * row_bytes + wave_offset + j * ES), ES) != 0;
+    free(pool);
+    return bad;
+}
+
+// Shapes (n, L) x layouts (wave at byte 76 / 0 / 2, and a 16-byte aligned one) x batch sizes (one row, three rows,
+// everything) x element types, pseudo-random contents; for int16 one run per case with a few sign bits set.
+int check_dense() {
+    const int64_t shapes[][2] = {{0, 5}, {3, 0}, {1, 1}, {3, 7}, {5, 8}, {4, 9}, {7, 33}, {64, 800}, {9, 16}, {2, 4099}};
+    uint64_t s = 0x9e3779b97f4a7c15ull;
+    auto next = [&] { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return s; };
+    int64_t cases = 0, lanes = 0, widths[17] = {0};
+    for (auto& sh : shapes) {
+        const int64_t n = sh[0], L = sh[1];
+        for (int es : {2, 4}) {
+            const int64_t layouts[][2] = {{76, 76 + L * es}, {0, L * es}, {es == 2 ? 2 : 4, (es == 2 ? 2 : 4) + L * es},
+                                          {32, (32 + L * es + 15) / 16 * 16}, {8, 8 + L * es + (L * es) % 8}};
+            for (auto& lay : layouts) {
+                const int64_t off = lay[0], rb = lay[1];
+                if (rb == 0) continue;
+                std::vector<uint8_t> rows((size_t)(n * rb));
+                for (auto& x : rows) x = (uint8_t)next();
+                if (es == 2)  // int16 contents without a sign bit
+                    for (int64_t r = 0; r < n; ++r)
+                        for (int64_t j = 0; j < L; ++j) rows[(size_t)(r * rb + off + 2 * j + 1)] &= 0x7f;
+                for (int64_t batch : {(int64_t)1, 3 * rb, (int64_t)1 << 30}) {
+                    int64_t neg = -1, bad;
+                    ++widths[wfa::host::dense_load_bytes(off, rb, es)];
+                    if (es == 4) bad = dense_upload<4, false>(rows, n, rb, off, L, batch, &neg, &lanes);
+                    else bad = dense_upload<2, true>(rows, n, rb, off, L, batch, &neg, &lanes);
+                    if (bad || neg != -1) { fprintf(stderr, "dense n=%lld L=%lld es=%d off=%lld rb=%lld batch=%lld: %lld bad, negative %lld\n", (long long)n, (long long)L, es, (long long)off, (long long)rb, (long long)batch, (long long)bad, (long long)neg); return 1; }
+                    ++cases;
+                    if (es == 2 && n > 0 && L > 0) {  // sign bits: last sample of the last row, then also a row in between
+                        std::vector<uint8_t> marked = rows;
+                        marked[(size_t)((n - 1) * rb + off + 2 * (L - 1) + 1)] |= 0x80;
+                        bad = dense_upload<2, true>(marked, n, rb, off, L, batch, &neg, &lanes);
+                        if (bad || neg != n - 1) { fprintf(stderr, "dense: negative in the last row reported as %lld\n", (long long)neg); return 1; }
+                        const int64_t mid = n / 2;
+                        marked[(size_t)(mid * rb + off + 1)] |= 0x80;
+                        bad = dense_upload<2, true>(marked, n, rb, off, L, batch, &neg, &lanes);
+                        if (bad || neg != mid) { fprintf(stderr, "dense: negative in row %lld reported as %lld\n", (long long)mid, (long long)neg); return 1; }
+                        bad = dense_upload<2, false>(marked, n, rb, off, L, batch, &neg, &lanes);  // the same bits as uint16
+                        if (bad || neg != -1) { fprintf(stderr, "dense: uint16 rows reported a negative\n"); return 1; }
+                        cases += 3;
+                    }
+                }
+            }
+        }
+    }
+    printf("{\"cases\": %lld, \"lanes\": %lld, \"load2\": %lld, \"load4\": %lld, \"load8\": %lld, \"load16\": %lld}\n", (long long)cases,
+           (long long)lanes, (long long)widths[2], (long long)widths[4], (long long)widths[8], (long long)widths[16]);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+    if (argc == 2 && !strcmp(argv[1], "dense")) return check_dense();
     if (argc == 3 && !strcmp(argv[1], "v1725")) return check_v1725(argv[2]);
     if (argc == 3 && !strcmp(argv[1], "v1725-prefixes")) return check_v1725_prefixes(argv[2]);
     if (argc == 4 && !strcmp(argv[1], "ring")) return check_ring((size_t)atoll(argv[2]), (size_t)atoll(argv[3]));

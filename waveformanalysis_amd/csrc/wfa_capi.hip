@@ -702,6 +702,59 @@ __global__ __launch_bounds__(256) void k_unpack_records(const uint8_t* __restric
     if (r > 0 && rid <= load_unaligned<int64_t>(row - f.row_bytes + f.rid)) atomicOr(&res->rid_not_increasing, 1);
 }
 
+// ---- dense rows (st_waveforms / filtered_waveforms), unpacked on the device -------------------------------------------
+// (reference: cpu/_wave_source.py load_wave_input hands the structured array to the dense branches, which read
+// data["wave"] -- a strided view of rows of 76 + 2 L bytes -- row by row.)  The rows go through the staging ring as they
+// are; a lane owns 16 bytes of the row-major pool and collects them from the rows of the batch (host::dense_unpack_lane,
+// wfa_host.hpp: the same function runs over exactly-sized buffers in host_check).  W = bytes per load, chosen on the host
+// from the alignment of (wave_offset, row_bytes).
+template <int ES, int W, bool SIGNED>
+__global__ __launch_bounds__(256) void k_dense_unpack(const uint8_t* __restrict__ rows, uint8_t* __restrict__ pool,
+                                                       host::DenseBatch b, uint64_t chunk0, uint32_t n_chunks,
+                                                       unsigned long long* __restrict__ first_negative) {
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= n_chunks) return;
+    const int64_t neg = host::dense_unpack_lane<ES, W, SIGNED>(rows, pool, b, chunk0 + g);
+    if constexpr (SIGNED) {
+        // (the plain read only spares the atomic once an earlier row is known: the word never grows)
+        if (neg >= 0 && (unsigned long long)neg < *(volatile unsigned long long*)first_negative)
+            atomicMin(first_negative, (unsigned long long)neg);
+    }
+}
+
+template <int ES, bool SIGNED>
+static int launch_dense_unpack(int load_bytes, hipStream_t stream, const uint8_t* rows, uint8_t* pool,
+                               const host::DenseBatch& b, unsigned long long* first_negative) {
+    const uint64_t chunk0 = host::dense_first_chunk(b, ES);
+    const uint64_t chunks = host::dense_chunk_count(b, ES);
+    if (chunks == 0) return WFA_OK;
+    if (chunks > 0xffffffffull) return fail(WFA_E_LIMIT, "dense batch too large");
+    const dim3 grid((unsigned)((chunks + 255) / 256)), block(256);
+    const uint32_t n = (uint32_t)chunks;
+    switch (load_bytes) {
+        case 2:
+            if constexpr (ES == 2) {
+                hipLaunchKernelGGL((k_dense_unpack<ES, 2, SIGNED>), grid, block, 0, stream, rows, pool, b, chunk0, n, first_negative);
+                break;
+            }
+            return fail(WFA_E_INVALID, "load width below the element size");
+        case 4: hipLaunchKernelGGL((k_dense_unpack<ES, 4, SIGNED>), grid, block, 0, stream, rows, pool, b, chunk0, n, first_negative); break;
+        case 8: hipLaunchKernelGGL((k_dense_unpack<ES, 8, SIGNED>), grid, block, 0, stream, rows, pool, b, chunk0, n, first_negative); break;
+        case 16: hipLaunchKernelGGL((k_dense_unpack<ES, 16, SIGNED>), grid, block, 0, stream, rows, pool, b, chunk0, n, first_negative); break;
+        default: return fail(WFA_E_INVALID, "bad load width %d", load_bytes);
+    }
+    WFA_HIP_CHECK(hipGetLastError());
+    return WFA_OK;
+}
+
+// the second stream and the three events of wfa_upload_dense_rows (see wfa_ctx::dense_stream)
+static int ensure_dense_stream(wfa_ctx* c) {
+    if (!c->dense_stream) WFA_HIP_CHECK(hipStreamCreateWithFlags(&c->dense_stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : c->dense_ev)
+        if (!e) WFA_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return WFA_OK;
+}
+
 
 extern "C" {
 
@@ -761,6 +814,10 @@ void wfa_ctx_destroy(wfa_ctx* c) {
     }
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
+    if (c->dense_stream) (void)hipStreamSynchronize(c->dense_stream);
+    for (hipEvent_t e : c->dense_ev)
+        if (e) (void)hipEventDestroy(e);
+    if (c->dense_stream) (void)hipStreamDestroy(c->dense_stream);
     (void)profile_flush(c);
     for (hipEvent_t e : c->prof_free) (void)hipEventDestroy(e);
     c->prof_free.clear();
@@ -846,6 +903,98 @@ int wfa_upload_pool_f32(wfa_ctx* c, const float* pool, int64_t n) {
     if ((rc = h2d(c, c->pool_f32, pool, (size_t)n * sizeof(float)))) return rc;
     WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
     pool_replaced(c, n, false);
+    return WFA_OK;
+}
+
+int wfa_upload_dense_rows(wfa_ctx* c, const void* rows, int64_t n_rows, int64_t row_bytes, int32_t wave_offset,
+                          int32_t wave_length, int elem, int64_t batch_bytes, int64_t* first_negative_row) {
+    int rc = use_device(c);
+    if (rc) return rc;
+    if (first_negative_row) *first_negative_row = -1;
+    if (elem != WFA_DENSE_I16 && elem != WFA_DENSE_U16 && elem != WFA_DENSE_F32)
+        return fail(WFA_E_INVALID, "unknown dense element type %d", elem);
+    const int es = elem == WFA_DENSE_F32 ? 4 : 2;
+    const bool u16 = es == 2;
+    if (n_rows < 0 || row_bytes < 0 || wave_offset < 0 || wave_length < 0) return fail(WFA_E_INVALID, "negative size");
+    if (wave_offset % es != 0 || row_bytes % es != 0)
+        return fail(WFA_E_INVALID, "wave_offset %d and row_bytes %lld must be multiples of the element size %d", wave_offset,
+                    (long long)row_bytes, es);
+    if ((int64_t)wave_offset + (int64_t)wave_length * es > row_bytes)
+        return fail(WFA_E_INVALID, "wave of %d elements at byte %d does not fit a %lld-byte row", wave_length, wave_offset,
+                    (long long)row_bytes);
+    const int64_t n = n_rows * (int64_t)wave_length;
+    if (n > 0 && !rows) return fail(WFA_E_INVALID, "rows is null");
+    DevBuf& pool = u16 ? c->pool_u16 : c->pool_f32;
+    int64_t rows_per_batch = 0;
+    if (n > 0) {
+        rows_per_batch = host::dense_rows_per_batch(n_rows, row_bytes, batch_bytes);
+        if ((uint64_t)rows_per_batch * (uint64_t)row_bytes >= (1ull << 31))
+            return fail(WFA_E_LIMIT, "row of %lld bytes too long", (long long)row_bytes);
+    }
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));  // nothing reads the pool that is about to change
+    if ((rc = pool.ensure((size_t)n * es))) return rc;
+    // from here on a failure leaves the context without this pool (and, for a wave_pool, without records)
+    if (u16) {
+        c->have_u16 = c->have_f32 = c->filter_keep = false;
+        records_dropped(c);
+    } else {
+        if (c->have_u16 && n != c->pool_n) c->have_u16 = false;  // a different run: the resident wave_pool is stale
+        c->have_f32 = false;
+    }
+    if (n > 0) {
+        const size_t buf_bytes = (size_t)rows_per_batch * (size_t)row_bytes;
+        if ((rc = ensure_dense_stream(c)) || (rc = c->dense_rows[0].ensure(buf_bytes)) ||
+            (rc = c->dense_rows[1].ensure(n_rows > rows_per_batch ? buf_bytes : 1)) || (rc = c->dense_neg.ensure(8)))
+            return rc;
+        const int load_bytes = host::dense_load_bytes(wave_offset, row_bytes, es);
+        unsigned long long* d_neg = c->dense_neg.as<unsigned long long>();
+        // batch k: copied on the context's stream into buffer k & 1, unpacked on the second stream once the copy has
+        // landed; the copy of batch k + 1 runs meanwhile, and batch k + 2 waits for this unpack before it reuses the buffer
+        auto run = [&]() -> int {
+            if (elem == WFA_DENSE_I16) WFA_HIP_CHECK(hipMemsetAsync(d_neg, 0xff, 8, c->dense_stream));
+            int64_t k = 0;
+            for (int64_t row = 0; row < n_rows; row += rows_per_batch, ++k) {
+                const int64_t nr = std::min(rows_per_batch, n_rows - row);
+                const int b = (int)(k & 1);
+                if (k >= 2) WFA_HIP_CHECK(hipEventSynchronize(c->dense_ev[b]));
+                if (int e = h2d_copy(c, c->dense_rows[b].ptr, (const uint8_t*)rows + (size_t)row * (size_t)row_bytes,
+                                     (size_t)nr * (size_t)row_bytes))
+                    return e;
+                WFA_HIP_CHECK(hipEventRecord(c->dense_ev[2], c->stream));
+                WFA_HIP_CHECK(hipStreamWaitEvent(c->dense_stream, c->dense_ev[2], 0));
+                host::DenseBatch db{};
+                db.out_begin = (uint64_t)row * (uint64_t)wave_length;
+                db.out_end = (uint64_t)(row + nr) * (uint64_t)wave_length;
+                db.row0 = row;
+                db.L = (uint32_t)wave_length;
+                db.row_elems = (uint32_t)(row_bytes / es);
+                db.wave_elem = (uint32_t)(wave_offset / es);
+                const uint8_t* src = c->dense_rows[b].as<uint8_t>();
+                int e;
+                if (elem == WFA_DENSE_I16) e = launch_dense_unpack<2, true>(load_bytes, c->dense_stream, src, pool.as<uint8_t>(), db, d_neg);
+                else if (elem == WFA_DENSE_U16) e = launch_dense_unpack<2, false>(load_bytes, c->dense_stream, src, pool.as<uint8_t>(), db, d_neg);
+                else e = launch_dense_unpack<4, false>(load_bytes, c->dense_stream, src, pool.as<uint8_t>(), db, d_neg);
+                if (e) return e;
+                WFA_HIP_CHECK(hipEventRecord(c->dense_ev[b], c->dense_stream));
+            }
+            return WFA_OK;
+        };
+        rc = run();
+        // both streams are idle before anything is reported: the buffers and the events belong to the next call
+        const hipError_t e0 = hipStreamSynchronize(c->stream), e1 = hipStreamSynchronize(c->dense_stream);
+        if (rc) return rc;
+        if (e0 != hipSuccess || e1 != hipSuccess)
+            return fail(WFA_E_HIP, "dense upload failed: %s", hipGetErrorString(e0 != hipSuccess ? e0 : e1));
+        if (elem == WFA_DENSE_I16) {
+            unsigned long long neg = ~0ull;
+            WFA_HIP_CHECK(hipMemcpy(&neg, d_neg, 8, hipMemcpyDeviceToHost));
+            if (neg != ~0ull) {
+                if (first_negative_row) *first_negative_row = (int64_t)neg;
+                return fail(WFA_E_INVALID, "dense rows hold negative samples (first in row %lld)", (long long)neg);
+            }
+        }
+    }
+    pool_replaced(c, n, u16);
     return WFA_OK;
 }
 

@@ -79,8 +79,11 @@ struct SgPlanDev {
 struct wfa_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    std::vector<wfa::DevBuf*> scratch;  // the buffers declared `{scratch}` below, and ht[]
-    wfa_ctx() { for (wfa::DevBuf& b : ht) scratch.push_back(&b); }
+    std::vector<wfa::DevBuf*> scratch;  // the buffers declared `{scratch}` below, ht[] and dense_rows[]
+    wfa_ctx() {
+        for (wfa::DevBuf& b : ht) scratch.push_back(&b);
+        for (wfa::DevBuf& b : dense_rows) scratch.push_back(&b);
+    }
 
     // resident pool
     wfa::DevBuf pool_u16;
@@ -130,6 +133,13 @@ struct wfa_ctx {
     hipEvent_t stage_ev[2] = {nullptr, nullptr};
     size_t stage_bytes = 0;
     double last_h2d_GBps = 0.0;  // rate of the last staged upload (wfa_last_h2d_rate)
+    // wfa_upload_dense_rows: two buffers of packed rows, the second stream k_dense_unpack runs on while the next batch
+    // is copied on `stream`, one event per buffer (its unpack has finished) and one for "the copy has landed"; the
+    // stream and the events are created by the first dense upload
+    wfa::DevBuf dense_rows[2];
+    wfa::DevBuf dense_neg;  // int64: first row with a negative sample
+    hipStream_t dense_stream = nullptr;
+    hipEvent_t dense_ev[3] = {nullptr, nullptr, nullptr};
 
     // wfa_set_option: choice between code paths that give identical results (tests compare them; a caller never needs to)
     struct {

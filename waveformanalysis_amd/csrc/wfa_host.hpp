@@ -5,7 +5,9 @@
 //   * staged_copy: host -> device through two pinned staging buffers, a few host threads filling one while the other is
 //     on the wire (the ring of wfa_upload_pool_u16 / wfa_upload_pool_f32);
 //   * records_uniform / uniform_layout: the uniform-record layout of a records upload (both upload routes);
-//   * baseline_window: the clamp of a baseline window to the longest uploaded record (wfa_baseline_mean, the hit pass).
+//   * baseline_window: the clamp of a baseline window to the longest uploaded record (wfa_baseline_mean, the hit pass);
+//   * dense_load_bytes / dense_rows_per_batch / dense_unpack_lane: load width, batch size and the per-lane body of
+//     k_dense_unpack (wfa_upload_dense_rows).
 #pragma once
 
 #include <cstdint>
@@ -107,6 +109,120 @@ inline int v1725_index(const uint8_t* buf, int64_t n_bytes, int64_t capacity, in
     }
     *n_waves = k;
     return 0;
+}
+
+// ---- dense rows (wfa_upload_dense_rows): the batch / alignment arithmetic and the per-lane body of k_dense_unpack ----
+// The body is plain C++ shared by the kernel and by host_check, which runs every lane of every batch over exactly-sized
+// heap buffers under the sanitizers: an out-of-range or misaligned access of the kernel is one of this function.
+#if defined(__HIPCC__)
+#define WFA_HD __host__ __device__ __forceinline__
+#else
+#define WFA_HD inline
+#endif
+
+// Widest load (bytes, a power of two <= 16) every row of a (wave_offset, row_bytes) layout allows: the batch buffer is
+// 256-byte aligned, so row r's wave starts at r * row_bytes + wave_offset, a multiple of the result, and a load of that
+// width aligned inside the buffer never leaves the row (row_bytes is a multiple of it too).  elem_bytes divides both.
+inline int dense_load_bytes(int64_t wave_offset, int64_t row_bytes, int elem_bytes) {
+    int w = elem_bytes;
+    while (w < 16 && wave_offset % (2 * w) == 0 && row_bytes % (2 * w) == 0) w *= 2;
+    return w;
+}
+
+// Rows per batch: whole rows, at least one, at most batch_bytes and at most 1 GiB of them (the rule of wfa_st_pack and
+// wfa_view_gather).
+inline int64_t dense_rows_per_batch(int64_t n_rows, int64_t row_bytes, int64_t batch_bytes) {
+    const int64_t cap = batch_bytes < 1 ? 1 : (batch_bytes > (1ll << 30) ? (1ll << 30) : batch_bytes);
+    const int64_t fit = cap / row_bytes;
+    const int64_t rows = fit < 1 ? 1 : fit;
+    return rows < n_rows ? rows : n_rows;
+}
+
+// One batch of whole rows in its device buffer.  Elements are elem_bytes wide; the pool is the flat row-major matrix.
+struct DenseBatch {
+    uint64_t out_begin, out_end;  // pool elements [row0 * L, (row0 + rows) * L) this batch writes
+    int64_t row0;                 // first row of the batch
+    uint32_t L;                   // elements per row (> 0)
+    uint32_t row_elems;           // row_bytes / elem_bytes
+    uint32_t wave_elem;           // wave_offset / elem_bytes
+};
+
+// 16-byte chunks of the pool (absolute, so every full chunk is a 16-byte aligned store) that hold an element of the batch
+inline uint64_t dense_first_chunk(const DenseBatch& b, int elem_bytes) { return b.out_begin / (16u / elem_bytes); }
+inline uint64_t dense_chunk_count(const DenseBatch& b, int elem_bytes) {
+    const uint64_t epl = 16u / elem_bytes;
+    return b.out_end > b.out_begin ? (b.out_end + epl - 1) / epl - b.out_begin / epl : 0;
+}
+
+struct alignas(16) DenseV16 { uint64_t lo, hi; };
+
+template <int W>
+WFA_HD void dense_load_word(const uint8_t* p, uint64_t& q0, uint64_t& q1) {
+    if constexpr (W == 2) q0 = *reinterpret_cast<const uint16_t*>(p);
+    else if constexpr (W == 4) q0 = *reinterpret_cast<const uint32_t*>(p);
+    else if constexpr (W == 8) q0 = *reinterpret_cast<const uint64_t*>(p);
+    else { const DenseV16 v = *reinterpret_cast<const DenseV16*>(p); q0 = v.lo; q1 = v.hi; }
+}
+
+// The lane that owns pool chunk `chunk` (16 bytes = 16 / ES consecutive elements; the lanes of a wave own consecutive
+// chunks, so they read consecutive bytes of a row).  Reads its elements with aligned W-byte loads, each word once, and
+// only words that hold an element of the batch; writes one 16-byte vector when the whole chunk belongs to the batch,
+// single elements at the batch's two ragged ends.  SIGNED (ES == 2): returns the first row (absolute) among its elements
+// with the sign bit set, else -1.
+template <int ES, int W, bool SIGNED>
+WFA_HD int64_t dense_unpack_lane(const uint8_t* src, uint8_t* pool, const DenseBatch& b, uint64_t chunk) {
+    constexpr uint32_t EPL = 16 / ES, WE = W / ES;
+    const uint64_t i0 = chunk * EPL;
+    const uint64_t first = i0 > b.out_begin ? i0 : b.out_begin;
+    const uint64_t last = i0 + EPL < b.out_end ? i0 + EPL : b.out_end;
+    if (first >= last) return -1;
+    const uint32_t e = (uint32_t)(first - b.out_begin);  // < 2^31 / ES: a batch buffer is shorter than 2 GiB
+    uint32_t r = e / b.L, j = e - r * b.L;
+    uint32_t a = r * b.row_elems + b.wave_elem + j;      // element address inside the batch buffer
+    uint32_t cur = 0xffffffffu;
+    uint64_t q0 = 0, q1 = 0;
+    uint32_t o[4] = {0u, 0u, 0u, 0u};
+    int64_t negative = -1;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t t = 0; t < EPL; ++t) {
+        const uint64_t i = i0 + t;
+        if (i < first || i >= last) continue;
+        const uint32_t w = a / WE;
+        if (w != cur) {
+            dense_load_word<W>(src + (size_t)w * W, q0, q1);
+            cur = w;
+        }
+        const uint32_t bit = (a % WE) * (ES * 8);
+        uint64_t q = q0;
+        if constexpr (W == 16) q = bit < 64 ? q0 : q1;
+        const uint32_t v = (uint32_t)(q >> (bit & 63u)) & (ES == 2 ? 0xffffu : 0xffffffffu);
+        if (SIGNED && (v & 0x8000u) && negative < 0) negative = b.row0 + r;
+        if constexpr (ES == 2) o[t / 2] |= v << (16 * (t & 1));
+        else o[t] = v;
+        ++a;
+        if (++j == b.L) {
+            j = 0;
+            ++r;
+            a += b.row_elems - b.L;
+        }
+    }
+    uint8_t* dst = pool + i0 * ES;
+    if (last - first == EPL) {
+        DenseV16 v;
+        v.lo = o[0] | ((uint64_t)o[1] << 32);
+        v.hi = o[2] | ((uint64_t)o[3] << 32);
+        *reinterpret_cast<DenseV16*>(dst) = v;
+    } else {
+        for (uint32_t t = 0; t < EPL; ++t) {
+            const uint64_t i = i0 + t;
+            if (i < first || i >= last) continue;
+            if constexpr (ES == 2) reinterpret_cast<uint16_t*>(dst)[t] = (uint16_t)(o[t / 2] >> (16 * (t & 1)));
+            else reinterpret_cast<uint32_t*>(dst)[t] = o[t];
+        }
+    }
+    return negative;
 }
 
 constexpr int kStageThreads = 4;

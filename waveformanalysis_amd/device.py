@@ -101,6 +101,12 @@ class DeviceSession:
         # who uploaded the resident records table last (note_records), while the device columns still hold what it
         # uploaded: every records upload, pool replacement and baseline-writing pass resets it
         self._res_records = None
+        # the dense structured arrays (st_waveforms / filtered_waveforms) whose `wave` rows the device pools hold in
+        # row-major order (upload_dense / note_dense), one per device buffer: same rule as _res_pool
+        self._res_dense = None      # int16 / uint16 rows: the device uint16 pool
+        self._res_dense_f32 = None  # float32 rows: the device float32 pool
+
+    _res_dense = _res_dense_f32 = None  # (sessions built without __init__ -- test doubles -- hold no dense array)
 
     # -- lifetime -------------------------------------------------------------------------------
     def close(self) -> None:
@@ -114,13 +120,15 @@ class DeviceSession:
         self._res_pool = None
         self._res_filtered = None
         self._res_records = None
+        self._res_dense = self._res_dense_f32 = None
 
     def _drop_f32_tags(self) -> None:
         """The device float32 buffer is about to be overwritten: forget every host array remembered as its content (the
-        filtered twin, and a float32 array that was uploaded as the pool itself)."""
+        filtered twin, a float32 array that was uploaded as the pool itself, a dense array of float32 rows)."""
         self._res_filtered = None
         if self._res_pool is not None and self._res_pool.dtype == np.float32:
             self._res_pool = None
+        self._res_dense_f32 = None
 
     def ensure_pool(self, wave_pool: np.ndarray, cacheable: bool = True) -> bool:
         """Upload `wave_pool` unless this very array object is what the device pool already holds.
@@ -202,6 +210,75 @@ class DeviceSession:
         self._res_records = None  # (the library drops the records when the float32 pool stands alone)
         _lib.check(self._lib.wfa_upload_pool_f32(self._h, _ptr(arr), arr.size))
         self.uploads += 1
+
+    # ---- dense arrays (st_waveforms / filtered_waveforms): rows uploaded as they are, unpacked on the device ----------
+    dense_rows = True  # False: always the host route (dense.dense_pool + upload_pool; tests compare the two)
+    DENSE_BATCH_BYTES = 64 << 20
+    first_negative_row = -1  # of the last upload_dense: the first row with a negative int16 sample, -1 = none
+    _DENSE_ELEMS = {"<i2": _lib.DENSE_I16, "<u2": _lib.DENSE_U16, "<f4": _lib.DENSE_F32}
+
+    @classmethod
+    def _dense_layout(cls, data):
+        """(wave byte offset, wave length, row bytes, WFA_DENSE_* code) when the structured array can go to the device
+        as it is: one contiguous block of rows whose `wave` is a 1-D subarray of int16 / uint16 / float32 at an offset
+        and a stride that are multiples of the element size; None for anything else (views with gaps, a 2-D `wave`,
+        other types or byte orders, a plain matrix): the host route takes those."""
+        if not isinstance(data, np.ndarray) or data.dtype.names is None or "wave" not in data.dtype.names:
+            return None
+        dt = data.dtype
+        if not (data.flags.c_contiguous and data.ndim == 1 and (data.strides == (dt.itemsize,) or len(data) <= 1)):
+            return None  # (numpy gives arrays of no or one row whatever stride they were cut with)
+        ftype, foff = dt.fields["wave"][0], dt.fields["wave"][1]
+        if ftype.subdtype is None:
+            return None
+        base, shape = ftype.subdtype
+        if len(shape) != 1 or base.str not in cls._DENSE_ELEMS or shape[0] > _I32_MAX:
+            return None
+        if foff % base.itemsize or dt.itemsize % base.itemsize:
+            return None
+        return int(foff), int(shape[0]), int(dt.itemsize), cls._DENSE_ELEMS[base.str]
+
+    def upload_dense(self, data: np.ndarray, batch_bytes: int | None = None, what: str = "st_waveforms") -> None:
+        """The `wave` rows of a dense array as the device pool (wfa_upload_dense_rows): int16 / uint16 rows become the
+        uint16 pool, float32 rows the float32 pool, row r at samples [r L, (r + 1) L).  Read-only memmaps are fine.
+        int16 rows with a negative sample are refused (`first_negative_row` then names the first such row) and the
+        session is left without a pool."""
+        layout = self._dense_layout(data)
+        if layout is None:
+            raise ValueError(f"{what} cannot be uploaded as packed rows (see DeviceSession._dense_layout)")
+        wave_offset, L, row_bytes, elem = layout
+        self.forget_resident()
+        first = C.c_int64(-1)
+        rc = self._lib.wfa_upload_dense_rows(self._h, _ptr(data), len(data), row_bytes, wave_offset, L, elem,
+                                             int(batch_bytes or self.DENSE_BATCH_BYTES), C.byref(first))
+        self.first_negative_row = int(first.value)
+        if rc == _lib.WFA_E_INVALID and first.value >= 0:
+            raise ValueError(f"{what}['wave'] holds negative samples; the HIP backend reads unsigned ADC codes")
+        _lib.check(rc)
+        self.uploads += 1
+        self.n_samples = len(data) * L
+
+    def note_dense(self, data: np.ndarray) -> None:
+        """The device pool of `data`'s sample type holds the `wave` rows of this very array in row-major order (just
+        uploaded, or just written by this session's filters and copied into it): ensure_dense(data) uploads nothing
+        from now on until a call replaces that device pool."""
+        if data.dtype["wave"].base == np.float32:
+            self._res_dense_f32 = data
+        else:
+            self._res_dense = data
+
+    def holds_dense(self, data: np.ndarray) -> bool:
+        """True while a device pool still holds the rows of this very array object (the `is` test of ensure_dense)."""
+        return data is not None and (self._res_dense is data or self._res_dense_f32 is data)
+
+    def ensure_dense(self, data: np.ndarray, what: str = "st_waveforms") -> bool:
+        """Upload the rows of `data` unless this very array object is what a device pool already holds.  Returns True
+        when an upload happened.  A dense upload replaces whatever else was resident."""
+        if self.holds_dense(data):
+            return False
+        self.upload_dense(data, what=what)
+        self.note_dense(data)
+        return True
 
     packed_records = True  # False: always the column route (tests compare the two)
     _PACKED_FIELDS = (("wave_offset", "<i8", True), ("event_length", "<i4", True), ("baseline", "<f8", True),

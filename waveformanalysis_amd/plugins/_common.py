@@ -243,6 +243,24 @@ def resident_session(context: Any, pool: np.ndarray, pool_filtered: np.ndarray |
     return sess
 
 
+def dense_session(context: Any, data: np.ndarray, data_name: str) -> tuple[DeviceSession, int, int]:
+    """(session of this thread with the `wave` rows of the dense array `data` on the device, wave source, row length).
+
+    An array DeviceSession._dense_layout accepts goes up as it is and is unpacked on the device; it stays resident under
+    the rule of resident_session (this very array OBJECT, until a call replaces the device pool), so a chain of dense
+    plugins over one st_waveforms / filtered_waveforms array uploads its samples once.  Anything else (a view with
+    gaps, another sample type) takes the host route: dense.dense_pool's contiguous copy, uploaded every time."""
+    layout = DeviceSession._dense_layout(data) if DeviceSession.dense_rows else None
+    if layout is None:
+        from .. import dense
+
+        pool, source, L = dense.dense_pool(data, data_name)  # (its errors need no device)
+        return resident_session(context, pool, cacheable=False), source, L
+    sess = note_session(_device_pool(context).session())
+    sess.ensure_dense(data, what=data_name)
+    return sess, (SRC_F32 if layout[3] == _lib.DENSE_F32 else SRC_RAW), layout[1]
+
+
 # ---- the records route of the per-record plugins, on one device or on several ---------------------------------------
 DEVICES_HELP = ("None: one device (the calling thread's session); a list of device ids (repeats allowed) or 'all': the "
                 "records route runs on those devices, one contiguous record range each, output identical "

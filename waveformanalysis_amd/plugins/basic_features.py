@@ -65,9 +65,8 @@ class HipBasicFeaturesPlugin(K.HipPlugin):
         data = K.load_dense_input(context, self, run_id, data_name)
         if len(data) == 0:
             return np.zeros(0, dtype=BASIC_FEATURES_DTYPE)
-        pool, source, L = dense.dense_pool(data, data_name)
+        sess, source, L = K.dense_session(context, data, data_name)
         records = dense.dense_records(data, L)
         fixed = K.fixed_baseline_per_record(records, channel_config, run_id)
-        sess = K.resident_session(context, pool, cacheable=False)  # temporary of the dense `wave` field
         sess.upload_records(records, polarity=dense.dense_polarity_wave_rule(data))
         return sess.basic_features(source, height_range, area_range, fixed)

@@ -67,11 +67,16 @@ class HipFilteredWaveformsPlugin(K.HipPlugin):
                 output[name] = st[name]
         boards = st["board"] if "board" in names else np.zeros(len(st), dtype=np.int16)
         groups = plan_filter_groups(context, self, run_id, boards, st["channel"])
-        pool, source, L = dense.dense_pool(st, "st_waveforms")
+        sess, source, L = K.dense_session(context, st, "st_waveforms")
         if source != K.SRC_RAW:
             raise ValueError(f"st_waveforms['wave'] must be int16, got {st['wave'].dtype}")
-        sess = K.resident_session(context, pool, cacheable=False)
         filtered = run_filter_groups(sess, dense.dense_records(st, L), groups)
-        sess.forget_resident()
         output["wave"] = filtered.reshape(len(st), L)
+        if sess.dense_rows and sess._dense_layout(output) is not None:
+            # the device float32 pool is exactly output["wave"] in row-major order: hit / waveform_width / hit_threshold
+            # on filtered_waveforms upload no samples (the dense twin of note_filtered).  The filters read the uint16
+            # pool and leave it as it is, so st_waveforms keeps its own tag.
+            sess.note_dense(output)
+        else:
+            sess.forget_resident()
         return output

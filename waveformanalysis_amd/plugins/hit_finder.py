@@ -105,10 +105,9 @@ class HipHitFinderPlugin(K.HipPlugin):
         dt_values = _dt_values(data, explicit_dt, "st_waveforms")  # the reference's text, whatever data_name is
         if "baseline" not in (data.dtype.names or ()) and not peak_kw["use_derivative"]:
             raise ValueError(f"hit (HIP backend) needs a 'baseline' field on {data_name} when use_derivative=False")
-        pool, source, L = dense.dense_pool(data, data_name)
+        sess, source, L = K.dense_session(context, data, data_name)
         rec = dense.dense_records(data, L, keep_record_id=True, truncate_to_event_length=True)
         rec["dt"] = dt_values
-        sess = K.resident_session(context, pool, cacheable=False)  # `pool` is a temporary of the dense `wave` field
         sess.upload_records(rec, np.zeros(len(rec), dtype=np.float64))
         return sess.find_peaks(source, dense_rows=True, **peak_kw)
 

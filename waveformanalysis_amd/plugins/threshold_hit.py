@@ -125,7 +125,7 @@ class HipThresholdHitPlugin(K.HipPlugin):
         if len(data) == 0:
             return np.zeros(0, dtype=THRESHOLD_HIT_DTYPE)
         names = data.dtype.names or ()
-        pool, source, L = dense.dense_pool(data, data_name)
+        sess, source, L = K.dense_session(context, data, data_name)
         rec = dense.dense_records(data, L, keep_record_id=True)
         rec["dt"] = K.require_dt_array(data, explicit_dt=explicit_dt, plugin_name=self.provides, data_name=data_name)
         if "event_length" in names:
@@ -134,7 +134,6 @@ class HipThresholdHitPlugin(K.HipPlugin):
             source_lengths = np.full(len(data), L, dtype=np.int64)
         record_lengths = _lengths_from_records(context, run_id, rec["record_id"], source_lengths)
         thresholds = K.per_record_channel_option(rec, channel_config, run_id, "threshold", threshold, threshold)
-        sess = K.resident_session(context, pool, cacheable=False)  # temporary of the dense `wave` field
         sess.upload_records(rec, thresholds)
         if "baseline" not in names:
             if source != K.SRC_RAW:

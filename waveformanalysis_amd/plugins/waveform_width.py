@@ -19,7 +19,6 @@ from typing import Any
 
 import numpy as np
 
-from .. import dense
 from ..dtypes import WAVEFORM_WIDTH_DTYPE
 from ..plugin_api import Option, Plugin
 from . import _common as K
@@ -93,8 +92,7 @@ class HipWaveformWidthPlugin(K.HipPlugin):
         else:
             row = np.where((record_id >= 0) & (record_id < len(waveform_data)), record_id, -1)
 
-        pool, source, L = dense.dense_pool(waveform_data, data_name)
-        sess = K.resident_session(context, pool, cacheable=False)  # temporary of the dense `wave` field
+        sess, source, L = K.dense_session(context, waveform_data, data_name)
         rows, valid = sess.waveform_width(source, position, row, len(waveform_data), L, rise_low, rise_high,
                                           fall_high, fall_low, float(sampling_rate), interpolation)
         return _kept_rows(rows, valid, hits, record_id)
