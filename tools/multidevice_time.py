@@ -10,7 +10,14 @@ rule keys on the array object), and the median of calls with the pool resident. 
 the H2D rate of the last upload of every session.  Every set's output is checked byte-identical to devices=None.  One
 JSON line per leg and set.
 
-    python tools/multidevice_time.py [--samples 1e9] [--calls 5] [--legs hit_threshold,wave_pool_filtered,hit]
+The `dense` leg times the default route (wave_source="auto") on the array tools/dense_time.py uses (`--dense-records` x
+800 samples, default 625 000 = 5e8 samples, the positive twin of the synthetic V1725 run): the chain hit_threshold ->
+basic_features -> waveform_width_integral -> hit -> waveform_width, then filtered_waveforms on its own, with
+devices=None, [0] and every visible device.  Per set, on one context: the first run (rows uploaded), then `--calls`
+repetitions with the context's results forgotten and the rows resident; wall time of the chain and of every plugin,
+pool uploads per session, tables compared byte for byte with devices=None.
+
+    python tools/multidevice_time.py [--samples 1e9] [--calls 5] [--legs hit_threshold,wave_pool_filtered,hit,dense]
 """
 
 from __future__ import annotations
@@ -30,8 +37,12 @@ from waveformanalysis_amd import multidevice as MD, synth  # noqa: E402
 from waveformanalysis_amd.device import default_pool, device_count  # noqa: E402
 from waveformanalysis_amd.plugin_api import SimpleContext  # noqa: E402
 from waveformanalysis_amd.plugins import (  # noqa: E402
+    HipBasicFeaturesPlugin,
+    HipFilteredWaveformsPlugin,
     HipHitFinderPlugin,
     HipThresholdHitPlugin,
+    HipWaveformWidthIntegralPlugin,
+    HipWaveformWidthPlugin,
     HipWavePoolFilteredPlugin,
 )
 
@@ -81,16 +92,77 @@ def time_set(leg, data, devices, calls, want=None):
     return rows, out
 
 
+DENSE_CHAIN = ("hit_threshold", "basic_features", "waveform_width_integral", "hit", "waveform_width")
+
+
+def dense_set(st, rec, devices, calls, want=None):
+    """The dense chain and filtered_waveforms on one context with `devices`: (tables of the first run, JSON line)."""
+    ctx = SimpleContext({"hit": {"use_filtered": False}, "devices": devices}, {"st_waveforms": st, "records": rec},
+                        plugins=[HipThresholdHitPlugin(), HipBasicFeaturesPlugin(), HipWaveformWidthIntegralPlugin(),
+                                 HipHitFinderPlugin(), HipWaveformWidthPlugin(), HipFilteredWaveformsPlugin()])
+    sessions = _sessions(ctx, devices)
+    if devices is None:
+        sessions[0].forget_resident()  # the calling thread's session outlives the sets: start from an empty one
+
+    def once():
+        ctx._results.clear()
+        before = [s.uploads for s in sessions]
+        took, tables = {}, {}
+        for name in DENSE_CHAIN + ("filtered_waveforms",):
+            t0 = time.perf_counter()
+            tables[name] = ctx.get_data("run", name)
+            took[name] = time.perf_counter() - t0
+        return tables, took, [s.uploads - b for s, b in zip(sessions, before)]
+
+    def chain_s(took):
+        return sum(took[name] for name in DENSE_CHAIN)
+
+    tables, first, first_uploads = once()
+    same = None if want is None else all(tables[k].tobytes() == want[k].tobytes() for k in tables)
+    repeats = [once()[1:] for _ in range(calls)]  # (the tables of a repetition are dropped: filtered_waveforms is large)
+    MD.close_sharded_runs(ctx)
+    walls = [chain_s(took) for took, _u in repeats]
+    line = {"leg": "dense", "devices": devices, "rows": len(st), "samples": int(st["wave"].size),
+            "table_rows": {k: len(tables[k]) for k in DENSE_CHAIN}, "identical_to_single": same,
+            "first_chain_s": round(chain_s(first), 4), "first_uploads_per_session": first_uploads,
+            "chain_s": {"median": round(statistics.median(walls), 4), "min": round(min(walls), 4),
+                        "max": round(max(walls), 4)},
+            "plugins_s": {k: round(statistics.median(took[k] for took, _u in repeats), 4) for k in first},
+            "first_filtered_waveforms_s": round(first["filtered_waveforms"], 4),
+            "uploads_per_session": repeats[-1][1]}
+    return tables, line
+
+
+def dense_leg(n_records, calls) -> None:
+    from waveformanalysis_amd import replay
+
+    rec, pool = replay.mirror_positive(*synth.make_run(n_records, "v1725", cfg=7))
+    st = replay.st_waveforms_from_records(rec, pool)
+    del pool
+    n_dev = device_count()
+    want = None
+    for devices in [None, [0]] + ([list(range(n_dev))] if n_dev > 1 else []):
+        tables, line = dense_set(st, rec, devices, calls, want)
+        want = tables if devices is None else want
+        print(json.dumps(line), flush=True)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--samples", type=float, default=1e9)
     ap.add_argument("--calls", type=int, default=5)
-    ap.add_argument("--legs", default=",".join(LEGS), help="comma-separated: " + ", ".join(LEGS))
+    ap.add_argument("--dense-records", type=int, default=625000)
+    ap.add_argument("--legs", default=",".join(LEGS) + ",dense", help="comma-separated: " + ", ".join(LEGS) + ", dense")
     args = ap.parse_args()
     legs = [leg.strip() for leg in args.legs.split(",") if leg.strip()]
-    unknown = [leg for leg in legs if leg not in LEGS]
+    unknown = [leg for leg in legs if leg not in LEGS and leg != "dense"]
     if unknown:
         ap.error(f"unknown legs {unknown}")
+    if "dense" in legs:
+        legs.remove("dense")
+        dense_leg(args.dense_records, args.calls)
+        if not legs:
+            return
     L = synth.PRESETS["v1725"][0]
     t0 = time.perf_counter()
     rec, pool = synth.make_run(int(args.samples) // L, "v1725", cfg=0)

@@ -19,12 +19,23 @@ A worker's first step is always to put its shard's pool slice on its device (ski
 take its records with wave_offset shifted to the slice.
 The uploads and downloads are ctypes calls, which release the GIL: the links of different devices work at once.
 
+The dense routes (st_waveforms / filtered_waveforms, plugins/_common.py::dense_route) are the same runs with another
+answer to "what a shard puts on its device" (`_plan(rows=...)`): the rows are uniform, so shards are contiguous row
+ranges balanced by row count (split_rows), cut at multiples of 8 // gcd(L, 8) rows so that r0 * L is a multiple of
+POOL_ALIGN; worker k uploads `data[r0:r1]` as it is (DeviceSession.ensure_dense: a pointer offset and a row count) and
+gets dense_records' rows with wave_offset shifted by r0 * L.  Residency is a per-shard tag (array, r0, r1, view) per
+device buffer (_dense: uint16 rows, _dense_f32: float32 rows), under the same `is` rule as the pool slices; a pool
+upload voids the dense tags of its session and a dense upload the pool tags.  filtered_waveforms is a one-row-per-record
+run whose table is its output array: every shard's slice of it is noted as the content of its float32 pool.
+run_hits (waveform_width, both routes) cuts a hit table by the shard the hit's record falls in (partition_hits).
+
 This is the in-process path.  `bench.py --gpus N` keeps its multi-process route (one rank per GPU, channel shards, hit
 rows gathered over RCCL) for the event-grouping chain, which needs the rows of every channel on one device.
 """
 
 from __future__ import annotations
 
+import math
 import threading
 import weakref
 from concurrent.futures import ThreadPoolExecutor
@@ -105,6 +116,40 @@ def _split(offsets: np.ndarray, lengths: np.ndarray, n_shards: int) -> list[Reco
     return shards
 
 
+def dense_unit(row_length: int) -> int:
+    """Rows per split unit of a dense array: the fewest rows whose samples are a multiple of POOL_ALIGN."""
+    return POOL_ALIGN // math.gcd(int(row_length), POOL_ALIGN)
+
+
+def split_rows(n_rows: int, row_length: int, n_shards: int) -> list[tuple[int, int]]:
+    """Contiguous row ranges [r0, r1) of a dense array (uniform rows), one per shard, balanced by row count.
+
+    Every boundary is a multiple of dense_unit(row_length) rows, so r0 * row_length is a multiple of POOL_ALIGN: row r
+    of the array sits at sample (r - r0) * row_length of its shard's pool, the same offset modulo POOL_ALIGN as
+    r * row_length in the whole array's, and the upload picks the same layout route for it.  The units (the last one
+    may be short) are dealt floor-wise, so the shards' sizes differ by at most one unit; with fewer units than shards
+    some shards are empty (r0 == r1)."""
+    n_rows, n_shards = int(n_rows), int(n_shards)
+    if n_shards < 1:
+        raise ValueError("n_shards must be >= 1")
+    unit = dense_unit(row_length)
+    units = -(-n_rows // unit)
+    bounds = [min((k * units) // n_shards * unit, n_rows) for k in range(n_shards + 1)]
+    return list(zip(bounds[:-1], bounds[1:]))
+
+
+def partition_hits(index: np.ndarray, bounds: Sequence[int]) -> list[np.ndarray]:
+    """Per shard k, the positions (ascending: hit order kept) of the entries of `index` inside [bounds[k], bounds[k + 1]).
+    Entries below bounds[0] or at / above bounds[-1] (a hit with no row: -1, an index out of range) go to no shard."""
+    index = np.asarray(index, dtype=np.int64)
+    edges = np.asarray(bounds, dtype=np.int64)
+    shard = np.searchsorted(edges, index, side="right") - 1  # of equal edges (empty shards) the last one: the non-empty
+    shard[(index < edges[0]) | (index >= edges[-1])] = -1
+    order = np.argsort(shard, kind="stable")
+    first = np.searchsorted(shard[order], np.arange(len(edges)), side="left")
+    return [order[first[k]:first[k + 1]] for k in range(len(edges) - 1)]
+
+
 def _copy_rows(rows: np.ndarray) -> np.ndarray:
     """A copy of a record range: one memcpy for a contiguous structured array (numpy's structured copy goes field by
     field, several times slower on the reference's records dtype)."""
@@ -119,9 +164,12 @@ def _per_record(per_record: Sequence, n: int, rows) -> list:
     return [a[rows] if isinstance(a, np.ndarray) and a.ndim == 1 and len(a) == n else a for a in per_record]
 
 
-def _shard_inputs(records: np.ndarray, sh: RecordShard, per_record: Sequence) -> tuple:
-    """(slice start, records of the shard with wave_offset shifted to the slice, its per-record arguments)."""
+def _shard_inputs(records: np.ndarray | None, sh: RecordShard, per_record: Sequence) -> tuple:
+    """(slice start, records of the shard with wave_offset shifted to the slice, its per-record arguments).  A run that
+    reads no records table (waveform_width on dense rows) passes None and gets None."""
     lo = sh.span_start - sh.span_start % POOL_ALIGN
+    if records is None:
+        return lo, None, list(per_record)
     rec = _copy_rows(records[sh.r0:sh.r1])
     if lo:
         rec["wave_offset"] -= lo
@@ -189,6 +237,9 @@ class ShardedRun:
         self._workers = [ThreadPoolExecutor(max_workers=1, thread_name_prefix=f"wfa-shard{k}") for k in range(len(ids))]
         self._resident: list[tuple | None] = [None] * len(ids)  # (pool, lo, hi, view) the session holds
         self._filtered: list[tuple | None] = [None] * len(ids)  # (output, lo, hi, view) its filters wrote (run_pool)
+        # (dense array, r0, r1, view) whose `wave` rows the session holds, one tag per device buffer as in DeviceSession
+        self._dense: list[tuple | None] = [None] * len(ids)      # int16 / uint16 rows: the device uint16 pool
+        self._dense_f32: list[tuple | None] = [None] * len(ids)  # float32 rows: the device float32 pool
         self._lock = threading.Lock()  # one run at a time: the sessions hold one run's rows
         self.closed = False
         futures = [w.submit(self._factory, d) for w, d in zip(self._workers, ids)]
@@ -229,9 +280,14 @@ class ShardedRun:
         raise ShardError(f"shard {k} on device {self.device_ids[k]} failed: {type(exc).__name__}: {exc}",
                          self.device_ids[k], k) from exc
 
+    def _drop_tags(self, k: int) -> None:
+        """Session k holds nothing this run knows of (replaced, closed, or an upload has just replaced its pools)."""
+        self._resident[k] = self._filtered[k] = self._dense[k] = self._dense_f32[k] = None
+
     def _replace_session(self, k: int) -> None:
-        self._resident[k] = self._filtered[k] = None
+        self._drop_tags(k)
         old = self.sessions[k]
+        negative_row = getattr(old, "first_negative_row", -1)
 
         def swap():
             try:
@@ -245,6 +301,9 @@ class ShardedRun:
         except BaseException:  # noqa: BLE001  (no new context on that device: this run is done, the next call starts anew)
             self.sessions[k] = None
             self.close()
+            return
+        if negative_row >= 0:  # the dense upload that failed: what it found stays readable where the caller looks for it
+            self.sessions[k].first_negative_row = negative_row
 
     def _ensure_slice(self, k: int, sess, pool: np.ndarray, lo: int, hi: int, cacheable: bool) -> None:
         f32 = self._filtered[k]
@@ -256,32 +315,75 @@ class ShardedRun:
             view = tag[3]  # the object the session remembers: its own `is` test decides
         else:
             view = pool[lo:hi]
-        sess.ensure_pool(view, cacheable=cacheable)
+        if sess.ensure_pool(view, cacheable=cacheable):
+            self._drop_tags(k)  # a pool upload replaces whatever else was resident, dense rows included
         self._resident[k] = (pool, lo, hi, view) if cacheable else None
+
+    def _ensure_rows(self, k: int, sess, data: np.ndarray, r0: int, r1: int, what: str) -> None:
+        """Rows [r0, r1) of the dense array `data` on session k: `data[r0:r1]` goes up as it is
+        (DeviceSession.ensure_dense) unless the session still holds that very view of that very array."""
+        tags = self._dense_f32 if data.dtype["wave"].base == np.float32 else self._dense
+        tag = tags[k]
+        if tag is not None and tag[0] is data and tag[1] == r0 and tag[2] == r1:
+            view = tag[3]  # the object the session remembers: its own `is` test decides
+        else:
+            view = data[r0:r1]
+        try:
+            uploaded = sess.ensure_dense(view, what=what)
+        except ValueError:
+            if getattr(sess, "first_negative_row", -1) >= 0:
+                sess.first_negative_row += r0  # the row of the whole array; the lowest failing shard's is its first
+            raise
+        if uploaded:
+            self._drop_tags(k)  # a dense upload replaces whatever else was resident
+        tags[k] = (data, r0, r1, view)
 
     # -- a run -----------------------------------------------------------------------------------------------------
     @contextmanager
-    def _plan(self, records: np.ndarray, pool: np.ndarray, per_record: Sequence, cacheable: bool):
+    def _plan(self, records: np.ndarray | None, pool: np.ndarray, per_record: Sequence, cacheable: bool,
+              rows: tuple[str, int, int] | None = None):
         """What every run starts with, the run's lock held inside: (shards, the shards that have records, ready, the
-        run's longest event_length).  ready(k), on worker k, puts the shard's pool slice on its device and returns
-        (session, shard, slice start, records_k, per-record arguments of shard k)."""
+        run's longest event_length).  ready(k), on worker k, puts the shard's samples on its device and returns
+        (session, shard, slice start, records_k, per-record arguments of shard k).
+
+        rows=None: `pool` is the flat pool the records point into; shards are record ranges balanced by sample count and
+        a shard's samples are its pool slice.  rows=(name, row length L, row count): a dense run, record r is row r;
+        shards are row ranges (split_rows) and a shard's samples are the rows `pool[r0:r1]` of the dense structured array
+        itself (resident under _ensure_rows), or, when `pool` is the flat row-major copy of an array that cannot go up
+        as it is, the slice [r0 L, r1 L) of that copy, uploaded every time.  The run's width is then L."""
         if self.closed:
             raise RuntimeError("ShardedRun is closed")
-        offsets, lengths = _columns(records)
-        shards = _split(offsets, lengths, self.n_shards)
+        if rows is None:
+            offsets, lengths = _columns(records)
+            shards = _split(offsets, lengths, self.n_shards)
+            width = int(lengths.max(initial=0))
+
+            def put(k, sess, sh, lo):
+                self._ensure_slice(k, sess, pool, lo, sh.span_end, cacheable)
+        else:
+            what, width, n_rows = rows
+            shards = [RecordShard(r0, r1, r0 * width, r1 * width) if r1 > r0 else RecordShard(r0, r0, 0, 0)
+                      for r0, r1 in split_rows(n_rows, width, self.n_shards)]
+
+            def put(k, sess, sh, lo):
+                if pool.dtype.names is not None:
+                    self._ensure_rows(k, sess, pool, sh.r0, sh.r1, what)
+                else:
+                    self._ensure_slice(k, sess, pool, lo, sh.span_end, False)
 
         def ready(k):
             sh, sess = shards[k], self.sessions[k]
             lo, rec, extra = _shard_inputs(records, sh, per_record)
-            self._ensure_slice(k, sess, pool, lo, sh.span_end, cacheable)
+            put(k, sess, sh, lo)
             return sess, sh, lo, rec, extra
 
         with self._lock:
-            yield shards, [k for k, sh in enumerate(shards) if sh.n_records > 0], ready, int(lengths.max(initial=0))
+            yield shards, [k for k, sh in enumerate(shards) if sh.n_records > 0], ready, width
 
     def run(self, records: np.ndarray, pool: np.ndarray, row_dtype, task: Callable, *, fetch: Callable | None = None,
             per_record: Sequence = (), cacheable: bool = True, record_index_field: str | None = None,
-            width_arg: str | None = None) -> np.ndarray:
+            width_arg: str | None = None, rows: tuple[str, int, int] | None = None, out: np.ndarray | None = None,
+            note_out: bool | None = None) -> np.ndarray:
         """The run's table, shards placed one after another in shard order.
 
         task(sess, records_k, *per_record_k, out=...) runs on worker k after the shard's pool slice is resident, with
@@ -289,15 +391,21 @@ class ShardedRun:
         the same way (scalars, 0-d arrays and None go through as they are).
           * fetch=None: one row per record.  `out` is the shard's slice of the table; task writes it.
             record_index_field: a field that holds the record index; the shard's r0 is added to it.
+            out: the table to write into instead of a new zeroed one (filtered_waveforms: the rows it has filled but for
+            `wave`).  note_out (filtered_waveforms): the pass leaves the `wave` rows it wrote into its slice of `out` in
+            the session's float32 pool; True tags that slice as resident (note_dense on the view, keyed on `out`, r0,
+            r1), False (a layout that could not be uploaded as it is) forgets what the session held.
           * fetch given: task(..., out=None) runs the pass and returns the shard's row count, rows left on the device;
             then fetch(sess, out_k) downloads them into the shard's slice of the table.
             width_arg: a keyword under which task also gets the run's longest event_length (the hit pass pads every
             shard to the run's width, hit_finder.py:354-370, not to the shard's own).
+        rows: a dense run (see _plan); `pool` is then the dense array, or the flat copy of its rows.
         A failure raises ShardError and returns no table."""
         row_dtype = np.dtype(row_dtype)
-        with self._plan(records, pool, per_record, cacheable) as (_shards, busy, ready, width):
+        with self._plan(records, pool, per_record, cacheable, rows) as (_shards, busy, ready, width):
             if fetch is None:
-                out = np.zeros(len(records), dtype=row_dtype)
+                if out is None:
+                    out = np.zeros(len(records), dtype=row_dtype)
 
                 def one_pass(k):
                     sess, sh, _lo, rec, extra = ready(k)
@@ -305,6 +413,13 @@ class ShardedRun:
                     task(sess, rec, *extra, out=part)
                     if record_index_field is not None and sh.r0:
                         part[record_index_field] += sh.r0
+                    if note_out:
+                        sess.note_dense(part)
+                        self._filtered[k] = None  # (the filters overwrote the device float32 pool)
+                        self._dense_f32[k] = (out, sh.r0, sh.r1, part)
+                    elif note_out is not None:
+                        sess.forget_resident()
+                        self._drop_tags(k)
 
                 self._on_all(one_pass, busy)
                 return out
@@ -323,6 +438,28 @@ class ShardedRun:
             self._on_all(lambda k: fetch(self.sessions[k], out[first[k]:first[k + 1]]),
                          [k for k in busy if rows[k] > 0])
             return out
+
+    def run_hits(self, index: np.ndarray, task: Callable, records: np.ndarray | None, pool: np.ndarray, *,
+                 cacheable: bool = True, rows: tuple[str, int, int] | None = None) -> list[tuple[np.ndarray, object]]:
+        """Per-hit work on the shard that holds the hit's record (waveform_width): [(positions in the hit table, what
+        task returned)] for every shard that has hits.
+
+        index: per hit, the record (row) it points at.  The hit table is cut by the shard that record falls in
+        (partition_hits over the shards of _plan: a hit with a negative or out-of-range index goes to no shard, the
+        caller marks it invalid).  task(sess, records_k, positions, index - r0, r1 - r0) runs on worker k after the
+        shard's samples are resident; positions are ascending, so a shard sees its hits in hit order.  A shard with no hits
+        uploads nothing.  records=None with `rows`: the pass reads rows, no records table (the dense route)."""
+        with self._plan(records, pool, (), cacheable, rows) as (shards, _busy, ready, _width):
+            index = np.asarray(index, dtype=np.int64)
+            picks = partition_hits(index, [sh.r0 for sh in shards] + [shards[-1].r1])
+            busy = [k for k, mine in enumerate(picks) if len(mine)]
+
+            def one(k):
+                sess, sh, _lo, rec, _extra = ready(k)
+                return task(sess, rec, picks[k], index[picks[k]] - sh.r0, sh.n_records)
+
+            results = self._on_all(one, busy)
+            return [(picks[k], results[k]) for k in busy]
 
     def run_pool(self, records: np.ndarray, pool: np.ndarray, task: Callable, *, per_record: Sequence = (),
                  cacheable: bool = True) -> np.ndarray:
@@ -356,6 +493,7 @@ class ShardedRun:
                     view = out[lo:hi]
                     sess.note_filtered(view)
                     self._filtered[k] = (out, lo, hi, view)
+                self._dense_f32[k] = None  # (the filters overwrote the device float32 pool)
 
             def alone(k):
                 sess = self.sessions[k]
@@ -392,8 +530,8 @@ class ShardedRun:
         if self.closed:
             return
         self.closed = True
-        self._resident = [None] * self.n_shards
-        self._filtered = [None] * self.n_shards
+        for k in range(self.n_shards):
+            self._drop_tags(k)
         for k, w in enumerate(self._workers):
             s = self.sessions[k] if k < len(self.sessions) else None
             try:
@@ -472,5 +610,5 @@ def close_sharded_runs(context) -> None:
         r.close()
 
 
-__all__ = ["POOL_ALIGN", "RecordShard", "ShardError", "ShardedRun", "split_records", "resolve_devices", "sharded_run",
-           "peek_sharded_runs", "close_sharded_runs"]
+__all__ = ["POOL_ALIGN", "RecordShard", "ShardError", "ShardedRun", "split_records", "dense_unit", "split_rows",
+           "partition_hits", "resolve_devices", "sharded_run", "peek_sharded_runs", "close_sharded_runs"]

@@ -11,7 +11,7 @@ from __future__ import annotations
 import threading
 import warnings
 from functools import partial
-from typing import Any
+from typing import Any, NamedTuple
 
 import numpy as np
 
@@ -250,28 +250,53 @@ def dense_session(context: Any, data: np.ndarray, data_name: str) -> tuple[Devic
     the rule of resident_session (this very array OBJECT, until a call replaces the device pool), so a chain of dense
     plugins over one st_waveforms / filtered_waveforms array uploads its samples once.  Anything else (a view with
     gaps, another sample type) takes the host route: dense.dense_pool's contiguous copy, uploaded every time."""
+    rows = dense_input(data, data_name)
+    return _dense_session(context, rows), rows.source, rows.L
+
+
+class DenseInput(NamedTuple):
+    """A dense array as a route sees it, worked out on the host (no device is touched): the array and its name, the
+    wave source and the row length, and `pool`: None when the rows can go to the device as they are, else
+    dense.dense_pool's contiguous copy of every sample (the host route)."""
+
+    data: np.ndarray
+    name: str
+    source: int
+    L: int
+    pool: np.ndarray | None
+
+
+def dense_input(data: np.ndarray, data_name: str) -> DenseInput:
     layout = DeviceSession._dense_layout(data) if DeviceSession.dense_rows else None
     if layout is None:
         from .. import dense
 
         pool, source, L = dense.dense_pool(data, data_name)  # (its errors need no device)
-        return resident_session(context, pool, cacheable=False), source, L
+        return DenseInput(data, data_name, source, L, pool)
+    return DenseInput(data, data_name, SRC_F32 if layout[3] == _lib.DENSE_F32 else SRC_RAW, layout[1], None)
+
+
+def _dense_session(context: Any, rows: DenseInput) -> DeviceSession:
+    if rows.pool is not None:
+        return resident_session(context, rows.pool, cacheable=False)
     sess = note_session(_device_pool(context).session())
-    sess.ensure_dense(data, what=data_name)
-    return sess, (SRC_F32 if layout[3] == _lib.DENSE_F32 else SRC_RAW), layout[1]
+    sess.ensure_dense(rows.data, what=rows.name)
+    return sess
 
 
-# ---- the records route of the per-record plugins, on one device or on several ---------------------------------------
+# ---- the routes of the per-record plugins, on one device or on several ----------------------------------------------
 DEVICES_HELP = ("None: one device (the calling thread's session); a list of device ids (repeats allowed) or 'all': the "
-                "records route runs on those devices, one contiguous record range each, output identical "
+                "pass runs on those devices, output identical.  Records route: one contiguous record range each "
                 "(wave_pool_filtered: each device fills the samples of its records, and its slice stays resident for "
-                "the use_filtered plugins and hit).  The dense routes (st_waveforms / filtered_waveforms) stay on one "
-                "device whatever this says.")
+                "the use_filtered plugins and hit).  The dense routes (st_waveforms / filtered_waveforms): one contiguous "
+                "row range each, cut at multiples of 8 samples; each device keeps its rows resident, and the rows "
+                "filtered_waveforms wrote, for the plugins that follow with the same devices.")
 
 
 def records_route(context: Any, plugin: Any, records: np.ndarray, pool: np.ndarray, row_dtype, run_pass,
                   per_record=(), *, cacheable: bool = True, download=None, record_index_field: str | None = None):
-    """A plugin's pass over records + pool, on the devices its `devices` option names (read here and nowhere else).
+    """A plugin's pass over records + pool, on the devices its `devices` option names (read here and in the routes below, nowhere
+    in a plugin).
 
     run_pass(sess, records, *per_record, ...) is the pass on a session whose pool is resident: it uploads the records
     it is given and runs the kernels.  `per_record`: arguments with one entry per record (or scalars, 0-d arrays,
@@ -302,6 +327,97 @@ def records_route(context: Any, plugin: Any, records: np.ndarray, pool: np.ndarr
     return run.run(records, pool, row_dtype,
                    lambda sess, rec, *args, out, max_len: run_pass(sess, rec, *args, max_len=max_len, download=False),
                    fetch=download, per_record=per_record, cacheable=cacheable, width_arg="max_len")
+
+
+def dense_route(context: Any, plugin: Any, rows: DenseInput, records: np.ndarray, row_dtype, run_pass, per_record=(), *,
+                download=None, record_index_field: str | None = None, out: np.ndarray | None = None):
+    """A plugin's pass over a dense array, on the devices its `devices` option names (read here, in records_route and,
+    for waveform_width's hit table, in _hit_route).
+
+    rows: dense_input(array, name); records: dense.dense_records of it (row r = the record at wave_offset r L).
+    run_pass and the three kinds of output are those of records_route.  The float32 kind (row_dtype None,
+    filtered_waveforms) takes `out`, the output array: run_pass(sess, records, *per_record, download=True) returns the
+    filtered samples of its records, which become out["wave"]; `out` is returned.
+
+    devices=None: the calling thread's session with the rows resident (dense_session), run_pass once on `records` as
+    they are.  Otherwise the context's ShardedRun of those devices cuts the array into contiguous row ranges
+    (multidevice.split_rows), every worker puts `rows.data[r0:r1]` on its device as it is, where it stays resident, and
+    runs run_pass on its records; the slice of `out` a worker filled is tagged resident too.  An array the device
+    cannot take as it is (rows.pool: dense.dense_pool's contiguous copy) goes through records_route with that copy as
+    the pool, cacheable=False: sharded as well, nothing resident."""
+    devices = context.get_config(plugin, "devices")
+    L, n = rows.L, len(rows.data)
+    if row_dtype is None:
+        resident = DeviceSession.dense_rows and DeviceSession._dense_layout(out) is not None
+        if devices is None:
+            sess = _dense_session(context, rows)
+            out["wave"] = run_pass(sess, records, *per_record).reshape(n, L)
+            # when resident, the device float32 pool is exactly out["wave"] in row-major order: hit / waveform_width /
+            # hit_threshold on it upload no samples (the dense twin of note_filtered).  The filters read the uint16 pool
+            # and leave it as it is, so st_waveforms keeps its own tag.
+            if resident:
+                sess.note_dense(out)
+            else:
+                sess.forget_resident()
+        elif rows.pool is not None:
+            out["wave"] = records_route(context, plugin, records, rows.pool, None, run_pass, per_record,
+                                        cacheable=False).reshape(n, L)
+        else:
+            def fill(sess, rec, *args, out):
+                out["wave"] = run_pass(sess, rec, *args).reshape(len(rec), L)
+
+            multidevice.sharded_run(context, devices).run(records, rows.data, out.dtype, fill, per_record=per_record,
+                                                          rows=(rows.name, L, n), out=out, note_out=resident)
+        return out
+    if devices is None:
+        return run_pass(_dense_session(context, rows), records, *per_record)
+    if rows.pool is not None:
+        return records_route(context, plugin, records, rows.pool, row_dtype, run_pass, per_record, cacheable=False,
+                             download=download, record_index_field=record_index_field)
+    run = multidevice.sharded_run(context, devices)
+    if download is None:
+        return run.run(records, rows.data, row_dtype, run_pass, per_record=per_record,
+                       record_index_field=record_index_field, rows=(rows.name, L, n))
+    return run.run(records, rows.data, row_dtype,
+                   lambda sess, rec, *args, out, max_len: run_pass(sess, rec, *args, max_len=max_len, download=False),
+                   fetch=download, per_record=per_record, width_arg="max_len", rows=(rows.name, L, n))
+
+
+def dense_hit_route(context: Any, plugin: Any, rows: DenseInput, row: np.ndarray, run_pass):
+    """waveform_width's pass over the rows of a dense array, per hit: (rows, valid) in hit order.
+
+    row: per hit, the row of `rows.data` it points at (-1: none).  run_pass(sess, None, positions in the hit table, row
+    index, n_rows) -> (WAVEFORM_WIDTH_DTYPE rows, valid mask) of those hits on a session that holds n_rows rows.
+    devices=None: once, on the calling thread's session, every hit.  Otherwise the hits are cut by the shard their row
+    falls in (multidevice.ShardedRun.run_hits; `devices` is read in _hit_route for both routes of the plugin), each
+    shard gets its hits with the row index shifted to its first row, and the results are scattered back into hit
+    order; hits with no row stay invalid, as the device marks them.  An array the device cannot take as it is is cut
+    the same way, every shard uploading its slice of rows.pool each time."""
+    return _hit_route(context, plugin, row, run_pass, None, rows.data if rows.pool is None else rows.pool,
+                      (rows.name, rows.L, len(rows.data)), lambda: _dense_session(context, rows), False)
+
+
+def records_hit_route(context: Any, plugin: Any, records: np.ndarray, pool: np.ndarray, record_index: np.ndarray,
+                      run_pass, *, cacheable: bool = True):
+    """waveform_width's pass over records + pool, per hit: as dense_hit_route, the hits cut by the shard that holds the
+    record they index; run_pass(sess, records_k, positions, record index shifted to records_k,
+    len(records_k)) uploads records_k."""
+    return _hit_route(context, plugin, record_index, run_pass, records, pool, None,
+                      lambda: resident_session(context, pool, cacheable=cacheable), cacheable)
+
+
+def _hit_route(context, plugin, index, run_pass, records, pool, rows, own_session, cacheable):
+    from ..dtypes import WAVEFORM_WIDTH_DTYPE
+
+    devices = context.get_config(plugin, "devices")
+    if devices is None:
+        return run_pass(own_session(), records, slice(None), index, rows[2] if rows else len(records))
+    out = np.zeros(len(index), dtype=WAVEFORM_WIDTH_DTYPE)
+    valid = np.zeros(len(index), dtype=bool)
+    run = multidevice.sharded_run(context, devices)
+    for mine, (rows_k, valid_k) in run.run_hits(index, run_pass, records, pool, cacheable=cacheable, rows=rows):
+        out[mine], valid[mine] = rows_k, valid_k
+    return out, valid
 
 
 # ---- the reference's profiling / statistics / cleanup hooks (SURVEY section 5) --------------------------------------

@@ -65,8 +65,13 @@ class HipBasicFeaturesPlugin(K.HipPlugin):
         data = K.load_dense_input(context, self, run_id, data_name)
         if len(data) == 0:
             return np.zeros(0, dtype=BASIC_FEATURES_DTYPE)
-        sess, source, L = K.dense_session(context, data, data_name)
-        records = dense.dense_records(data, L)
+        rows = K.dense_input(data, data_name)
+        records = dense.dense_records(data, rows.L)
         fixed = K.fixed_baseline_per_record(records, channel_config, run_id)
-        sess.upload_records(records, polarity=dense.dense_polarity_wave_rule(data))
-        return sess.basic_features(source, height_range, area_range, fixed)
+
+        def features(sess, rec, polarity_k, fixed_k, out=None):
+            sess.upload_records(rec, polarity=polarity_k)
+            return sess.basic_features(rows.source, height_range, area_range, fixed_k, out=out)
+
+        return K.dense_route(context, self, rows, records, BASIC_FEATURES_DTYPE, features,
+                             (dense.dense_polarity_wave_rule(data), fixed), record_index_field="event_index")

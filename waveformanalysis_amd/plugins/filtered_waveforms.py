@@ -39,6 +39,7 @@ class HipFilteredWaveformsPlugin(K.HipPlugin):
         "max_workers": Option(default=None, type=int, help="ignored by the HIP backend", track=False),
         "batch_size": Option(default=0, type=int, help="ignored by the HIP backend (must be >= 0)"),
         "channel_config": Option(default=None, type=dict, help="per (board, channel) overrides of the filter options"),
+        "devices": Option(default=None, track=False, help=K.DEVICES_HELP),
     }
 
     def compute(self, context: Any, run_id: str, **_kwargs) -> np.ndarray:
@@ -67,16 +68,16 @@ class HipFilteredWaveformsPlugin(K.HipPlugin):
                 output[name] = st[name]
         boards = st["board"] if "board" in names else np.zeros(len(st), dtype=np.int16)
         groups = plan_filter_groups(context, self, run_id, boards, st["channel"])
-        sess, source, L = K.dense_session(context, st, "st_waveforms")
-        if source != K.SRC_RAW:
+        rows = K.dense_input(st, "st_waveforms")
+        if rows.source != K.SRC_RAW:
             raise ValueError(f"st_waveforms['wave'] must be int16, got {st['wave'].dtype}")
-        filtered = run_filter_groups(sess, dense.dense_records(st, L), groups)
-        output["wave"] = filtered.reshape(len(st), L)
-        if sess.dense_rows and sess._dense_layout(output) is not None:
-            # the device float32 pool is exactly output["wave"] in row-major order: hit / waveform_width / hit_threshold
-            # on filtered_waveforms upload no samples (the dense twin of note_filtered).  The filters read the uint16
-            # pool and leave it as it is, so st_waveforms keeps its own tag.
-            sess.note_dense(output)
-        else:
-            sess.forget_resident()
-        return output
+        keys, masks = zip(*groups)
+
+        def filters(sess, rec, *masks_k, download=True):
+            # the groups in the order one device runs them; of a shard's rows, the groups that have any
+            mine = [(key, m) for key, m in zip(keys, masks_k) if m.any()]
+            return run_filter_groups(sess, rec, mine, download=download)
+
+        # devices: every shard filters its rows and copies them into output["wave"][r0:r1]; the device float32 pool is
+        # then exactly that slice in row-major order and is noted as resident when the layout allows it (K.dense_route)
+        return K.dense_route(context, self, rows, dense.dense_records(st, rows.L), None, filters, masks, out=output)

@@ -105,11 +105,17 @@ class HipHitFinderPlugin(K.HipPlugin):
         dt_values = _dt_values(data, explicit_dt, "st_waveforms")  # the reference's text, whatever data_name is
         if "baseline" not in (data.dtype.names or ()) and not peak_kw["use_derivative"]:
             raise ValueError(f"hit (HIP backend) needs a 'baseline' field on {data_name} when use_derivative=False")
-        sess, source, L = K.dense_session(context, data, data_name)
-        rec = dense.dense_records(data, L, keep_record_id=True, truncate_to_event_length=True)
+        rows = K.dense_input(data, data_name)
+        rec = dense.dense_records(data, rows.L, keep_record_id=True, truncate_to_event_length=True)
         rec["dt"] = dt_values
-        sess.upload_records(rec, np.zeros(len(rec), dtype=np.float64))
-        return sess.find_peaks(source, dense_rows=True, **peak_kw)
+
+        def peaks(sess, rec_k, max_len=0, download=True):  # (find_peaks pads nothing: the run's width is not used)
+            sess.upload_records(rec_k, np.zeros(len(rec_k), dtype=np.float64))
+            return sess.find_peaks(rows.source, dense_rows=True, download=download, **peak_kw)
+
+        # rows carry record_id and timestamp, no row index: nothing to shift; shards in order = row order
+        return K.dense_route(context, self, rows, rec, HIT_DTYPE, peaks,
+                             download=lambda sess, out: sess.download_peaks(out))
 
 
 def _dt_values(data: np.ndarray, explicit_dt, data_name: str) -> np.ndarray:

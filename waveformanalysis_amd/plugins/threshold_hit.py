@@ -125,7 +125,8 @@ class HipThresholdHitPlugin(K.HipPlugin):
         if len(data) == 0:
             return np.zeros(0, dtype=THRESHOLD_HIT_DTYPE)
         names = data.dtype.names or ()
-        sess, source, L = K.dense_session(context, data, data_name)
+        rows = K.dense_input(data, data_name)
+        source, L = rows.source, rows.L
         rec = dense.dense_records(data, L, keep_record_id=True)
         rec["dt"] = K.require_dt_array(data, explicit_dt=explicit_dt, plugin_name=self.provides, data_name=data_name)
         if "event_length" in names:
@@ -134,12 +135,18 @@ class HipThresholdHitPlugin(K.HipPlugin):
             source_lengths = np.full(len(data), L, dtype=np.int64)
         record_lengths = _lengths_from_records(context, run_id, rec["record_id"], source_lengths)
         thresholds = K.per_record_channel_option(rec, channel_config, run_id, "threshold", threshold, threshold)
-        sess.upload_records(rec, thresholds)
-        if "baseline" not in names:
-            if source != K.SRC_RAW:
-                raise ValueError(f"hit_threshold (HIP backend) needs a 'baseline' field on float32 {data_name}")
-            sess.baseline_mean(0, L, update_records=True)  # waves.mean(axis=1): exact integer sum / L
-        hits = sess.threshold_hits(source, le, re)
+        if "baseline" not in names and source != K.SRC_RAW:
+            raise ValueError(f"hit_threshold (HIP backend) needs a 'baseline' field on float32 {data_name}")
+
+        def whole_rows(sess, rec_k, thresholds_k, max_len=0, download=True):
+            sess.upload_records(rec_k, thresholds_k)
+            if "baseline" not in names:
+                sess.baseline_mean(0, L, update_records=True)  # waves.mean(axis=1): exact integer sum / L
+            return sess.threshold_hits(source, le, re, max_len=max_len, download=download)
+
+        # the rows above and the clamp below concern the whole run and stay on the whole table; the pass is per shard
+        hits = K.dense_route(context, self, rows, rec, THRESHOLD_HIT_DTYPE, whole_rows, (thresholds,),
+                             download=lambda sess, out: sess.download_hits(out))
         if len(hits) and np.any(record_lengths < L):
             order = np.argsort(rec["record_id"], kind="stable")
             row = order[np.searchsorted(rec["record_id"][order], hits["record_id"])]

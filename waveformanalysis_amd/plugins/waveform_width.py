@@ -56,6 +56,7 @@ class HipWaveformWidthPlugin(K.HipPlugin):
         "fall_high": Option(default=0.9, type=float, help="high fraction of the fall time"),
         "fall_low": Option(default=0.1, type=float, help="low fraction of the fall time"),
         "interpolation": Option(default=True, type=bool, help="linear interpolation of the crossings"),
+        "devices": Option(default=None, track=False, help=K.DEVICES_HELP),
     }
 
     def resolve_depends_on(self, context: Any, run_id: str | None = None) -> list[str]:
@@ -92,9 +93,14 @@ class HipWaveformWidthPlugin(K.HipPlugin):
         else:
             row = np.where((record_id >= 0) & (record_id < len(waveform_data)), record_id, -1)
 
-        sess, source, L = K.dense_session(context, waveform_data, data_name)
-        rows, valid = sess.waveform_width(source, position, row, len(waveform_data), L, rise_low, rise_high,
-                                          fall_high, fall_low, float(sampling_rate), interpolation)
+        dense_in = K.dense_input(waveform_data, data_name)
+
+        def widths(sess, _records, mine, row_k, n_rows):
+            return sess.waveform_width(dense_in.source, position[mine], row_k, n_rows, dense_in.L, rise_low, rise_high,
+                                       fall_high, fall_low, float(sampling_rate), interpolation)
+
+        # devices: the hit table is cut by the shard its row falls in, rows and valid scattered back into hit order
+        rows, valid = K.dense_hit_route(context, self, dense_in, row, widths)
         return _kept_rows(rows, valid, hits, record_id)
 
     def _compute_records(self, context, run_id, pool_name, hits, rise_low, rise_high, fall_high, fall_low, sampling_rate,
@@ -113,12 +119,16 @@ class HipWaveformWidthPlugin(K.HipPlugin):
             source = K.SRC_F32
         else:
             source = K.pool_source(pool, raw_only=True)
-        sess = K.resident_session(context, pool, cacheable=cacheable)
-        if not sess.holds_records(records):  # (a pool upload above has dropped the note)
-            sess.upload_records(records)
-            sess.note_records(records)
-        rows, valid = sess.waveform_width_records(source, position, record_id, rise_low, rise_high, fall_high,
-                                                  fall_low, sampling_rate, interpolation)
+
+        def widths(sess, rec_k, mine, record_k, _n_records):
+            if not sess.holds_records(rec_k):  # (a pool upload has dropped the note; a shard's records are new every run)
+                sess.upload_records(rec_k)
+                sess.note_records(rec_k)
+            return sess.waveform_width_records(source, position[mine], record_k, rise_low, rise_high, fall_high,
+                                               fall_low, sampling_rate, interpolation)
+
+        # devices: the hit table is cut by the shard that holds record `record_id`; a shard with no hits uploads nothing
+        rows, valid = K.records_hit_route(context, self, records, pool, record_id, widths, cacheable=cacheable)
         return _kept_rows(rows, valid, hits, record_id)
 
 

@@ -63,9 +63,15 @@ class HipWaveformWidthIntegralPlugin(K.HipPlugin):
             for name in ("baseline", "timestamp"):
                 if name not in (data.dtype.names or ()):
                     raise ValueError(f"no field of name {name}")  # numpy's message for data[i][name]
-            sess, source, L = K.dense_session(context, data, pool_name)
-            sess.upload_records(dense.dense_records(data, L), polarity=dense.dense_polarity_wave_rule(data))
-            return sess.width_integral(source, q_low, q_high, float(dt))
+            rows = K.dense_input(data, pool_name)
+
+            def whole_rows(sess, rec, polarity_k, out=None):
+                sess.upload_records(rec, polarity=polarity_k)
+                return sess.width_integral(rows.source, q_low, q_high, float(dt), out=out)
+
+            return K.dense_route(context, self, rows, dense.dense_records(data, rows.L),
+                                 WAVEFORM_WIDTH_INTEGRAL_DTYPE, whole_rows, (dense.dense_polarity_wave_rule(data),),
+                                 record_index_field="event_index")
         if len(records) == 0:
             return np.zeros(0, dtype=WAVEFORM_WIDTH_INTEGRAL_DTYPE)
         source = K.pool_source(pool)
