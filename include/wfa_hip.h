@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define WFA_ABI_VERSION 2
+#define WFA_ABI_VERSION 3
 
 #define WFA_OK 0
 #define WFA_E_INVALID (-1)   /* bad argument / malformed records (maps to ValueError) */
@@ -236,6 +236,37 @@ int wfa_fused_baseline_filter_hits(wfa_ctx* ctx, int32_t bl_start, int32_t bl_en
 int wfa_hits_enqueue(wfa_ctx* ctx, int source, int32_t bl_start, int32_t bl_end, int32_t left_extension,
                      int32_t right_extension, int32_t max_len);
 int wfa_hits_wait(wfa_ctx* ctx, int64_t* n_hits);
+
+/* Several hit passes over ONE uploaded records table, merged into one table on the device: the fused pass on a run whose
+ * channels resolve to different filter settings (reference: cpu/filtering.py:339-374 groups the records by their resolved
+ * settings; hit_finder.py:288-327 resolves the per-channel threshold; hit_finder.py:354-366 emits the hits of all records in
+ * one loop, i.e. by (record index, start)).  One pass runs per distinct setting, each with the threshold column set to
+ * +inf for the records of the other settings (sig >= +inf holds for no finite sample: no hit on any route).
+ *
+ * wfa_set_thresholds replaces the device threshold column of the uploaded records (n_records doubles) and nothing else:
+ * the layout record, the padded shadow pool, the device baselines (those a fused-baseline pass wrote included), the
+ * Savitzky-Golay plan, the resident pools and the rows of the last pass stand.  (A second wfa_upload_records_* would void
+ * the shadow of a padded layout.)  WFA_E_STATE without records, WFA_E_INVALID when n_records differs from the uploaded
+ * count; a queued pass (wfa_hits_enqueue) is waited for first.
+ *
+ * wfa_hit_rows_merge_begin opens an empty merge set (dropping an unfinished one).
+ * wfa_hit_rows_merge_add takes the rows of the last completed hit pass into the set, with the record index (position in
+ * the uploaded records table) of every row; a queued pass is waited for, a pass without rows is legal.  WFA_E_STATE
+ * without an open set, without a pass, or when the resident rows are a merged table; WFA_E_INVALID when the records
+ * table has another size than at the set's first pass.
+ * wfa_hit_rows_merge_end merges the set (k_hit_rows_merge_*: per-record row count, exclusive scan, scatter of the 60-byte
+ * rows as 15 dwords each) and closes it.  Order: ascending record index; the rows of one record keep the order of the
+ * pass that produced them, and rows of one record that come from two passes stand in pass order (the order of the _add
+ * calls) -- the plugins never produce that, their passes own disjoint records.  Afterwards the merged table IS "the rows
+ * of the last hit pass": wfa_threshold_hits_fill, wfa_hits_wait, wfa_rccl_gather_rows(rows = NULL) and, through
+ * wfa_hit_rows_source(ctx, 1), the resident hit-table stages read it; the row count also sizes the next pass's
+ * speculative launch.  An empty set gives 0 rows.  WFA_E_STATE without an open set.
+ * The stash of the added passes is scratch (wfa_release_scratch frees it and with it an open set; wfa_scratch_bytes
+ * counts it): 64 bytes per stashed row + 8 per merged row, beside the table itself. */
+int wfa_set_thresholds(wfa_ctx* ctx, const double* threshold, int64_t n_records);
+int wfa_hit_rows_merge_begin(wfa_ctx* ctx);
+int wfa_hit_rows_merge_add(wfa_ctx* ctx);
+int wfa_hit_rows_merge_end(wfa_ctx* ctx, int64_t* n_hits);
 
 /* K8 find_peaks-based hit detector, records source (reference: cpu/peak_finding.py:395-614 calling
  * scipy.signal.find_peaks(det, height, distance, prominence, width, threshold) with scalar lower bounds, then

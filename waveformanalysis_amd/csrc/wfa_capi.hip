@@ -277,6 +277,7 @@ static int run_rows(wfa_ctx* c, const PoolView& pv, const RecView& rv, const SgP
     };
     auto finish = [&](int64_t total) {
         c->n_hits = total;
+        c->rows_index = 1;
         *n_hits = total;
         *done = true;
         return WFA_OK;
@@ -302,6 +303,7 @@ static int run_rows(wfa_ctx* c, const PoolView& pv, const RecView& rv, const SgP
             c->pending = true;
             c->pend = pend;
             c->n_hits = -1;
+            c->rows_index = 1;
             *done = true;
             return WFA_OK;
         }
@@ -470,6 +472,7 @@ static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int
         bl_start = w.start; bl_end = w.end;
     }
     c->n_hits = -1;
+    c->rows_index = 0;
     if (c->R == 0) {
         c->n_hits = 0;
         *n_hits = 0;
@@ -610,6 +613,7 @@ static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int
         if ((rc = t.end("k_hits_gather"))) return rc;
     }
     c->n_hits = total;
+    c->rows_index = 2;
     *n_hits = total;
     return WFA_OK;
 }
@@ -851,6 +855,9 @@ int wfa_release_scratch(wfa_ctx* c, int64_t* freed_bytes) {
     c->csv_filled = false;
     pass_caches_dropped(c);
     c->hit_tmp_rows = 0;
+    c->merge_open = false;  // the stash of an open merge set went with the scratch: wfa_hit_rows_merge_begin starts over
+    c->merge_n = 0;
+    c->merge_start.clear();
     if (freed_bytes) *freed_bytes = freed;
     return WFA_OK;
 }
@@ -1366,6 +1373,246 @@ int wfa_threshold_hits_fill(wfa_ctx* c, void* out_rows, int64_t n_hits) {
     return WFA_OK;
 }
 
+int wfa_set_thresholds(wfa_ctx* c, const double* threshold, int64_t n_records) {
+    int rc = use_device(c);
+    if (rc) return rc;
+    if (!c->have_records) return fail(WFA_E_STATE, "records not uploaded");
+    if (n_records != c->R)
+        return fail(WFA_E_INVALID, "caller passes %lld thresholds, %lld records are uploaded", (long long)n_records, (long long)c->R);
+    if (n_records > 0 && !threshold) return fail(WFA_E_INVALID, "threshold is null");
+    if (c->pending) {  // the queued pass reads the column that is about to change
+        int64_t n = 0;
+        if ((rc = wfa_hits_wait(c, &n))) return rc;
+    }
+    // the column alone: no records_replaced(), so the layout record, the padded shadow, the device baselines, the plan and
+    // the rows of the last pass stand
+    if ((rc = h2d_copy(c, c->thr.ptr, threshold, (size_t)n_records * sizeof(double)))) return rc;
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return WFA_OK;
+}
+
+}  // extern "C"
+
+// ---- rows of several hit passes merged into one table (wfa_hit_rows_merge_*) ---------------------------------------
+// The passes run over the same uploaded records with thresholds that leave every record to one of them (per-channel
+// filter settings: cpu/filtering.py:339-374 resolved per record, hit_finder.py:288-327 for the thresholds); the reference
+// finds the hits of all records in one loop and so emits them by (record index, start) (hit_finder.py:354-366).  Every
+// added pass is stashed as it is -- its 60-byte rows and the record index of each -- and the merge is a per-record row
+// count, an exclusive scan over the records and a scatter of the rows.  `rec` of one pass ascends, so the rows of a
+// record inside a pass are found by binary search.
+constexpr int kMergeBlock = 256;
+
+// which pass (set) row i belongs to: sets[0] = 0 <= ... <= sets[G] = n (empty passes repeat a boundary)
+__device__ __forceinline__ int merge_set_of(const int64_t* __restrict__ sets, int G, int64_t i) {
+    int g = 0;
+    while (g + 1 < G && sets[g + 1] <= i) ++g;
+    return g;
+}
+
+// first index in [lo, hi) whose record is >= r (Upper: > r)
+template <bool Upper>
+__device__ __forceinline__ int64_t merge_bound(const int32_t* __restrict__ rec, int64_t lo, int64_t hi, int32_t r) {
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        const int32_t v = rec[mid];
+        if (Upper ? v <= r : v < r) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// record index of every row of the pass just run.  desc != null: the run descriptors of the streaming / bitmap routes;
+// otherwise the general route's exclusive scan of the per-record counts (row i belongs to the last record whose first row
+// is <= i: the records behind it without a hit start past i)
+__global__ __launch_bounds__(kMergeBlock) void k_hit_rows_merge_index(int64_t n, const int4* __restrict__ desc,
+                                                                      const int64_t* __restrict__ out_start, int64_t R,
+                                                                      int32_t* __restrict__ rec) {
+    const int64_t i = (int64_t)blockIdx.x * kMergeBlock + threadIdx.x;
+    if (i >= n) return;
+    if (desc) { rec[i] = desc[i].x; return; }
+    int64_t lo = 0, hi = R;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (out_start[mid] <= i) lo = mid + 1; else hi = mid;
+    }
+    rec[i] = (int32_t)(lo - 1);
+}
+
+// per-record row count over all passes: the first row of a record inside a pass adds that pass's rows of the record
+__global__ __launch_bounds__(kMergeBlock) void k_hit_rows_merge_count(int64_t n, const int32_t* __restrict__ rec,
+                                                                      const int64_t* __restrict__ sets, int G, int64_t R,
+                                                                      int32_t* __restrict__ counts) {
+    const int64_t i = (int64_t)blockIdx.x * kMergeBlock + threadIdx.x;
+    if (i >= n) return;
+    const int g = merge_set_of(sets, G, i);
+    const int32_t r = rec[i];
+    if (r < 0 || r >= R) return;
+    if (i > sets[g] && rec[i - 1] == r) return;
+    const int64_t end = merge_bound<true>(rec, i, sets[g + 1], r);
+    atomicAdd(&counts[r], (int32_t)(end - i));
+}
+
+// final place of every row: first row of its record, + the record's rows in earlier passes, + its rank inside its own pass
+__global__ __launch_bounds__(kMergeBlock) void k_hit_rows_merge_place(int64_t n, const int32_t* __restrict__ rec,
+                                                                      const int64_t* __restrict__ sets, int G, int64_t R,
+                                                                      const int64_t* __restrict__ out_start,
+                                                                      int64_t* __restrict__ dest) {
+    const int64_t i = (int64_t)blockIdx.x * kMergeBlock + threadIdx.x;
+    if (i >= n) return;
+    const int g = merge_set_of(sets, G, i);
+    const int32_t r = rec[i];
+    if (r < 0 || r >= R) { dest[i] = -1; return; }
+    int64_t pos = out_start[r] + (i - merge_bound<false>(rec, sets[g], i, r));
+    for (int e = 0; e < g; ++e) {
+        const int64_t lo = merge_bound<false>(rec, sets[e], sets[e + 1], r);
+        pos += merge_bound<true>(rec, lo, sets[e + 1], r) - lo;
+    }
+    dest[i] = pos;
+}
+
+// 60-byte rows as 15 dwords: consecutive lanes read consecutive dwords of the stash and write runs of 15 into the table
+__global__ __launch_bounds__(kMergeBlock) void k_hit_rows_merge_scatter(int64_t n, const uint32_t* __restrict__ src,
+                                                                        const int64_t* __restrict__ dest,
+                                                                        uint32_t* __restrict__ out) {
+    const int64_t d = (int64_t)blockIdx.x * kMergeBlock + threadIdx.x;
+    if (d >= n * 15) return;
+    const int64_t i = d / 15;
+    const int64_t to = dest[i];
+    if (to < 0 || to >= n) return;
+    out[to * 15 + (d - i * 15)] = src[d];
+}
+
+static unsigned merge_grid(int64_t n) { return (unsigned)((n + kMergeBlock - 1) / kMergeBlock); }
+
+// grow a stash buffer to `want` bytes and keep its first `used` bytes (DevBuf::ensure drops the contents)
+static int merge_grow(wfa_ctx* c, DevBuf& b, size_t used, size_t want) {
+    if (want <= b.cap) return WFA_OK;
+    if (used == 0) return b.ensure(want);
+    want = std::max(want, 2 * b.cap);
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, want + 256);
+    if (e != hipSuccess) return fail(WFA_E_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
+    e = hipMemcpyAsync(p, b.ptr, used, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return fail(WFA_E_HIP, "growing the merge stash failed: %s", hipGetErrorString(e));
+    }
+    (void)hipFree(b.ptr);
+    b.ptr = p;
+    b.cap = want;
+    return WFA_OK;
+}
+
+extern "C" {
+
+int wfa_hit_rows_merge_begin(wfa_ctx* c) {
+    int rc = use_device(c);
+    if (rc) return rc;
+    c->merge_open = true;
+    c->merge_n = 0;
+    c->merge_R = -1;
+    c->merge_start.assign(1, 0);
+    return WFA_OK;
+}
+
+int wfa_hit_rows_merge_add(wfa_ctx* c) {
+    int rc = use_device(c);
+    if (rc) return rc;
+    if (!c->merge_open) return fail(WFA_E_STATE, "no merge set is open (wfa_hit_rows_merge_begin)");
+    if (c->pending) {
+        int64_t n = 0;
+        if ((rc = wfa_hits_wait(c, &n))) return rc;
+    }
+    if (c->n_hits < 0) return fail(WFA_E_STATE, "no hit pass has been run");
+    if (c->merge_R >= 0 && c->merge_R != c->R)
+        return fail(WFA_E_INVALID, "the passes of a merge set run over one records table (%lld records, now %lld)",
+                    (long long)c->merge_R, (long long)c->R);
+    c->merge_R = c->R;
+    const int64_t n = c->n_hits, at = c->merge_n;
+    if (n > 0) {
+        if (c->rows_index == 0)
+            return fail(WFA_E_STATE, "the resident rows carry no record index (a merged table, or another stage ran since the pass)");
+        if ((rc = merge_grow(c, c->merge_rows, (size_t)at * 60, (size_t)(at + n) * 60))) return rc;
+        if ((rc = merge_grow(c, c->merge_rec, (size_t)at * sizeof(int32_t), (size_t)(at + n) * sizeof(int32_t)))) return rc;
+        LaunchTimer t(c);
+        WFA_HIP_CHECK(hipMemcpyAsync(c->merge_rows.as<uint8_t>() + at * 60, c->hit_out.ptr, (size_t)n * 60,
+                                     hipMemcpyDeviceToDevice, c->stream));
+        hipLaunchKernelGGL(k_hit_rows_merge_index, dim3(merge_grid(n)), dim3(kMergeBlock), 0, c->stream, n,
+                           c->rows_index == 1 ? c->hit_desc.as<int4>() : nullptr, c->rec_out_start.as<int64_t>(), c->R,
+                           c->merge_rec.as<int32_t>() + at);
+        WFA_HIP_CHECK(hipGetLastError());
+        if ((rc = t.end("k_hit_rows_merge_index (+ row stash)"))) return rc;
+        WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    }
+    c->merge_n = at + n;
+    c->merge_start.push_back(c->merge_n);
+    return WFA_OK;
+}
+
+int wfa_hit_rows_merge_end(wfa_ctx* c, int64_t* n_hits) {
+    int rc = use_device(c);
+    if (rc) return rc;
+    if (!n_hits) return fail(WFA_E_INVALID, "n_hits is null");
+    if (!c->merge_open) return fail(WFA_E_STATE, "no merge set is open (wfa_hit_rows_merge_begin)");
+    if (c->pending) {  // a pass that was queued and never added: it ends here, its rows are replaced
+        int64_t n = 0;
+        if ((rc = wfa_hits_wait(c, &n))) return rc;
+    }
+    c->merge_open = false;
+    const int64_t total = c->merge_n, R = c->merge_R;
+    const int G = (int)c->merge_start.size() - 1;
+    c->merge_n = 0;
+    if (total > 0) {
+        const int64_t nb = scan_blocks_for(R);
+        const int64_t want = rows_bound(total);  // head room, so that a later single pass can speculate
+        if ((rc = c->rec_nhits.ensure((size_t)R * sizeof(int32_t))) || (rc = c->rec_out_start.ensure((size_t)R * sizeof(int64_t))) ||
+            (rc = c->scan_blocks.ensure((size_t)(nb + 1) * sizeof(int64_t))) || (rc = c->merge_dest.ensure((size_t)total * sizeof(int64_t))) ||
+            (rc = c->merge_sets.ensure((size_t)(G + 1) * sizeof(int64_t))) || (rc = c->hit_out.ensure((size_t)want * 60)) ||
+            (rc = c->hit_desc.ensure((size_t)want * sizeof(int4))))
+            return rc;
+        const int32_t* rec = c->merge_rec.as<int32_t>();
+        const int64_t* sets = c->merge_sets.as<int64_t>();
+        int32_t* counts = c->rec_nhits.as<int32_t>();
+        WFA_HIP_CHECK(hipMemcpyAsync(c->merge_sets.ptr, c->merge_start.data(), (size_t)(G + 1) * sizeof(int64_t),
+                                     hipMemcpyHostToDevice, c->stream));
+        WFA_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)R * sizeof(int32_t), c->stream));
+        {
+            LaunchTimer t(c);
+            hipLaunchKernelGGL(k_hit_rows_merge_count, dim3(merge_grid(total)), dim3(kMergeBlock), 0, c->stream, total, rec,
+                               sets, G, R, counts);
+            WFA_HIP_CHECK(hipGetLastError());
+            if ((rc = t.end("k_hit_rows_merge_count"))) return rc;
+        }
+        {
+            LaunchTimer t(c);
+            WFA_HIP_CHECK(launch_scan(c->stream, counts, R, c->scan_blocks.as<int64_t>(), c->rec_out_start.as<int64_t>()));
+            if ((rc = t.end("k_scan(merged hit counts)"))) return rc;
+        }
+        {
+            LaunchTimer t(c);
+            hipLaunchKernelGGL(k_hit_rows_merge_place, dim3(merge_grid(total)), dim3(kMergeBlock), 0, c->stream, total, rec,
+                               sets, G, R, c->rec_out_start.as<int64_t>(), c->merge_dest.as<int64_t>());
+            WFA_HIP_CHECK(hipGetLastError());
+            if ((rc = t.end("k_hit_rows_merge_place"))) return rc;
+        }
+        {
+            LaunchTimer t(c);
+            hipLaunchKernelGGL(k_hit_rows_merge_scatter, dim3(merge_grid(total * 15)), dim3(kMergeBlock), 0, c->stream, total,
+                               c->merge_rows.as<uint32_t>(), c->merge_dest.as<int64_t>(), c->hit_out.as<uint32_t>());
+            WFA_HIP_CHECK(hipGetLastError());
+            if ((rc = t.end("k_hit_rows_merge_scatter"))) return rc;
+        }
+        WFA_HIP_CHECK(hipStreamSynchronize(c->stream));  // (merge_start is read by the copy above until here)
+    }
+    c->merge_start.clear();
+    // the merged table is "the rows of the last hit pass" from here on, for wfa_threshold_hits_fill and the resident stages
+    c->n_hits = total;
+    c->last_hits = total;
+    c->rows_index = 0;
+    *n_hits = total;
+    return WFA_OK;
+}
+
 int wfa_find_peaks_count(wfa_ctx* c, int source, int signal_mode, int use_derivative, double height, int has_threshold,
                          double threshold, int32_t distance, double prominence, double width, int height_method,
                          int32_t ext, int64_t* n_peaks) {
@@ -1381,6 +1628,7 @@ int wfa_find_peaks_count(wfa_ctx* c, int source, int signal_mode, int use_deriva
         return fail(WFA_E_INVALID, "signal_mode must be WFA_PEAK_SIGNAL_RECORDS, _ROWS or _ROWS_F64");
     c->n_peaks = -1;
     if (c->R == 0) { c->n_peaks = 0; *n_peaks = 0; return WFA_OK; }
+    if (c->rows_index == 2) c->rows_index = 0;  // rec_nhits / rec_out_start are this pass's from here on
     const int64_t R = c->R;
     if ((rc = c->rec_nhits.ensure(R * sizeof(int32_t)))) return rc;
     if ((rc = c->rec_out_start.ensure(R * sizeof(int64_t)))) return rc;
@@ -1561,6 +1809,7 @@ int wfa_find_hits_count(wfa_ctx* c, int source, int64_t n_rows, int32_t row_leng
                     row_length, (long long)c->pool_n);
     c->n_legacy = -1;
     if (n_rows == 0 || row_length == 0) { c->n_legacy = 0; *n_hits = 0; return WFA_OK; }
+    if (c->rows_index == 2) c->rows_index = 0;  // rec_nhits / rec_out_start are this pass's from here on
     if (!baselines) return fail(WFA_E_INVALID, "baselines is null");
     if ((rc = c->fixed_bl.ensure((size_t)n_rows * sizeof(double)))) return rc;
     WFA_HIP_CHECK(hipMemcpyAsync(c->fixed_bl.ptr, baselines, (size_t)n_rows * sizeof(double), hipMemcpyHostToDevice, c->stream));

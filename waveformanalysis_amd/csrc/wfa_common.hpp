@@ -159,6 +159,16 @@ struct wfa_ctx {
     bool no_runs32 = false;   // a span outgrew the event buffer of its wave: this records upload takes the general route
     int64_t n_hits = -1;
     int64_t last_hits = -1;  // hits of the previous fast-path pass on this context (sizes the speculative tail)
+    // where the record index of every row of the last hit pass stands: 0 nowhere (no pass yet, a merged table, or the
+    // per-record buffers taken by another stage), 1 hit_desc[i].x (streaming and bitmap routes), 2 rec_nhits /
+    // rec_out_start (general route: per-record counts and their exclusive scan)
+    int rows_index = 0;
+    // merge set of several hit passes over one records table (wfa_hit_rows_merge_*): the rows of the added passes back
+    // to back, the record index of every row, and where each pass's rows start (merge_start: one entry per pass + end)
+    bool merge_open = false;
+    int64_t merge_n = 0, merge_R = -1;
+    std::vector<int64_t> merge_start;
+    wfa::DevBuf merge_rows{scratch}, merge_rec{scratch}, merge_dest{scratch}, merge_sets{scratch};
 
     wfa::DevBuf out_rows;  // per-record feature rows
     wfa::DevBuf out_rows2; // the second table of wfa_features_both (width rows)

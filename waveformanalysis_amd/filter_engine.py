@@ -82,6 +82,28 @@ def plan_filter_groups(context: Any, plugin: Any, run_id: str, boards: np.ndarra
     return list(by_key.items())
 
 
+def plan_fused_groups(context: Any, filter_plugin: Any, run_id: str, records: np.ndarray):
+    """The filter groups of a fused hit pass (hit_threshold, fuse_filter=True): what `filter_plugin`, the registered
+    wave_pool_filtered plugin, would apply to `records`, as [(filter key, bool mask or None)] -- None = every record.
+
+    No such plugin: one group ("SG", 11, 2), the reference's defaults.  A plugin without a channel_config: one group from
+    its run-wide options, nothing per record happens on the host.  Otherwise plan_filter_groups, with the reference's
+    validation messages (filtering.py:76-124) for a bad run-wide or per-channel setting."""
+    if filter_plugin is None:
+        return [(("SG", 11, 2), None)]
+    channel_config = context.get_config(filter_plugin, "channel_config") if "channel_config" in filter_plugin.options else None
+    if not channel_config:
+        base = {name: context.get_config(filter_plugin, name) for name in FILTER_OPTION_NAMES}
+        with warnings.catch_warnings():  # (the even-window note belongs to wave_pool_filtered's own run)
+            warnings.simplefilter("ignore")
+            return [(resolve_filter_key(base), None)]
+    n = len(records)
+    names = records.dtype.names or ()
+    boards = records["board"] if "board" in names else np.zeros(n, dtype=np.int16)
+    channels = records["channel"] if "channel" in names else np.zeros(n, dtype=np.int16)
+    return plan_filter_groups(context, filter_plugin, run_id, boards, channels)
+
+
 def run_filter_groups(sess, records: np.ndarray, groups, download: bool = True) -> np.ndarray | None:
     """Filter every group into the session's float32 pool and return it (host copy; download=False: left on the
     device, None returned).  Groups run in list order: where records of two groups share samples the later group's

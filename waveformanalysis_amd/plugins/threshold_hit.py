@@ -12,6 +12,7 @@ from .. import dense
 from ..dtypes import THRESHOLD_HIT_DTYPE
 from ..plugin_api import Option, Plugin
 from ..records_builder import _baseline_window
+from ..filter_engine import design_bw, plan_fused_groups
 from ..sg_plan import normalize_window
 from . import _common as K
 
@@ -52,8 +53,11 @@ class HipThresholdHitPlugin(K.HipPlugin):
         "use_filtered": Option(default=False, type=bool, help="threshold the filtered waveform"),
         "fuse_filter": Option(
             default=False, type=bool,
-            help="with use_filtered: evaluate the Savitzky-Golay filter inside the hit kernel from "
-                 "wave_pool instead of reading a materialised wave_pool_filtered (same result)"),
+            help="with use_filtered: evaluate the filter inside the hit kernel from wave_pool instead of reading a "
+                 "materialised wave_pool_filtered (same result).  The filter settings are those of the registered "
+                 "wave_pool_filtered plugin, resolved per record (filter_type, channel_config): one Savitzky-Golay "
+                 "setting for the run is one pass; several settings run one pass each over the resident pool, their "
+                 "rows merged on the device; a Butterworth group is filtered on the device first (never downloaded)"),
         "fuse_baseline": Option(
             default=None, validate=_valid_fuse_baseline,
             help="None, or (start, end) with 0 <= start < end: re-estimate records.baseline as the mean of samples "
@@ -108,15 +112,21 @@ class HipThresholdHitPlugin(K.HipPlugin):
             source = K.pool_source(pool, raw_only=True)
             if fused:
                 source = K.SRC_SG_FUSED
-        sg = None
+        sg, groups, masks = None, None, ()
         if fused:
+            # the filter settings per record, exactly as wave_pool_filtered resolves them (filtering.py:339-374)
             fplugin = context.get_plugin("wave_pool_filtered") if "wave_pool_filtered" in getattr(context, "_plugins", {}) else None
-            w = context.get_config(fplugin, "sg_window_size") if fplugin else 11
-            p = context.get_config(fplugin, "sg_poly_order") if fplugin else 2
-            sg = normalize_window(w, p)
+            plan = plan_fused_groups(context, fplugin, run_id, rec)
+            if len(plan) == 1 and plan[0][0][0] == "SG":  # the common case: one Savitzky-Golay pair for the run
+                sg = normalize_window(*plan[0][0][1:])
+            else:  # one pass per group, the rows merged on the device (records_pass)
+                groups = [key for key, _mask in plan]
+                masks = tuple(np.ones(len(rec), dtype=bool) if mask is None else mask for _key, mask in plan)
         return K.records_route(context, self, rec, pool, THRESHOLD_HIT_DTYPE,
-                               partial(records_pass, source=source, sg=sg, fuse_baseline=fuse_baseline, le=le, re=re),
-                               (thresholds,), cacheable=cacheable, download=lambda sess, out: sess.download_hits(out))
+                               partial(records_pass, source=source, sg=sg, fuse_baseline=fuse_baseline, le=le, re=re,
+                                       groups=groups),
+                               (thresholds,) + masks, cacheable=cacheable,
+                               download=lambda sess, out: sess.download_hits(out))
 
     def _compute_dense(self, context, run_id, data_name, threshold, le, re, explicit_dt, channel_config) -> np.ndarray:
         """hit_finder.py:179-255: the whole row is searched; the records/wave_pool length of the same record_id
@@ -158,12 +168,18 @@ class HipThresholdHitPlugin(K.HipPlugin):
         return hits
 
 
-def records_pass(sess, records: np.ndarray, thresholds, *, source: int, sg: tuple[int, int] | None, fuse_baseline,
-                 le: int, re: int, max_len: int = 0, download: bool = True):
+def records_pass(sess, records: np.ndarray, thresholds, *masks, source: int, sg: tuple[int, int] | None, fuse_baseline,
+                 le: int, re: int, groups=None, max_len: int = 0, download: bool = True):
     """The pass K.records_route runs, on a session whose pool is resident: records in, hit pass run ->
     THRESHOLD_HIT_DTYPE rows, or their count with download=False (rows left on the device).  sg: the Savitzky-Golay
     (window, order) of the fused filter, None for the raw / materialised sources.  max_len: the padded width (0 = the
-    longest uploaded record; a shard gets the run's width, hit_finder.py:354-370, not its own)."""
+    longest uploaded record; a shard gets the run's width, hit_finder.py:354-370, not its own).
+
+    groups: None, or the filter keys of a fused pass over records with several resolved filter settings
+    (filter_engine.plan_fused_groups), `masks` then holding one bool array per key: the records it applies to."""
+    if groups is not None:
+        return _grouped_pass(sess, records, thresholds, masks, groups=groups, fuse_baseline=fuse_baseline, le=le, re=re,
+                             max_len=max_len, download=download)
     sess.upload_records(records, thresholds)
     if sg is not None:
         sess.set_sg_plan(*sg)
@@ -172,6 +188,62 @@ def records_pass(sess, records: np.ndarray, thresholds, *, source: int, sg: tupl
     if fuse_baseline is not None:
         sess.baseline_mean(int(fuse_baseline[0]), int(fuse_baseline[1]), update_records=True)
     return sess.threshold_hits(source, le, re, max_len=max_len, download=download)
+
+
+def _grouped_pass(sess, records: np.ndarray, thresholds, masks, *, groups, fuse_baseline, le: int, re: int, max_len: int,
+                  download: bool):
+    """Fused pass over records whose channels resolve to several filter settings: one device pass per group, in list
+    order, over ALL uploaded records -- the uniform layout, and with it the streaming / span routes and the padded
+    shadow, stays -- with the threshold column at the record's own threshold inside the group and +inf outside
+    (sig >= +inf holds for no finite sample: no hit, on every route).  The rows of the passes are merged on the device
+    into the reference's order (record index, start) and stay resident like the rows of one pass.
+
+    A Savitzky-Golay group sets its plan and runs the fused pass (with fuse_baseline: the fused-baseline pass).  A
+    Butterworth group cannot be fused: its records are filtered into the device float32 twin first (scratch here: no
+    download, and nobody's wave_pool_filtered afterwards), its pass reads that twin; what the twin holds for other
+    records is irrelevant under +inf.  Groups without a record among `records` (a shard) are skipped; with one group
+    left the single pass runs: no threshold rewrite, no merge."""
+    n = len(records)
+    mine = [(key, np.asarray(mask, dtype=bool)) for key, mask in zip(groups, masks) if np.any(mask)]
+    if not mine:
+        mine = [(groups[0], np.ones(n, dtype=bool))]
+    if len(mine) == 1 and mine[0][0][0] == "SG":
+        return records_pass(sess, records, thresholds, source=K.SRC_SG_FUSED, sg=mine[0][0][1:], fuse_baseline=fuse_baseline,
+                            le=le, re=re, max_len=max_len, download=download)
+    butterworth = [(key, mask) for key, mask in mine if key[0] == "BW"]
+    if butterworth:  # before the table of the passes is uploaded: a records upload after it would void the padded shadow
+        sess.filter_keep_output(False)
+        try:
+            for k, (key, mask) in enumerate(butterworth):
+                sess.upload_records(records if mask.all() else records[mask])
+                if k == 1:
+                    sess.filter_keep_output(True)
+                sess.sosfiltfilt(*design_bw(*key[1:]), download=False)  # (drops the float32 residency tags itself)
+        finally:
+            sess.filter_keep_output(False)
+
+    def one_pass(key, download=False):
+        if key[0] == "SG":
+            sess.set_sg_plan(key[1], key[2])
+            if fuse_baseline is not None:
+                return sess.fused_baseline_filter_hits(tuple(fuse_baseline), le, re, max_len=max_len, download=download)
+            return sess.threshold_hits(K.SRC_SG_FUSED, le, re, max_len=max_len, download=download)
+        if fuse_baseline is not None:
+            sess.baseline_mean(int(fuse_baseline[0]), int(fuse_baseline[1]), update_records=True)
+        return sess.threshold_hits(K.SRC_F32, le, re, max_len=max_len, download=download)
+
+    if len(mine) == 1:
+        sess.upload_records(records, thresholds)
+        return one_pass(mine[0][0], download)
+    own = np.broadcast_to(np.asarray(thresholds, dtype=np.float64), (n,))
+    sess.upload_records(records, np.where(mine[0][1], own, np.inf))
+    with sess.merged_hit_rows() as merge:
+        for k, (key, mask) in enumerate(mine):
+            if k:
+                sess.set_thresholds(np.where(mask, own, np.inf))
+            one_pass(key)
+            merge.add()
+    return sess._fill_hits(merge.n_hits) if download else merge.n_hits
 
 
 def _lengths_from_records(context: Any, run_id: str, record_ids: np.ndarray, source_lengths: np.ndarray) -> np.ndarray:

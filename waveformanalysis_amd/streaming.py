@@ -320,7 +320,11 @@ class HipThresholdHitStream(HipStreamingPlugin):
     hits are instantaneous rows (time = `timestamp`).  Parallel runs (`_compute_parallel`) drive two borrowed sessions as
     a double buffer: chunk k + 1 goes through the pinned staging ring of one session while the kernels of chunk k run on
     the other.  Options are read from the Context like those of HipThresholdHitPlugin (hit_finder.py:82-130); a value
-    given to the constructor wins."""
+    given to the constructor wins.
+
+    The fused filter here is the stream's own Savitzky-Golay pair, one for every record: unlike HipThresholdHitPlugin's
+    fuse_filter route, the stream has no channel configuration and reads nothing from a wave_pool_filtered plugin (no
+    per-channel filter settings, no Butterworth groups, no merge of several passes)."""
 
     provides = "hit_threshold_stream"
     depends_on = ["records", "wave_pool"]
