@@ -1049,9 +1049,14 @@ class DevicePool:
         self._borrowable = 0                       # sessions created for borrow() and still alive
         self._thread_bound = weakref.WeakSet()     # sessions handed out by session()
 
-    def _new_session(self) -> DeviceSession:
-        dev = self.device_ids[self._next % len(self.device_ids)]
-        self._next += 1
+    def _new_session(self, among: list[int] | None = None) -> DeviceSession:
+        """A new session on the next device of the round-robin (`among`: the next of these devices)."""
+        n = len(self.device_ids)
+        for step in range(n):
+            dev = self.device_ids[(self._next + step) % n]
+            if among is None or dev in among:
+                break
+        self._next += step + 1
         return self._factory(dev)
 
     def session(self) -> DeviceSession:
@@ -1087,8 +1092,10 @@ class DevicePool:
     @contextlib.contextmanager
     def borrow_many(self, n: int):
         """`n` sessions at once, taken atomically (two callers that each hold one session and wait for a second would
-        wait for ever), on as many different devices as the pool has: free sessions are preferred by device, new ones
-        are created round-robin.  Raises when the pool can never hold that many."""
+        wait for ever), spread evenly over the devices of the pool.  Every slot goes to a device this borrower uses
+        least: a free session there is taken, a new one is created only where no free session is that good (so
+        repeated borrowers of several sessions per device reuse what is there and do not grow the pool to
+        max_sessions).  Raises when the pool can never hold that many."""
         n = int(n)
         if n < 1 or n > self.max_sessions:
             raise ValueError(f"cannot borrow {n} sessions from a pool of max_sessions={self.max_sessions}")
@@ -1098,14 +1105,15 @@ class DevicePool:
             got: list[DeviceSession] = []
             for _ in range(n):
                 used = [getattr(s, "device_id", None) for s in got]
-                # a free session on the device this borrower uses least, else a new one (round-robin over the devices)
+                fewest = min(used.count(d) for d in self.device_ids)
+                # a free session on a device this borrower uses least, else a new one on such a device
                 pick = min(self._free, key=lambda s: used.count(getattr(s, "device_id", None)), default=None)
-                if pick is not None and (used.count(getattr(pick, "device_id", None)) == 0
+                if pick is not None and (used.count(getattr(pick, "device_id", None)) <= fewest
                                          or self._borrowable >= self.max_sessions):
                     self._free.remove(pick)
                     got.append(pick)
                 elif self._borrowable < self.max_sessions:
-                    got.append(self._new_session())
+                    got.append(self._new_session([d for d in self.device_ids if used.count(d) == fewest]))
                     self._borrowable += 1
                 else:
                     self._free.remove(pick)

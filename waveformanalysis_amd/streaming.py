@@ -17,6 +17,7 @@ class sits on the restatement below.
 
 from __future__ import annotations
 
+import weakref
 from concurrent.futures import ThreadPoolExecutor
 from typing import Any
 
@@ -324,7 +325,17 @@ class HipThresholdHitStream(HipStreamingPlugin):
 
     The fused filter here is the stream's own Savitzky-Golay pair, one for every record: unlike HipThresholdHitPlugin's
     fuse_filter route, the stream has no channel configuration and reads nothing from a wave_pool_filtered plugin (no
-    per-channel filter settings, no Butterworth groups, no merge of several passes)."""
+    per-channel filter settings, no Butterworth groups, no merge of several passes).
+
+    Padded width.  The reference evaluates hit windows on a matrix padded to the longest record of the RUN
+    (hit_finder.py:364,370), and a window that reaches behind a short record's end reads that padding.  Every chunk
+    is therefore passed the run's width: the longest `event_length` of the Context's `records`, resolved once per
+    compute() / run_chunks() / compute_chunk() (`_run_width`), so that the stream gives the rows of hit_threshold
+    whatever the chunk size.  `max_len` given to the constructor wins; one below the run's longest record is refused
+    with a ValueError before anything is uploaded.  Only a Context that holds no `records` (a caller that hands
+    ready-made chunks to run_chunks / compute_chunk with nothing but a wave_pool behind them) keeps the old meaning
+    of max_len=0: run_chunks then takes the longest record of the chunks it was given, compute_chunk the chunk's
+    own."""
 
     provides = "hit_threshold_stream"
     depends_on = ["records", "wave_pool"]
@@ -351,8 +362,10 @@ class HipThresholdHitStream(HipStreamingPlugin):
         given = dict(threshold=threshold, left_extension=left_extension, right_extension=right_extension,
                      use_filtered=use_filtered, sg_window_size=sg_window_size, sg_poly_order=sg_poly_order)
         self._given = {k: v for k, v in given.items() if v is not _UNSET}
-        self.max_len = int(max_len)   # padded width of the whole run (hit_finder.py:364), 0 = per chunk
+        # padded width of the whole run (hit_finder.py:364); 0 = the longest record of the Context's `records`
+        self.max_len = int(max_len)
         self.device_pool = device_pool
+        self._width_of = None         # (weak reference to a records array, its longest record): _run_width's last run
         self._configure(None)
 
     def _configure(self, context: Any) -> None:
@@ -370,6 +383,30 @@ class HipThresholdHitStream(HipStreamingPlugin):
         self.le, self.re = max(0, int(value("left_extension"))), max(0, int(value("right_extension")))
         self.use_filtered = bool(value("use_filtered"))
         self.sg = normalize_window(value("sg_window_size"), value("sg_poly_order"))
+
+    def _run_width(self, context: Any, run_id: str, chunks: list | None = None) -> int:
+        """The padded width every chunk of this run is evaluated at: the constructor's max_len, else the longest
+        record of the Context's `records`.  A constructor value below the run's longest record is refused here, on
+        the host (wfa_hits_enqueue would refuse it for the first chunk that holds a longer record, after the uploads
+        of the chunks before it).  Without `records` in the Context: the longest record of `chunks` when the caller
+        has the whole list, else 0 = the chunk's own longest record (see the class docstring)."""
+        records = context.get_data(run_id, "records") if hasattr(context, "get_data") else None
+        if isinstance(records, np.ndarray) and records.dtype.names and "event_length" in records.dtype.names:
+            seen = self._width_of     # (one read: worker threads share the plugin)
+            if seen is None or seen[0]() is not records:
+                seen = (weakref.ref(records), int(records["event_length"].max()) if len(records) else 0)
+                self._width_of = seen
+            longest = seen[1]
+        elif chunks is not None:
+            longest = max((int(c.data["event_length"].max()) for c in chunks if len(c.data)), default=0)
+        else:
+            longest = 0
+        if self.max_len > 0:
+            if self.max_len < longest:
+                raise ValueError(f"hit_threshold_stream: max_len ({self.max_len}) is below the longest record of the "
+                                 f"run ({longest})")
+            return self.max_len
+        return longest
 
     def _endtime_of(self, data: np.ndarray, time_field: str) -> np.ndarray:
         # records: timestamp in ps, dt in ns per sample -> the end of a record in ps
@@ -399,11 +436,12 @@ class HipThresholdHitStream(HipStreamingPlugin):
         return Chunk(np.zeros(0, dtype=THRESHOLD_HIT_DTYPE), chunk.start, chunk.end, run_id, self.provides,
                      data_kind="hits", time_field="timestamp")
 
-    def _stage(self, sess, chunk: Chunk, wave_pool: np.ndarray) -> None:
-        """Upload the chunk's samples + records and queue its hit pass on `sess` (returns without waiting for the kernels
-        once the session has sized its row buffers: wfa_hits_enqueue)."""
+    def _stage(self, sess, chunk: Chunk, wave_pool: np.ndarray, max_len: int) -> None:
+        """Upload the chunk's samples + records and queue its hit pass on `sess` at the run's padded width `max_len`
+        (returns without waiting for the kernels once the session has sized its row buffers: wfa_hits_enqueue)."""
         recs = chunk.data
-        # the chunk's samples are one contiguous slice of the pool for time-sorted records
+        # the slice of the pool from the chunk's first sample to its last: exactly its records for time-sorted records
+        # packed back to back, with other chunks' samples and gaps in between for any other packing
         lo = int(recs["wave_offset"].min())
         hi = int((recs["wave_offset"].astype(np.int64) + recs["event_length"]).max())
         sub = recs.copy()
@@ -412,7 +450,7 @@ class HipThresholdHitStream(HipStreamingPlugin):
         sess.upload_records(sub, self.threshold)
         if self.use_filtered:
             sess.set_sg_plan(*self.sg)
-        sess.hits_enqueue(_lib.SRC_SG_FUSED if self.use_filtered else _lib.SRC_RAW, (0, 0), self.le, self.re, self.max_len)
+        sess.hits_enqueue(_lib.SRC_SG_FUSED if self.use_filtered else _lib.SRC_RAW, (0, 0), self.le, self.re, int(max_len))
 
     def _collect(self, sess, chunk: Chunk, run_id: str) -> Chunk:
         hits = sess._fill_hits(sess.hits_wait())
@@ -423,13 +461,19 @@ class HipThresholdHitStream(HipStreamingPlugin):
                      metadata=dict(chunk.metadata))
 
     def compute_chunk(self, chunk: Chunk, context: Any, run_id: str, **_kw) -> Chunk:
+        return self._compute_one(chunk, context, run_id, None)
+
+    def _compute_one(self, chunk: Chunk, context: Any, run_id: str, max_len: int | None) -> Chunk:
+        """compute_chunk at a padded width the caller has resolved (None: resolve it here)."""
         if len(chunk.data) == 0:
             return self._empty(chunk, run_id)
         self._configure(context)
+        if max_len is None:
+            max_len = self._run_width(context, run_id)
         wave_pool = context.get_data(run_id, "wave_pool")
         # worker threads come and go with every compute(): the session is borrowed for this chunk only
         with self._pool(context).borrow() as sess:
-            self._stage(sess, chunk, wave_pool)
+            self._stage(sess, chunk, wave_pool, max_len)
             return self._collect(sess, chunk, run_id)
 
     def _pipeline(self, input_chunks, context: Any, run_id: str, timeline: list | None = None,
@@ -444,6 +488,7 @@ class HipThresholdHitStream(HipStreamingPlugin):
         from collections import deque
 
         self._configure(context)
+        max_len = self._run_width(context, run_id, input_chunks if isinstance(input_chunks, (list, tuple)) else None)
         wave_pool = context.get_data(run_id, "wave_pool")
         pool = self._pool(context)
         n = max(2, 2 * len(pool.device_ids))
@@ -472,7 +517,7 @@ class HipThresholdHitStream(HipStreamingPlugin):
                 sess = ring[staged % n]  # free: results are collected in order, at most n - 1 are pending here
                 staged += 1
                 t0 = time.perf_counter()
-                self._stage(sess, chunk, wave_pool)
+                self._stage(sess, chunk, wave_pool, max_len)
                 t1 = time.perf_counter()
                 pending.append((k, chunk, sess, (t0, t1)))
                 while len(pending) > n - 1:
@@ -493,7 +538,8 @@ class HipThresholdHitStream(HipStreamingPlugin):
                    timeline: list | None = None) -> list[Chunk]:
         """The raw results of `chunks`, in order (the bench and the parity tests call this with ready-made chunks)."""
         if not self.parallel or max_workers <= 1 or len(chunks) <= 1:
-            return [self.compute_chunk(c, context, run_id) for c in chunks]
+            max_len = self._run_width(context, run_id, list(chunks))
+            return [self._compute_one(c, context, run_id, max_len) for c in chunks]
         return [raw for _chunk, raw in self._pipeline(chunks, context, run_id, timeline, max_workers=max_workers)]
 
 
