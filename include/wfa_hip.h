@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define WFA_ABI_VERSION 3
+#define WFA_ABI_VERSION 4
 
 #define WFA_OK 0
 #define WFA_E_INVALID (-1)   /* bad argument / malformed records (maps to ValueError) */
@@ -46,6 +46,8 @@ extern "C" {
 #define WFA_MAX_SG_WINDOW 63
 /* wfa_sosfiltfilt: second-order sections per filter (a Butterworth band-pass of order N has N sections) */
 #define WFA_MAX_SOS_SECTIONS 32
+/* wfa_hits_enqueue_groups: filter groups of one grouped hit pass, and resident plan slots (wfa_sg_plan_store) */
+#define WFA_MAX_HIT_GROUPS 8
 
 /* wave source of a consumer (reference: cpu/_wave_source.py:119-165, records branch) */
 #define WFA_SRC_RAW 0        /* wave_pool (uint16)                                        */
@@ -267,6 +269,52 @@ int wfa_set_thresholds(wfa_ctx* ctx, const double* threshold, int64_t n_records)
 int wfa_hit_rows_merge_begin(wfa_ctx* ctx);
 int wfa_hit_rows_merge_add(wfa_ctx* ctx);
 int wfa_hit_rows_merge_end(wfa_ctx* ctx, int64_t* n_hits);
+
+/* The same table from ONE queued call (streaming callers: nobody waits for chunk k before chunk k + 1 is queued).
+ *
+ * wfa_sg_plan_store keeps a Savitzky-Golay plan in slot `slot` (0 <= slot < WFA_MAX_HIT_GROUPS), arguments as for
+ * wfa_set_sg_plan.  A slot's tables stay on the device across pool and records uploads; wfa_set_sg_plan and the plan it
+ * sets are untouched.
+ *
+ * wfa_sosfiltfilt_group is wfa_sosfiltfilt restricted to the records r with group_of_record[r] == group (one int32 per
+ * uploaded record), over the uploaded table: no second records upload, so the padded shadow and the layout record stand.
+ * It writes those records' slices of the float32 twin and nothing else (a twin that did not exist is zeroed first),
+ * downloads nothing and does not wait for the device.
+ *
+ * wfa_hits_enqueue_groups runs, on the context's stream, what this synchronous sequence gives:
+ *     wfa_hit_rows_merge_begin; per group g in order { threshold column = the record's own value where
+ *     group_of_record[r] == g, +inf elsewhere; the plan of groups[g].plan_slot; one hit pass from groups[g].source
+ *     (WFA_SRC_SG_FUSED or WFA_SRC_F32) with the uploaded baselines; wfa_hit_rows_merge_add }; wfa_hit_rows_merge_end
+ * -- the byte-identical table, in (record index, start) order.  group_of_record[r] = -1: no pass owns record r, it gives
+ * no rows.  The masked column of a group is written by a kernel from group_of_record, the plan is chosen by slot, the
+ * rows of a pass go to the stash under a row count read on the device (launches sized for the pass's bound), the stash
+ * offsets are written on the device and the merge kernels take their totals from there.  Where every group's pass takes
+ * the speculative row launch (a warm context: each group's previous row count is kept, per group index; uniform records
+ * on the streaming or bitmap route) the call returns with nothing waited for and wfa_hits_wait delivers the merged
+ * count; if a group found more rows than its bound, or a span's events overflowed, wfa_hits_wait redoes the grouped pass
+ * the exact way.  A group whose pass cannot speculate (the general route on ragged records, a context's first grouped
+ * pass, no_speculate) runs to completion inside the call, as in wfa_hits_enqueue.  Afterwards the merged table is "the
+ * rows of the last hit pass" exactly as after wfa_hit_rows_merge_end, and the uploaded threshold column reads as the
+ * caller uploaded it.  n_groups == 1 without a -1 runs the single pass: no mask kernel, no stash, no merge.
+ * The stash is the scratch of wfa_hit_rows_merge_* (same cost per row).
+ * WFA_E_INVALID: n_groups outside [1, WFA_MAX_HIT_GROUPS], a source other than the two above, a plan slot or a
+ * group_of_record value out of range, max_len below the longest uploaded record (0 = that record).  WFA_E_STATE: no
+ * records or no wave_pool uploaded, a slot without a stored plan, a WFA_SRC_F32 group without a resident float32 pool
+ * (wfa_sosfiltfilt_group / wfa_upload_pool_f32 first).
+ *
+ * wfa_hits_pending: *pending = 1 from a queued pass (wfa_hits_enqueue / _groups) until wfa_hits_wait or
+ * wfa_threshold_hits_fill has consumed it, else 0.  Reads state only. */
+typedef struct wfa_hit_group {
+    int32_t source;    /* WFA_SRC_SG_FUSED or WFA_SRC_F32 */
+    int32_t plan_slot; /* WFA_SRC_SG_FUSED: the slot of wfa_sg_plan_store; ignored for WFA_SRC_F32 */
+} wfa_hit_group;
+int wfa_sg_plan_store(wfa_ctx* ctx, int slot, int window, int polyorder, const double* tab, const uint8_t* symmetric,
+                      int int_ok, const int32_t* itab, int32_t den, int32_t den_edge, int64_t guard, int64_t guard_edge);
+int wfa_sosfiltfilt_group(wfa_ctx* ctx, int n_sections, const double* sos, const double* zi, int32_t padlen,
+                          const int32_t* group_of_record, int32_t group);
+int wfa_hits_enqueue_groups(wfa_ctx* ctx, int n_groups, const wfa_hit_group* groups, const int32_t* group_of_record,
+                            int32_t left_extension, int32_t right_extension, int32_t max_len);
+int wfa_hits_pending(wfa_ctx* ctx, int* pending);
 
 /* K8 find_peaks-based hit detector, records source (reference: cpu/peak_finding.py:395-614 calling
  * scipy.signal.find_peaks(det, height, distance, prominence, width, threshold) with scalar lower bounds, then

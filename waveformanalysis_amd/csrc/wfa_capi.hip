@@ -622,6 +622,10 @@ static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int
 
 using namespace wfa;
 
+// wfa_hits_enqueue_groups (below): PendingPass::source of a queued grouped pass, and what wfa_hits_wait does for it
+constexpr int kSrcGroups = -2;
+static int groups_wait(wfa_ctx* c, int64_t* n_hits);
+
 // ---- records as packed rows, unpacked on the device --------------------------------------------------------------------
 // (reference row layout: processing/dtypes.py:80-100, 102 bytes, numpy packs without alignment.)  The column route above
 // makes the caller extract ten columns on the host -- for 1.25e6 records that is 0.6 s of numpy, 0.47 s of it comparing
@@ -812,6 +816,7 @@ void wfa_ctx_destroy(wfa_ctx* c) {
     if (c->comm) (void)wfa_rccl_destroy(c);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->h_total) (void)hipHostFree(c->h_total);
+    if (c->h_grp) (void)hipHostFree(c->h_grp);
     for (int b = 0; b < 2; ++b) {
         if (c->stage[b]) (void)hipHostFree(c->stage[b]);
         if (c->stage_ev[b]) (void)hipEventDestroy(c->stage_ev[b]);
@@ -1150,11 +1155,11 @@ int wfa_upload_records_packed(wfa_ctx* c, const void* rows, int64_t R, int32_t r
     return WFA_OK;
 }
 
-int wfa_set_sg_plan(wfa_ctx* c, int window, int polyorder, const double* tab, const uint8_t* symmetric,
-                    int int_ok, const int32_t* itab, int32_t den, int32_t den_edge, int64_t guard,
-                    int64_t guard_edge) {
-    int rc = use_device(c);
-    if (rc) return rc;
+// validate a Savitzky-Golay plan and upload its tables into `s` (the context's plan, or a resident slot)
+static int sg_plan_upload(wfa_ctx* c, SgPlanDev& s, int window, int polyorder, const double* tab, const uint8_t* symmetric,
+                          int int_ok, const int32_t* itab, int32_t den, int32_t den_edge, int64_t guard,
+                          int64_t guard_edge) {
+    int rc;
     if (window < 1 || (window & 1) == 0 || window > WFA_MAX_SG_WINDOW)
         return fail(WFA_E_INVALID, "Savitzky-Golay window must be odd and in [1, %d], got %d",
                     WFA_MAX_SG_WINDOW, window);
@@ -1162,7 +1167,6 @@ int wfa_set_sg_plan(wfa_ctx* c, int window, int polyorder, const double* tab, co
         return fail(WFA_E_INVALID, "polyorder %d must be in [0, window)", polyorder);
     if (!tab || !symmetric) return fail(WFA_E_INVALID, "null plan table");
     if (int_ok && (!itab || den <= 0 || den_edge <= 0)) return fail(WFA_E_INVALID, "bad integer plan");
-    SgPlanDev& s = c->sg;
     s.W = window; s.P = polyorder; s.H = window / 2;
     s.n_tables = (window + 1) / 2;
     s.stride = window + 2 * s.H * window;
@@ -1181,7 +1185,36 @@ int wfa_set_sg_plan(wfa_ctx* c, int window, int polyorder, const double* tab, co
         if ((rc = s.itab.ensure(isz))) return rc;
     }
     WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return WFA_OK;
+}
+
+int wfa_set_sg_plan(wfa_ctx* c, int window, int polyorder, const double* tab, const uint8_t* symmetric,
+                    int int_ok, const int32_t* itab, int32_t den, int32_t den_edge, int64_t guard,
+                    int64_t guard_edge) {
+    int rc = use_device(c);
+    if (rc) return rc;
+    if ((rc = sg_plan_upload(c, c->sg, window, polyorder, tab, symmetric, int_ok, itab, den, den_edge, guard, guard_edge)))
+        return rc;
     c->have_sg = true;
+    return WFA_OK;
+}
+
+int wfa_sg_plan_store(wfa_ctx* c, int slot, int window, int polyorder, const double* tab, const uint8_t* symmetric,
+                      int int_ok, const int32_t* itab, int32_t den, int32_t den_edge, int64_t guard,
+                      int64_t guard_edge) {
+    int rc = use_device(c);
+    if (rc) return rc;
+    if (slot < 0 || slot >= WFA_MAX_HIT_GROUPS)
+        return fail(WFA_E_INVALID, "plan slot must be in [0, %d), got %d", WFA_MAX_HIT_GROUPS, slot);
+    if (c->pending) {  // a queued pass may read the slot's tables
+        int64_t n = 0;
+        if ((rc = wfa_hits_wait(c, &n))) return rc;
+    }
+    c->have_slot[slot] = false;
+    if ((rc = sg_plan_upload(c, c->sg_slot[slot], window, polyorder, tab, symmetric, int_ok, itab, den, den_edge, guard,
+                             guard_edge)))
+        return rc;
+    c->have_slot[slot] = true;
     return WFA_OK;
 }
 
@@ -1337,6 +1370,7 @@ int wfa_hits_wait(wfa_ctx* c, int64_t* n_hits) {
     int rc = use_device(c);
     if (rc) return rc;
     if (!n_hits) return fail(WFA_E_INVALID, "n_hits is null");
+    if (c->pending && c->pend.source == kSrcGroups) return groups_wait(c, n_hits);  // a queued grouped pass (wfa_hits_enqueue_groups)
     if (c->pending) {
         WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
         c->pending = false;
@@ -1440,8 +1474,10 @@ __global__ __launch_bounds__(kMergeBlock) void k_hit_rows_merge_index(int64_t n,
 // per-record row count over all passes: the first row of a record inside a pass adds that pass's rows of the record
 __global__ __launch_bounds__(kMergeBlock) void k_hit_rows_merge_count(int64_t n, const int32_t* __restrict__ rec,
                                                                       const int64_t* __restrict__ sets, int G, int64_t R,
-                                                                      int32_t* __restrict__ counts) {
+                                                                      int32_t* __restrict__ counts,
+                                                                      const int64_t* __restrict__ n_dev) {
     const int64_t i = (int64_t)blockIdx.x * kMergeBlock + threadIdx.x;
+    if (n_dev && *n_dev < n) n = *n_dev;  // launched for a bound: the total stands on the device
     if (i >= n) return;
     const int g = merge_set_of(sets, G, i);
     const int32_t r = rec[i];
@@ -1455,8 +1491,10 @@ __global__ __launch_bounds__(kMergeBlock) void k_hit_rows_merge_count(int64_t n,
 __global__ __launch_bounds__(kMergeBlock) void k_hit_rows_merge_place(int64_t n, const int32_t* __restrict__ rec,
                                                                       const int64_t* __restrict__ sets, int G, int64_t R,
                                                                       const int64_t* __restrict__ out_start,
-                                                                      int64_t* __restrict__ dest) {
+                                                                      int64_t* __restrict__ dest,
+                                                                      const int64_t* __restrict__ n_dev) {
     const int64_t i = (int64_t)blockIdx.x * kMergeBlock + threadIdx.x;
+    if (n_dev && *n_dev < n) n = *n_dev;
     if (i >= n) return;
     const int g = merge_set_of(sets, G, i);
     const int32_t r = rec[i];
@@ -1472,8 +1510,10 @@ __global__ __launch_bounds__(kMergeBlock) void k_hit_rows_merge_place(int64_t n,
 // 60-byte rows as 15 dwords: consecutive lanes read consecutive dwords of the stash and write runs of 15 into the table
 __global__ __launch_bounds__(kMergeBlock) void k_hit_rows_merge_scatter(int64_t n, const uint32_t* __restrict__ src,
                                                                         const int64_t* __restrict__ dest,
-                                                                        uint32_t* __restrict__ out) {
+                                                                        uint32_t* __restrict__ out,
+                                                                        const int64_t* __restrict__ n_dev) {
     const int64_t d = (int64_t)blockIdx.x * kMergeBlock + threadIdx.x;
+    if (n_dev && *n_dev < n) n = *n_dev;
     if (d >= n * 15) return;
     const int64_t i = d / 15;
     const int64_t to = dest[i];
@@ -1579,7 +1619,7 @@ int wfa_hit_rows_merge_end(wfa_ctx* c, int64_t* n_hits) {
         {
             LaunchTimer t(c);
             hipLaunchKernelGGL(k_hit_rows_merge_count, dim3(merge_grid(total)), dim3(kMergeBlock), 0, c->stream, total, rec,
-                               sets, G, R, counts);
+                               sets, G, R, counts, (const int64_t*)nullptr);
             WFA_HIP_CHECK(hipGetLastError());
             if ((rc = t.end("k_hit_rows_merge_count"))) return rc;
         }
@@ -1591,14 +1631,15 @@ int wfa_hit_rows_merge_end(wfa_ctx* c, int64_t* n_hits) {
         {
             LaunchTimer t(c);
             hipLaunchKernelGGL(k_hit_rows_merge_place, dim3(merge_grid(total)), dim3(kMergeBlock), 0, c->stream, total, rec,
-                               sets, G, R, c->rec_out_start.as<int64_t>(), c->merge_dest.as<int64_t>());
+                               sets, G, R, c->rec_out_start.as<int64_t>(), c->merge_dest.as<int64_t>(), (const int64_t*)nullptr);
             WFA_HIP_CHECK(hipGetLastError());
             if ((rc = t.end("k_hit_rows_merge_place"))) return rc;
         }
         {
             LaunchTimer t(c);
             hipLaunchKernelGGL(k_hit_rows_merge_scatter, dim3(merge_grid(total * 15)), dim3(kMergeBlock), 0, c->stream, total,
-                               c->merge_rows.as<uint32_t>(), c->merge_dest.as<int64_t>(), c->hit_out.as<uint32_t>());
+                               c->merge_rows.as<uint32_t>(), c->merge_dest.as<int64_t>(), c->hit_out.as<uint32_t>(),
+                               (const int64_t*)nullptr);
             WFA_HIP_CHECK(hipGetLastError());
             if ((rc = t.end("k_hit_rows_merge_scatter"))) return rc;
         }
@@ -1610,6 +1651,408 @@ int wfa_hit_rows_merge_end(wfa_ctx* c, int64_t* n_hits) {
     c->last_hits = total;
     c->rows_index = 0;
     *n_hits = total;
+    return WFA_OK;
+}
+
+}  // extern "C"
+
+// ---- the grouped pass, queued (wfa_hits_enqueue_groups) ------------------------------------------------------------
+// What the synchronous sequence above does with four host waits per group, on the context's stream: per group a kernel
+// writes the own-or-+inf threshold column from group_of_record, the group's plan is swapped in from its resident slot,
+// the existing pass is queued (run_hits, enqueue_only), one thread takes the pass's row count where the pass reported it
+// (the pinned words of a queued pass, or the count the host already holds) and writes the group's stash offset, and a copy
+// kernel launched for the pass's row bound moves that many rows and record indices to the stash.  The merge kernels are
+// launched for the sum of the bounds and read the total from the last stash offset.  The caller's threshold column is
+// saved before the first group and copied back behind the last.
+//
+// Pinned block (int64 words): per group (rows, overflow flags) of its pass, the stash offsets as the device wrote them
+// ([n_groups] = the merged row count), the fail flag (a group outgrew its bound, its events or the stash).
+constexpr int kGrpSets = 2 * WFA_MAX_HIT_GROUPS;
+constexpr int kGrpFail = kGrpSets + WFA_MAX_HIT_GROUPS + 1;
+constexpr int kGrpWords = 32;
+constexpr int kGrpFailDev = WFA_MAX_HIT_GROUPS + 1;  // grp_sets: [0, WFA_MAX_HIT_GROUPS] stash offsets, then the fail flag
+static_assert(kGrpFail < kGrpWords, "pinned block of the grouped pass");
+
+__global__ __launch_bounds__(kMergeBlock) void k_grp_mask(int64_t R, const int32_t* __restrict__ group_of_record, int32_t g,
+                                                          const double* __restrict__ own, double* __restrict__ thr) {
+    const int64_t r = (int64_t)blockIdx.x * kMergeBlock + threadIdx.x;
+    if (r >= R) return;
+    thr[r] = group_of_record[r] == g ? own[r] : __longlong_as_double(0x7ff0000000000000ll);  // +inf: no hit on any route
+}
+
+// One thread, behind group g's pass: its row count (n_host >= 0: the host read it; otherwise the words the queued pass
+// reported to pinned memory), whether its speculative launch stands, and the stash offset of the next group.
+__global__ void k_grp_take(int g, int64_t n_host, int runs32, int64_t bound, int64_t cap_rows,
+                           const volatile int64_t* pass_report, int64_t* sets, volatile int64_t* h) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    int64_t n = n_host, flags = 0;
+    if (n_host < 0) {
+        n = pass_report[0];
+        if (runs32) flags = pass_report[2] & 0xffffffffll;
+    }
+    bool ok = n_host >= 0 || (n >= 0 && n <= bound && flags == 0);
+    if (g == 0) { sets[0] = 0; sets[kGrpFailDev] = 0; }
+    const int64_t at = g == 0 ? 0 : sets[g];
+    int64_t take = ok ? n : 0;
+    if (at + take > cap_rows) { take = 0; ok = false; }
+    if (!ok) sets[kGrpFailDev] = 1;
+    sets[g + 1] = at + take;
+    h[2 * g] = n;
+    h[2 * g + 1] = flags;
+    h[kGrpSets + g + 1] = at + take;
+    h[kGrpFail] = sets[kGrpFailDev];
+}
+
+// Rows of group g's pass into the stash, 15 dwords per row, and the record index of every row (k_hit_rows_merge_index's
+// two sources).  Launched for the pass's row bound; the count stands in sets[].
+__global__ __launch_bounds__(kMergeBlock) void k_grp_stash(int g, const int64_t* __restrict__ sets,
+                                                           const uint32_t* __restrict__ rows, const int4* __restrict__ desc,
+                                                           const int64_t* __restrict__ out_start, int64_t R,
+                                                           uint32_t* __restrict__ stash_rows, int32_t* __restrict__ stash_rec) {
+    const int64_t at = sets[g], n = sets[g + 1] - at;
+    const int64_t d = (int64_t)blockIdx.x * kMergeBlock + threadIdx.x;
+    if (d >= n * 15) return;
+    stash_rows[at * 15 + d] = rows[d];
+    if (d >= n) return;
+    if (desc) { stash_rec[at + d] = desc[d].x; return; }
+    int64_t lo = 0, hi = R;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (out_start[mid] <= d) lo = mid + 1; else hi = mid;
+    }
+    stash_rec[at + d] = (int32_t)(lo - 1);
+}
+
+static void sg_plan_swap(SgPlanDev& a, SgPlanDev& b) {
+    std::swap(a.W, b.W); std::swap(a.P, b.P); std::swap(a.H, b.H);
+    std::swap(a.n_tables, b.n_tables); std::swap(a.stride, b.stride); std::swap(a.int_ok, b.int_ok);
+    std::swap(a.den, b.den); std::swap(a.den_edge, b.den_edge);
+    std::swap(a.guard, b.guard); std::swap(a.guard_edge, b.guard_edge);
+    std::swap(a.rden, b.rden); std::swap(a.rden_edge, b.rden_edge);
+    for (DevBuf SgPlanDev::*m : {&SgPlanDev::tab, &SgPlanDev::itab, &SgPlanDev::sym}) {
+        std::swap((a.*m).ptr, (b.*m).ptr);
+        std::swap((a.*m).cap, (b.*m).cap);
+    }
+    a.sym_host.swap(b.sym_host);
+}
+
+static int groups_pinned(wfa_ctx* c) {
+    if (c->h_grp) return WFA_OK;
+    const size_t bytes = kGrpWords * sizeof(int64_t) + WFA_MAX_HIT_GROUPS * sizeof(RunsCold);
+    WFA_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&c->h_grp), bytes, hipHostMallocDefault));
+    memset(c->h_grp, 0, bytes);
+    c->h_grp_cold = reinterpret_cast<RunsCold*>(c->h_grp + kGrpWords);
+    return WFA_OK;
+}
+
+// The streaming route keeps what its float64 paths read (pool view + plan) in a device block and refreshes it, with a
+// host wait, when it changes (run_hits_runs32).  Under a grouped pass it changes with every group: here group g's block
+// is queued from the group's own pinned copy, which is rewritten only when the plan's or the pool's buffers moved, so the
+// pass that follows finds its block current and waits for nothing.  Where the pass will not take that route, or its control
+// block does not exist yet, nothing is done and the pass looks after itself.
+static int groups_prime_cold(wfa_ctx* c, int g) {
+    if (c->no_runs32 || c->opt.no_runs32 || c->opt.no_fast) return WFA_OK;
+    const SgParams sp0 = sg_params(c);
+    if (!sg_mask_supported(sp0)) return WFA_OK;
+    const UniformLayout& u = c->layout;
+    const bool in_place = u.span && u.L % 32 == 0;
+    const bool padded = !in_place && u.pad && u.S % 32 == 0 && !c->opt.no_pad;
+    if (!in_place && !padded) return WFA_OK;
+    if (!sg_runs32_supported(sp0, u.L, padded ? u.S : u.L, 0, 0, false)) return WFA_OK;
+    if (c->run_ctrl.cap < 256 + sizeof(RunsCold)) return WFA_OK;
+    int rc;
+    LayoutView v;
+    if ((rc = layout_view(c, padded, &v))) return rc;
+    RunsCold cold{v.pool, sp0};
+    if (c->run_cold_valid && memcmp(&cold, &c->run_cold_host, sizeof(cold)) == 0) return WFA_OK;
+    RunsCold* mine = c->h_grp_cold + g;
+    if (memcmp(mine, &cold, sizeof(cold)) != 0) {
+        WFA_HIP_CHECK(hipStreamSynchronize(c->stream));  // an earlier copy from this block may be in flight
+        memcpy(mine, &cold, sizeof(cold));
+    }
+    WFA_HIP_CHECK(hipMemcpyAsync(c->run_ctrl.as<unsigned long long>() + 32, mine, sizeof(cold), hipMemcpyHostToDevice,
+                                 c->stream));
+    c->run_cold_host = cold;
+    c->run_cold_valid = true;
+    return WFA_OK;
+}
+
+// One pass of the grouped call under group g's plan (SG groups) on the threshold column as it stands.
+static int groups_one_pass(wfa_ctx* c, int g, bool exact) {
+    wfa_ctx::GroupsPass& G = c->grp;
+    const bool sg = G.groups[g].source == WFA_SRC_SG_FUSED;
+    const bool had_sg = c->have_sg;
+    int rc = WFA_OK;
+    if (sg) {
+        sg_plan_swap(c->sg, c->sg_slot[G.groups[g].plan_slot]);
+        c->have_sg = true;
+        rc = groups_prime_cold(c, g);
+    }
+    c->last_hits = exact ? -1 : G.last[g];
+    if (!rc) rc = run_hits(c, G.groups[g].source, false, 0, 0, G.le, G.re, G.max_len, nullptr, true);
+    if (sg) {
+        sg_plan_swap(c->sg, c->sg_slot[G.groups[g].plan_slot]);
+        c->have_sg = had_sg;
+    }
+    return rc;
+}
+
+// exact: every pass with the host round trip for its count (the redo of wfa_hits_wait; nothing stays pending)
+static int groups_run(wfa_ctx* c, bool exact) {
+    wfa_ctx::GroupsPass& G = c->grp;
+    const int n = G.n_groups;
+    const int64_t R = c->R;
+    int rc;
+    const bool old_nospec = c->opt.no_speculate;
+    if (exact) c->opt.no_speculate = true;
+    c->pending = false;
+    if (G.single) {
+        rc = groups_one_pass(c, 0, exact);
+        c->opt.no_speculate = old_nospec;
+        if (rc) return rc;
+        if (c->pending) c->pend.source = kSrcGroups;
+        else G.last[0] = c->n_hits;
+        return WFA_OK;
+    }
+    auto planned = [&](int g) { return !exact && G.last[g] >= 0 ? rows_bound(G.last[g]) : (int64_t)0; };
+    int64_t plan_rows = 0;
+    for (int g = 0; g < n; ++g) plan_rows += planned(g);
+    if ((rc = c->merge_rows.ensure((size_t)plan_rows * 60)) || (rc = c->merge_rec.ensure((size_t)plan_rows * sizeof(int32_t))) ||
+        (rc = c->grp_thr.ensure((size_t)R * sizeof(double))) || (rc = c->grp_sets.ensure(16 * sizeof(int64_t)))) {
+        c->opt.no_speculate = old_nospec;
+        return rc;
+    }
+    int64_t* sets = c->grp_sets.as<int64_t>();
+    WFA_HIP_CHECK(hipMemcpyAsync(c->grp_thr.ptr, c->thr.ptr, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    // whatever happens below, the caller's column goes back behind the queued work and the options stand as they were
+    auto leave = [&](int code) {
+        (void)hipMemcpyAsync(c->thr.ptr, c->grp_thr.ptr, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
+        c->opt.no_speculate = old_nospec;
+        return code;
+    };
+    int64_t n_bound = 0;  // rows the merge kernels are launched for
+    bool queued = false;
+    for (int g = 0; g < n; ++g) {
+        {
+            LaunchTimer t(c);
+            hipLaunchKernelGGL(k_grp_mask, dim3(merge_grid(R)), dim3(kMergeBlock), 0, c->stream, R, c->grp_gor.as<int32_t>(),
+                               (int32_t)g, c->grp_thr.as<double>(), c->thr.as<double>());
+            if (hipGetLastError() != hipSuccess) return leave(fail(WFA_E_HIP, "k_grp_mask launch failed"));
+            if ((rc = t.end("k_grp_mask"))) return leave(rc);
+        }
+        if ((rc = groups_one_pass(c, g, exact))) return leave(rc);
+        int64_t launch_rows;
+        if (c->pending) {  // queued: its count is on its way to the pinned words of the single pass
+            c->pending = false;
+            queued = true;
+            G.bound[g] = c->pend.bound;
+            G.runs32[g] = c->pend.runs32;
+            G.n_host[g] = -1;
+            launch_rows = G.bound[g];
+        } else {  // ran to completion, the stream is idle: every earlier stash offset has reached the pinned block
+            G.n_host[g] = G.last[g] = c->n_hits;
+            G.bound[g] = c->n_hits;
+            G.runs32[g] = false;
+            launch_rows = c->n_hits;
+            const int64_t at = g == 0 ? 0 : c->h_grp[kGrpSets + g];
+            int64_t later = 0;
+            for (int e = g + 1; e < n; ++e) later += planned(e);
+            const int64_t want = at + launch_rows + later;
+            if ((rc = merge_grow(c, c->merge_rows, (size_t)at * 60, (size_t)want * 60)) ||
+                (rc = merge_grow(c, c->merge_rec, (size_t)at * sizeof(int32_t), (size_t)want * sizeof(int32_t))))
+                return leave(rc);
+        }
+        const int64_t cap_rows = (int64_t)std::min(c->merge_rows.cap / 60, c->merge_rec.cap / sizeof(int32_t));
+        LaunchTimer t(c);
+        hipLaunchKernelGGL(k_grp_take, dim3(1), dim3(64), 0, c->stream, g, G.n_host[g], G.runs32[g] ? 1 : 0, G.bound[g], cap_rows,
+                           (const volatile int64_t*)c->h_total, sets, (volatile int64_t*)c->h_grp);
+        if (launch_rows > 0 && c->rows_index != 0)
+            hipLaunchKernelGGL(k_grp_stash, dim3(merge_grid(launch_rows * 15)), dim3(kMergeBlock), 0, c->stream, g, sets,
+                               c->hit_out.as<uint32_t>(), c->rows_index == 1 ? c->hit_desc.as<int4>() : nullptr,
+                               c->rec_out_start.as<int64_t>(), R, c->merge_rows.as<uint32_t>(), c->merge_rec.as<int32_t>());
+        if (hipGetLastError() != hipSuccess) return leave(fail(WFA_E_HIP, "k_grp_stash launch failed"));
+        if ((rc = t.end("k_grp_take + k_grp_stash"))) return leave(rc);
+        n_bound += launch_rows;
+    }
+    c->rows_index = 0;
+    c->n_hits = -1;
+    if (n_bound > 0) {
+        const int64_t nb = scan_blocks_for(R);
+        const int64_t room = rows_bound(n_bound);  // head room: the next call's bounds fit without a reallocation
+        if (c->hit_out.cap < (size_t)n_bound * 60 || c->hit_desc.cap < (size_t)n_bound * sizeof(int4) ||
+            c->merge_dest.cap < (size_t)n_bound * sizeof(int64_t)) {
+            if (hipStreamSynchronize(c->stream) != hipSuccess)  // the stash kernels read the buffers that are about to move
+                return leave(fail(WFA_E_HIP, "waiting for the stash of the grouped pass failed"));
+            if ((rc = c->hit_out.ensure((size_t)room * 60)) || (rc = c->hit_desc.ensure((size_t)room * sizeof(int4))) ||
+                (rc = c->merge_dest.ensure((size_t)room * sizeof(int64_t))))
+                return leave(rc);
+        }
+        if ((rc = c->rec_nhits.ensure((size_t)R * sizeof(int32_t))) || (rc = c->rec_out_start.ensure((size_t)R * sizeof(int64_t))) ||
+            (rc = c->scan_blocks.ensure((size_t)(nb + 1) * sizeof(int64_t))))
+            return leave(rc);
+        const int32_t* rec = c->merge_rec.as<int32_t>();
+        int32_t* counts = c->rec_nhits.as<int32_t>();
+        const int64_t* total = sets + n;
+        if (hipMemsetAsync(counts, 0, (size_t)R * sizeof(int32_t), c->stream) != hipSuccess)
+            return leave(fail(WFA_E_HIP, "clearing the merge counts failed"));
+        LaunchTimer t(c);
+        hipLaunchKernelGGL(k_hit_rows_merge_count, dim3(merge_grid(n_bound)), dim3(kMergeBlock), 0, c->stream, n_bound, rec,
+                           (const int64_t*)sets, n, R, counts, total);
+        if (launch_scan(c->stream, counts, R, c->scan_blocks.as<int64_t>(), c->rec_out_start.as<int64_t>()) != hipSuccess)
+            return leave(fail(WFA_E_HIP, "k_scan(merged hit counts) launch failed"));
+        hipLaunchKernelGGL(k_hit_rows_merge_place, dim3(merge_grid(n_bound)), dim3(kMergeBlock), 0, c->stream, n_bound, rec,
+                           (const int64_t*)sets, n, R, c->rec_out_start.as<int64_t>(), c->merge_dest.as<int64_t>(), total);
+        hipLaunchKernelGGL(k_hit_rows_merge_scatter, dim3(merge_grid(n_bound * 15)), dim3(kMergeBlock), 0, c->stream, n_bound,
+                           c->merge_rows.as<uint32_t>(), c->merge_dest.as<int64_t>(), c->hit_out.as<uint32_t>(), total);
+        if (hipGetLastError() != hipSuccess) return leave(fail(WFA_E_HIP, "k_hit_rows_merge_* launch failed"));
+        if ((rc = t.end("k_hit_rows_merge_* (device totals)"))) return leave(rc);
+    }
+    (void)leave(WFA_OK);
+    if (queued) {  // wfa_hits_wait reads the pinned block
+        c->pending = true;
+        c->pend = {kSrcGroups, false, 0, 0, G.le, G.re, G.max_len, n_bound, false};
+        return WFA_OK;
+    }
+    int64_t total = 0;
+    for (int g = 0; g < n; ++g) total += G.n_host[g];
+    c->n_hits = c->last_hits = total;
+    return WFA_OK;
+}
+
+static int groups_wait(wfa_ctx* c, int64_t* n_hits) {
+    wfa_ctx::GroupsPass& G = c->grp;
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->pending = false;
+    bool redo = false;
+    if (G.single) {
+        const int64_t total = *c->h_total;
+        const int flags = c->pend.runs32 ? (int)(c->h_total[2] & 0xffffffffll) : 0;
+        if (flags) c->no_runs32 = true;
+        G.last[0] = c->last_hits = total;
+        redo = !spec_rows_stand(total, c->pend.bound, flags);
+        if (!redo) c->n_hits = total;
+    } else {
+        for (int g = 0; g < G.n_groups; ++g) {
+            if (G.n_host[g] >= 0) continue;
+            if (c->h_grp[2 * g + 1]) c->no_runs32 = true;  // a span outgrew its events: the general route from now on
+            G.last[g] = c->h_grp[2 * g];
+        }
+        redo = c->h_grp[kGrpFail] != 0;
+        if (!redo) c->n_hits = c->last_hits = c->h_grp[kGrpSets + G.n_groups];
+    }
+    if (redo) {
+        if (!c->have_records || c->R != G.R)
+            return fail(WFA_E_STATE, "the queued grouped pass must be redone, but its records table has been replaced");
+        if (int rc = groups_run(c, true)) return rc;
+    }
+    *n_hits = c->n_hits;
+    return WFA_OK;
+}
+
+extern "C" {
+
+int wfa_sosfiltfilt_group(wfa_ctx* c, int n_sections, const double* sos, const double* zi, int32_t padlen,
+                          const int32_t* group_of_record, int32_t group) {
+    int rc = use_device(c);
+    if (rc) return rc;
+    if ((rc = need_source(c, WFA_SRC_RAW))) return rc;
+    if (n_sections < 1 || n_sections > WFA_MAX_SOS_SECTIONS)
+        return fail(WFA_E_INVALID, "n_sections must be in [1, %d], got %d", WFA_MAX_SOS_SECTIONS, n_sections);
+    if (!sos || !zi || padlen < 0) return fail(WFA_E_INVALID, "bad sosfiltfilt arguments");
+    if (c->R > 0 && !group_of_record) return fail(WFA_E_INVALID, "group_of_record is null");
+    if (c->pending) {  // a queued pass may read the twin
+        int64_t n = 0;
+        if ((rc = wfa_hits_wait(c, &n))) return rc;
+    }
+    const bool fresh = !c->have_f32 || c->pool_f32.cap < (size_t)c->pool_n * sizeof(float);
+    if ((rc = c->pool_f32.ensure((size_t)c->pool_n * sizeof(float)))) return rc;
+    // a twin that did not exist: gaps and the other groups' records read 0.0 until their own filter call
+    if (fresh) WFA_HIP_CHECK(hipMemsetAsync(c->pool_f32.ptr, 0, (size_t)c->pool_n * sizeof(float), c->stream));
+    if (c->R > 0) {
+        if ((rc = c->grp_gor.ensure((size_t)c->R * sizeof(int32_t)))) return rc;
+        if ((rc = h2d_copy(c, c->grp_gor.ptr, group_of_record, (size_t)c->R * sizeof(int32_t)))) return rc;
+        const int64_t n_ext = (int64_t)c->max_len + 2 * (int64_t)padlen;
+        int64_t batch = (int64_t)(2147483648LL / (n_ext * 8));
+        batch = batch / 256 * 256;
+        if (batch < 256) batch = 256;
+        if (batch > c->R) batch = (c->R + 255) / 256 * 256;
+        if ((rc = c->bw_scratch.ensure((size_t)(n_ext * batch * 8)))) return rc;
+        const PoolView pv = pool_view(c);
+        const RecView rv = rec_view(c);
+        LaunchTimer t(c);
+        for (int64_t r0 = 0; r0 < c->R; r0 += batch) {
+            const int64_t r1 = r0 + batch < c->R ? r0 + batch : c->R;
+            WFA_HIP_CHECK(launch_sosfiltfilt(c->stream, pv, rv, n_sections, sos, zi, padlen, r0, r1,
+                                             c->bw_scratch.as<double>(), batch, c->pool_f32.as<float>(),
+                                             c->grp_gor.as<int32_t>(), group));
+        }
+        if ((rc = t.end("k_sosfiltfilt<group>"))) return rc;
+    }
+    c->have_f32 = true;
+    return WFA_OK;
+}
+
+int wfa_hits_enqueue_groups(wfa_ctx* c, int n_groups, const wfa_hit_group* groups, const int32_t* group_of_record,
+                            int32_t le, int32_t re, int32_t max_len) {
+    int rc = use_device(c);
+    if (rc) return rc;
+    if (n_groups < 1 || n_groups > WFA_MAX_HIT_GROUPS)
+        return fail(WFA_E_INVALID, "n_groups must be in [1, %d], got %d", WFA_MAX_HIT_GROUPS, n_groups);
+    if (!groups) return fail(WFA_E_INVALID, "groups is null");
+    if (!c->have_records) return fail(WFA_E_STATE, "records not uploaded");
+    if (!c->have_u16) return fail(WFA_E_STATE, "wave_pool (uint16) not uploaded");
+    for (int g = 0; g < n_groups; ++g) {
+        if (groups[g].source == WFA_SRC_SG_FUSED) {
+            const int slot = groups[g].plan_slot;
+            if (slot < 0 || slot >= WFA_MAX_HIT_GROUPS)
+                return fail(WFA_E_INVALID, "group %d: plan slot must be in [0, %d), got %d", g, WFA_MAX_HIT_GROUPS, slot);
+            if (!c->have_slot[slot]) return fail(WFA_E_STATE, "group %d: plan slot %d holds no plan (wfa_sg_plan_store)", g, slot);
+        } else if (groups[g].source == WFA_SRC_F32) {
+            if (!c->have_f32)
+                return fail(WFA_E_STATE, "group %d: wave_pool_filtered (float32) not resident (wfa_sosfiltfilt_group first)", g);
+        } else {
+            return fail(WFA_E_INVALID, "group %d: source must be WFA_SRC_SG_FUSED or WFA_SRC_F32, got %d", g, groups[g].source);
+        }
+    }
+    if (c->R > 0 && !group_of_record) return fail(WFA_E_INVALID, "group_of_record is null");
+    bool unowned = false;
+    for (int64_t r = 0; r < c->R; ++r) {
+        const int32_t v = group_of_record[r];
+        if (v < -1 || v >= n_groups)
+            return fail(WFA_E_INVALID, "group_of_record[%lld] = %d is outside [-1, %d)", (long long)r, v, n_groups);
+        unowned |= v < 0;
+    }
+    if (le < 0) le = 0;
+    if (re < 0) re = 0;
+    if (max_len <= 0) max_len = c->max_len;
+    if (max_len < c->max_len)
+        return fail(WFA_E_INVALID, "max_len (%d) < longest uploaded record (%d)", max_len, c->max_len);
+    if ((rc = groups_pinned(c))) return rc;
+    c->pending = false;  // (a queued pass nobody waited for ends here, like in wfa_hits_enqueue)
+    wfa_ctx::GroupsPass& G = c->grp;
+    if (G.n_groups != n_groups || memcmp(G.groups, groups, (size_t)n_groups * sizeof(wfa_hit_group)) != 0)
+        for (int64_t& v : G.last) v = -1;  // other groups than last time: their previous counts say nothing
+    G.n_groups = n_groups;
+    memcpy(G.groups, groups, (size_t)n_groups * sizeof(wfa_hit_group));
+    G.le = le; G.re = re; G.max_len = max_len;
+    G.single = n_groups == 1 && !unowned;
+    G.R = c->R;
+    c->n_hits = -1;
+    c->rows_index = 0;
+    if (c->R == 0) {
+        c->n_hits = 0;
+        return WFA_OK;
+    }
+    if (!G.single) {
+        if ((rc = c->grp_gor.ensure((size_t)c->R * sizeof(int32_t)))) return rc;
+        if ((rc = h2d_copy(c, c->grp_gor.ptr, group_of_record, (size_t)c->R * sizeof(int32_t)))) return rc;
+    }
+    return groups_run(c, false);
+}
+
+int wfa_hits_pending(wfa_ctx* c, int* pending) {
+    if (!c || !pending) return fail(WFA_E_INVALID, "null argument");
+    *pending = c->pending ? 1 : 0;
     return WFA_OK;
 }
 

@@ -169,6 +169,31 @@ struct wfa_ctx {
     int64_t merge_n = 0, merge_R = -1;
     std::vector<int64_t> merge_start;
     wfa::DevBuf merge_rows{scratch}, merge_rec{scratch}, merge_dest{scratch}, merge_sets{scratch};
+    // resident plan slots (wfa_sg_plan_store): one Savitzky-Golay plan per filter group of a grouped pass, kept across
+    // pool and records uploads like `sg`
+    wfa::SgPlanDev sg_slot[WFA_MAX_HIT_GROUPS];
+    bool have_slot[WFA_MAX_HIT_GROUPS] = {};
+    // queued grouped pass (wfa_hits_enqueue_groups): its arguments, kept for the exact redo of wfa_hits_wait; per
+    // group the row bound its launches were sized for (queued) or the row count the host already read (n_host >= 0);
+    // `last` = the row count of the group's previous pass on this context (sizes its speculative launch; -1: none yet)
+    struct GroupsPass {
+        bool single = false;   // one group, no unowned record: the plain pass with the slot's plan
+        int n_groups = 0;
+        int64_t R = -1;        // records the pass was queued over (the redo needs the same table)
+        wfa_hit_group groups[WFA_MAX_HIT_GROUPS] = {};
+        int32_t le = 0, re = 0, max_len = 0;
+        int64_t bound[WFA_MAX_HIT_GROUPS] = {};
+        int64_t n_host[WFA_MAX_HIT_GROUPS] = {};
+        bool runs32[WFA_MAX_HIT_GROUPS] = {};
+        int64_t last[WFA_MAX_HIT_GROUPS] = {-1, -1, -1, -1, -1, -1, -1, -1};
+    } grp;
+    wfa::DevBuf grp_gor;   // int32 per record: group_of_record of the last grouped pass
+    wfa::DevBuf grp_thr;   // double per record: the caller's threshold column while the passes run on masked copies
+    wfa::DevBuf grp_sets;  // int64 [WFA_MAX_HIT_GROUPS + 1] stash offsets written on the device, then [fail flag]
+    // pinned: per group (row count, overflow flags), the stash offsets as the device wrote them, the merged count and
+    // the fail flag; behind them one RunsCold per group (what k_sg_runs32's float64 paths read under that group's plan)
+    int64_t* h_grp = nullptr;
+    wfa::RunsCold* h_grp_cold = nullptr;
 
     wfa::DevBuf out_rows;  // per-record feature rows
     wfa::DevBuf out_rows2; // the second table of wfa_features_both (width rows)

@@ -3011,6 +3011,8 @@ __global__ __launch_bounds__(kPeakBlock) void k_peak_rows(PoolView pool, RecView
 // The section loops are unrolled over a compile-time bound NS, so the per-section state stays in registers: one instance
 // per bucket of section counts (8 covers orders 1..8, the common case; 16 and 32 the higher orders up to
 // WFA_MAX_SOS_SECTIONS).
+// Record selection (wfa_sosfiltfilt_group): with `sel` only the records r with sel[r] == sel_group are filtered, the
+// lanes of the others leave at once and their slices of the output stay as they are.
 template <int NS>
 struct SosParams {
     int n_sections;
@@ -3022,9 +3024,11 @@ struct SosParams {
 template <int NS>
 __global__ __launch_bounds__(kBlock) void k_sosfiltfilt(PoolView pool, RecView rec, SosParams<NS> sp, int64_t r_begin,
                                                         int64_t r_end, double* __restrict__ scratch,
-                                                        int64_t batch_stride, float* __restrict__ out) {
+                                                        int64_t batch_stride, float* __restrict__ out,
+                                                        const int32_t* __restrict__ sel, int32_t sel_group) {
     const int64_t r = r_begin + (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (r >= r_end) return;
+    if (sel && sel[r] != sel_group) return;
     const int L = rec.len[r];
     if (L <= 0) return;
     const int64_t off = rec.off[r];
@@ -3180,7 +3184,8 @@ hipError_t launch_width_integral(hipStream_t st, int source, const PoolView& poo
 template <int NS>
 static hipError_t launch_sosfiltfilt_ns(hipStream_t st, const PoolView& pool, const RecView& rec, int n_sections,
                                        const double* sos, const double* zi, int edge, int64_t r_begin, int64_t r_end,
-                                       double* scratch, int64_t batch_stride, float* out) {
+                                       double* scratch, int64_t batch_stride, float* out, const int32_t* sel,
+                                       int32_t sel_group) {
     SosParams<NS> sp{};
     sp.n_sections = n_sections;
     sp.edge = edge;
@@ -3193,20 +3198,24 @@ static hipError_t launch_sosfiltfilt_ns(hipStream_t st, const PoolView& pool, co
     if (n <= 0) return hipSuccess;
     const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
     hipLaunchKernelGGL((k_sosfiltfilt<NS>), dim3(grid), dim3(kBlock), 0, st, pool, rec, sp, r_begin, r_end, scratch,
-                       batch_stride, out);
+                       batch_stride, out, sel, sel_group);
     return hipGetLastError();
 }
 
 hipError_t launch_sosfiltfilt(hipStream_t st, const PoolView& pool, const RecView& rec, int n_sections,
                               const double* sos, const double* zi, int edge, int64_t r_begin, int64_t r_end,
-                              double* scratch, int64_t batch_stride, float* out) {
+                              double* scratch, int64_t batch_stride, float* out, const int32_t* group_of_record,
+                              int32_t group) {
     static_assert(WFA_MAX_SOS_SECTIONS == 32, "one k_sosfiltfilt bucket per power of two up to the maximum");
     if (n_sections < 1 || n_sections > WFA_MAX_SOS_SECTIONS) return hipErrorInvalidValue;
     if (n_sections <= 8)
-        return launch_sosfiltfilt_ns<8>(st, pool, rec, n_sections, sos, zi, edge, r_begin, r_end, scratch, batch_stride, out);
+        return launch_sosfiltfilt_ns<8>(st, pool, rec, n_sections, sos, zi, edge, r_begin, r_end, scratch, batch_stride, out,
+                                        group_of_record, group);
     if (n_sections <= 16)
-        return launch_sosfiltfilt_ns<16>(st, pool, rec, n_sections, sos, zi, edge, r_begin, r_end, scratch, batch_stride, out);
-    return launch_sosfiltfilt_ns<32>(st, pool, rec, n_sections, sos, zi, edge, r_begin, r_end, scratch, batch_stride, out);
+        return launch_sosfiltfilt_ns<16>(st, pool, rec, n_sections, sos, zi, edge, r_begin, r_end, scratch, batch_stride, out,
+                                        group_of_record, group);
+    return launch_sosfiltfilt_ns<32>(st, pool, rec, n_sections, sos, zi, edge, r_begin, r_end, scratch, batch_stride, out,
+                                        group_of_record, group);
 }
 
 hipError_t launch_find_hits_legacy(hipStream_t st, int source, bool fill, const PoolView& pool, int64_t n_rows, int32_t L,

@@ -189,7 +189,8 @@ hipError_t launch_hits_gather(hipStream_t st, const uint8_t* tmp, const int64_t*
                               const int32_t* nhits, const int64_t* out_start, int64_t R, uint8_t* out);
 hipError_t launch_sosfiltfilt(hipStream_t st, const PoolView& pool, const RecView& rec, int n_sections,
                               const double* sos, const double* zi, int edge, int64_t r_begin, int64_t r_end,
-                              double* scratch, int64_t batch_stride, float* out);
+                              double* scratch, int64_t batch_stride, float* out,
+                              const int32_t* group_of_record = nullptr, int32_t group = 0);
 hipError_t launch_find_hits_legacy(hipStream_t st, int source, bool fill, const PoolView& pool, int64_t n_rows, int32_t L,
                                    const double* baselines, double threshold, int32_t* counts, const int64_t* out_start,
                                    int64_t* out_event, int64_t* out_time);

@@ -103,6 +103,7 @@ class DeviceSession:
         self.max_len = 0
         self._plan: SgPlan | None = None
         self._keep: list = []  # host arrays referenced by in-flight calls
+        self._plan_slots: dict = {}  # resident plan slot -> (window, order) it holds (store_sg_plan)
         # residency: the host array OBJECTS (strong references, compared with `is`) whose contents the device
         # pools hold.  An address / size / dtype key does not identify contents: a freed temporary's address is
         # handed to the next same-shaped array.  Every call that changes a device pool resets these.
@@ -506,7 +507,60 @@ class DeviceSession:
     def hits_wait(self) -> int:
         n = C.c_int64(0)
         _lib.check(self._lib.wfa_hits_wait(self._h, C.byref(n)))
+        self._keep.clear()
         return int(n.value)
+
+    # -- the grouped pass, queued (wfa_hits_enqueue_groups) ---------------------------------------
+    def store_sg_plan(self, slot: int, sg_window_size: int, sg_poly_order: int) -> None:
+        """Keep the Savitzky-Golay plan (window, order) in the resident slot `slot` (wfa_sg_plan_store).  A slot that
+        already holds that pair is left alone: no rebuild, no upload."""
+        slot, pair = int(slot), (int(sg_window_size), int(sg_poly_order))
+        slots = self._plan_slots
+        if slots.get(slot) == pair:
+            return
+        plan = build_plan(*pair)
+        slots.pop(slot, None)
+        _lib.check(self._lib.wfa_sg_plan_store(
+            self._h, slot, plan.window, plan.polyorder, _ptr(plan.tab), _ptr(plan.symmetric), int(plan.int_ok),
+            _ptr(plan.itab), plan.den, plan.den_edge, plan.guard, plan.guard_edge))
+        slots[slot] = pair
+
+    def _group_column(self, group_of_record) -> np.ndarray:
+        gor = np.ascontiguousarray(group_of_record, dtype=np.int32)
+        if gor.shape != (self.n_records,):
+            raise ValueError("group_of_record must hold one group index per uploaded record")
+        return gor
+
+    def sosfiltfilt_group(self, sos: np.ndarray, zi: np.ndarray, padlen: int, group_of_record, group: int) -> None:
+        """sosfiltfilt over the uploaded records table, restricted to the records of `group`, into the device float32
+        twin (wfa_sosfiltfilt_group): no records upload, nothing downloaded, nothing waited for."""
+        sos = np.ascontiguousarray(sos, dtype=np.float64)
+        zi = np.ascontiguousarray(zi, dtype=np.float64)
+        if sos.ndim != 2 or sos.shape[1] != 6 or zi.shape != (sos.shape[0], 2):
+            raise ValueError("sos must be (n_sections, 6) and zi (n_sections, 2)")
+        gor = self._group_column(group_of_record)
+        self._drop_f32_tags()  # the device float32 pool is this filter's output now
+        _lib.check(self._lib.wfa_sosfiltfilt_group(self._h, int(sos.shape[0]), _ptr(sos), _ptr(zi), int(padlen), _ptr(gor),
+                                                   int(group)))
+        self._keep.append(gor)
+
+    def hits_enqueue_groups(self, groups, group_of_record, left_extension: int = 2, right_extension: int = 2,
+                            max_len: int = 0) -> None:
+        """Queue the grouped hit pass (wfa_hits_enqueue_groups): groups = [(source, plan slot)], group_of_record = one
+        group index per uploaded record (-1: no pass owns the record).  hits_wait() / _fill_hits deliver the merged table."""
+        groups = [(int(s), int(p)) for s, p in groups]
+        arr = (C.c_int32 * (2 * max(len(groups), 1)))(*[v for pair in groups for v in pair])
+        gor = self._group_column(group_of_record)
+        self._res_records = None  # as for hits_enqueue
+        _lib.check(self._lib.wfa_hits_enqueue_groups(self._h, len(groups), arr, _ptr(gor), int(left_extension),
+                                                     int(right_extension), int(max_len)))
+        self._keep.append(gor)
+
+    def hits_pending(self) -> bool:
+        """True from a queued pass until hits_wait() / _fill_hits has consumed it (wfa_hits_pending)."""
+        p = C.c_int(0)
+        _lib.check(self._lib.wfa_hits_pending(self._h, C.byref(p)))
+        return bool(p.value)
 
     def find_peaks(self, source: int = _lib.SRC_F32, use_derivative: bool = True, height: float = 30.0,
                    distance: int = 2, prominence: float = 0.7, width: float = 4, threshold: float | None = None,

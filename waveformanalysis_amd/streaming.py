@@ -314,6 +314,78 @@ def records_to_chunks(records: np.ndarray, chunk_size: int, run_id: str = "") ->
 _UNSET = object()
 
 
+def _filter_signature(context: Any, fplugin: Any):
+    """What the registered wave_pool_filtered plugin is configured with, as a comparable value."""
+    if fplugin is None:
+        return None
+    from .filter_engine import FILTER_OPTION_NAMES
+
+    names = FILTER_OPTION_NAMES + (("channel_config",) if "channel_config" in fplugin.options else ())
+    return tuple(repr(context.get_config(fplugin, name)) for name in names)
+
+
+def _channel_keys(data: np.ndarray) -> np.ndarray:
+    """One 64-bit key per row: board * 65536 + channel (0 where the column is missing)."""
+    names = data.dtype.names or ()
+    board = np.asarray(data["board"], dtype=np.int64) if "board" in names else np.zeros(len(data), dtype=np.int64)
+    chan = np.asarray(data["channel"], dtype=np.int64) if "channel" in names else np.zeros(len(data), dtype=np.int64)
+    return board * 65536 + (chan & 0xFFFF)
+
+
+class _RunPlan:
+    """The per-channel settings of one run: the sorted (board, channel) keys of its records, the filter group and the
+    threshold of each, and the filter key of every group (empty: the raw samples).  Immutable once resolved; worker
+    threads share it."""
+
+    def __init__(self, channel_key, group_of_key, threshold_of_key, keys):
+        self.channel_key, self.group_of_key, self.threshold_of_key = channel_key, group_of_key, threshold_of_key
+        self.keys = keys
+        self._designs = {}
+
+    @classmethod
+    def resolve(cls, plugin, context: Any, run_id: str, fplugin: Any, tables: list) -> "_RunPlan":
+        from .filter_engine import plan_fused_groups
+        from .plugins import _common as K
+
+        uniq = np.unique(np.concatenate([_channel_keys(t) for t in tables])) if tables else np.zeros(0, dtype=np.int64)
+        channels = np.zeros(len(uniq), dtype=[("board", np.int16), ("channel", np.int16)])
+        channels["board"] = uniq >> 16
+        channels["channel"] = (uniq & 0xFFFF).astype(np.uint16).astype(np.int16)
+        thresholds = K.per_record_channel_option(channels, plugin.channel_config, run_id, "threshold", plugin.threshold,
+                                                 plugin.threshold)
+        thresholds = np.ascontiguousarray(np.broadcast_to(thresholds, (len(uniq),)), dtype=np.float64)
+        group = np.zeros(len(uniq), dtype=np.int32)
+        keys: list = []
+        if plugin.use_filtered and plugin.filter_source == "wave_pool_filtered":
+            for g, (key, mask) in enumerate(plan_fused_groups(context, fplugin, run_id, channels)):
+                keys.append(tuple(key))
+                if mask is not None:
+                    group[np.asarray(mask, dtype=bool)] = g
+        elif plugin.use_filtered:
+            keys.append(("SG",) + tuple(plugin.sg))
+        if len(keys) > _lib.MAX_HIT_GROUPS:
+            raise ValueError(f"hit_threshold_stream: the run resolves to {len(keys)} distinct filter settings, the grouped "
+                             f"pass takes at most {_lib.MAX_HIT_GROUPS}")
+        return cls(uniq, group, thresholds, keys)
+
+    def lookup(self, records: np.ndarray):
+        """(group_of_record int32, thresholds float64) of a chunk's records."""
+        key = _channel_keys(records)
+        at = np.searchsorted(self.channel_key, key)
+        at[at >= len(self.channel_key)] = 0
+        if len(self.channel_key) == 0 or np.any(self.channel_key[at] != key):
+            raise ValueError("hit_threshold_stream: a chunk holds a (board, channel) the run's records do not")
+        return self.group_of_key[at], self.threshold_of_key[at]
+
+    def design(self, g: int):
+        """(sos, zi, padlen) of Butterworth group g, designed once."""
+        if g not in self._designs:
+            from .filter_engine import design_bw
+
+            self._designs[g] = design_bw(*self.keys[g][1:])
+        return self._designs[g]
+
+
 class HipThresholdHitStream(HipStreamingPlugin):
     """compute_chunk() = threshold hits of one chunk of records (fused SG filter optional).
 
@@ -323,9 +395,19 @@ class HipThresholdHitStream(HipStreamingPlugin):
     the other.  Options are read from the Context like those of HipThresholdHitPlugin (hit_finder.py:82-130); a value
     given to the constructor wins.
 
-    The fused filter here is the stream's own Savitzky-Golay pair, one for every record: unlike HipThresholdHitPlugin's
-    fuse_filter route, the stream has no channel configuration and reads nothing from a wave_pool_filtered plugin (no
-    per-channel filter settings, no Butterworth groups, no merge of several passes).
+    Per-channel settings.  `channel_config` gives per (board, channel) thresholds, resolved exactly as
+    HipThresholdHitPlugin resolves them (hit_finder.py:288-327).  With use_filtered, `filter_source` says where the filter
+    comes from: "own" (default) is the stream's own Savitzky-Golay pair, one for every record; "wave_pool_filtered" takes
+    the settings of the registered wave_pool_filtered plugin resolved per record (filter_type, SG / Butterworth
+    parameters, that plugin's channel_config: filtering.py:339-374), as HipThresholdHitPlugin's fuse_filter route does.
+    The settings are resolved once per run into a (board, channel) -> (filter group, threshold) table (`_run_plan`,
+    cached like the run's width); a chunk gets its group index and threshold per record by one vectorised lookup.  Groups
+    are numbered over the whole run, so group g always uses the resident plan slot g of its session; a group without a
+    record in a chunk is empty there.  Several groups go through ONE queued call (wfa_hits_enqueue_groups: every group's
+    pass, the stash and the merge on the session's stream, row counts taken on the device), so the ring still never waits
+    for chunk k before chunk k + 1 is queued; a Butterworth group is filtered on the device first, over the uploaded
+    table (wfa_sosfiltfilt_group), and its pass reads the float32 twin.  K groups read the chunk's samples K times.
+    Without channel_config and with filter_source="own" nothing of this runs: the device calls are those of one pass.
 
     Padded width.  The reference evaluates hit windows on a matrix padded to the longest record of the RUN
     (hit_finder.py:364,370), and a window that reaches behind a short record's end reads that padding.  Every chunk
@@ -354,14 +436,22 @@ class HipThresholdHitStream(HipStreamingPlugin):
         "use_filtered": Option(default=False, type=bool, help="threshold the Savitzky-Golay filtered waveform (fused)"),
         "sg_window_size": Option(default=11, type=int, help="Savitzky-Golay window"),
         "sg_poly_order": Option(default=2, type=int, help="Savitzky-Golay polynomial order"),
+        "channel_config": Option(default=None, type=dict, help="per (board, channel) threshold"),
+        "filter_source": Option(default="own", type=str,
+                                help="with use_filtered: own (sg_window_size / sg_poly_order for every record) | "
+                                     "wave_pool_filtered (the registered wave_pool_filtered plugin's settings per record)"),
     }
+    FILTER_SOURCES = ("own", "wave_pool_filtered")
 
     def __init__(self, threshold=_UNSET, left_extension=_UNSET, right_extension=_UNSET, use_filtered=_UNSET,
-                 sg_window_size=_UNSET, sg_poly_order=_UNSET, max_len: int = 0, device_pool: DevicePool | None = None):
+                 sg_window_size=_UNSET, sg_poly_order=_UNSET, max_len: int = 0, device_pool: DevicePool | None = None,
+                 channel_config=_UNSET, filter_source=_UNSET):
         super().__init__()
         given = dict(threshold=threshold, left_extension=left_extension, right_extension=right_extension,
-                     use_filtered=use_filtered, sg_window_size=sg_window_size, sg_poly_order=sg_poly_order)
+                     use_filtered=use_filtered, sg_window_size=sg_window_size, sg_poly_order=sg_poly_order,
+                     channel_config=channel_config, filter_source=filter_source)
         self._given = {k: v for k, v in given.items() if v is not _UNSET}
+        self._plan_of = None          # (weak reference to a records array, config signature, _RunPlan): _run_plan's last run
         # padded width of the whole run (hit_finder.py:364); 0 = the longest record of the Context's `records`
         self.max_len = int(max_len)
         self.device_pool = device_pool
@@ -383,6 +473,36 @@ class HipThresholdHitStream(HipStreamingPlugin):
         self.le, self.re = max(0, int(value("left_extension"))), max(0, int(value("right_extension")))
         self.use_filtered = bool(value("use_filtered"))
         self.sg = normalize_window(value("sg_window_size"), value("sg_poly_order"))
+        self.channel_config = value("channel_config") or None
+        self.filter_source = str(value("filter_source"))
+        if self.filter_source not in self.FILTER_SOURCES:
+            raise ValueError(f"hit_threshold_stream: filter_source must be one of {self.FILTER_SOURCES}, "
+                             f"got {self.filter_source!r}")
+        if self.filter_source == "wave_pool_filtered" and ("sg_window_size" in self._given or "sg_poly_order" in self._given):
+            raise ValueError("hit_threshold_stream: sg_window_size / sg_poly_order given to the constructor contradict "
+                             "filter_source='wave_pool_filtered' (the filter settings are that plugin's)")
+
+    def _run_plan(self, context: Any, run_id: str, chunks: list | None = None):
+        """None on the default path (no channel_config, the stream's own filter): nothing per record happens on the
+        host.  Otherwise the run's (board, channel) -> (filter group, threshold) table, resolved once per run: from the
+        Context's `records` (cached on that array and the resolved configuration), else from the chunks at hand.  More
+        than WFA_MAX_HIT_GROUPS distinct filter settings: ValueError, before anything is uploaded."""
+        grouped = self.use_filtered and self.filter_source == "wave_pool_filtered"
+        if not self.channel_config and not grouped:
+            return None
+        fplugin = None
+        if grouped and "wave_pool_filtered" in getattr(context, "_plugins", {}):
+            fplugin = context.get_plugin("wave_pool_filtered")
+        signature = (self.threshold, self.use_filtered, self.filter_source, self.sg, repr(self.channel_config), run_id,
+                     _filter_signature(context, fplugin))
+        records = context.get_data(run_id, "records") if hasattr(context, "get_data") else None
+        if isinstance(records, np.ndarray) and records.dtype.names:
+            seen = self._plan_of      # (one read: worker threads share the plugin)
+            if seen is None or seen[0]() is not records or seen[1] != signature:
+                seen = (weakref.ref(records), signature, _RunPlan.resolve(self, context, run_id, fplugin, [records]))
+                self._plan_of = seen
+            return seen[2]
+        return _RunPlan.resolve(self, context, run_id, fplugin, [c.data for c in (chunks or []) if len(c.data)])
 
     def _run_width(self, context: Any, run_id: str, chunks: list | None = None) -> int:
         """The padded width every chunk of this run is evaluated at: the constructor's max_len, else the longest
@@ -436,9 +556,12 @@ class HipThresholdHitStream(HipStreamingPlugin):
         return Chunk(np.zeros(0, dtype=THRESHOLD_HIT_DTYPE), chunk.start, chunk.end, run_id, self.provides,
                      data_kind="hits", time_field="timestamp")
 
-    def _stage(self, sess, chunk: Chunk, wave_pool: np.ndarray, max_len: int) -> None:
+    def _stage(self, sess, chunk: Chunk, wave_pool: np.ndarray, max_len: int, plan=None) -> None:
         """Upload the chunk's samples + records and queue its hit pass on `sess` at the run's padded width `max_len`
-        (returns without waiting for the kernels once the session has sized its row buffers: wfa_hits_enqueue)."""
+        (returns without waiting for the kernels once the session has sized its row buffers: wfa_hits_enqueue).
+        `plan`: the run's per-channel table (`_run_plan`), None on the default path."""
+        if plan is not None:
+            return self._stage_planned(sess, chunk, wave_pool, max_len, plan)
         recs = chunk.data
         # the slice of the pool from the chunk's first sample to its last: exactly its records for time-sorted records
         # packed back to back, with other chunks' samples and gaps in between for any other packing
@@ -452,6 +575,35 @@ class HipThresholdHitStream(HipStreamingPlugin):
             sess.set_sg_plan(*self.sg)
         sess.hits_enqueue(_lib.SRC_SG_FUSED if self.use_filtered else _lib.SRC_RAW, (0, 0), self.le, self.re, int(max_len))
 
+    def _stage_planned(self, sess, chunk: Chunk, wave_pool: np.ndarray, max_len: int, plan) -> None:
+        """_stage under a per-channel table: per-record thresholds, and with several filter groups the one queued
+        grouped pass.  Group g of the run uses plan slot g on every session and in every chunk."""
+        recs = chunk.data
+        lo = int(recs["wave_offset"].min())
+        hi = int((recs["wave_offset"].astype(np.int64) + recs["event_length"]).max())
+        sub = recs.copy()
+        sub["wave_offset"] -= lo
+        group_of_record, thresholds = plan.lookup(recs)
+        sess.upload_pool(np.ascontiguousarray(wave_pool[lo:hi]))
+        sess.upload_records(sub, thresholds)
+        keys = plan.keys
+        if not keys:  # the raw samples
+            sess.hits_enqueue(_lib.SRC_RAW, (0, 0), self.le, self.re, int(max_len))
+            return
+        if len(keys) == 1 and keys[0][0] == "SG":
+            sess.set_sg_plan(keys[0][1], keys[0][2])
+            sess.hits_enqueue(_lib.SRC_SG_FUSED, (0, 0), self.le, self.re, int(max_len))
+            return
+        groups = []
+        for g, key in enumerate(keys):
+            if key[0] == "BW":  # filtered over the uploaded table: the layout record and the padded shadow stand
+                sess.sosfiltfilt_group(*plan.design(g), group_of_record, g)
+                groups.append((_lib.SRC_F32, 0))
+            else:
+                sess.store_sg_plan(g, key[1], key[2])
+                groups.append((_lib.SRC_SG_FUSED, g))
+        sess.hits_enqueue_groups(groups, group_of_record, self.le, self.re, int(max_len))
+
     def _collect(self, sess, chunk: Chunk, run_id: str) -> Chunk:
         hits = sess._fill_hits(sess.hits_wait())
         # a record that overlaps the chunk's end (non-strict halo selection) has hits behind it: the result chunk
@@ -463,17 +615,23 @@ class HipThresholdHitStream(HipStreamingPlugin):
     def compute_chunk(self, chunk: Chunk, context: Any, run_id: str, **_kw) -> Chunk:
         return self._compute_one(chunk, context, run_id, None)
 
-    def _compute_one(self, chunk: Chunk, context: Any, run_id: str, max_len: int | None) -> Chunk:
-        """compute_chunk at a padded width the caller has resolved (None: resolve it here)."""
+    def _compute_one(self, chunk: Chunk, context: Any, run_id: str, max_len: int | None, plan=_UNSET) -> Chunk:
+        """compute_chunk at a padded width and under a per-channel table the caller has resolved (None / unset: resolve
+        them here)."""
         if len(chunk.data) == 0:
             return self._empty(chunk, run_id)
         self._configure(context)
         if max_len is None:
             max_len = self._run_width(context, run_id)
+        if plan is _UNSET:
+            plan = self._run_plan(context, run_id, [chunk])
         wave_pool = context.get_data(run_id, "wave_pool")
         # worker threads come and go with every compute(): the session is borrowed for this chunk only
         with self._pool(context).borrow() as sess:
-            self._stage(sess, chunk, wave_pool, max_len)
+            if plan is None:
+                self._stage(sess, chunk, wave_pool, max_len)
+            else:
+                self._stage(sess, chunk, wave_pool, max_len, plan)
             return self._collect(sess, chunk, run_id)
 
     def _pipeline(self, input_chunks, context: Any, run_id: str, timeline: list | None = None,
@@ -489,6 +647,7 @@ class HipThresholdHitStream(HipStreamingPlugin):
 
         self._configure(context)
         max_len = self._run_width(context, run_id, input_chunks if isinstance(input_chunks, (list, tuple)) else None)
+        plan = self._run_plan(context, run_id, input_chunks if isinstance(input_chunks, (list, tuple)) else None)
         wave_pool = context.get_data(run_id, "wave_pool")
         pool = self._pool(context)
         n = max(2, 2 * len(pool.device_ids))
@@ -517,7 +676,10 @@ class HipThresholdHitStream(HipStreamingPlugin):
                 sess = ring[staged % n]  # free: results are collected in order, at most n - 1 are pending here
                 staged += 1
                 t0 = time.perf_counter()
-                self._stage(sess, chunk, wave_pool, max_len)
+                if plan is None:
+                    self._stage(sess, chunk, wave_pool, max_len)
+                else:
+                    self._stage(sess, chunk, wave_pool, max_len, plan)
                 t1 = time.perf_counter()
                 pending.append((k, chunk, sess, (t0, t1)))
                 while len(pending) > n - 1:
@@ -538,8 +700,10 @@ class HipThresholdHitStream(HipStreamingPlugin):
                    timeline: list | None = None) -> list[Chunk]:
         """The raw results of `chunks`, in order (the bench and the parity tests call this with ready-made chunks)."""
         if not self.parallel or max_workers <= 1 or len(chunks) <= 1:
+            self._configure(context)
             max_len = self._run_width(context, run_id, list(chunks))
-            return [self._compute_one(c, context, run_id, max_len) for c in chunks]
+            plan = self._run_plan(context, run_id, list(chunks))
+            return [self._compute_one(c, context, run_id, max_len, plan) for c in chunks]
         return [raw for _chunk, raw in self._pipeline(chunks, context, run_id, timeline, max_workers=max_workers)]
 
 
