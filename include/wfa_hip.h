@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define WFA_ABI_VERSION 4
+#define WFA_ABI_VERSION 5
 
 #define WFA_OK 0
 #define WFA_E_INVALID (-1)   /* bad argument / malformed records (maps to ValueError) */
@@ -239,68 +239,51 @@ int wfa_hits_enqueue(wfa_ctx* ctx, int source, int32_t bl_start, int32_t bl_end,
                      int32_t right_extension, int32_t max_len);
 int wfa_hits_wait(wfa_ctx* ctx, int64_t* n_hits);
 
-/* Several hit passes over ONE uploaded records table, merged into one table on the device: the fused pass on a run whose
- * channels resolve to different filter settings (reference: cpu/filtering.py:339-374 groups the records by their resolved
- * settings; hit_finder.py:288-327 resolves the per-channel threshold; hit_finder.py:354-366 emits the hits of all records in
- * one loop, i.e. by (record index, start)).  One pass runs per distinct setting, each with the threshold column set to
- * +inf for the records of the other settings (sig >= +inf holds for no finite sample: no hit on any route).
- *
- * wfa_set_thresholds replaces the device threshold column of the uploaded records (n_records doubles) and nothing else:
- * the layout record, the padded shadow pool, the device baselines (those a fused-baseline pass wrote included), the
- * Savitzky-Golay plan, the resident pools and the rows of the last pass stand.  (A second wfa_upload_records_* would void
- * the shadow of a padded layout.)  WFA_E_STATE without records, WFA_E_INVALID when n_records differs from the uploaded
- * count; a queued pass (wfa_hits_enqueue) is waited for first.
- *
- * wfa_hit_rows_merge_begin opens an empty merge set (dropping an unfinished one).
- * wfa_hit_rows_merge_add takes the rows of the last completed hit pass into the set, with the record index (position in
- * the uploaded records table) of every row; a queued pass is waited for, a pass without rows is legal.  WFA_E_STATE
- * without an open set, without a pass, or when the resident rows are a merged table; WFA_E_INVALID when the records
- * table has another size than at the set's first pass.
- * wfa_hit_rows_merge_end merges the set (k_hit_rows_merge_*: per-record row count, exclusive scan, scatter of the 60-byte
- * rows as 15 dwords each) and closes it.  Order: ascending record index; the rows of one record keep the order of the
- * pass that produced them, and rows of one record that come from two passes stand in pass order (the order of the _add
- * calls) -- the plugins never produce that, their passes own disjoint records.  Afterwards the merged table IS "the rows
- * of the last hit pass": wfa_threshold_hits_fill, wfa_hits_wait, wfa_rccl_gather_rows(rows = NULL) and, through
- * wfa_hit_rows_source(ctx, 1), the resident hit-table stages read it; the row count also sizes the next pass's
- * speculative launch.  An empty set gives 0 rows.  WFA_E_STATE without an open set.
- * The stash of the added passes is scratch (wfa_release_scratch frees it and with it an open set; wfa_scratch_bytes
- * counts it): 64 bytes per stashed row + 8 per merged row, beside the table itself. */
-int wfa_set_thresholds(wfa_ctx* ctx, const double* threshold, int64_t n_records);
-int wfa_hit_rows_merge_begin(wfa_ctx* ctx);
-int wfa_hit_rows_merge_add(wfa_ctx* ctx);
-int wfa_hit_rows_merge_end(wfa_ctx* ctx, int64_t* n_hits);
-
-/* The same table from ONE queued call (streaming callers: nobody waits for chunk k before chunk k + 1 is queued).
+/* The grouped hit pass: hits of ONE uploaded records table whose channels resolve to several filter settings, merged on
+ * the device into one table (reference: cpu/filtering.py:339-374 groups the records by their resolved settings;
+ * hit_finder.py:288-327 resolves the per-channel threshold; hit_finder.py:354-366 emits the hits of all records in one
+ * loop, i.e. by (record index, start)).  Streaming callers queue it: nobody waits for chunk k before chunk k + 1.
  *
  * wfa_sg_plan_store keeps a Savitzky-Golay plan in slot `slot` (0 <= slot < WFA_MAX_HIT_GROUPS), arguments as for
  * wfa_set_sg_plan.  A slot's tables stay on the device across pool and records uploads; wfa_set_sg_plan and the plan it
  * sets are untouched.
  *
  * wfa_sosfiltfilt_group is wfa_sosfiltfilt restricted to the records r with group_of_record[r] == group (one int32 per
- * uploaded record), over the uploaded table: no second records upload, so the padded shadow and the layout record stand.
- * It writes those records' slices of the float32 twin and nothing else (a twin that did not exist is zeroed first),
- * downloads nothing and does not wait for the device.
+ * uploaded record), over the uploaded table: the records are not uploaded again, so the padded shadow and the layout
+ * record stand.  It writes those records' slices of the float32 twin and nothing else (a twin that did not exist is
+ * zeroed first), downloads nothing and does not wait for the device.
  *
- * wfa_hits_enqueue_groups runs, on the context's stream, what this synchronous sequence gives:
- *     wfa_hit_rows_merge_begin; per group g in order { threshold column = the record's own value where
- *     group_of_record[r] == g, +inf elsewhere; the plan of groups[g].plan_slot; one hit pass from groups[g].source
- *     (WFA_SRC_SG_FUSED or WFA_SRC_F32) with the uploaded baselines; wfa_hit_rows_merge_add }; wfa_hit_rows_merge_end
- * -- the byte-identical table, in (record index, start) order.  group_of_record[r] = -1: no pass owns record r, it gives
- * no rows.  The masked column of a group is written by a kernel from group_of_record, the plan is chosen by slot, the
- * rows of a pass go to the stash under a row count read on the device (launches sized for the pass's bound), the stash
- * offsets are written on the device and the merge kernels take their totals from there.  Where every group's pass takes
- * the speculative row launch (a warm context: each group's previous row count is kept, per group index; uniform records
- * on the streaming or bitmap route) the call returns with nothing waited for and wfa_hits_wait delivers the merged
- * count; if a group found more rows than its bound, or a span's events overflowed, wfa_hits_wait redoes the grouped pass
- * the exact way.  A group whose pass cannot speculate (the general route on ragged records, a context's first grouped
- * pass, no_speculate) runs to completion inside the call, as in wfa_hits_enqueue.  Afterwards the merged table is "the
- * rows of the last hit pass" exactly as after wfa_hit_rows_merge_end, and the uploaded threshold column reads as the
- * caller uploaded it.  n_groups == 1 without a -1 runs the single pass: no mask kernel, no stash, no merge.
- * The stash is the scratch of wfa_hit_rows_merge_* (same cost per row).
+ * wfa_hits_enqueue_groups queues, on the context's stream, the table of n_groups passes over the uploaded records.
+ * The table: group g (in order) contributes the rows of one hit pass under the plan of groups[g].plan_slot
+ * (WFA_SRC_SG_FUSED) or from the float32 twin (WFA_SRC_F32), in which only the records with group_of_record[r] == g can
+ * hit: every other record's threshold reads +inf during that pass (sig >= +inf holds for no finite sample: no hit on any
+ * route).  group_of_record[r] = -1: no pass owns record r, it gives no rows.  Baselines: [bl_start, bl_end) as in
+ * wfa_hits_enqueue -- the WFA_SRC_SG_FUSED groups estimate the baselines over that window inside their pass (and leave
+ * them on the device), bl_end <= bl_start means the uploaded baselines; WFA_SRC_F32 groups always read the baselines as
+ * they stand.
+ * Merge order: ascending record index; the rows of one record keep the order of the pass that produced them (by start),
+ * and rows of one record that came from two passes would stand in group order -- group_of_record gives a record to one
+ * group, so that does not occur.  The table is byte-identical to the host merge of the groups' single passes.
+ * How it is queued: the masked column of a group is written by a kernel from group_of_record, the plan is chosen by
+ * slot, the rows of a pass go to a stash under a row count read on the device (launches sized for the pass's bound), the
+ * stash offsets are written on the device and the merge kernels (k_hit_rows_merge_*: per-record row count, exclusive
+ * scan, scatter of the 60-byte rows as 15 dwords each) take their totals from there.
+ * Speculation and redo: where every group's pass takes the speculative row launch (a warm context: each group's
+ * previous row count is kept, per group index; uniform records on the streaming or bitmap route) the call returns with
+ * nothing waited for and wfa_hits_wait delivers the merged count; if a group found more rows than its bound, or a span's
+ * events overflowed, wfa_hits_wait redoes the grouped pass the exact way.  A group whose pass cannot speculate (the
+ * general route on ragged records, a context's first grouped pass, no_speculate) runs to completion inside the call, as
+ * in wfa_hits_enqueue.  n_groups == 1 without a -1 runs the single pass: no mask kernel, no stash, no merge.
+ * Afterwards the merged table IS "the rows of the last hit pass": wfa_threshold_hits_fill, wfa_hits_wait,
+ * wfa_rccl_gather_rows(rows = NULL) and, through wfa_hit_rows_source(ctx, 1), the resident hit-table stages read it; its
+ * row count sizes the next single pass's speculative launch; and the uploaded threshold column reads as the caller
+ * uploaded it.
+ * The stash is scratch (wfa_release_scratch frees it, wfa_scratch_bytes counts it): 64 bytes per stashed row + 8 per
+ * merged row, beside the table itself.
  * WFA_E_INVALID: n_groups outside [1, WFA_MAX_HIT_GROUPS], a source other than the two above, a plan slot or a
- * group_of_record value out of range, max_len below the longest uploaded record (0 = that record).  WFA_E_STATE: no
- * records or no wave_pool uploaded, a slot without a stored plan, a WFA_SRC_F32 group without a resident float32 pool
- * (wfa_sosfiltfilt_group / wfa_upload_pool_f32 first).
+ * group_of_record value out of range, bl_start < 0 with bl_end > bl_start, max_len below the longest uploaded record
+ * (0 = that record).  WFA_E_STATE: no records or no wave_pool uploaded, a slot without a stored plan, a WFA_SRC_F32
+ * group without a resident float32 pool (wfa_sosfiltfilt_group / wfa_upload_pool_f32 first).
  *
  * wfa_hits_pending: *pending = 1 from a queued pass (wfa_hits_enqueue / _groups) until wfa_hits_wait or
  * wfa_threshold_hits_fill has consumed it, else 0.  Reads state only. */
@@ -313,7 +296,8 @@ int wfa_sg_plan_store(wfa_ctx* ctx, int slot, int window, int polyorder, const d
 int wfa_sosfiltfilt_group(wfa_ctx* ctx, int n_sections, const double* sos, const double* zi, int32_t padlen,
                           const int32_t* group_of_record, int32_t group);
 int wfa_hits_enqueue_groups(wfa_ctx* ctx, int n_groups, const wfa_hit_group* groups, const int32_t* group_of_record,
-                            int32_t left_extension, int32_t right_extension, int32_t max_len);
+                            int32_t bl_start, int32_t bl_end, int32_t left_extension, int32_t right_extension,
+                            int32_t max_len);
 int wfa_hits_pending(wfa_ctx* ctx, int* pending);
 
 /* K8 find_peaks-based hit detector, records source (reference: cpu/peak_finding.py:395-614 calling

@@ -51,30 +51,50 @@ def group_plan(records: np.ndarray) -> list[tuple[tuple, np.ndarray]]:
     return [(key, records["channel"] == c) for c, key in enumerate(KEYS)]
 
 
+def group_column(plan) -> np.ndarray:
+    """group_of_record of a plan's masks: int32, the index of the record's group, -1 where no mask holds."""
+    column = np.full(len(plan[0][1]), -1, dtype=np.int32)
+    for g, (_key, mask) in enumerate(plan):
+        column[mask] = g
+    return column
+
+
 def thresholds_of(records: np.ndarray) -> np.ndarray:
     """HIT_CC per record."""
     return np.asarray(THRESHOLDS)[records["channel"]]
 
 
 def run_groups(sess, records: np.ndarray, thresholds: np.ndarray, plan) -> tuple[list[np.ndarray], int]:
-    """Every group's pass alone on a session that holds the pool, +inf outside the group, each downloaded and added to
-    a device merge -> (the downloads in pass order, the row count of the device-merged table, left resident)."""
+    """Every group's single pass alone on a session that holds the pool, +inf outside the group, each downloaded; then
+    the queued grouped call -> (the downloads in pass order, the row count of the device-merged table, left resident)."""
     for key, mask in plan:  # the Butterworth records into the float32 twin, before the table of the passes is uploaded
         if key[0] == "BW":
             sess.upload_records(records[mask])
             sess.sosfiltfilt(*design_bw(*key[1:]), download=False)
-    sess.upload_records(records, np.inf)
     parts = []
-    with sess.merged_hit_rows() as merge:
-        for key, mask in plan:
-            sess.set_thresholds(np.where(mask, thresholds, np.inf))
-            if key[0] == "SG":
-                sess.set_sg_plan(key[1], key[2])
-                parts.append(sess.threshold_hits(_lib.SRC_SG_FUSED))
-            else:
-                parts.append(sess.threshold_hits(_lib.SRC_F32))
-            merge.add()
-    return parts, merge.n_hits
+    for key, mask in plan:
+        sess.upload_records(records, np.where(mask, thresholds, np.inf))
+        if key[0] == "SG":
+            sess.set_sg_plan(key[1], key[2])
+            parts.append(sess.threshold_hits(_lib.SRC_SG_FUSED))
+        else:
+            parts.append(sess.threshold_hits(_lib.SRC_F32))
+    sess.upload_records(records, thresholds)
+    stage_groups(sess, [key for key, _mask in plan], group_column(plan))
+    return parts, sess.hits_wait()
+
+
+def stage_groups(sess, keys, group_of_record, baseline_window=(0, 0)) -> None:
+    """The queued grouped pass over the uploaded records, group g in plan slot g; hits_wait() delivers."""
+    groups = []
+    for g, key in enumerate(keys):
+        if key[0] == "BW":
+            sess.sosfiltfilt_group(*design_bw(*key[1:]), group_of_record, g)
+            groups.append((_lib.SRC_F32, 0))
+        else:
+            sess.store_sg_plan(g, key[1], key[2])
+            groups.append((_lib.SRC_SG_FUSED, g))
+    sess.hits_enqueue_groups(groups, group_of_record, 2, 2, baseline_window=baseline_window)
 
 
 def host_merge(records: np.ndarray, parts: list[np.ndarray]) -> np.ndarray:

@@ -165,8 +165,10 @@ class GroupOracleSession(S.OracleSession):
         self._rows = H.oracle_rows(rec, src, self._thresholds(), left_extension, right_extension, int(max_len))
         self._queued = True
 
-    def hits_enqueue_groups(self, groups, group_of_record, left_extension=2, right_extension=2, max_len=0):
+    def hits_enqueue_groups(self, groups, group_of_record, left_extension=2, right_extension=2, max_len=0,
+                            baseline_window=(0, 0)):
         self.calls.append("hits_enqueue_groups")
+        assert tuple(baseline_window) == (0, 0), "the stream passes no baseline window"
         rec, pool = self._rec, self._pool
         gor = np.asarray(group_of_record)
         assert 1 <= len(groups) <= _lib.MAX_HIT_GROUPS and len(gor) == len(rec)

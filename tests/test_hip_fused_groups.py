@@ -1,21 +1,26 @@
 """hit_threshold with use_filtered=True, fuse_filter=True on runs whose channels resolve to different filter settings
 (wave_pool_filtered's filter_type / channel_config): one device pass per setting over the resident pool, the rows merged
-on the device (wfa_set_thresholds, wfa_hit_rows_merge_*).
+on the device (wfa_hits_enqueue_groups).
 
 Fixture: tests/golden/c5_fused_groups.npz (tests/golden/make_fused_groups_golden.py) -- three runs of 4 channels x 40
 records, channels interleaved: "a" L = 128 (in-place streaming), "b" L = 100 (padded), "c" ragged 20..300 samples (general
 route); channel 0 SG(11, 2), 1 SG(7, 3), 2 SG(21, 4), 3 Butterworth; per-channel thresholds on channels 1 and 3."""
 
+import functools
+
 import numpy as np
 import pytest
 
+from oracle import wfa_oracle as O
 from tests import golden_util as G
-from tests.fused_groups_util import (FILTER_CC, HIT_CC, RUNS, context, group_plan, host_merge, load_run, run_groups,
-                                     thresholds_of)
+from tests import stream_groups_util as U
+from tests.fused_groups_util import (FILTER_CC, HIT_CC, KEYS, RUNS, context, group_column, group_plan, host_merge, load_run,
+                                     run_groups, stage_groups, thresholds_of)
 from waveformanalysis_amd import _lib
 from waveformanalysis_amd import multidevice as MD
 from waveformanalysis_amd.device import DeviceSession, device_count
 from waveformanalysis_amd.dtypes import THRESHOLD_HIT_DTYPE
+from waveformanalysis_amd.filter_engine import design_bw
 from waveformanalysis_amd.plugins.threshold_hit import records_pass
 
 pytestmark = pytest.mark.gpu
@@ -118,8 +123,8 @@ def test_device_merge_with_an_empty_pass_and_with_no_rows(sess):
                           what="single pass after an empty merge")
 
 
-# ---- 3. set_thresholds keeps the state of the context ---------------------------------------------------------------------
-def test_set_thresholds_keeps_baselines_and_the_padded_shadow(sess):
+# ---- 3. the masked passes keep the state of the context -------------------------------------------------------------------
+def test_masked_passes_keep_baselines_and_the_padded_shadow(sess):
     run = load_run("b")
     rec, pool = run["records"], run["wave_pool"]
     blank = rec.copy()
@@ -130,19 +135,22 @@ def test_set_thresholds_keeps_baselines_and_the_padded_shadow(sess):
     sess.profile(True)
     try:
         first = sess.fused_baseline_filter_hits((0, 40))
-        sess.set_thresholds(np.full(len(rec), 10.0))
-        second = sess.threshold_hits(_lib.SRC_SG_FUSED)  # no baseline window: the baselines the first pass left
+        # two masked passes under the same plan, no baseline window: the baselines the first pass left, the shadow it built
+        sess.store_sg_plan(2, 7, 3)
+        sess.store_sg_plan(3, 7, 3)
+        sess.hits_enqueue_groups([(_lib.SRC_SG_FUSED, 2), (_lib.SRC_SG_FUSED, 3)], rec["channel"] % 2, 2, 2)
+        second = sess._fill_hits(sess.hits_wait())
         report = sess.profile_report()
     finally:
         sess.profile(False)
     assert len(first) > 100 and first.tobytes() == second.tobytes()
-    assert report["k_pad_rows (once per upload)"][1] == 1, report
+    assert report["k_pad_rows (once per upload)"][1] == 1 and report["k_grp_mask"][1] == 2, report
     # two groups whose passes both read the shadow: built once, not once per group
     even = rec["channel"] % 2 == 0
     sess.profile(True)
     try:
-        got = records_pass(sess, blank, 10.0, even, ~even, source=_lib.SRC_SG_FUSED, sg=None, fuse_baseline=(0, 40), le=2,
-                           re=2, groups=[("SG", 7, 3), ("SG", 5, 2)])
+        got = records_pass(sess, blank, 10.0, np.where(even, 0, 1).astype(np.int32), source=_lib.SRC_SG_FUSED, sg=None,
+                           fuse_baseline=(0, 40), le=2, re=2, groups=[("SG", 7, 3), ("SG", 5, 2)])
         report = sess.profile_report()
     finally:
         sess.profile(False)
@@ -152,7 +160,7 @@ def test_set_thresholds_keeps_baselines_and_the_padded_shadow(sess):
     plan = group_plan(rec)
     sess.profile(True)
     try:
-        got = records_pass(sess, blank, thresholds_of(rec), *[m for _k, m in plan], source=_lib.SRC_SG_FUSED, sg=None,
+        got = records_pass(sess, blank, thresholds_of(rec), group_column(plan), source=_lib.SRC_SG_FUSED, sg=None,
                            fuse_baseline=(0, 40), le=2, re=2, groups=[k for k, _m in plan])
         report = sess.profile_report()
     finally:
@@ -170,7 +178,7 @@ def test_resident_stages_read_the_merged_table(sess, tag):
     rec = run["records"]
     plan = group_plan(rec)
     sess.upload_pool(run["wave_pool"])
-    n = records_pass(sess, rec, thresholds_of(rec), *[m for _k, m in plan], source=_lib.SRC_SG_FUSED, sg=None,
+    n = records_pass(sess, rec, thresholds_of(rec), group_column(plan), source=_lib.SRC_SG_FUSED, sg=None,
                      fuse_baseline=None, le=2, re=2, groups=[k for k, _m in plan], download=False)
     rows = np.empty(n, dtype=THRESHOLD_HIT_DTYPE)
     sess.download_hits(rows)
@@ -199,11 +207,11 @@ def test_single_group_takes_the_single_pass(sess):
     sess.set_sg_plan(7, 3)
     want = sess.threshold_hits(_lib.SRC_SG_FUSED)
     # one group, and two groups of which the second has no record here (a shard): the single pass either way
-    one = np.ones(len(rec), dtype=bool)
-    for groups, group_masks in (([("SG", 7, 3)], [one]), ([("SG", 7, 3), ("SG", 21, 4)], [one, ~one])):
+    first = np.zeros(len(rec), dtype=np.int32)
+    for groups in ([("SG", 7, 3)], [("SG", 7, 3), ("SG", 21, 4)]):
         sess.profile(True)
         try:
-            got = records_pass(sess, rec, thr, *group_masks, source=_lib.SRC_SG_FUSED, sg=None, fuse_baseline=None, le=2, re=2,
+            got = records_pass(sess, rec, thr, first, source=_lib.SRC_SG_FUSED, sg=None, fuse_baseline=None, le=2, re=2,
                                groups=groups)
             report = sess.profile_report()
         finally:
@@ -247,39 +255,107 @@ def test_sharded_run_is_byte_identical(tag, which):
     assert len(want) > 200 and got.tobytes() == want.tobytes()
 
 
-# ---- 7. error contract ----------------------------------------------------------------------------------------------------
+# ---- 7. the baseline window through the grouped call ------------------------------------------------------------------------
+@functools.cache
+def _window_oracle(tag):
+    """The oracle's rows of a run under FILTER_CC / HIT_CC with every baseline the mean of samples [0, min(40, length))."""
+    run = load_run(tag)
+    rec, pool = run["records"].copy(), run["wave_pool"]
+    rec["baseline"] = [pool[o : o + min(40, n)].astype(np.float64).mean() for o, n in zip(rec["wave_offset"], rec["event_length"])]
+    return O.threshold_hits(rec, U.oracle_filtered(rec, pool, list(KEYS)), thresholds=thresholds_of(rec), left_extension=2,
+                            right_extension=2)
+
+
+@pytest.mark.parametrize("tag", RUNS)
+def test_baseline_window_through_the_grouped_call(tag):
+    """Window (0, 40) on the queued grouped call over records whose Savitzky-Golay groups are uploaded with NaN
+    baselines -- a pass that did not get the window finds nothing there -- cold, twice warm, and once behind a call that
+    found nothing (its bounds are exceeded, hits_wait redoes).  Each time: the host merge of the groups' single passes
+    (fused_baseline_filter_hits for the Savitzky-Golay groups, baseline_mean + threshold_hits for the Butterworth one),
+    byte for byte; the oracle's rows under window baselines; and the reference's rows.  The fixture's baselines are the
+    mean of the first 40 samples the run was generated with; run "c" cut seven records to 20..33 samples afterwards,
+    where the window ends with the record, so the reference's own rows are compared on the records that hold the whole
+    window (all of "a" and "b", 153 of 160 in "c") and the oracle's on all of them."""
+    run = load_run(tag)
+    rec, pool = run["records"], run["wave_pool"]
+    blank = rec.copy()
+    blank["baseline"] = np.nan
+    plan, thr = group_plan(rec), thresholds_of(rec)
+    whole = rec["record_id"][rec["event_length"] >= 40]
+    assert len(whole) >= len(rec) - 7
+
+    def equals_reference(rows, what):
+        G.assert_struct_equal(rows, _window_oracle(tag), float_rtol=FLOAT_RTOL, what=what + " vs oracle")
+        want_rows = run["hits"][np.isin(run["hits"]["record_id"], whole)]
+        assert len(want_rows) >= len(run["hits"]) - 8
+        G.assert_struct_equal(rows[np.isin(rows["record_id"], whole)], want_rows, float_rtol=FLOAT_RTOL, what=what)
+
+    with DeviceSession(0) as s:  # its own context: the first grouped call is a cold one
+        s.upload_pool(pool)
+        s.upload_records(blank[plan[3][1]])
+        s.sosfiltfilt(*design_bw(*KEYS[3][1:]), download=False)
+        parts = []
+        for key, mask in plan:
+            s.upload_records(blank, np.where(mask, thr, np.inf))
+            if key[0] == "SG":
+                s.set_sg_plan(key[1], key[2])
+                parts.append(s.fused_baseline_filter_hits((0, 40)))
+            else:
+                s.baseline_mean(0, 40, update_records=True)
+                parts.append(s.threshold_hits(_lib.SRC_F32))
+        want = host_merge(rec, parts)
+        assert all(len(p) >= 20 for p in parts) and len(want) > 300
+        equals_reference(want, f"run {tag}: single passes with the window")
+        # the Butterworth records alone get a baseline on the host (its pass reads the uploaded ones); the Savitzky-Golay
+        # records stay NaN, so their rows can only come from the window of the grouped call
+        s.upload_records(blank)
+        sg_blank = blank.copy()
+        sg_blank["baseline"][plan[3][1]] = s.baseline_mean(0, 40)[plan[3][1]]
+        assert np.isnan(sg_blank["baseline"]).sum() == int((~plan[3][1]).sum())
+
+        def grouped(thresholds, window=(0, 40)):
+            s.upload_records(sg_blank, thresholds)
+            stage_groups(s, KEYS, group_column(plan), baseline_window=window)
+            return s._fill_hits(s.hits_wait())
+
+        s.upload_pool(pool)  # (drops the float32 twin of the single passes)
+        for call in ("cold", "warm", "warm again"):
+            got = grouped(thr)
+            assert got.tobytes() == want.tobytes(), (tag, call)
+            equals_reference(got, f"run {tag} {call}: grouped call with the window")
+        assert len(grouped(np.full(len(rec), 1e9))) == 0
+        got = grouped(thr)  # every group's launch was sized by a pass without rows
+        assert got.tobytes() == want.tobytes(), (tag, "after an empty call")
+        equals_reference(got, f"run {tag}: grouped call after an empty one")
+        # and without the window only the Butterworth records, the ones with a baseline, give rows
+        got = grouped(thr, window=(0, 0))
+        assert got.tobytes() == parts[3].tobytes()
+
+
+# ---- 8. error contract ----------------------------------------------------------------------------------------------------
 def test_error_codes_of_the_new_calls():
     run = load_run("a")
     rec, pool = run["records"], run["wave_pool"]
     with DeviceSession(0) as s:
         lib, h = s._lib, s._h
-        thr = np.full(len(rec), 10.0)
-        ptr = thr.ctypes.data
-        assert lib.wfa_set_thresholds(h, ptr, len(rec)) == _lib.WFA_E_STATE  # no records
-        assert lib.wfa_hit_rows_merge_add(h) == _lib.WFA_E_STATE  # no open set
-        n = _lib.C.c_int64(-1)
-        assert lib.wfa_hit_rows_merge_end(h, _lib.C.byref(n)) == _lib.WFA_E_STATE
         s.upload_pool(pool)
         s.upload_records(rec, 10.0)
-        assert lib.wfa_set_thresholds(h, ptr, len(rec) - 1) == _lib.WFA_E_INVALID  # wrong count
-        assert lib.wfa_set_thresholds(h, ptr, len(rec)) == 0
-        assert lib.wfa_hit_rows_merge_begin(h) == 0
-        assert lib.wfa_hit_rows_merge_add(h) == _lib.WFA_E_STATE  # no pass yet
-        assert lib.wfa_hit_rows_merge_end(h, _lib.C.byref(n)) == 0 and n.value == 0  # an empty set: 0 rows
-        assert len(s._fill_hits(0)) == 0
-        assert lib.wfa_hit_rows_merge_add(h) == _lib.WFA_E_STATE  # the set is closed
-        # a merged table carries no record index: it cannot be added to another set
-        s.set_sg_plan(11, 2)
-        with s.merged_hit_rows() as merge:
-            assert s.threshold_hits(_lib.SRC_SG_FUSED, download=False) > 100
-            merge.add()
-        assert merge.n_hits > 100
-        assert lib.wfa_hit_rows_merge_begin(h) == 0
-        assert lib.wfa_hit_rows_merge_add(h) == _lib.WFA_E_STATE
+        s.store_sg_plan(0, 11, 2)
+        s.store_sg_plan(1, 11, 2)
+        groups = (_lib.C.c_int32 * 4)(_lib.SRC_SG_FUSED, 0, _lib.SRC_SG_FUSED, 1)
+        gor = np.ascontiguousarray(rec["channel"] % 2, dtype=np.int32)
+        assert lib.wfa_hits_enqueue_groups(h, 2, groups, gor.ctypes.data, -1, 40, 2, 2, 0) == _lib.WFA_E_INVALID
+        assert "baseline window start" in _lib.last_error()
+        assert lib.wfa_hits_enqueue_groups(h, 2, groups, gor.ctypes.data, -1, -1, 2, 2, 0) == 0  # an empty window: none
+        n = s.hits_wait()
+        assert n > 100
+        first = s._fill_hits(n)
+        # a merged table carries no record index: the next call stashes the rows of its own passes, never the table
+        assert lib.wfa_hits_enqueue_groups(h, 2, groups, gor.ctypes.data, 0, 0, 2, 2, 0) == 0
+        assert s.hits_wait() == n and s._fill_hits(n).tobytes() == first.tobytes()
         # the stash is scratch
         held = s.scratch_bytes()
-        assert held >= merge.n_hits * 64
+        assert held >= n * 64
         s.release_scratch()
         assert s.scratch_bytes() == 0
-        assert lib.wfa_hit_rows_merge_add(h) == _lib.WFA_E_STATE  # the open set went with the scratch
-        assert len(s._fill_hits(merge.n_hits)) == merge.n_hits  # the merged table stays
+        assert len(s._fill_hits(n)) == n  # the merged table stays

@@ -3,8 +3,8 @@ the calls below it: wfa_sg_plan_store, wfa_sosfiltfilt_group, wfa_hits_enqueue_g
 
 The stream must give the rows of hit_threshold under the same Context whatever the chunk size: the reference's rows on
 the fixture runs of tests/golden/c5_fused_groups.npz, the run-wide oracle on the runs of tests/stream_groups_util.py.
-The queued grouped call must give, byte for byte, the table of the synchronous sequence it replaces
-(tests/fused_groups_util.run_groups)."""
+The queued grouped call must give, byte for byte, the host merge of the groups' single passes run one after another
+(tests/fused_groups_util.run_groups, host_merge)."""
 
 from __future__ import annotations
 
@@ -112,15 +112,7 @@ def test_sg_only_configuration_and_the_exact_redo(dp):
 def _queued(s, rec, thr, keys, gor, option=None):
     """upload + the queued grouped pass on a session that holds the pool -> (rows, pending right after the call)."""
     s.upload_records(rec, thr)
-    groups = []
-    for g, key in enumerate(keys):
-        if key[0] == "BW":
-            s.sosfiltfilt_group(*design_bw(*key[1:]), gor, g)
-            groups.append((_lib.SRC_F32, 0))
-        else:
-            s.store_sg_plan(g, key[1], key[2])
-            groups.append((_lib.SRC_SG_FUSED, g))
-    s.hits_enqueue_groups(groups, gor, 2, 2)
+    F.stage_groups(s, keys, gor)
     pending = s.hits_pending()
     n = s.hits_wait()
     assert not s.hits_pending()
@@ -128,8 +120,13 @@ def _queued(s, rec, thr, keys, gor, option=None):
 
 
 def _synchronous(s, rec, thr, keys, gor):
-    n_parts, n = F.run_groups(s, rec, thr, [(key, gor == g) for g, key in enumerate(keys)])
-    return s._fill_hits(n), n_parts
+    """The groups' single passes, each waited for and downloaded, merged on the host -> (table, the passes' rows).
+    run_groups ends with a queued grouped call of its own -- on a context that has not seen these groups, the cold one --
+    whose table must already be that merge."""
+    parts, n = F.run_groups(s, rec, thr, [(key, gor == g) for g, key in enumerate(keys)])
+    want = F.host_merge(rec, parts)
+    assert s._fill_hits(n).tobytes() == want.tobytes()
+    return want, parts
 
 
 def _channel_groups(rec):
@@ -165,7 +162,7 @@ def test_queued_call_equals_the_synchronous_sequence(sess, tag, case):
         sess.set_option("no_speculate", True)
     try:
         sess.upload_pool(pool)
-        for call in range(3):      # a cold context, then warm ones: every group's previous count is known
+        for call in range(3):      # warm calls (the cold one ran inside _synchronous): every group's previous count is known
             got, pending = _queued(sess, rec, thr, keys, gor)
             print(f"run {tag} {case} call {call}: {len(got)} rows, pending after the call: {pending}")
             assert got.tobytes() == want.tobytes(), (tag, case, call)
@@ -201,7 +198,7 @@ def test_resident_stages_read_the_queued_merged_table(sess, tag):
                                   rows["board"], rows["channel"], rows["record_id"], 1000.0)
     for name in want:
         np.testing.assert_array_equal(got[name], want[name], err_msg=name)
-    # the stash is scratch, at the cost per row of the synchronous merge
+    # the stash is scratch: 64 bytes per stashed row
     before = sess.scratch_bytes()
     assert before >= 64 * n
     assert sess.release_scratch() == before and sess.scratch_bytes() == 0
@@ -279,7 +276,7 @@ def test_error_codes_of_the_new_calls():
         one = (C.c_int32 * 2)(_lib.SRC_SG_FUSED, 0)
 
         def enqueue(n_groups, groups, column, max_len=0):
-            return lib.wfa_hits_enqueue_groups(h, n_groups, groups, column.ctypes.data, 2, 2, max_len)
+            return lib.wfa_hits_enqueue_groups(h, n_groups, groups, column.ctypes.data, 0, 0, 2, 2, max_len)
 
         def bw(column, group=0):
             return lib.wfa_sosfiltfilt_group(h, len(sos), sos.ctypes.data, zi.ctypes.data, padlen, column.ctypes.data, group)
@@ -328,7 +325,7 @@ def test_error_codes_of_the_new_calls():
 def test_exceeded_bound_is_redone_exactly():
     """A warm context whose groups found nothing sizes every group's launch for 4096 rows; the next call finds about
     6000 rows per group.  The call still returns with the pass pending, wfa_hits_wait sees the bounds exceeded and redoes
-    the grouped pass the exact way: the table of the synchronous sequence, byte for byte."""
+    the grouped pass the exact way: the host merge of the groups' single passes, byte for byte."""
     n, L = 12_000, 64
     rng = np.random.default_rng(31)
     pool = np.concatenate([S._wave(L, 4, rng) for _ in range(n)])       # two hits per record

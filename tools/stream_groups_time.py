@@ -3,18 +3,15 @@
 Data: a synthetic V1725 run (synth.make_run, uniform L = 800) cut into bench-sized chunks (`--chunk-records`, default
 50 000 = 4e7 samples per chunk); the records' channels are rewritten to k % 3 of board 0 and the three channels take the
 Savitzky-Golay pairs (11, 2), (7, 3) and (21, 4) -- the last one outside the streaming kernel's windows -- with thresholds
-10 / 8 / 10.  The ring (HipThresholdHitStream.run_chunks, two sessions on device 0) runs the chunk list in three ways:
+10 / 8 / 10.  The ring (HipThresholdHitStream.run_chunks, two sessions on device 0) runs the chunk list in two ways:
 
   one_group     the default path: SG(11, 2) and one threshold for every record, one queued pass per chunk;
-  queued        filter_source="wave_pool_filtered": the three groups through one wfa_hits_enqueue_groups per chunk;
-  synchronous   the same three groups, per chunk the sequence the static plugin runs (wfa_set_thresholds,
-                wfa_set_sg_plan, one pass, wfa_hit_rows_merge_add per group, then wfa_hit_rows_merge_end): four host
-                waits per group.
+  queued        filter_source="wave_pool_filtered": the three groups through one wfa_hits_enqueue_groups per chunk.
 
-After `--warmup` rounds (every way once per round: buffers sized, clocks up) the three ways alternate for `--repeats`
+After `--warmup` rounds (every way once per round: buffers sized, clocks up) the two ways alternate for `--repeats`
 rounds; per way the median, the fastest and the slowest round, Gsamples/s at the median, and the median host time one
-chunk spends in _stage (uploads, queueing and whatever the host waits for there).  `queued` and `synchronous`
-must give the same bytes.  One JSON line per way, then one with the ratios.
+chunk spends in _stage (uploads, queueing and whatever the host waits for there).  One JSON line per way, then one with
+the ratio.
 
     python tools/stream_groups_time.py [--records 400000] [--chunk-records 50000] [--warmup 2] [--repeats 7]
 """
@@ -32,7 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import numpy as np  # noqa: E402
 
-from waveformanalysis_amd import _lib, synth  # noqa: E402
+from waveformanalysis_amd import synth  # noqa: E402
 from waveformanalysis_amd.device import DevicePool  # noqa: E402
 from waveformanalysis_amd.plugin_api import SimpleContext  # noqa: E402
 from waveformanalysis_amd.plugins import HipWavePoolFilteredPlugin  # noqa: E402
@@ -40,26 +37,6 @@ from waveformanalysis_amd.streaming import HipThresholdHitStream, records_to_chu
 
 FILTER_CC = {"0:1": {"sg_window_size": 7, "sg_poly_order": 3}, "0:2": {"sg_window_size": 21, "sg_poly_order": 4}}
 HIT_CC = {"0:1": {"threshold": 8.0}}
-
-
-class SynchronousGroups(HipThresholdHitStream):
-    """The stream with the grouped pass of a chunk run as the synchronous sequence of the static plugin."""
-
-    def _stage_planned(self, sess, chunk, wave_pool, max_len, plan):
-        recs = chunk.data
-        lo = int(recs["wave_offset"].min())
-        hi = int((recs["wave_offset"].astype(np.int64) + recs["event_length"]).max())
-        sub = recs.copy()
-        sub["wave_offset"] -= lo
-        group_of_record, own = plan.lookup(recs)
-        sess.upload_pool(np.ascontiguousarray(wave_pool[lo:hi]))
-        sess.upload_records(sub, np.inf)
-        with sess.merged_hit_rows() as merge:
-            for g, key in enumerate(plan.keys):
-                sess.set_thresholds(np.where(group_of_record == g, own, np.inf))
-                sess.set_sg_plan(key[1], key[2])
-                sess.threshold_hits(_lib.SRC_SG_FUSED, self.le, self.re, max_len=int(max_len), download=False)
-                merge.add()
 
 
 def main() -> None:
@@ -84,7 +61,6 @@ def main() -> None:
     ways = {
         "one_group": (HipThresholdHitStream(device_pool=dp), ctx_one),
         "queued": (HipThresholdHitStream(device_pool=dp), ctx_groups),
-        "synchronous": (SynchronousGroups(device_pool=dp), ctx_groups),
     }
     times = {name: [] for name in ways}
     stage = {name: [] for name in ways}     # host time inside _stage per chunk: uploads + whatever the host waits for
@@ -100,7 +76,6 @@ def main() -> None:
                 stage[name] += [queued - begin for _k, begin, queued, _collected in timeline]
             tables[name] = np.concatenate([o.data for o in outs])
     dp.close()
-    assert tables["queued"].tobytes() == tables["synchronous"].tobytes(), "queued and synchronous tables differ"
     med = {}
     for name, ts in times.items():
         med[name] = statistics.median(ts)
@@ -108,9 +83,7 @@ def main() -> None:
                           "median_s": round(med[name], 5), "min_s": round(min(ts), 5), "max_s": round(max(ts), 5),
                           "gsamples_per_s": round(pool.size / med[name] / 1e9, 3), "rounds": len(ts),
                           "stage_ms_per_chunk_median": round(1e3 * statistics.median(stage[name]), 3)}))
-    print(json.dumps({"queued_over_synchronous": round(med["queued"] / med["synchronous"], 4),
-                      "queued_over_one_group": round(med["queued"] / med["one_group"], 4),
-                      "tables_identical": True}))
+    print(json.dumps({"queued_over_one_group": round(med["queued"] / med["one_group"], 4)}))
 
 
 if __name__ == "__main__":

@@ -26,7 +26,7 @@ ST_SRC_HOST, ST_SRC_CSV, ST_SRC_ARENA, ST_SRC_POOL = 0, 1, 2, 3
 VIEW_WAVES, VIEW_WAVES_BASELINE, VIEW_SIGNALS = 0, 1, 2
 VIEW_U16, VIEW_F32, VIEW_F64 = 0, 1, 2
 DENSE_I16, DENSE_U16, DENSE_F32 = 0, 1, 2
-ABI_VERSION = 4
+ABI_VERSION = 5
 MAX_HIT_GROUPS = 8
 
 _p = C.c_void_p
@@ -62,13 +62,9 @@ SIGNATURES = {
     "wfa_fused_baseline_filter_hits": (_int, [_p, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64)]),
     "wfa_hits_enqueue": (_int, [_p, _int, _i32, _i32, _i32, _i32, _i32]),
     "wfa_hits_wait": (_int, [_p, C.POINTER(_i64)]),
-    "wfa_set_thresholds": (_int, [_p, _p, _i64]),
-    "wfa_hit_rows_merge_begin": (_int, [_p]),
-    "wfa_hit_rows_merge_add": (_int, [_p]),
-    "wfa_hit_rows_merge_end": (_int, [_p, C.POINTER(_i64)]),
     "wfa_sg_plan_store": (_int, [_p, _int, _int, _int, _p, _p, _int, _p, _i32, _i32, _i64, _i64]),
     "wfa_sosfiltfilt_group": (_int, [_p, _int, _p, _p, _i32, _p, _i32]),
-    "wfa_hits_enqueue_groups": (_int, [_p, _int, _p, _p, _i32, _i32, _i32]),
+    "wfa_hits_enqueue_groups": (_int, [_p, _int, _p, _p, _i32, _i32, _i32, _i32, _i32]),
     "wfa_hits_pending": (_int, [_p, C.POINTER(_int)]),
     "wfa_find_peaks_count": (_int, [_p, _int, _int, _int, _f64, _int, _f64, _i32, _f64, _f64, _int, _i32, C.POINTER(_i64)]),
     "wfa_find_peaks_fill": (_int, [_p, _p, _i64]),

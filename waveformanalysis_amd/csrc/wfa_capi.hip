@@ -860,9 +860,6 @@ int wfa_release_scratch(wfa_ctx* c, int64_t* freed_bytes) {
     c->csv_filled = false;
     pass_caches_dropped(c);
     c->hit_tmp_rows = 0;
-    c->merge_open = false;  // the stash of an open merge set went with the scratch: wfa_hit_rows_merge_begin starts over
-    c->merge_n = 0;
-    c->merge_start.clear();
     if (freed_bytes) *freed_bytes = freed;
     return WFA_OK;
 }
@@ -1407,31 +1404,13 @@ int wfa_threshold_hits_fill(wfa_ctx* c, void* out_rows, int64_t n_hits) {
     return WFA_OK;
 }
 
-int wfa_set_thresholds(wfa_ctx* c, const double* threshold, int64_t n_records) {
-    int rc = use_device(c);
-    if (rc) return rc;
-    if (!c->have_records) return fail(WFA_E_STATE, "records not uploaded");
-    if (n_records != c->R)
-        return fail(WFA_E_INVALID, "caller passes %lld thresholds, %lld records are uploaded", (long long)n_records, (long long)c->R);
-    if (n_records > 0 && !threshold) return fail(WFA_E_INVALID, "threshold is null");
-    if (c->pending) {  // the queued pass reads the column that is about to change
-        int64_t n = 0;
-        if ((rc = wfa_hits_wait(c, &n))) return rc;
-    }
-    // the column alone: no records_replaced(), so the layout record, the padded shadow, the device baselines, the plan and
-    // the rows of the last pass stand
-    if ((rc = h2d_copy(c, c->thr.ptr, threshold, (size_t)n_records * sizeof(double)))) return rc;
-    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return WFA_OK;
-}
-
 }  // extern "C"
 
-// ---- rows of several hit passes merged into one table (wfa_hit_rows_merge_*) ---------------------------------------
+// ---- the grouped pass: one pass per filter group, the rows merged into one table (wfa_hits_enqueue_groups) ----------
 // The passes run over the same uploaded records with thresholds that leave every record to one of them (per-channel
 // filter settings: cpu/filtering.py:339-374 resolved per record, hit_finder.py:288-327 for the thresholds); the reference
 // finds the hits of all records in one loop and so emits them by (record index, start) (hit_finder.py:354-366).  Every
-// added pass is stashed as it is -- its 60-byte rows and the record index of each -- and the merge is a per-record row
+// pass is stashed as it is -- its 60-byte rows and the record index of each -- and the merge is a per-record row
 // count, an exclusive scan over the records and a scatter of the rows.  `rec` of one pass ascends, so the rows of a
 // record inside a pass are found by binary search.
 constexpr int kMergeBlock = 256;
@@ -1452,23 +1431,6 @@ __device__ __forceinline__ int64_t merge_bound(const int32_t* __restrict__ rec, 
         if (Upper ? v <= r : v < r) lo = mid + 1; else hi = mid;
     }
     return lo;
-}
-
-// record index of every row of the pass just run.  desc != null: the run descriptors of the streaming / bitmap routes;
-// otherwise the general route's exclusive scan of the per-record counts (row i belongs to the last record whose first row
-// is <= i: the records behind it without a hit start past i)
-__global__ __launch_bounds__(kMergeBlock) void k_hit_rows_merge_index(int64_t n, const int4* __restrict__ desc,
-                                                                      const int64_t* __restrict__ out_start, int64_t R,
-                                                                      int32_t* __restrict__ rec) {
-    const int64_t i = (int64_t)blockIdx.x * kMergeBlock + threadIdx.x;
-    if (i >= n) return;
-    if (desc) { rec[i] = desc[i].x; return; }
-    int64_t lo = 0, hi = R;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (out_start[mid] <= i) lo = mid + 1; else hi = mid;
-    }
-    rec[i] = (int32_t)(lo - 1);
 }
 
 // per-record row count over all passes: the first row of a record inside a pass adds that pass's rows of the record
@@ -1543,127 +1505,13 @@ static int merge_grow(wfa_ctx* c, DevBuf& b, size_t used, size_t want) {
     return WFA_OK;
 }
 
-extern "C" {
-
-int wfa_hit_rows_merge_begin(wfa_ctx* c) {
-    int rc = use_device(c);
-    if (rc) return rc;
-    c->merge_open = true;
-    c->merge_n = 0;
-    c->merge_R = -1;
-    c->merge_start.assign(1, 0);
-    return WFA_OK;
-}
-
-int wfa_hit_rows_merge_add(wfa_ctx* c) {
-    int rc = use_device(c);
-    if (rc) return rc;
-    if (!c->merge_open) return fail(WFA_E_STATE, "no merge set is open (wfa_hit_rows_merge_begin)");
-    if (c->pending) {
-        int64_t n = 0;
-        if ((rc = wfa_hits_wait(c, &n))) return rc;
-    }
-    if (c->n_hits < 0) return fail(WFA_E_STATE, "no hit pass has been run");
-    if (c->merge_R >= 0 && c->merge_R != c->R)
-        return fail(WFA_E_INVALID, "the passes of a merge set run over one records table (%lld records, now %lld)",
-                    (long long)c->merge_R, (long long)c->R);
-    c->merge_R = c->R;
-    const int64_t n = c->n_hits, at = c->merge_n;
-    if (n > 0) {
-        if (c->rows_index == 0)
-            return fail(WFA_E_STATE, "the resident rows carry no record index (a merged table, or another stage ran since the pass)");
-        if ((rc = merge_grow(c, c->merge_rows, (size_t)at * 60, (size_t)(at + n) * 60))) return rc;
-        if ((rc = merge_grow(c, c->merge_rec, (size_t)at * sizeof(int32_t), (size_t)(at + n) * sizeof(int32_t)))) return rc;
-        LaunchTimer t(c);
-        WFA_HIP_CHECK(hipMemcpyAsync(c->merge_rows.as<uint8_t>() + at * 60, c->hit_out.ptr, (size_t)n * 60,
-                                     hipMemcpyDeviceToDevice, c->stream));
-        hipLaunchKernelGGL(k_hit_rows_merge_index, dim3(merge_grid(n)), dim3(kMergeBlock), 0, c->stream, n,
-                           c->rows_index == 1 ? c->hit_desc.as<int4>() : nullptr, c->rec_out_start.as<int64_t>(), c->R,
-                           c->merge_rec.as<int32_t>() + at);
-        WFA_HIP_CHECK(hipGetLastError());
-        if ((rc = t.end("k_hit_rows_merge_index (+ row stash)"))) return rc;
-        WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    }
-    c->merge_n = at + n;
-    c->merge_start.push_back(c->merge_n);
-    return WFA_OK;
-}
-
-int wfa_hit_rows_merge_end(wfa_ctx* c, int64_t* n_hits) {
-    int rc = use_device(c);
-    if (rc) return rc;
-    if (!n_hits) return fail(WFA_E_INVALID, "n_hits is null");
-    if (!c->merge_open) return fail(WFA_E_STATE, "no merge set is open (wfa_hit_rows_merge_begin)");
-    if (c->pending) {  // a pass that was queued and never added: it ends here, its rows are replaced
-        int64_t n = 0;
-        if ((rc = wfa_hits_wait(c, &n))) return rc;
-    }
-    c->merge_open = false;
-    const int64_t total = c->merge_n, R = c->merge_R;
-    const int G = (int)c->merge_start.size() - 1;
-    c->merge_n = 0;
-    if (total > 0) {
-        const int64_t nb = scan_blocks_for(R);
-        const int64_t want = rows_bound(total);  // head room, so that a later single pass can speculate
-        if ((rc = c->rec_nhits.ensure((size_t)R * sizeof(int32_t))) || (rc = c->rec_out_start.ensure((size_t)R * sizeof(int64_t))) ||
-            (rc = c->scan_blocks.ensure((size_t)(nb + 1) * sizeof(int64_t))) || (rc = c->merge_dest.ensure((size_t)total * sizeof(int64_t))) ||
-            (rc = c->merge_sets.ensure((size_t)(G + 1) * sizeof(int64_t))) || (rc = c->hit_out.ensure((size_t)want * 60)) ||
-            (rc = c->hit_desc.ensure((size_t)want * sizeof(int4))))
-            return rc;
-        const int32_t* rec = c->merge_rec.as<int32_t>();
-        const int64_t* sets = c->merge_sets.as<int64_t>();
-        int32_t* counts = c->rec_nhits.as<int32_t>();
-        WFA_HIP_CHECK(hipMemcpyAsync(c->merge_sets.ptr, c->merge_start.data(), (size_t)(G + 1) * sizeof(int64_t),
-                                     hipMemcpyHostToDevice, c->stream));
-        WFA_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)R * sizeof(int32_t), c->stream));
-        {
-            LaunchTimer t(c);
-            hipLaunchKernelGGL(k_hit_rows_merge_count, dim3(merge_grid(total)), dim3(kMergeBlock), 0, c->stream, total, rec,
-                               sets, G, R, counts, (const int64_t*)nullptr);
-            WFA_HIP_CHECK(hipGetLastError());
-            if ((rc = t.end("k_hit_rows_merge_count"))) return rc;
-        }
-        {
-            LaunchTimer t(c);
-            WFA_HIP_CHECK(launch_scan(c->stream, counts, R, c->scan_blocks.as<int64_t>(), c->rec_out_start.as<int64_t>()));
-            if ((rc = t.end("k_scan(merged hit counts)"))) return rc;
-        }
-        {
-            LaunchTimer t(c);
-            hipLaunchKernelGGL(k_hit_rows_merge_place, dim3(merge_grid(total)), dim3(kMergeBlock), 0, c->stream, total, rec,
-                               sets, G, R, c->rec_out_start.as<int64_t>(), c->merge_dest.as<int64_t>(), (const int64_t*)nullptr);
-            WFA_HIP_CHECK(hipGetLastError());
-            if ((rc = t.end("k_hit_rows_merge_place"))) return rc;
-        }
-        {
-            LaunchTimer t(c);
-            hipLaunchKernelGGL(k_hit_rows_merge_scatter, dim3(merge_grid(total * 15)), dim3(kMergeBlock), 0, c->stream, total,
-                               c->merge_rows.as<uint32_t>(), c->merge_dest.as<int64_t>(), c->hit_out.as<uint32_t>(),
-                               (const int64_t*)nullptr);
-            WFA_HIP_CHECK(hipGetLastError());
-            if ((rc = t.end("k_hit_rows_merge_scatter"))) return rc;
-        }
-        WFA_HIP_CHECK(hipStreamSynchronize(c->stream));  // (merge_start is read by the copy above until here)
-    }
-    c->merge_start.clear();
-    // the merged table is "the rows of the last hit pass" from here on, for wfa_threshold_hits_fill and the resident stages
-    c->n_hits = total;
-    c->last_hits = total;
-    c->rows_index = 0;
-    *n_hits = total;
-    return WFA_OK;
-}
-
-}  // extern "C"
-
-// ---- the grouped pass, queued (wfa_hits_enqueue_groups) ------------------------------------------------------------
-// What the synchronous sequence above does with four host waits per group, on the context's stream: per group a kernel
-// writes the own-or-+inf threshold column from group_of_record, the group's plan is swapped in from its resident slot,
-// the existing pass is queued (run_hits, enqueue_only), one thread takes the pass's row count where the pass reported it
-// (the pinned words of a queued pass, or the count the host already holds) and writes the group's stash offset, and a copy
-// kernel launched for the pass's row bound moves that many rows and record indices to the stash.  The merge kernels are
-// launched for the sum of the bounds and read the total from the last stash offset.  The caller's threshold column is
-// saved before the first group and copied back behind the last.
+// Everything is queued on the context's stream: per group a kernel writes the own-or-+inf threshold column from
+// group_of_record, the group's plan is swapped in from its resident slot, the single pass is queued (run_hits,
+// enqueue_only), one thread takes the pass's row count where the pass reported it (the pinned words of a queued pass, or
+// the count the host already holds) and writes the group's stash offset, and a copy kernel launched for the pass's row
+// bound moves that many rows and record indices to the stash.  The merge kernels are launched for the sum of the bounds
+// and read the total from the last stash offset.  The caller's threshold column is saved before the first group and
+// copied back behind the last.
 //
 // Pinned block (int64 words): per group (rows, overflow flags) of its pass, the stash offsets as the device wrote them
 // ([n_groups] = the merged row count), the fail flag (a group outgrew its bound, its events or the stash).
@@ -1703,8 +1551,10 @@ __global__ void k_grp_take(int g, int64_t n_host, int runs32, int64_t bound, int
     h[kGrpFail] = sets[kGrpFailDev];
 }
 
-// Rows of group g's pass into the stash, 15 dwords per row, and the record index of every row (k_hit_rows_merge_index's
-// two sources).  Launched for the pass's row bound; the count stands in sets[].
+// Rows of group g's pass into the stash, 15 dwords per row, and the record index of every row.  desc != null: the run
+// descriptors of the streaming / bitmap routes; otherwise the general route's exclusive scan of the per-record counts (row
+// d belongs to the last record whose first row is <= d: the records behind it without a hit start past d).  Launched for
+// the pass's row bound; the count stands in sets[].
 __global__ __launch_bounds__(kMergeBlock) void k_grp_stash(int g, const int64_t* __restrict__ sets,
                                                            const uint32_t* __restrict__ rows, const int4* __restrict__ desc,
                                                            const int64_t* __restrict__ out_start, int64_t R,
@@ -1777,19 +1627,21 @@ static int groups_prime_cold(wfa_ctx* c, int g) {
     return WFA_OK;
 }
 
-// One pass of the grouped call under group g's plan (SG groups) on the threshold column as it stands.
+// One pass of the grouped call under group g's plan and the call's baseline window (SG groups) on the threshold column as
+// it stands.
 static int groups_one_pass(wfa_ctx* c, int g, bool exact) {
     wfa_ctx::GroupsPass& G = c->grp;
     const bool sg = G.groups[g].source == WFA_SRC_SG_FUSED;
     const bool had_sg = c->have_sg;
+    const bool fused_bl = sg && G.bl_end > G.bl_start;  // (WFA_SRC_F32 reads the uploaded baselines, as in wfa_hits_enqueue)
     int rc = WFA_OK;
     if (sg) {
         sg_plan_swap(c->sg, c->sg_slot[G.groups[g].plan_slot]);
         c->have_sg = true;
-        rc = groups_prime_cold(c, g);
+        rc = groups_prime_cold(c, g);  // (a window the streaming kernel does not take: the block is queued for nothing)
     }
     c->last_hits = exact ? -1 : G.last[g];
-    if (!rc) rc = run_hits(c, G.groups[g].source, false, 0, 0, G.le, G.re, G.max_len, nullptr, true);
+    if (!rc) rc = run_hits(c, G.groups[g].source, fused_bl, G.bl_start, G.bl_end, G.le, G.re, G.max_len, nullptr, true);
     if (sg) {
         sg_plan_swap(c->sg, c->sg_slot[G.groups[g].plan_slot]);
         c->have_sg = had_sg;
@@ -1895,17 +1747,33 @@ static int groups_run(wfa_ctx* c, bool exact) {
         const int64_t* total = sets + n;
         if (hipMemsetAsync(counts, 0, (size_t)R * sizeof(int32_t), c->stream) != hipSuccess)
             return leave(fail(WFA_E_HIP, "clearing the merge counts failed"));
-        LaunchTimer t(c);
-        hipLaunchKernelGGL(k_hit_rows_merge_count, dim3(merge_grid(n_bound)), dim3(kMergeBlock), 0, c->stream, n_bound, rec,
-                           (const int64_t*)sets, n, R, counts, total);
-        if (launch_scan(c->stream, counts, R, c->scan_blocks.as<int64_t>(), c->rec_out_start.as<int64_t>()) != hipSuccess)
-            return leave(fail(WFA_E_HIP, "k_scan(merged hit counts) launch failed"));
-        hipLaunchKernelGGL(k_hit_rows_merge_place, dim3(merge_grid(n_bound)), dim3(kMergeBlock), 0, c->stream, n_bound, rec,
-                           (const int64_t*)sets, n, R, c->rec_out_start.as<int64_t>(), c->merge_dest.as<int64_t>(), total);
-        hipLaunchKernelGGL(k_hit_rows_merge_scatter, dim3(merge_grid(n_bound * 15)), dim3(kMergeBlock), 0, c->stream, n_bound,
-                           c->merge_rows.as<uint32_t>(), c->merge_dest.as<int64_t>(), c->hit_out.as<uint32_t>(), total);
-        if (hipGetLastError() != hipSuccess) return leave(fail(WFA_E_HIP, "k_hit_rows_merge_* launch failed"));
-        if ((rc = t.end("k_hit_rows_merge_* (device totals)"))) return leave(rc);
+        {
+            LaunchTimer t(c);
+            hipLaunchKernelGGL(k_hit_rows_merge_count, dim3(merge_grid(n_bound)), dim3(kMergeBlock), 0, c->stream, n_bound, rec,
+                               (const int64_t*)sets, n, R, counts, total);
+            if (hipGetLastError() != hipSuccess) return leave(fail(WFA_E_HIP, "k_hit_rows_merge_count launch failed"));
+            if ((rc = t.end("k_hit_rows_merge_count"))) return leave(rc);
+        }
+        {
+            LaunchTimer t(c);
+            if (launch_scan(c->stream, counts, R, c->scan_blocks.as<int64_t>(), c->rec_out_start.as<int64_t>()) != hipSuccess)
+                return leave(fail(WFA_E_HIP, "k_scan(merged hit counts) launch failed"));
+            if ((rc = t.end("k_scan(merged hit counts)"))) return leave(rc);
+        }
+        {
+            LaunchTimer t(c);
+            hipLaunchKernelGGL(k_hit_rows_merge_place, dim3(merge_grid(n_bound)), dim3(kMergeBlock), 0, c->stream, n_bound, rec,
+                               (const int64_t*)sets, n, R, c->rec_out_start.as<int64_t>(), c->merge_dest.as<int64_t>(), total);
+            if (hipGetLastError() != hipSuccess) return leave(fail(WFA_E_HIP, "k_hit_rows_merge_place launch failed"));
+            if ((rc = t.end("k_hit_rows_merge_place"))) return leave(rc);
+        }
+        {
+            LaunchTimer t(c);
+            hipLaunchKernelGGL(k_hit_rows_merge_scatter, dim3(merge_grid(n_bound * 15)), dim3(kMergeBlock), 0, c->stream, n_bound,
+                               c->merge_rows.as<uint32_t>(), c->merge_dest.as<int64_t>(), c->hit_out.as<uint32_t>(), total);
+            if (hipGetLastError() != hipSuccess) return leave(fail(WFA_E_HIP, "k_hit_rows_merge_scatter launch failed"));
+            if ((rc = t.end("k_hit_rows_merge_scatter"))) return leave(rc);
+        }
     }
     (void)leave(WFA_OK);
     if (queued) {  // wfa_hits_wait reads the pinned block
@@ -1993,7 +1861,7 @@ int wfa_sosfiltfilt_group(wfa_ctx* c, int n_sections, const double* sos, const d
 }
 
 int wfa_hits_enqueue_groups(wfa_ctx* c, int n_groups, const wfa_hit_group* groups, const int32_t* group_of_record,
-                            int32_t le, int32_t re, int32_t max_len) {
+                            int32_t bl_start, int32_t bl_end, int32_t le, int32_t re, int32_t max_len) {
     int rc = use_device(c);
     if (rc) return rc;
     if (n_groups < 1 || n_groups > WFA_MAX_HIT_GROUPS)
@@ -2022,6 +1890,7 @@ int wfa_hits_enqueue_groups(wfa_ctx* c, int n_groups, const wfa_hit_group* group
             return fail(WFA_E_INVALID, "group_of_record[%lld] = %d is outside [-1, %d)", (long long)r, v, n_groups);
         unowned |= v < 0;
     }
+    if (bl_end > bl_start && bl_start < 0) return fail(WFA_E_INVALID, "baseline window start must be >= 0");
     if (le < 0) le = 0;
     if (re < 0) re = 0;
     if (max_len <= 0) max_len = c->max_len;
@@ -2034,6 +1903,7 @@ int wfa_hits_enqueue_groups(wfa_ctx* c, int n_groups, const wfa_hit_group* group
         for (int64_t& v : G.last) v = -1;  // other groups than last time: their previous counts say nothing
     G.n_groups = n_groups;
     memcpy(G.groups, groups, (size_t)n_groups * sizeof(wfa_hit_group));
+    G.bl_start = bl_start; G.bl_end = bl_end;
     G.le = le; G.re = re; G.max_len = max_len;
     G.single = n_groups == 1 && !unowned;
     G.R = c->R;

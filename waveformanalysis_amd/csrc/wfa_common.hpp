@@ -163,12 +163,9 @@ struct wfa_ctx {
     // per-record buffers taken by another stage), 1 hit_desc[i].x (streaming and bitmap routes), 2 rec_nhits /
     // rec_out_start (general route: per-record counts and their exclusive scan)
     int rows_index = 0;
-    // merge set of several hit passes over one records table (wfa_hit_rows_merge_*): the rows of the added passes back
-    // to back, the record index of every row, and where each pass's rows start (merge_start: one entry per pass + end)
-    bool merge_open = false;
-    int64_t merge_n = 0, merge_R = -1;
-    std::vector<int64_t> merge_start;
-    wfa::DevBuf merge_rows{scratch}, merge_rec{scratch}, merge_dest{scratch}, merge_sets{scratch};
+    // stash of a grouped pass (wfa_hits_enqueue_groups): the rows of the groups' passes back to back, the record index of
+    // every row, and the final place of every row in the merged table
+    wfa::DevBuf merge_rows{scratch}, merge_rec{scratch}, merge_dest{scratch};
     // resident plan slots (wfa_sg_plan_store): one Savitzky-Golay plan per filter group of a grouped pass, kept across
     // pool and records uploads like `sg`
     wfa::SgPlanDev sg_slot[WFA_MAX_HIT_GROUPS];
@@ -181,6 +178,7 @@ struct wfa_ctx {
         int n_groups = 0;
         int64_t R = -1;        // records the pass was queued over (the redo needs the same table)
         wfa_hit_group groups[WFA_MAX_HIT_GROUPS] = {};
+        int32_t bl_start = 0, bl_end = 0;  // baseline window of the WFA_SRC_SG_FUSED groups (bl_end <= bl_start: none)
         int32_t le = 0, re = 0, max_len = 0;
         int64_t bound[WFA_MAX_HIT_GROUPS] = {};
         int64_t n_host[WFA_MAX_HIT_GROUPS] = {};

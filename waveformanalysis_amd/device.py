@@ -78,17 +78,6 @@ def device_count() -> int:
     return int(n.value)
 
 
-class _HitRowsMerge:
-    """What DeviceSession.merged_hit_rows yields: add() after every pass, n_hits once the block is left."""
-
-    def __init__(self, sess: "DeviceSession"):
-        self._sess = sess
-        self.n_hits: int | None = None
-
-    def add(self) -> None:
-        _lib.check(self._sess._lib.wfa_hit_rows_merge_add(self._sess._h))
-
-
 class DeviceSession:
     """Owns a wfa_ctx.  Not thread-safe: use one session per thread (see device_pool)."""
 
@@ -377,39 +366,6 @@ class DeviceSession:
             dup = ordered[np.flatnonzero(np.diff(ordered) == 0)[0]]
             raise ValueError(f"records field record_id must be unique, got duplicate {int(dup)}")
 
-    def set_thresholds(self, thresholds: np.ndarray | float) -> None:
-        """Replace the device threshold column of the uploaded records (one float64 per record, a scalar is broadcast) and
-        nothing else: layout, padded shadow, device baselines, plan and pools stand (wfa_set_thresholds)."""
-        thr = np.asarray(thresholds, dtype=np.float64)
-        if thr.ndim == 0:
-            thr = np.broadcast_to(thr, (self.n_records,))
-        if thr.ndim != 1:
-            raise ValueError("thresholds must hold one value per record")
-        thr = np.ascontiguousarray(thr)
-        self._res_records = None  # the device columns are no longer what their owner uploaded
-        _lib.check(self._lib.wfa_set_thresholds(self._h, _ptr(thr), len(thr)))
-
-    @contextlib.contextmanager
-    def merged_hit_rows(self):
-        """Merge the rows of several hit passes over the uploaded records into one table on the device, in the
-        reference's order (record index, start):
-
-            with sess.merged_hit_rows() as merge:
-                for thr in per_pass_thresholds:      # +inf for the records another pass owns
-                    sess.set_thresholds(thr)
-                    sess.threshold_hits(..., download=False)
-                    merge.add()
-            merge.n_hits                             # rows of the merged table, resident like the rows of one pass
-
-        add() takes the rows of the last completed pass (wfa_hit_rows_merge_add); leaving the block merges
-        (wfa_hit_rows_merge_end).  An exception inside the block leaves the set open: the next block starts over."""
-        merge = _HitRowsMerge(self)
-        _lib.check(self._lib.wfa_hit_rows_merge_begin(self._h))
-        yield merge
-        n = C.c_int64(0)
-        _lib.check(self._lib.wfa_hit_rows_merge_end(self._h, C.byref(n)))
-        merge.n_hits = int(n.value)
-
     def set_sg_plan(self, sg_window_size: int = 11, sg_poly_order: int = 2) -> SgPlan:
         plan = build_plan(int(sg_window_size), int(sg_poly_order))
         _lib.check(
@@ -545,14 +501,16 @@ class DeviceSession:
         self._keep.append(gor)
 
     def hits_enqueue_groups(self, groups, group_of_record, left_extension: int = 2, right_extension: int = 2,
-                            max_len: int = 0) -> None:
+                            max_len: int = 0, baseline_window: tuple[int, int] = (0, 0)) -> None:
         """Queue the grouped hit pass (wfa_hits_enqueue_groups): groups = [(source, plan slot)], group_of_record = one
-        group index per uploaded record (-1: no pass owns the record).  hits_wait() / _fill_hits deliver the merged table."""
+        group index per uploaded record (-1: no pass owns the record), baseline_window as for hits_enqueue (the
+        SRC_SG_FUSED groups).  hits_wait() / _fill_hits deliver the merged table."""
         groups = [(int(s), int(p)) for s, p in groups]
         arr = (C.c_int32 * (2 * max(len(groups), 1)))(*[v for pair in groups for v in pair])
         gor = self._group_column(group_of_record)
+        start, end = baseline_window_i32(*baseline_window)
         self._res_records = None  # as for hits_enqueue
-        _lib.check(self._lib.wfa_hits_enqueue_groups(self._h, len(groups), arr, _ptr(gor), int(left_extension),
+        _lib.check(self._lib.wfa_hits_enqueue_groups(self._h, len(groups), arr, _ptr(gor), start, end, int(left_extension),
                                                      int(right_extension), int(max_len)))
         self._keep.append(gor)
 

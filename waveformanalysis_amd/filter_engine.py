@@ -13,6 +13,7 @@ from typing import Any
 
 import numpy as np
 
+from . import _lib
 from .channel_config import per_record_option
 
 # WFA_MAX_SOS_SECTIONS: the device filters at most this many second-order sections, i.e. band-pass orders up to it
@@ -102,6 +103,25 @@ def plan_fused_groups(context: Any, filter_plugin: Any, run_id: str, records: np
     boards = records["board"] if "board" in names else np.zeros(n, dtype=np.int16)
     channels = records["channel"] if "channel" in names else np.zeros(n, dtype=np.int16)
     return plan_filter_groups(context, filter_plugin, run_id, boards, channels)
+
+
+def stage_fused_groups(sess, keys, slots, design, group_of_record, le: int, re: int, max_len: int, **window) -> None:
+    """The fused hit pass over several filter groups, queued on a session whose pool and records are uploaded: group g
+    = keys[g], for the records with group_of_record == g.  A Butterworth group is filtered over the uploaded table into
+    the device float32 twin (design(g) -> (sos, zi, padlen)): no second records upload, the layout record and the padded
+    shadow stand.  A Savitzky-Golay group keeps its plan in slots[g], the key's index in the run-wide key list, so a
+    session finds its slots current in every chunk and shard of the run.  A group without a record stays in the call:
+    group g keeps its own previous row count.  `window`: baseline_window=(start, end) for the Savitzky-Golay groups, as
+    hits_enqueue_groups takes it; nothing for the uploaded baselines.  hits_wait() / _fill_hits deliver the merged table."""
+    groups = []
+    for g, key in enumerate(keys):
+        if key[0] == "BW":
+            sess.sosfiltfilt_group(*design(g), group_of_record, g)
+            groups.append((_lib.SRC_F32, 0))
+        else:
+            sess.store_sg_plan(slots[g], key[1], key[2])
+            groups.append((_lib.SRC_SG_FUSED, slots[g]))
+    sess.hits_enqueue_groups(groups, group_of_record, le, re, max_len, **window)
 
 
 def run_filter_groups(sess, records: np.ndarray, groups, download: bool = True) -> np.ndarray | None:

@@ -8,11 +8,11 @@ from typing import Any
 
 import numpy as np
 
-from .. import dense
+from .. import _lib, dense
 from ..dtypes import THRESHOLD_HIT_DTYPE
 from ..plugin_api import Option, Plugin
 from ..records_builder import _baseline_window
-from ..filter_engine import design_bw, plan_fused_groups
+from ..filter_engine import design_bw, plan_fused_groups, stage_fused_groups
 from ..sg_plan import normalize_window
 from . import _common as K
 
@@ -56,8 +56,9 @@ class HipThresholdHitPlugin(K.HipPlugin):
             help="with use_filtered: evaluate the filter inside the hit kernel from wave_pool instead of reading a "
                  "materialised wave_pool_filtered (same result).  The filter settings are those of the registered "
                  "wave_pool_filtered plugin, resolved per record (filter_type, channel_config): one Savitzky-Golay "
-                 "setting for the run is one pass; several settings run one pass each over the resident pool, their "
-                 "rows merged on the device; a Butterworth group is filtered on the device first (never downloaded)"),
+                 "setting for the run is one pass; several settings (at most 8; fuse_filter=False takes any number) "
+                 "run one pass each over the resident pool, their rows merged on the device; a Butterworth group is "
+                 "filtered on the device first (never downloaded)"),
         "fuse_baseline": Option(
             default=None, validate=_valid_fuse_baseline,
             help="None, or (start, end) with 0 <= start < end: re-estimate records.baseline as the mean of samples "
@@ -112,7 +113,7 @@ class HipThresholdHitPlugin(K.HipPlugin):
             source = K.pool_source(pool, raw_only=True)
             if fused:
                 source = K.SRC_SG_FUSED
-        sg, groups, masks = None, None, ()
+        sg, groups, group_of_record = None, None, ()
         if fused:
             # the filter settings per record, exactly as wave_pool_filtered resolves them (filtering.py:339-374)
             fplugin = context.get_plugin("wave_pool_filtered") if "wave_pool_filtered" in getattr(context, "_plugins", {}) else None
@@ -121,11 +122,19 @@ class HipThresholdHitPlugin(K.HipPlugin):
                 sg = normalize_window(*plan[0][0][1:])
             else:  # one pass per group, the rows merged on the device (records_pass)
                 groups = [key for key, _mask in plan]
-                masks = tuple(np.ones(len(rec), dtype=bool) if mask is None else mask for _key, mask in plan)
+                if len(groups) > _lib.MAX_HIT_GROUPS:
+                    raise ValueError(f"hit_threshold: the run resolves to {len(groups)} distinct filter settings, the "
+                                     f"grouped pass takes at most {_lib.MAX_HIT_GROUPS} (fuse_filter=False takes any "
+                                     "number of settings)")
+                column = np.zeros(len(rec), dtype=np.int32)
+                for g, (_key, mask) in enumerate(plan):
+                    if mask is not None:
+                        column[mask] = g
+                group_of_record = (column,)
         return K.records_route(context, self, rec, pool, THRESHOLD_HIT_DTYPE,
                                partial(records_pass, source=source, sg=sg, fuse_baseline=fuse_baseline, le=le, re=re,
                                        groups=groups),
-                               (thresholds,) + masks, cacheable=cacheable,
+                               (thresholds,) + group_of_record, cacheable=cacheable,
                                download=lambda sess, out: sess.download_hits(out))
 
     def _compute_dense(self, context, run_id, data_name, threshold, le, re, explicit_dt, channel_config) -> np.ndarray:
@@ -168,18 +177,18 @@ class HipThresholdHitPlugin(K.HipPlugin):
         return hits
 
 
-def records_pass(sess, records: np.ndarray, thresholds, *masks, source: int, sg: tuple[int, int] | None, fuse_baseline,
-                 le: int, re: int, groups=None, max_len: int = 0, download: bool = True):
+def records_pass(sess, records: np.ndarray, thresholds, group_of_record=None, *, source: int, sg: tuple[int, int] | None,
+                 fuse_baseline, le: int, re: int, groups=None, max_len: int = 0, download: bool = True):
     """The pass K.records_route runs, on a session whose pool is resident: records in, hit pass run ->
     THRESHOLD_HIT_DTYPE rows, or their count with download=False (rows left on the device).  sg: the Savitzky-Golay
     (window, order) of the fused filter, None for the raw / materialised sources.  max_len: the padded width (0 = the
     longest uploaded record; a shard gets the run's width, hit_finder.py:354-370, not its own).
 
     groups: None, or the filter keys of a fused pass over records with several resolved filter settings
-    (filter_engine.plan_fused_groups), `masks` then holding one bool array per key: the records it applies to."""
+    (filter_engine.plan_fused_groups), `group_of_record` then holding one int32 per record: the index of its key."""
     if groups is not None:
-        return _grouped_pass(sess, records, thresholds, masks, groups=groups, fuse_baseline=fuse_baseline, le=le, re=re,
-                             max_len=max_len, download=download)
+        return _grouped_pass(sess, records, thresholds, group_of_record, groups=groups, fuse_baseline=fuse_baseline, le=le,
+                             re=re, max_len=max_len, download=download)
     sess.upload_records(records, thresholds)
     if sg is not None:
         sess.set_sg_plan(*sg)
@@ -190,60 +199,32 @@ def records_pass(sess, records: np.ndarray, thresholds, *masks, source: int, sg:
     return sess.threshold_hits(source, le, re, max_len=max_len, download=download)
 
 
-def _grouped_pass(sess, records: np.ndarray, thresholds, masks, *, groups, fuse_baseline, le: int, re: int, max_len: int,
-                  download: bool):
-    """Fused pass over records whose channels resolve to several filter settings: one device pass per group, in list
-    order, over ALL uploaded records -- the uniform layout, and with it the streaming / span routes and the padded
-    shadow, stays -- with the threshold column at the record's own threshold inside the group and +inf outside
-    (sig >= +inf holds for no finite sample: no hit, on every route).  The rows of the passes are merged on the device
-    into the reference's order (record index, start) and stay resident like the rows of one pass.
+def _grouped_pass(sess, records: np.ndarray, thresholds, group_of_record, *, groups, fuse_baseline, le: int, re: int,
+                  max_len: int, download: bool):
+    """Fused pass over records whose channels resolve to several filter settings: the one queued grouped pass of the
+    library (filter_engine.stage_fused_groups), one device pass per group over ALL uploaded records -- the uniform
+    layout, and with it the streaming / span routes and the padded shadow, stays -- the rows merged on the device into
+    the reference's order (record index, start), resident like the rows of one pass.
 
-    A Savitzky-Golay group sets its plan and runs the fused pass (with fuse_baseline: the fused-baseline pass).  A
-    Butterworth group cannot be fused: its records are filtered into the device float32 twin first (scratch here: no
-    download, and nobody's wave_pool_filtered afterwards), its pass reads that twin; what the twin holds for other
-    records is irrelevant under +inf.  Groups without a record among `records` (a shard) are skipped; with one group
-    left the single pass runs: no threshold rewrite, no merge."""
-    n = len(records)
-    mine = [(key, np.asarray(mask, dtype=bool)) for key, mask in zip(groups, masks) if np.any(mask)]
-    if not mine:
-        mine = [(groups[0], np.ones(n, dtype=bool))]
-    if len(mine) == 1 and mine[0][0][0] == "SG":
-        return records_pass(sess, records, thresholds, source=K.SRC_SG_FUSED, sg=mine[0][0][1:], fuse_baseline=fuse_baseline,
+    `groups` are the run's keys and a key's index is its plan slot on every shard; the groups without a record among
+    `records` (a shard) are dropped and group_of_record is renumbered to the positions that are left.  With one
+    Savitzky-Golay group left the single pass runs.  A Butterworth group is filtered over the uploaded table into the
+    device float32 twin (never downloaded, nobody's wave_pool_filtered afterwards); with fuse_baseline its pass reads
+    the baselines one baseline_mean wrote, the Savitzky-Golay groups estimate theirs inside their pass."""
+    column = np.asarray(group_of_record, dtype=np.int32)
+    slots = [int(g) for g in np.unique(column)] or [0]
+    keys = [groups[g] for g in slots]
+    if len(keys) == 1 and keys[0][0] == "SG":
+        return records_pass(sess, records, thresholds, source=K.SRC_SG_FUSED, sg=keys[0][1:], fuse_baseline=fuse_baseline,
                             le=le, re=re, max_len=max_len, download=download)
-    butterworth = [(key, mask) for key, mask in mine if key[0] == "BW"]
-    if butterworth:  # before the table of the passes is uploaded: a records upload after it would void the padded shadow
-        sess.filter_keep_output(False)
-        try:
-            for k, (key, mask) in enumerate(butterworth):
-                sess.upload_records(records if mask.all() else records[mask])
-                if k == 1:
-                    sess.filter_keep_output(True)
-                sess.sosfiltfilt(*design_bw(*key[1:]), download=False)  # (drops the float32 residency tags itself)
-        finally:
-            sess.filter_keep_output(False)
-
-    def one_pass(key, download=False):
-        if key[0] == "SG":
-            sess.set_sg_plan(key[1], key[2])
-            if fuse_baseline is not None:
-                return sess.fused_baseline_filter_hits(tuple(fuse_baseline), le, re, max_len=max_len, download=download)
-            return sess.threshold_hits(K.SRC_SG_FUSED, le, re, max_len=max_len, download=download)
-        if fuse_baseline is not None:
-            sess.baseline_mean(int(fuse_baseline[0]), int(fuse_baseline[1]), update_records=True)
-        return sess.threshold_hits(K.SRC_F32, le, re, max_len=max_len, download=download)
-
-    if len(mine) == 1:
-        sess.upload_records(records, thresholds)
-        return one_pass(mine[0][0], download)
-    own = np.broadcast_to(np.asarray(thresholds, dtype=np.float64), (n,))
-    sess.upload_records(records, np.where(mine[0][1], own, np.inf))
-    with sess.merged_hit_rows() as merge:
-        for k, (key, mask) in enumerate(mine):
-            if k:
-                sess.set_thresholds(np.where(mask, own, np.inf))
-            one_pass(key)
-            merge.add()
-    return sess._fill_hits(merge.n_hits) if download else merge.n_hits
+    sess.upload_records(records, thresholds)
+    if fuse_baseline is not None and any(key[0] == "BW" for key in keys):
+        sess.baseline_mean(int(fuse_baseline[0]), int(fuse_baseline[1]), update_records=True)
+    window = {} if fuse_baseline is None else {"baseline_window": tuple(fuse_baseline)}
+    stage_fused_groups(sess, keys, slots, lambda g: design_bw(*keys[g][1:]), np.searchsorted(slots, column).astype(np.int32),
+                       le, re, max_len, **window)
+    n = sess.hits_wait()
+    return sess._fill_hits(n) if download else n
 
 
 def _lengths_from_records(context: Any, run_id: str, record_ids: np.ndarray, source_lengths: np.ndarray) -> np.ndarray:

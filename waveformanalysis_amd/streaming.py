@@ -39,6 +39,7 @@ from .chunk import (
 )
 from .device import DevicePool, default_pool
 from .dtypes import THRESHOLD_HIT_DTYPE
+from .filter_engine import stage_fused_groups
 from .plugin_api import Option
 from .sg_plan import normalize_window
 
@@ -594,15 +595,7 @@ class HipThresholdHitStream(HipStreamingPlugin):
             sess.set_sg_plan(keys[0][1], keys[0][2])
             sess.hits_enqueue(_lib.SRC_SG_FUSED, (0, 0), self.le, self.re, int(max_len))
             return
-        groups = []
-        for g, key in enumerate(keys):
-            if key[0] == "BW":  # filtered over the uploaded table: the layout record and the padded shadow stand
-                sess.sosfiltfilt_group(*plan.design(g), group_of_record, g)
-                groups.append((_lib.SRC_F32, 0))
-            else:
-                sess.store_sg_plan(g, key[1], key[2])
-                groups.append((_lib.SRC_SG_FUSED, g))
-        sess.hits_enqueue_groups(groups, group_of_record, self.le, self.re, int(max_len))
+        stage_fused_groups(sess, keys, range(len(keys)), plan.design, group_of_record, self.le, self.re, int(max_len))
 
     def _collect(self, sess, chunk: Chunk, run_id: str) -> Chunk:
         hits = sess._fill_hits(sess.hits_wait())
