@@ -52,6 +52,21 @@ def run(name: str) -> S.Run:
     return missing() if name == "missing" else S.run(name)
 
 
+@functools.cache
+def exceeding_run() -> tuple[np.ndarray, np.ndarray]:
+    """(records, pool) of a run whose groups outgrow the smallest speculative row bound: 12 000 uniform records of 64
+    samples with two hits each over four channels, about 6000 rows per channel, against the 4096 + 4096 / 8 rows a
+    launch is sized for behind a pass that found nothing.  A grouped call over it on a context whose previous calls
+    found nothing returns with the pass pending, and wfa_hits_wait redoes it the exact way."""
+    n, L = 12_000, 64
+    rng = np.random.default_rng(31)
+    pool = np.concatenate([S._wave(L, 4, rng) for _ in range(n)])       # two hits per record
+    rec = S._records(np.full(n, L), np.arange(n, dtype=np.int64) * L, 10**12 + np.arange(n, dtype=np.int64) * 300_000)
+    rec.setflags(write=False)
+    pool.setflags(write=False)
+    return rec, pool
+
+
 def filter_kwargs(key: tuple) -> dict:
     """A filter key of filter_engine.resolve_filter_key as the oracle's keyword arguments."""
     if key[0] == "BW":

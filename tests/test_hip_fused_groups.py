@@ -332,7 +332,77 @@ def test_baseline_window_through_the_grouped_call(tag):
         assert got.tobytes() == parts[3].tobytes()
 
 
-# ---- 8. error contract ----------------------------------------------------------------------------------------------------
+# ---- 8. the grouped call only reads the context's own plan, thresholds and options ------------------------------------------
+def test_grouped_calls_leave_the_plan_thresholds_and_options_of_the_context():
+    """One session, plan (7, 3) and the records' own thresholds set once; `want` is the plain pass under them.  Every
+    kind of grouped call over slots (11, 2) -- streaming route, queued when warm -- and (21, 4) -- general route, completed
+    -- is followed by the same plain pass, which must give `want` byte for byte: a call that is waited for, a warm one
+    nobody waits for (the plain pass ends it), one refused in the middle of its validation (slot 5 holds no plan), and one
+    whose wait takes the exact redo.  Run "a" has a few hundred rows and never outgrows the smallest row bound (4096), so
+    the last case uploads U.exceeding_run() once (the run of test_exceeded_bound_is_redone_exactly) and gets its calls
+    that find nothing from a group column that owns no record: no upload stands between a grouped call and the plain
+    pass that checks it.  The redo is seen from outside (k_grp_mask: two queued passes + two exact ones) and leaves
+    no_speculate false: a plain warm hits_enqueue stays pending."""
+    run = load_run("a")
+    rec, pool = run["records"], run["wave_pool"]
+    groups = [(_lib.SRC_SG_FUSED, 0), (_lib.SRC_SG_FUSED, 1)]
+
+    def parity(records):
+        return np.ascontiguousarray(records["channel"] % 2, dtype=np.int32)
+
+    with DeviceSession(0) as s:
+        def plain():
+            return s.threshold_hits(_lib.SRC_SG_FUSED).tobytes()
+
+        s.upload_pool(pool)
+        s.upload_records(rec, thresholds_of(rec))
+        s.set_sg_plan(7, 3)
+        want = plain()
+        assert len(want) > 300 * THRESHOLD_HIT_DTYPE.itemsize
+        s.store_sg_plan(0, 11, 2)
+        s.store_sg_plan(1, 21, 4)
+        # cold, waited for
+        s.hits_enqueue_groups(groups, parity(rec))
+        merged = s._fill_hits(s.hits_wait())
+        assert len(merged) > 100 and merged.tobytes() != want
+        assert plain() == want
+        # warm, not waited for: the plain pass ends the queued one
+        s.hits_enqueue_groups(groups, parity(rec))
+        assert s.hits_pending()
+        assert plain() == want and not s.hits_pending()
+        # refused after group 0 has been accepted
+        gor = parity(rec)
+        bad = (_lib.C.c_int32 * 4)(_lib.SRC_SG_FUSED, 0, _lib.SRC_SG_FUSED, 5)
+        assert s._lib.wfa_hits_enqueue_groups(s._h, 2, bad, gor.ctypes.data, 0, 0, 2, 2, 0) == _lib.WFA_E_STATE
+        assert "slot 5" in _lib.last_error()
+        assert plain() == want
+        # the exact redo
+        big, big_pool = U.exceeding_run()
+        s.upload_pool(big_pool)
+        s.upload_records(big, thresholds_of(big))
+        want = plain()
+        for _call in range(2):      # every record unowned: both groups find nothing, their next launches are sized for 4096 rows
+            s.hits_enqueue_groups(groups, np.full(len(big), -1, dtype=np.int32))
+            assert s.hits_wait() == 0
+        s.profile(True)
+        try:
+            s.hits_enqueue_groups(groups, parity(big))
+            assert s.hits_pending()
+            redone = s._fill_hits(s.hits_wait())
+            report = s.profile_report()
+        finally:
+            s.profile(False)
+        assert report["k_grp_mask"][1] == 4, report
+        assert len(redone) > 2 * (4096 + 4096 // 8)
+        assert plain() == want
+        s.hits_enqueue(_lib.SRC_SG_FUSED)
+        assert s.hits_pending()
+        assert s._fill_hits(s.hits_wait()).tobytes() == want
+        s.hits_enqueue_groups(groups, parity(big))      # and the bounds the redo left behind hold: the same table, standing
+        assert s._fill_hits(s.hits_wait()).tobytes() == redone.tobytes()
+
+
+# ---- 9. error contract ----------------------------------------------------------------------------------------------------
 def test_error_codes_of_the_new_calls():
     run = load_run("a")
     rec, pool = run["records"], run["wave_pool"]

@@ -326,10 +326,8 @@ def test_exceeded_bound_is_redone_exactly():
     """A warm context whose groups found nothing sizes every group's launch for 4096 rows; the next call finds about
     6000 rows per group.  The call still returns with the pass pending, wfa_hits_wait sees the bounds exceeded and redoes
     the grouped pass the exact way: the host merge of the groups' single passes, byte for byte."""
-    n, L = 12_000, 64
-    rng = np.random.default_rng(31)
-    pool = np.concatenate([S._wave(L, 4, rng) for _ in range(n)])       # two hits per record
-    rec = S._records(np.full(n, L), np.arange(n, dtype=np.int64) * L, 10**12 + np.arange(n, dtype=np.int64) * 300_000)
+    rec, pool = U.exceeding_run()
+    n = len(rec)
     keys, gor, thr = U.KEYS["sg_only"], _channel_groups(rec), F.thresholds_of(rec)
     with DeviceSession(0) as s:
         s.upload_pool(pool)

@@ -137,7 +137,8 @@ static PoolView pool_view(wfa_ctx* c) {
     return p;
 }
 
-static RecView rec_view(wfa_ctx* c) {
+// thr: the threshold column the kernels compare against (a hit pass: HitPass::thr)
+static RecView rec_view(wfa_ctx* c, const double* thr) {
     RecView r;
     r.R = c->R;
     r.off = c->off.as<int64_t>();
@@ -145,7 +146,7 @@ static RecView rec_view(wfa_ctx* c) {
     r.baseline = c->baseline.as<double>();
     r.baseline_rw = c->baseline.as<double>();
     r.pol = c->pol.as<int8_t>();
-    r.thr = c->thr.as<double>();
+    r.thr = thr;
     r.ts = c->ts.as<int64_t>();
     r.dt = c->dt.as<int32_t>();
     r.board = c->board.as<int16_t>();
@@ -154,25 +155,29 @@ static RecView rec_view(wfa_ctx* c) {
     r.bm_off = c->bm_off.as<int64_t>();
     return r;
 }
+static RecView rec_view(wfa_ctx* c) { return rec_view(c, c->thr.as<double>()); }  // the uploaded thresholds
 
-static SgParams sg_params(wfa_ctx* c) {
+// the context's own plan (wfa_set_sg_plan), null before the first one
+static const SgPlanDev* ctx_plan(wfa_ctx* c) { return c->have_sg ? &c->sg : nullptr; }
+
+static SgParams sg_params(const SgPlanDev* plan) {
     SgParams s{};
-    if (!c->have_sg) return s;
-    s.W = c->sg.W; s.P = c->sg.P; s.H = c->sg.H; s.stride = c->sg.stride;
-    s.tab = c->sg.tab.as<double>();
-    s.sym = c->sg.sym.as<uint8_t>();
-    s.int_ok = c->sg.int_ok;
-    s.itab = c->sg.itab.as<int32_t>();
-    s.den = c->sg.den; s.den_edge = c->sg.den_edge;
-    s.guard = c->sg.guard; s.guard_edge = c->sg.guard_edge;
-    s.rden = c->sg.rden; s.rden_edge = c->sg.rden_edge;
+    if (!plan) return s;
+    s.W = plan->W; s.P = plan->P; s.H = plan->H; s.stride = plan->stride;
+    s.tab = plan->tab.as<double>();
+    s.sym = plan->sym.as<uint8_t>();
+    s.int_ok = plan->int_ok;
+    s.itab = plan->itab.as<int32_t>();
+    s.den = plan->den; s.den_edge = plan->den_edge;
+    s.guard = plan->guard; s.guard_edge = plan->guard_edge;
+    s.rden = plan->rden; s.rden_edge = plan->rden_edge;
     // |y| < 2^17 for uint16 samples (sum|c| < 2): float32 ulp <= 2^-7
-    s.margin = (int32_t)((c->sg.den + 127) / 128 + 2);
-    s.margin_edge = (int32_t)((c->sg.den_edge + 127) / 128 + 2);
+    s.margin = (int32_t)((plan->den + 127) / 128 + 2);
+    s.margin_edge = (int32_t)((plan->den_edge + 127) / 128 + 2);
     return s;
 }
 
-static int need_source(wfa_ctx* c, int source) {
+static int need_source(wfa_ctx* c, int source, const SgPlanDev* plan) {
     if (!c->have_records) return fail(WFA_E_STATE, "records not uploaded");
     switch (source) {
         case WFA_SRC_RAW:
@@ -183,12 +188,13 @@ static int need_source(wfa_ctx* c, int source) {
             return WFA_OK;
         case WFA_SRC_SG_FUSED:
             if (!c->have_u16) return fail(WFA_E_STATE, "wave_pool (uint16) not uploaded");
-            if (!c->have_sg) return fail(WFA_E_STATE, "Savitzky-Golay plan not set");
+            if (!plan) return fail(WFA_E_STATE, "Savitzky-Golay plan not set");
             return WFA_OK;
         default:
             return fail(WFA_E_INVALID, "unknown wave source %d", source);
     }
 }
+static int need_source(wfa_ctx* c, int source) { return need_source(c, source, ctx_plan(c)); }
 
 // padded shadow of the u16 pool (see wfa_ctx::layout): built once per upload, on the device
 static int ensure_shadow(wfa_ctx* c) {
@@ -218,9 +224,9 @@ struct LayoutView {
     int positive;
 };
 
-static int layout_view(wfa_ctx* c, bool padded, LayoutView* v) {
+static int layout_view(wfa_ctx* c, const double* thr, bool padded, LayoutView* v) {
     const UniformLayout& u = c->layout;
-    *v = LayoutView{pool_view(c), rec_view(c), u.L, u.L, u.off0, u.positive ? 1 : 0};
+    *v = LayoutView{pool_view(c), rec_view(c, thr), u.L, u.L, u.off0, u.positive ? 1 : 0};
     if (!padded) return WFA_OK;
     if (int rc = ensure_shadow(c)) return rc;
     v->pool.u16 = c->shadow_pool.as<uint16_t>();
@@ -237,12 +243,12 @@ static void row_layout(RowParams& rp, const LayoutView& v) {
 }
 
 // ---- row stage of the fused hit pass (both routes) ----------------------------------------------------------------
-// Speculative launch: a pass usually finds about as many hits as the previous one on this context.  When the row buffers
-// already hold that many (+12 %, + 4096), the descriptor kernel and the row kernels are launched for that bound straight
-// away and take the real count from the device; the host reads it once, after everything is queued, or not at all
-// (enqueue_only: wfa_hits_wait does).  Without one (first pass on this context, buffers too small, no_speculate), or when
-// the pass finds more, the host reads the count and launches the rows for exactly that many, into row buffers sized with
-// the same head room so that the next pass can speculate.
+// Speculative launch: a pass usually finds about as many hits as the previous one like it (HitPass::hint).  When the row
+// buffers already hold that many (+12 %, + 4096), the descriptor kernel and the row kernels are launched for that bound
+// straight away and take the real count from the device; the host reads it once, after everything is queued, or not at all
+// (enqueue_only: wfa_hits_wait does).  Without one (no hint, buffers too small, speculate off), or when the pass finds
+// more, the host reads the count and launches the rows for exactly that many, into row buffers sized with the same head
+// room so that the next pass can speculate.
 static int64_t rows_bound(int64_t hits) { return hits + hits / 8 + 4096; }
 
 // accept-or-redo of a speculative launch: its rows stand when the pass found no more hits than the launch covered and no
@@ -255,11 +261,11 @@ static bool spec_rows_stand(int64_t total, int64_t bound, int flags) { return to
 //             route, whose per-record scan has done so already);
 //   ctrl      streaming route: its control words ([1]: event-overflow flags) and `groups` its group sums, both reported
 //             and cleared by the last kernel of a queued pass; null on the bitmap route.
-// *done = false: a span's events overflowed, the caller takes the general route.
+// o->overflow (state kNone): a span's events overflowed, the caller takes the general route.
 template <class Desc, class Count>
-static int run_rows(wfa_ctx* c, const PoolView& pv, const RecView& rv, const SgParams& sg, RowParams rp,
+static int run_rows(wfa_ctx* c, const HitPass& p, const PoolView& pv, const RecView& rv, const SgParams& sg, RowParams rp,
                     const int64_t* d_total, unsigned long long* ctrl, unsigned long long* groups, Desc desc, Count count,
-                    wfa_ctx::PendingPass pend, bool enqueue_only, int64_t* n_hits, bool* done) {
+                    HitOutcome* o) {
     int rc;
     auto rows = [&](int64_t n_rows) -> int {
         int r2;
@@ -276,19 +282,18 @@ static int run_rows(wfa_ctx* c, const PoolView& pv, const RecView& rv, const SgP
         return t.end("k_hit_rows_literal");
     };
     auto finish = [&](int64_t total) {
-        c->n_hits = total;
         c->rows_index = 1;
-        *n_hits = total;
-        *done = true;
+        o->state = HitOutcome::kCompleted;
+        o->n_hits = total;
         return WFA_OK;
     };
     const int64_t held = (int64_t)std::min(c->hit_out.cap / 60, c->hit_desc.cap / sizeof(int4));
-    const int64_t bound = rows_bound(c->last_hits);
-    const bool spec = c->last_hits >= 0 && held >= bound && !c->opt.no_speculate;
+    const int64_t bound = rows_bound(p.hint);
+    const bool spec = p.hint >= 0 && held >= bound && p.speculate;
     if (spec) {
         rp.cap = bound;
         rp.n_dev = d_total;
-        if (enqueue_only) {  // nobody waits here: the row count goes to the pinned words
+        if (p.enqueue_only) {  // nobody waits here: the row count goes to the pinned words
             if (ctrl) {  // written there by the pass's last kernel, with the control words; it clears them and the group sums
                 rp.pass_report = c->h_total;
                 rp.pass_ctrl = ctrl;
@@ -298,13 +303,10 @@ static int run_rows(wfa_ctx* c, const PoolView& pv, const RecView& rv, const SgP
             if ((rc = rows(bound))) return rc;
             if (ctrl) c->run_dirty_groups = 0;  // (bound >= 4096: the literal kernel, and its clear, are queued)
             else WFA_HIP_CHECK(hipMemcpyAsync(c->h_total, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-            pend.bound = bound;
-            pend.runs32 = ctrl != nullptr;
-            c->pending = true;
-            c->pend = pend;
-            c->n_hits = -1;
             c->rows_index = 1;
-            *done = true;
+            o->state = HitOutcome::kQueued;
+            o->bound = bound;
+            o->runs32 = ctrl != nullptr;
             return WFA_OK;
         }
         if ((rc = rows(bound))) return rc;
@@ -317,11 +319,10 @@ static int run_rows(wfa_ctx* c, const PoolView& pv, const RecView& rv, const SgP
     if (ctrl) WFA_HIP_CHECK(hipMemcpyAsync(&ctl, ctrl + 1, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
     WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
     const int flags = (int)(ctl & 0xffffffffull);
-    if (flags) {  // a span outgrew the event buffer of its wave or its slot: the general route for this upload
-        c->no_runs32 = true;
+    if (flags) {  // a span outgrew the event buffer of its wave or its slot
+        o->overflow = true;
         return WFA_OK;
     }
-    c->last_hits = total;
     if (spec && spec_rows_stand(total, bound, flags)) return finish(total);
     rp.cap = 0;
     rp.n_dev = nullptr;
@@ -336,21 +337,19 @@ static int run_rows(wfa_ctx* c, const PoolView& pv, const RecView& rv, const SgP
 // Uniform records (span mode), Savitzky-Golay source: streaming kernel with ordered run events (wfa_stream.hip), then the
 // row stage: k_sg_runs32 -> k_runs_to_desc -> row kernels (plus a scan of the per-span hit counts when the host needs the
 // row count first).
-// *done = false: the layout / options are outside what that kernel covers, or a span outgrew its event buffer --
-// the caller takes the general route (per-record mask kernel + bitmap).
-static int run_hits_runs32(wfa_ctx* c, bool fused_bl, int32_t bl_start, int32_t bl_end, int32_t le, int32_t re,
-                           int32_t max_len, int64_t* n_hits, bool enqueue_only, bool* done) {
-    *done = false;
+// o->state stays kNone: the layout / options are outside what that kernel covers, or a span outgrew its event buffer
+// (o->overflow) -- the caller takes the general route (per-record mask kernel + bitmap).
+static int run_hits_runs32(wfa_ctx* c, const HitPass& p, HitOutcome* o) {
     if (c->no_runs32 || c->opt.no_runs32) return WFA_OK;
-    const SgParams sp0 = sg_params(c);
+    const SgParams sp0 = sg_params(p.plan);
     const UniformLayout& u = c->layout;
     const bool in_place = u.span && u.L % 32 == 0;
     const bool padded = !in_place && u.pad && u.S % 32 == 0 && !c->opt.no_pad;
     if (!in_place && !padded) return WFA_OK;
-    if (!sg_runs32_supported(sp0, u.L, padded ? u.S : u.L, bl_start, bl_end, fused_bl)) return WFA_OK;
+    if (!sg_runs32_supported(sp0, u.L, padded ? u.S : u.L, p.bl_start, p.bl_end, p.fused_bl)) return WFA_OK;
     int rc;
     LayoutView v;
-    if ((rc = layout_view(c, padded, &v))) return rc;
+    if ((rc = layout_view(c, p.thr, padded, &v))) return rc;
     SpanParams sp{};
     sp.off0 = v.off0; sp.L = v.L; sp.S = v.S; sp.positive = v.positive;
     const int64_t R = c->R;
@@ -373,7 +372,7 @@ static int run_hits_runs32(wfa_ctx* c, bool fused_bl, int32_t bl_start, int32_t 
     if (new_ctrl) c->run_cold_valid = false;
     if (new_ctrl || new_groups) c->run_dirty_groups = (int64_t)(c->run_groups.cap / sizeof(unsigned long long));
 
-    RowParams rp{le, re, max_len, sp0.W / 2};
+    RowParams rp{p.le, p.re, p.max_len, sp0.W / 2};
     row_layout(rp, v);
     int64_t* d_total = c->run_scan_blocks.as<int64_t>() + nb;
     auto* ctrl = c->run_ctrl.as<unsigned long long>();  // [0] event cursor, [1] flags, [2] hits listed for the literal kernel
@@ -419,12 +418,15 @@ static int run_hits_runs32(wfa_ctx* c, bool fused_bl, int32_t bl_start, int32_t 
     ra.group_sum = rn.group_sum;
     ra.cold = reinterpret_cast<const RunsCold*>(ctrl + 32);  // 256 bytes behind the atomically updated words
     {
-        // what the float64 reference paths read: a device copy next to the control words, refreshed when it changes
+        // what the float64 reference paths read: a device copy next to the control words, refreshed when it changes, from
+        // the pass's pinned slot; the slot is rewritten (an earlier copy from it may be in flight: wait) only when it differs
         RunsCold cold{v.pool, sp0};
         if (!c->run_cold_valid || memcmp(&cold, &c->run_cold_host, sizeof(cold)) != 0) {
-            memcpy(c->h_cold, &cold, sizeof(cold));
-            WFA_HIP_CHECK(hipMemcpyAsync(ctrl + 32, c->h_cold, sizeof(cold), hipMemcpyHostToDevice, c->stream));
-            WFA_HIP_CHECK(hipStreamSynchronize(c->stream));  // h_cold may be rewritten by the next pass
+            if (memcmp(p.cold_pin, &cold, sizeof(cold)) != 0) {
+                WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+                memcpy(p.cold_pin, &cold, sizeof(cold));
+            }
+            WFA_HIP_CHECK(hipMemcpyAsync(ctrl + 32, p.cold_pin, sizeof(cold), hipMemcpyHostToDevice, c->stream));
             c->run_cold_host = cold;
             c->run_cold_valid = true;
         }
@@ -432,8 +434,8 @@ static int run_hits_runs32(wfa_ctx* c, bool fused_bl, int32_t bl_start, int32_t 
     c->run_dirty_groups = n_groups;  // what the streaming kernel is about to write
     {
         LaunchTimer t(c, true);
-        WFA_HIP_CHECK(launch_sg_runs32(c->stream, fused_bl, ra));
-        if ((rc = t.end(fused_bl ? "k_sg_runs32<baseline>" : "k_sg_runs32"))) return rc;
+        WFA_HIP_CHECK(launch_sg_runs32(c->stream, p.fused_bl, ra));
+        if ((rc = t.end(p.fused_bl ? "k_sg_runs32<baseline>" : "k_sg_runs32"))) return rc;
     }
     auto desc = [&](const RowParams& r) -> int {
         LaunchTimer t(c);
@@ -446,36 +448,35 @@ static int run_hits_runs32(wfa_ctx* c, bool fused_bl, int32_t bl_start, int32_t 
                                   c->run_span_row0.as<int64_t>()));
         return t.end("k_scan(span hit counts)");
     };
-    return run_rows(c, v.pool, v.rec, sp0, rp, d_total, ctrl, rn.group_sum, desc, count,
-                    {WFA_SRC_SG_FUSED, fused_bl, bl_start, bl_end, le, re, max_len, 0, true}, enqueue_only, n_hits, done);
+    return run_rows(c, p, v.pool, v.rec, sp0, rp, d_total, ctrl, rn.group_sum, desc, count, o);
 }
 
-// enqueue_only: when the pass can take the speculative row launch, queue it and return without waiting for the row
-// count (n_hits may be null; wfa_hits_wait delivers it); otherwise the pass runs to completion as usual.
-static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int32_t bl_end,
-                    int32_t le, int32_t re, int32_t max_len, int64_t* n_hits, bool enqueue_only = false) {
-    int rc = use_device(c);
-    if (rc) return rc;
-    if ((rc = need_source(c, source))) return rc;
-    if (!n_hits && !enqueue_only) return fail(WFA_E_INVALID, "n_hits is null");
-    int64_t n_hits_local = 0;
-    if (!n_hits) n_hits = &n_hits_local;
-    c->pending = false;
-    if (le < 0) le = 0;  // hit_finder.py:124-125
-    if (re < 0) re = 0;
-    if (max_len <= 0) max_len = c->max_len;
-    if (max_len < c->max_len)
-        return fail(WFA_E_INVALID, "max_len (%d) < longest uploaded record (%d)", max_len, c->max_len);
-    if (fused_bl && bl_start < 0) return fail(WFA_E_INVALID, "baseline window start must be >= 0");
-    if (fused_bl) {  // (a queued pass that is redone comes back here with the clamped window: the clamp is idempotent)
-        const host::BaselineWindow w = host::baseline_window(bl_start, bl_end, c->max_len);
-        bl_start = w.start; bl_end = w.end;
+// One hit pass over the resident records as `p` describes it; *o says what it did.  A pass that starts ends the queued
+// one and voids the rows of the last one; what the context remembers of this one (row count, hint, pending record) is
+// the caller's to store.  p.enqueue_only: when the pass can take the speculative row launch, queue it and return without
+// waiting for the row count (wfa_hits_wait delivers it); otherwise the pass runs to completion as usual.
+static int run_hits(wfa_ctx* c, HitPass p, HitOutcome* o) {
+    *o = HitOutcome{};
+    int rc;
+    if ((rc = need_source(c, p.source, p.plan))) return rc;
+    c->pending = wfa_ctx::kPendNone;
+    if (p.le < 0) p.le = 0;  // hit_finder.py:124-125
+    if (p.re < 0) p.re = 0;
+    if (p.max_len <= 0) p.max_len = c->max_len;
+    if (p.max_len < c->max_len)
+        return fail(WFA_E_INVALID, "max_len (%d) < longest uploaded record (%d)", p.max_len, c->max_len);
+    if (p.fused_bl && p.bl_start < 0) return fail(WFA_E_INVALID, "baseline window start must be >= 0");
+    if (p.fused_bl) {
+        const host::BaselineWindow w = host::baseline_window(p.bl_start, p.bl_end, c->max_len);
+        p.bl_start = w.start; p.bl_end = w.end;
     }
+    const int source = p.source, bl_start = p.bl_start, bl_end = p.bl_end;
+    const bool fused_bl = p.fused_bl;
     c->n_hits = -1;
     c->rows_index = 0;
     if (c->R == 0) {
-        c->n_hits = 0;
-        *n_hits = 0;
+        o->state = HitOutcome::kCompleted;
+        o->n_hits = 0;
         return WFA_OK;
     }
 
@@ -487,13 +488,11 @@ static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int
     if ((rc = c->scan_blocks.ensure((nb + 1) * sizeof(int64_t)))) return rc;
     if ((rc = c->cursor.ensure(sizeof(unsigned long long)))) return rc;
 
-    const SgParams sp0 = sg_params(c);
+    const SgParams sp0 = sg_params(p.plan);
     if (source == WFA_SRC_SG_FUSED && sg_mask_supported(sp0) && !c->opt.no_fast) {
-        {
-            bool done = false;
-            if ((rc = run_hits_runs32(c, fused_bl, bl_start, bl_end, le, re, max_len, n_hits, enqueue_only, &done))) return rc;
-            if (done) return WFA_OK;
-        }
+        if ((rc = run_hits_runs32(c, p, o))) return rc;
+        if (o->state != HitOutcome::kNone) return WFA_OK;
+        if (o->overflow) c->no_runs32 = true;  // the general route for this upload
         // A: mask + run counts  ->  scan  ->  B1: run descriptors  ->  B2: rows (final order, no gather)
         if (c->bitmap.cap < (size_t)c->bitmap_bytes) c->bitmap_clean = false;
         if ((rc = c->bitmap.ensure((size_t)c->bitmap_bytes))) return rc;
@@ -509,7 +508,7 @@ static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int
         const UniformLayout& u = c->layout;
         const bool padded = u.pad && sg_mask_span16_padded_supported(sp0, u.L) && !c->opt.no_pad && !c->opt.no_span;
         LayoutView v;
-        if ((rc = layout_view(c, padded, &v))) return rc;
+        if ((rc = layout_view(c, p.thr, padded, &v))) return rc;
         {
             LaunchTimer t(c, true);
             if (padded || (u.span && u.L >= sp0.W && !c->opt.no_span && sg_mask_span16_supported(sp0, u.L))) {
@@ -533,7 +532,7 @@ static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int
                                       c->rec_out_start.as<int64_t>()));
             if ((rc = t.end("k_scan(hit counts)"))) return rc;
         }
-        RowParams rp{le, re, max_len, sp0.W / 2};
+        RowParams rp{p.le, p.re, p.max_len, sp0.W / 2};
         if (padded || u.span) row_layout(rp, v);
         {
             // mask bytes of one block's records (+16 for the aligned start), rounded up to 1 KiB
@@ -547,13 +546,13 @@ static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int
                                           c->rec_out_start.as<int64_t>(), c->hit_desc.as<int4>(), r));
             return t.end("k_hit_runs");
         };
-        bool done = false;  // (no event buffers on this route: always done)
-        return run_rows(c, v.pool, v.rec, sp0, rp, c->scan_blocks.as<int64_t>() + nb, nullptr, nullptr, desc, [] { return WFA_OK; },
-                        {source, fused_bl, bl_start, bl_end, le, re, max_len, 0, false}, enqueue_only, n_hits, &done);
+        // (no event buffers on this route: queued or completed)
+        return run_rows(c, p, v.pool, v.rec, sp0, rp, c->scan_blocks.as<int64_t>() + nb, nullptr, nullptr, desc,
+                        [] { return WFA_OK; }, o);
     }
 
     HitParams hp{};
-    hp.le = le; hp.re = re; hp.max_len = max_len;
+    hp.le = p.le; hp.re = p.re; hp.max_len = p.max_len;
     hp.bl_start = bl_start; hp.bl_end = bl_end;
     hp.bm_words = (c->max_len + 7 + 63) / 64 + 9;  // bits are indexed from the 16-byte aligned base
     hp.chunk_rows = 256;
@@ -566,8 +565,7 @@ static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int
     }
 
     const PoolView pv = pool_view(c);
-    const RecView rv = rec_view(c);
-    const SgParams sp = sg_params(c);
+    const RecView rv = rec_view(c, p.thr);
     for (int attempt = 0; attempt < 2; ++attempt) {
         hp.tmp = c->hit_tmp.as<uint8_t>();
         hp.tmp_rows = c->hit_tmp_rows;
@@ -577,7 +575,7 @@ static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int
         WFA_HIP_CHECK(hipMemsetAsync(c->cursor.ptr, 0, sizeof(unsigned long long), c->stream));
         {
             LaunchTimer t(c);
-            WFA_HIP_CHECK(launch_hits(c->stream, source, fused_bl, pv, rv, sp, hp));
+            WFA_HIP_CHECK(launch_hits(c->stream, source, fused_bl, pv, rv, sp0, hp));
             const char* name = source == WFA_SRC_SG_FUSED
                                    ? (fused_bl ? "k_hits<sg_fused,baseline>" : "k_hits<sg_fused>")
                                    : (source == WFA_SRC_F32 ? "k_hits<f32>" : (fused_bl ? "k_hits<raw,baseline>" : "k_hits<raw>"));
@@ -612,19 +610,51 @@ static int run_hits(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int
                                          c->hit_out.as<uint8_t>()));
         if ((rc = t.end("k_hits_gather"))) return rc;
     }
-    c->n_hits = total;
     c->rows_index = 2;
-    *n_hits = total;
+    o->state = HitOutcome::kCompleted;
+    o->n_hits = total;
     return WFA_OK;
+}
+
+// The single pass of the public entry points: described from the context's own plan, thresholds, hint and options, what
+// it did stored back.  The hint follows the passes with a row stage (rows_index 1).  n_hits: null if enqueue_only.
+static int ctx_pass(wfa_ctx* c, int source, bool fused_bl, int32_t bl_start, int32_t bl_end, int32_t le, int32_t re,
+                    int32_t max_len, int64_t* n_hits, bool enqueue_only) {
+    int rc = use_device(c);
+    if (rc) return rc;
+    if (!n_hits && !enqueue_only) return fail(WFA_E_INVALID, "n_hits is null");
+    HitPass p;
+    p.source = source; p.plan = ctx_plan(c); p.thr = c->thr.as<double>();
+    p.fused_bl = fused_bl; p.bl_start = bl_start; p.bl_end = bl_end; p.le = le; p.re = re; p.max_len = max_len;
+    p.hint = c->last_hits; p.speculate = !c->opt.no_speculate; p.enqueue_only = enqueue_only; p.cold_pin = c->h_cold;
+    HitOutcome o;
+    if ((rc = run_hits(c, p, &o))) return rc;
+    if (o.state == HitOutcome::kQueued) {
+        c->pending = wfa_ctx::kPendPass;
+        c->pend = {p, o};
+        return WFA_OK;
+    }
+    c->n_hits = o.n_hits;
+    if (c->rows_index == 1) c->last_hits = o.n_hits;
+    if (n_hits) *n_hits = o.n_hits;
+    return WFA_OK;
+}
+
+// A queued single pass has ended (the stream is idle): its row count and overflow flags from the pinned words, what they
+// mean for the next passes, and whether its speculative rows stand (otherwise the caller redoes the pass the exact way).
+static bool pass_settle(wfa_ctx* c, int64_t bound, bool runs32, int64_t* total) {
+    *total = *c->h_total;
+    const int flags = runs32 ? (int)(c->h_total[2] & 0xffffffffll) : 0;  // event buffers overflowed
+    if (flags) c->no_runs32 = true;  // a span outgrew its LDS buffer or its slot: the general route from now on
+    c->last_hits = *total;
+    return spec_rows_stand(*total, bound, flags);
 }
 
 }  // namespace wfa
 
 using namespace wfa;
 
-// wfa_hits_enqueue_groups (below): PendingPass::source of a queued grouped pass, and what wfa_hits_wait does for it
-constexpr int kSrcGroups = -2;
-static int groups_wait(wfa_ctx* c, int64_t* n_hits);
+static int groups_wait(wfa_ctx* c, int64_t* n_hits);  // a queued grouped pass (wfa_hits_enqueue_groups, below)
 
 // ---- records as packed rows, unpacked on the device --------------------------------------------------------------------
 // (reference row layout: processing/dtypes.py:80-100, 102 bytes, numpy packs without alignment.)  The column route above
@@ -801,6 +831,7 @@ int wfa_ctx_create(int device_id, wfa_ctx** out) {
     if (e == hipSuccess) e = hipEventCreate(&c->ev0);
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&c->h_total), 4 * sizeof(int64_t) + sizeof(wfa::RunsCold), hipHostMallocDefault);
     if (e == hipSuccess) c->h_cold = reinterpret_cast<wfa::RunsCold*>(c->h_total + 4);
+    if (e == hipSuccess) memset(c->h_cold, 0, sizeof(wfa::RunsCold));  // (a pass compares the slot with the block it needs)
     if (e == hipSuccess) e = hipEventCreate(&c->ev1);
     if (e != hipSuccess) {
         wfa_ctx_destroy(c);
@@ -1283,13 +1314,13 @@ int wfa_savgol(wfa_ctx* c, float* out) {
     // gaps between records stay 0.0 (records.py:382)
     if (!c->filter_keep) WFA_HIP_CHECK(hipMemsetAsync(c->pool_f32.ptr, 0, (size_t)c->pool_n * sizeof(float), c->stream));
     if (c->R > 0) {
-        const SgParams sp0 = sg_params(c);
+        const SgParams sp0 = sg_params(ctx_plan(c));
         const UniformLayout& u = c->layout;
         const bool fast = sg_mask_supported(sp0) && !c->opt.no_fast;
         // uniform records, L % 16 != 0: the span kernel reads the padded shadow and writes the packed pool
         const bool padded = u.pad && u.L >= sp0.W && fast && !c->opt.no_pad;
         LayoutView v;
-        if ((rc = layout_view(c, padded, &v))) return rc;
+        if ((rc = layout_view(c, c->thr.as<double>(), padded, &v))) return rc;
         LaunchTimer t(c);
         if (padded || (u.span && u.L >= 16 && u.L >= sp0.W && fast)) {
             SpanParams sp{};
@@ -1350,16 +1381,16 @@ int wfa_sosfiltfilt(wfa_ctx* c, int n_sections, const double* sos, const double*
 
 int wfa_threshold_hits_count(wfa_ctx* c, int source, int32_t le, int32_t re, int32_t max_len,
                              int64_t* n_hits) {
-    return run_hits(c, source, false, 0, 0, le, re, max_len, n_hits);
+    return ctx_pass(c, source, false, 0, 0, le, re, max_len, n_hits, false);
 }
 
 int wfa_fused_baseline_filter_hits(wfa_ctx* c, int32_t bl_start, int32_t bl_end, int32_t le, int32_t re,
                                    int32_t max_len, int64_t* n_hits) {
-    return run_hits(c, WFA_SRC_SG_FUSED, bl_end > bl_start, bl_start, bl_end, le, re, max_len, n_hits);
+    return ctx_pass(c, WFA_SRC_SG_FUSED, bl_end > bl_start, bl_start, bl_end, le, re, max_len, n_hits, false);
 }
 
 int wfa_hits_enqueue(wfa_ctx* c, int source, int32_t bl_start, int32_t bl_end, int32_t le, int32_t re, int32_t max_len) {
-    return run_hits(c, source, source == WFA_SRC_SG_FUSED && bl_end > bl_start, bl_start, bl_end, le, re, max_len,
+    return ctx_pass(c, source, source == WFA_SRC_SG_FUSED && bl_end > bl_start, bl_start, bl_end, le, re, max_len,
                     nullptr, true);
 }
 
@@ -1367,17 +1398,14 @@ int wfa_hits_wait(wfa_ctx* c, int64_t* n_hits) {
     int rc = use_device(c);
     if (rc) return rc;
     if (!n_hits) return fail(WFA_E_INVALID, "n_hits is null");
-    if (c->pending && c->pend.source == kSrcGroups) return groups_wait(c, n_hits);  // a queued grouped pass (wfa_hits_enqueue_groups)
+    if (c->pending == wfa_ctx::kPendGroups) return groups_wait(c, n_hits);
     if (c->pending) {
         WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-        c->pending = false;
-        const int64_t total = *c->h_total;
-        const int flags = c->pend.runs32 ? (int)(c->h_total[2] & 0xffffffffll) : 0;  // event buffers overflowed
-        if (flags) c->no_runs32 = true;  // a span outgrew its LDS buffer or its slot: the general route from now on
-        c->last_hits = total;
-        if (!spec_rows_stand(total, c->pend.bound, flags)) {  // redone the exact way, now
-            const auto p = c->pend;
-            return run_hits(c, p.source, p.fused_bl, p.bl_start, p.bl_end, p.le, p.re, p.max_len, n_hits);
+        c->pending = wfa_ctx::kPendNone;
+        int64_t total = 0;
+        if (!pass_settle(c, c->pend.out.bound, c->pend.out.runs32, &total)) {  // redone the exact way, now
+            const HitPass p = c->pend.pass;  // (its arguments; plan, thresholds and hint as the context holds them now)
+            return ctx_pass(c, p.source, p.fused_bl, p.bl_start, p.bl_end, p.le, p.re, p.max_len, n_hits, false);
         }
         c->n_hits = total;
     }
@@ -1505,13 +1533,12 @@ static int merge_grow(wfa_ctx* c, DevBuf& b, size_t used, size_t want) {
     return WFA_OK;
 }
 
-// Everything is queued on the context's stream: per group a kernel writes the own-or-+inf threshold column from
-// group_of_record, the group's plan is swapped in from its resident slot, the single pass is queued (run_hits,
-// enqueue_only), one thread takes the pass's row count where the pass reported it (the pinned words of a queued pass, or
-// the count the host already holds) and writes the group's stash offset, and a copy kernel launched for the pass's row
-// bound moves that many rows and record indices to the stash.  The merge kernels are launched for the sum of the bounds
-// and read the total from the last stash offset.  The caller's threshold column is saved before the first group and
-// copied back behind the last.
+// Everything is queued on the context's stream: per group a kernel writes the own-or-+inf copy of the threshold column
+// (grp_thr) from group_of_record, the single pass is queued on that copy under the plan of the group's resident slot
+// (run_hits, enqueue_only), one thread takes the pass's row count where the pass reported it (the pinned words of a queued
+// pass, or the count the host already holds) and writes the group's stash offset, and a copy kernel launched for the
+// pass's row bound moves that many rows and record indices to the stash.  The merge kernels are launched for the sum of
+// the bounds and read the total from the last stash offset.  The context's own plan, thresholds and options are only read.
 //
 // Pinned block (int64 words): per group (rows, overflow flags) of its pass, the stash offsets as the device wrote them
 // ([n_groups] = the merged row count), the fail flag (a group outgrew its bound, its events or the stash).
@@ -1573,19 +1600,6 @@ __global__ __launch_bounds__(kMergeBlock) void k_grp_stash(int g, const int64_t*
     stash_rec[at + d] = (int32_t)(lo - 1);
 }
 
-static void sg_plan_swap(SgPlanDev& a, SgPlanDev& b) {
-    std::swap(a.W, b.W); std::swap(a.P, b.P); std::swap(a.H, b.H);
-    std::swap(a.n_tables, b.n_tables); std::swap(a.stride, b.stride); std::swap(a.int_ok, b.int_ok);
-    std::swap(a.den, b.den); std::swap(a.den_edge, b.den_edge);
-    std::swap(a.guard, b.guard); std::swap(a.guard_edge, b.guard_edge);
-    std::swap(a.rden, b.rden); std::swap(a.rden_edge, b.rden_edge);
-    for (DevBuf SgPlanDev::*m : {&SgPlanDev::tab, &SgPlanDev::itab, &SgPlanDev::sym}) {
-        std::swap((a.*m).ptr, (b.*m).ptr);
-        std::swap((a.*m).cap, (b.*m).cap);
-    }
-    a.sym_host.swap(b.sym_host);
-}
-
 static int groups_pinned(wfa_ctx* c) {
     if (c->h_grp) return WFA_OK;
     const size_t bytes = kGrpWords * sizeof(int64_t) + WFA_MAX_HIT_GROUPS * sizeof(RunsCold);
@@ -1595,124 +1609,80 @@ static int groups_pinned(wfa_ctx* c) {
     return WFA_OK;
 }
 
-// The streaming route keeps what its float64 paths read (pool view + plan) in a device block and refreshes it, with a
-// host wait, when it changes (run_hits_runs32).  Under a grouped pass it changes with every group: here group g's block
-// is queued from the group's own pinned copy, which is rewritten only when the plan's or the pool's buffers moved, so the
-// pass that follows finds its block current and waits for nothing.  Where the pass will not take that route, or its control
-// block does not exist yet, nothing is done and the pass looks after itself.
-static int groups_prime_cold(wfa_ctx* c, int g) {
-    if (c->no_runs32 || c->opt.no_runs32 || c->opt.no_fast) return WFA_OK;
-    const SgParams sp0 = sg_params(c);
-    if (!sg_mask_supported(sp0)) return WFA_OK;
-    const UniformLayout& u = c->layout;
-    const bool in_place = u.span && u.L % 32 == 0;
-    const bool padded = !in_place && u.pad && u.S % 32 == 0 && !c->opt.no_pad;
-    if (!in_place && !padded) return WFA_OK;
-    if (!sg_runs32_supported(sp0, u.L, padded ? u.S : u.L, 0, 0, false)) return WFA_OK;
-    if (c->run_ctrl.cap < 256 + sizeof(RunsCold)) return WFA_OK;
-    int rc;
-    LayoutView v;
-    if ((rc = layout_view(c, padded, &v))) return rc;
-    RunsCold cold{v.pool, sp0};
-    if (c->run_cold_valid && memcmp(&cold, &c->run_cold_host, sizeof(cold)) == 0) return WFA_OK;
-    RunsCold* mine = c->h_grp_cold + g;
-    if (memcmp(mine, &cold, sizeof(cold)) != 0) {
-        WFA_HIP_CHECK(hipStreamSynchronize(c->stream));  // an earlier copy from this block may be in flight
-        memcpy(mine, &cold, sizeof(cold));
-    }
-    WFA_HIP_CHECK(hipMemcpyAsync(c->run_ctrl.as<unsigned long long>() + 32, mine, sizeof(cold), hipMemcpyHostToDevice,
-                                 c->stream));
-    c->run_cold_host = cold;
-    c->run_cold_valid = true;
-    return WFA_OK;
-}
-
-// One pass of the grouped call under group g's plan and the call's baseline window (SG groups) on the threshold column as
-// it stands.
-static int groups_one_pass(wfa_ctx* c, int g, bool exact) {
-    wfa_ctx::GroupsPass& G = c->grp;
+// One pass of the grouped call: group g's plan from its resident slot, the call's baseline window (SG groups), `thr` the
+// column it compares against, the group's own hint and pinned cold block.  exact: no hint, no speculative launch.
+static int groups_one_pass(wfa_ctx* c, int g, const double* thr, bool exact, HitOutcome* o) {
+    const wfa_ctx::GroupsPass& G = c->grp;
     const bool sg = G.groups[g].source == WFA_SRC_SG_FUSED;
-    const bool had_sg = c->have_sg;
-    const bool fused_bl = sg && G.bl_end > G.bl_start;  // (WFA_SRC_F32 reads the uploaded baselines, as in wfa_hits_enqueue)
-    int rc = WFA_OK;
-    if (sg) {
-        sg_plan_swap(c->sg, c->sg_slot[G.groups[g].plan_slot]);
-        c->have_sg = true;
-        rc = groups_prime_cold(c, g);  // (a window the streaming kernel does not take: the block is queued for nothing)
-    }
-    c->last_hits = exact ? -1 : G.last[g];
-    if (!rc) rc = run_hits(c, G.groups[g].source, fused_bl, G.bl_start, G.bl_end, G.le, G.re, G.max_len, nullptr, true);
-    if (sg) {
-        sg_plan_swap(c->sg, c->sg_slot[G.groups[g].plan_slot]);
-        c->have_sg = had_sg;
-    }
-    return rc;
+    HitPass p;
+    p.source = G.groups[g].source;
+    p.plan = sg ? &c->sg_slot[G.groups[g].plan_slot] : nullptr;
+    p.thr = thr;
+    p.fused_bl = sg && G.bl_end > G.bl_start;  // (WFA_SRC_F32 reads the uploaded baselines, as in wfa_hits_enqueue)
+    p.bl_start = G.bl_start; p.bl_end = G.bl_end; p.le = G.le; p.re = G.re; p.max_len = G.max_len;
+    p.hint = exact ? -1 : G.last[g];
+    p.speculate = !exact && !c->opt.no_speculate;
+    p.enqueue_only = true;
+    p.cold_pin = c->h_grp_cold + g;  // (rewritten only when the plan's or the pool's buffers moved: a warm call waits for nothing)
+    return run_hits(c, p, o);
 }
 
-// exact: every pass with the host round trip for its count (the redo of wfa_hits_wait; nothing stays pending)
+// exact: every pass with the host round trip for its count (the redo of wfa_hits_wait; nothing stays pending).  The
+// groups' outcomes are collected in c->grp; what the context remembers of the call is set once, at the end.
 static int groups_run(wfa_ctx* c, bool exact) {
     wfa_ctx::GroupsPass& G = c->grp;
     const int n = G.n_groups;
     const int64_t R = c->R;
     int rc;
-    const bool old_nospec = c->opt.no_speculate;
-    if (exact) c->opt.no_speculate = true;
-    c->pending = false;
+    HitOutcome o;
     if (G.single) {
-        rc = groups_one_pass(c, 0, exact);
-        c->opt.no_speculate = old_nospec;
-        if (rc) return rc;
-        if (c->pending) c->pend.source = kSrcGroups;
-        else G.last[0] = c->n_hits;
+        if ((rc = groups_one_pass(c, 0, c->thr.as<double>(), exact, &o))) return rc;
+        if (o.state == HitOutcome::kQueued) {
+            G.bound[0] = o.bound;
+            G.runs32[0] = o.runs32;
+            c->pending = wfa_ctx::kPendGroups;
+        } else {
+            c->n_hits = c->last_hits = G.last[0] = o.n_hits;
+        }
         return WFA_OK;
     }
     auto planned = [&](int g) { return !exact && G.last[g] >= 0 ? rows_bound(G.last[g]) : (int64_t)0; };
     int64_t plan_rows = 0;
     for (int g = 0; g < n; ++g) plan_rows += planned(g);
     if ((rc = c->merge_rows.ensure((size_t)plan_rows * 60)) || (rc = c->merge_rec.ensure((size_t)plan_rows * sizeof(int32_t))) ||
-        (rc = c->grp_thr.ensure((size_t)R * sizeof(double))) || (rc = c->grp_sets.ensure(16 * sizeof(int64_t)))) {
-        c->opt.no_speculate = old_nospec;
+        (rc = c->grp_thr.ensure((size_t)R * sizeof(double))) || (rc = c->grp_sets.ensure(16 * sizeof(int64_t))))
         return rc;
-    }
     int64_t* sets = c->grp_sets.as<int64_t>();
-    WFA_HIP_CHECK(hipMemcpyAsync(c->grp_thr.ptr, c->thr.ptr, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    // whatever happens below, the caller's column goes back behind the queued work and the options stand as they were
-    auto leave = [&](int code) {
-        (void)hipMemcpyAsync(c->thr.ptr, c->grp_thr.ptr, (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
-        c->opt.no_speculate = old_nospec;
-        return code;
-    };
     int64_t n_bound = 0;  // rows the merge kernels are launched for
     bool queued = false;
     for (int g = 0; g < n; ++g) {
-        {
+        {  // (one stream: the kernels of group g - 1 have read grp_thr before this one rewrites it)
             LaunchTimer t(c);
             hipLaunchKernelGGL(k_grp_mask, dim3(merge_grid(R)), dim3(kMergeBlock), 0, c->stream, R, c->grp_gor.as<int32_t>(),
-                               (int32_t)g, c->grp_thr.as<double>(), c->thr.as<double>());
-            if (hipGetLastError() != hipSuccess) return leave(fail(WFA_E_HIP, "k_grp_mask launch failed"));
-            if ((rc = t.end("k_grp_mask"))) return leave(rc);
+                               (int32_t)g, c->thr.as<double>(), c->grp_thr.as<double>());
+            if (hipGetLastError() != hipSuccess) return fail(WFA_E_HIP, "k_grp_mask launch failed");
+            if ((rc = t.end("k_grp_mask"))) return rc;
         }
-        if ((rc = groups_one_pass(c, g, exact))) return leave(rc);
+        if ((rc = groups_one_pass(c, g, c->grp_thr.as<double>(), exact, &o))) return rc;
         int64_t launch_rows;
-        if (c->pending) {  // queued: its count is on its way to the pinned words of the single pass
-            c->pending = false;
+        if (o.state == HitOutcome::kQueued) {  // its count is on its way to the pinned words of the single pass
             queued = true;
-            G.bound[g] = c->pend.bound;
-            G.runs32[g] = c->pend.runs32;
+            G.bound[g] = o.bound;
+            G.runs32[g] = o.runs32;
             G.n_host[g] = -1;
             launch_rows = G.bound[g];
         } else {  // ran to completion, the stream is idle: every earlier stash offset has reached the pinned block
-            G.n_host[g] = G.last[g] = c->n_hits;
-            G.bound[g] = c->n_hits;
+            G.n_host[g] = G.last[g] = o.n_hits;
+            G.bound[g] = o.n_hits;
             G.runs32[g] = false;
-            launch_rows = c->n_hits;
+            launch_rows = o.n_hits;
             const int64_t at = g == 0 ? 0 : c->h_grp[kGrpSets + g];
             int64_t later = 0;
             for (int e = g + 1; e < n; ++e) later += planned(e);
             const int64_t want = at + launch_rows + later;
             if ((rc = merge_grow(c, c->merge_rows, (size_t)at * 60, (size_t)want * 60)) ||
                 (rc = merge_grow(c, c->merge_rec, (size_t)at * sizeof(int32_t), (size_t)want * sizeof(int32_t))))
-                return leave(rc);
+                return rc;
         }
         const int64_t cap_rows = (int64_t)std::min(c->merge_rows.cap / 60, c->merge_rec.cap / sizeof(int32_t));
         LaunchTimer t(c);
@@ -1722,8 +1692,8 @@ static int groups_run(wfa_ctx* c, bool exact) {
             hipLaunchKernelGGL(k_grp_stash, dim3(merge_grid(launch_rows * 15)), dim3(kMergeBlock), 0, c->stream, g, sets,
                                c->hit_out.as<uint32_t>(), c->rows_index == 1 ? c->hit_desc.as<int4>() : nullptr,
                                c->rec_out_start.as<int64_t>(), R, c->merge_rows.as<uint32_t>(), c->merge_rec.as<int32_t>());
-        if (hipGetLastError() != hipSuccess) return leave(fail(WFA_E_HIP, "k_grp_stash launch failed"));
-        if ((rc = t.end("k_grp_take + k_grp_stash"))) return leave(rc);
+        if (hipGetLastError() != hipSuccess) return fail(WFA_E_HIP, "k_grp_stash launch failed");
+        if ((rc = t.end("k_grp_take + k_grp_stash"))) return rc;
         n_bound += launch_rows;
     }
     c->rows_index = 0;
@@ -1734,51 +1704,49 @@ static int groups_run(wfa_ctx* c, bool exact) {
         if (c->hit_out.cap < (size_t)n_bound * 60 || c->hit_desc.cap < (size_t)n_bound * sizeof(int4) ||
             c->merge_dest.cap < (size_t)n_bound * sizeof(int64_t)) {
             if (hipStreamSynchronize(c->stream) != hipSuccess)  // the stash kernels read the buffers that are about to move
-                return leave(fail(WFA_E_HIP, "waiting for the stash of the grouped pass failed"));
+                return fail(WFA_E_HIP, "waiting for the stash of the grouped pass failed");
             if ((rc = c->hit_out.ensure((size_t)room * 60)) || (rc = c->hit_desc.ensure((size_t)room * sizeof(int4))) ||
                 (rc = c->merge_dest.ensure((size_t)room * sizeof(int64_t))))
-                return leave(rc);
+                return rc;
         }
         if ((rc = c->rec_nhits.ensure((size_t)R * sizeof(int32_t))) || (rc = c->rec_out_start.ensure((size_t)R * sizeof(int64_t))) ||
             (rc = c->scan_blocks.ensure((size_t)(nb + 1) * sizeof(int64_t))))
-            return leave(rc);
+            return rc;
         const int32_t* rec = c->merge_rec.as<int32_t>();
         int32_t* counts = c->rec_nhits.as<int32_t>();
         const int64_t* total = sets + n;
         if (hipMemsetAsync(counts, 0, (size_t)R * sizeof(int32_t), c->stream) != hipSuccess)
-            return leave(fail(WFA_E_HIP, "clearing the merge counts failed"));
+            return fail(WFA_E_HIP, "clearing the merge counts failed");
         {
             LaunchTimer t(c);
             hipLaunchKernelGGL(k_hit_rows_merge_count, dim3(merge_grid(n_bound)), dim3(kMergeBlock), 0, c->stream, n_bound, rec,
                                (const int64_t*)sets, n, R, counts, total);
-            if (hipGetLastError() != hipSuccess) return leave(fail(WFA_E_HIP, "k_hit_rows_merge_count launch failed"));
-            if ((rc = t.end("k_hit_rows_merge_count"))) return leave(rc);
+            if (hipGetLastError() != hipSuccess) return fail(WFA_E_HIP, "k_hit_rows_merge_count launch failed");
+            if ((rc = t.end("k_hit_rows_merge_count"))) return rc;
         }
         {
             LaunchTimer t(c);
             if (launch_scan(c->stream, counts, R, c->scan_blocks.as<int64_t>(), c->rec_out_start.as<int64_t>()) != hipSuccess)
-                return leave(fail(WFA_E_HIP, "k_scan(merged hit counts) launch failed"));
-            if ((rc = t.end("k_scan(merged hit counts)"))) return leave(rc);
+                return fail(WFA_E_HIP, "k_scan(merged hit counts) launch failed");
+            if ((rc = t.end("k_scan(merged hit counts)"))) return rc;
         }
         {
             LaunchTimer t(c);
             hipLaunchKernelGGL(k_hit_rows_merge_place, dim3(merge_grid(n_bound)), dim3(kMergeBlock), 0, c->stream, n_bound, rec,
                                (const int64_t*)sets, n, R, c->rec_out_start.as<int64_t>(), c->merge_dest.as<int64_t>(), total);
-            if (hipGetLastError() != hipSuccess) return leave(fail(WFA_E_HIP, "k_hit_rows_merge_place launch failed"));
-            if ((rc = t.end("k_hit_rows_merge_place"))) return leave(rc);
+            if (hipGetLastError() != hipSuccess) return fail(WFA_E_HIP, "k_hit_rows_merge_place launch failed");
+            if ((rc = t.end("k_hit_rows_merge_place"))) return rc;
         }
         {
             LaunchTimer t(c);
             hipLaunchKernelGGL(k_hit_rows_merge_scatter, dim3(merge_grid(n_bound * 15)), dim3(kMergeBlock), 0, c->stream, n_bound,
                                c->merge_rows.as<uint32_t>(), c->merge_dest.as<int64_t>(), c->hit_out.as<uint32_t>(), total);
-            if (hipGetLastError() != hipSuccess) return leave(fail(WFA_E_HIP, "k_hit_rows_merge_scatter launch failed"));
-            if ((rc = t.end("k_hit_rows_merge_scatter"))) return leave(rc);
+            if (hipGetLastError() != hipSuccess) return fail(WFA_E_HIP, "k_hit_rows_merge_scatter launch failed");
+            if ((rc = t.end("k_hit_rows_merge_scatter"))) return rc;
         }
     }
-    (void)leave(WFA_OK);
     if (queued) {  // wfa_hits_wait reads the pinned block
-        c->pending = true;
-        c->pend = {kSrcGroups, false, 0, 0, G.le, G.re, G.max_len, n_bound, false};
+        c->pending = wfa_ctx::kPendGroups;
         return WFA_OK;
     }
     int64_t total = 0;
@@ -1790,14 +1758,12 @@ static int groups_run(wfa_ctx* c, bool exact) {
 static int groups_wait(wfa_ctx* c, int64_t* n_hits) {
     wfa_ctx::GroupsPass& G = c->grp;
     WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    c->pending = false;
+    c->pending = wfa_ctx::kPendNone;
     bool redo = false;
-    if (G.single) {
-        const int64_t total = *c->h_total;
-        const int flags = c->pend.runs32 ? (int)(c->h_total[2] & 0xffffffffll) : 0;
-        if (flags) c->no_runs32 = true;
-        G.last[0] = c->last_hits = total;
-        redo = !spec_rows_stand(total, c->pend.bound, flags);
+    if (G.single) {  // the single pass under the slot's plan: settled like wfa_hits_wait's own
+        int64_t total = 0;
+        redo = !pass_settle(c, G.bound[0], G.runs32[0], &total);
+        G.last[0] = total;
         if (!redo) c->n_hits = total;
     } else {
         for (int g = 0; g < G.n_groups; ++g) {
@@ -1897,7 +1863,7 @@ int wfa_hits_enqueue_groups(wfa_ctx* c, int n_groups, const wfa_hit_group* group
     if (max_len < c->max_len)
         return fail(WFA_E_INVALID, "max_len (%d) < longest uploaded record (%d)", max_len, c->max_len);
     if ((rc = groups_pinned(c))) return rc;
-    c->pending = false;  // (a queued pass nobody waited for ends here, like in wfa_hits_enqueue)
+    c->pending = wfa_ctx::kPendNone;  // (a queued pass nobody waited for ends here, like in wfa_hits_enqueue)
     wfa_ctx::GroupsPass& G = c->grp;
     if (G.n_groups != n_groups || memcmp(G.groups, groups, (size_t)n_groups * sizeof(wfa_hit_group)) != 0)
         for (int64_t& v : G.last) v = -1;  // other groups than last time: their previous counts say nothing
@@ -2099,7 +2065,7 @@ int wfa_basic_features(wfa_ctx* c, int source, int64_t h0, int64_t h1, int h_has
             WFA_HIP_CHECK(e);
             if ((rc = t.end("k_basic_features_leaf"))) return rc;
         } else {
-            WFA_HIP_CHECK(launch_basic_features(c->stream, source, pool_view(c), rec_view(c), sg_params(c), fp,
+            WFA_HIP_CHECK(launch_basic_features(c->stream, source, pool_view(c), rec_view(c), sg_params(ctx_plan(c)), fp,
                                                 c->out_rows.as<uint8_t>()));
             if ((rc = t.end("k_basic_features"))) return rc;
         }
@@ -2255,7 +2221,7 @@ int wfa_width_integral(wfa_ctx* c, int source, double q_low, double q_high, doub
             WFA_HIP_CHECK(e);
             if ((rc = t.end("k_width_integral_leaf"))) return rc;
         } else {
-            WFA_HIP_CHECK(launch_width_integral(c->stream, source, pool_view(c), rec_view(c), sg_params(c), wp,
+            WFA_HIP_CHECK(launch_width_integral(c->stream, source, pool_view(c), rec_view(c), sg_params(ctx_plan(c)), wp,
                                                 c->out_rows.as<uint8_t>()));
             if ((rc = t.end("k_width_integral"))) return rc;
         }
@@ -2292,7 +2258,7 @@ int wfa_features_both(wfa_ctx* c, int64_t h0, int64_t h1, int h_has_end, int64_t
                 WFA_HIP_CHECK(e);
                 if ((rc = t.end("k_basic_features_leaf"))) return rc;
             } else {
-                WFA_HIP_CHECK(launch_basic_features(c->stream, WFA_SRC_RAW, pool_view(c), rec_view(c), sg_params(c), fp, ob));
+                WFA_HIP_CHECK(launch_basic_features(c->stream, WFA_SRC_RAW, pool_view(c), rec_view(c), sg_params(ctx_plan(c)), fp, ob));
                 if ((rc = t.end("k_basic_features"))) return rc;
             }
             LaunchTimer t2(c);
@@ -2300,7 +2266,7 @@ int wfa_features_both(wfa_ctx* c, int64_t h0, int64_t h1, int h_has_end, int64_t
                 WFA_HIP_CHECK(e);
                 if ((rc = t2.end("k_width_integral_leaf"))) return rc;
             } else {
-                WFA_HIP_CHECK(launch_width_integral(c->stream, WFA_SRC_RAW, pool_view(c), rec_view(c), sg_params(c), wp, ow));
+                WFA_HIP_CHECK(launch_width_integral(c->stream, WFA_SRC_RAW, pool_view(c), rec_view(c), sg_params(ctx_plan(c)), wp, ow));
                 if ((rc = t2.end("k_width_integral"))) return rc;
             }
         }

@@ -74,6 +74,29 @@ struct SgPlanDev {
     std::vector<uint8_t> sym_host;
 };
 
+// One fused hit pass (run_hits, wfa_capi.hip): what it reads besides the resident pool, the records' other columns and the
+// route options of the context.  The single-pass entry points fill it from the context, the grouped pass once per group.
+struct HitPass {
+    int source = 0;
+    const SgPlanDev* plan = nullptr;  // Savitzky-Golay plan (null: none)
+    const double* thr = nullptr;      // device column the pass compares against, one threshold per record
+    bool fused_bl = false;
+    int32_t bl_start = 0, bl_end = 0, le = 0, re = 0, max_len = 0;
+    int64_t hint = -1;                // rows of the previous pass like this one: sizes the speculative launch (-1: none)
+    bool speculate = true;            // false: exact row launches (host round trip for the hit count)
+    bool enqueue_only = false;        // queue the speculative launch and return without the count, where the pass can
+    RunsCold* cold_pin = nullptr;     // pinned slot the streaming route's cold block is staged through
+};
+
+// What a pass did.  kNone: the streaming route declined (run_hits_runs32 alone).
+struct HitOutcome {
+    enum { kNone, kQueued, kCompleted } state = kNone;
+    int64_t bound = 0;      // kQueued: rows the launches were sized for; the count is on its way to the pinned words
+    bool runs32 = false;    // kQueued on the streaming route: the overflow flags come with the count
+    int64_t n_hits = -1;    // kCompleted: rows in hit_out
+    bool overflow = false;  // the streaming route found a span's events outgrowing their buffer
+};
+
 }  // namespace wfa
 
 struct wfa_ctx {
@@ -158,7 +181,9 @@ struct wfa_ctx {
     bool run_cold_valid = false;
     bool no_runs32 = false;   // a span outgrew the event buffer of its wave: this records upload takes the general route
     int64_t n_hits = -1;
-    int64_t last_hits = -1;  // hits of the previous fast-path pass on this context (sizes the speculative tail)
+    // rows of the last single pass with a row stage, or the merged total of the last grouped call: the hint of the next
+    // single pass (HitPass::hint).  Written by the entry points and by the settle step of wfa_hits_wait, never by a pass
+    int64_t last_hits = -1;
     // where the record index of every row of the last hit pass stands: 0 nowhere (no pass yet, a merged table, or the
     // per-record buffers taken by another stage), 1 hit_desc[i].x (streaming and bitmap routes), 2 rec_nhits /
     // rec_out_start (general route: per-record counts and their exclusive scan)
@@ -170,9 +195,10 @@ struct wfa_ctx {
     // pool and records uploads like `sg`
     wfa::SgPlanDev sg_slot[WFA_MAX_HIT_GROUPS];
     bool have_slot[WFA_MAX_HIT_GROUPS] = {};
-    // queued grouped pass (wfa_hits_enqueue_groups): its arguments, kept for the exact redo of wfa_hits_wait; per
-    // group the row bound its launches were sized for (queued) or the row count the host already read (n_host >= 0);
-    // `last` = the row count of the group's previous pass on this context (sizes its speculative launch; -1: none yet)
+    // the last grouped pass (wfa_hits_enqueue_groups): its arguments, all a queued one (pending == kPendGroups) keeps for
+    // wfa_hits_wait and its exact redo; per group the outcome of its pass -- the row bound its launches were sized for
+    // (queued) or the row count the host already read (n_host >= 0) -- and `last`, the row count of the group's previous
+    // pass on this context (the hint of its next one; -1: none yet)
     struct GroupsPass {
         bool single = false;   // one group, no unowned record: the plain pass with the slot's plan
         int n_groups = 0;
@@ -186,7 +212,7 @@ struct wfa_ctx {
         int64_t last[WFA_MAX_HIT_GROUPS] = {-1, -1, -1, -1, -1, -1, -1, -1};
     } grp;
     wfa::DevBuf grp_gor;   // int32 per record: group_of_record of the last grouped pass
-    wfa::DevBuf grp_thr;   // double per record: the caller's threshold column while the passes run on masked copies
+    wfa::DevBuf grp_thr;   // double per record: own-or-+inf copy of the threshold column, what the current group's pass compares against
     wfa::DevBuf grp_sets;  // int64 [WFA_MAX_HIT_GROUPS + 1] stash offsets written on the device, then [fail flag]
     // pinned: per group (row count, overflow flags), the stash offsets as the device wrote them, the merged count and
     // the fail flag; behind them one RunsCold per group (what k_sg_runs32's float64 paths read under that group's plan)
@@ -239,13 +265,15 @@ struct wfa_ctx {
     std::vector<hipEvent_t> prof_free;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // enqueue-only hit passes (wfa_hits_enqueue / wfa_hits_wait): the row count of the last enqueued pass lands in a
-    // pinned host word; the pass's arguments are kept in case it outgrew its speculative row bound and must be redone
+    // pinned host word
     int64_t* h_total = nullptr;
     // streaming route: the group sums [0, run_dirty_groups) of run_groups, and with any of them the two control words of
     // run_ctrl, may be non-zero.  Raised before k_sg_runs32, lowered only once a clear of the whole extent is enqueued.
     int64_t run_dirty_groups = 0;
-    bool pending = false;
-    struct PendingPass { int source; bool fused_bl; int32_t bl_start, bl_end, le, re, max_len; int64_t bound; bool runs32; } pend{};
+    // what wfa_hits_wait has to settle: nothing, a single pass (`pend`) or a grouped one (`grp`)
+    enum Pending { kPendNone = 0, kPendPass, kPendGroups } pending = kPendNone;
+    // queued single pass: its description, kept for the exact redo, and what it reported (bound, runs32)
+    struct PendingPass { wfa::HitPass pass; wfa::HitOutcome out; } pend{};
 
     // rccl (opaque, owned by wfa_rccl.hip)
     void* comm = nullptr;
