@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define WFA_ABI_VERSION 5
+#define WFA_ABI_VERSION 6
 
 #define WFA_OK 0
 #define WFA_E_INVALID (-1)   /* bad argument / malformed records (maps to ValueError) */
@@ -363,6 +363,41 @@ int wfa_waveform_width_records(wfa_ctx* ctx, int source, int64_t n_hits, const i
                                const int64_t* record_index, double rise_low, double rise_high, double fall_high,
                                double fall_low, double sampling_rate, int interpolation, void* out_rows,
                                uint8_t* valid);
+
+/* Peak chain: the S1/S2 rows of the resident find_peaks rows without a table leaving the device (reference: the chain
+ * hit -> waveform_width -> s1_s2 with basic_features on the side: cpu/waveform_width.py:205-374,
+ * cpu/basic_features.py:108-195, cpu/s1_s2_classifier.py:57-69,133-228).  Two-phase like the other row stages.
+ * Needs uploaded records, the pool(s) of the two sources, and a wfa_find_peaks_count pass in signal mode
+ * WFA_PEAK_SIGNAL_RECORDS whose rows are still resident (WFA_E_STATE otherwise).  count, on the context's stream:
+ *  1. basic_features of the uploaded records (feature_source, height / area ranges as for wfa_basic_features, no
+ *     fixed baseline) into a buffer of the stage -- the leaf kernel where wfa_basic_features would take it;
+ *  2. k_peak_chain, one lane per peak row: the width of wfa_waveform_width_records (width_source) at (record_id,
+ *     position) of the row, record_id being the INDEX of the record and of its feature row; a peak that call would mark
+ *     valid = 0 is dropped.  Range cuts on float64(width), float64(area), float64(height): class_ranges = 6 x (lo, hi)
+ *     in the order s1 width, s1 area, s1 height, s2 width, s2 area, s2 height; bit 2k / 2k + 1 of range_bounds says
+ *     range k has a lower / an upper bound (the other reads as None), neither bit: the range is disabled.  NaN is outside
+ *     every enabled range, a class with no enabled range never matches.  width_in_samples != 0 cuts on
+ *     total_width_samples instead of total_width.  Both classes match: conflict_policy decides;
+ *  3. scan of the keep flags, k_peak_chain_compact: the kept rows in peak order.
+ * Rows are S1_S2_CLASSIFIER_DTYPE (45 B packed: label i1, width_ns f4, width_samples f4, height f4, area f4,
+ * timestamp i8, board i2, channel i2, record_id i8, peak_position i8), bit-exact; record_id = the peak's record_id +
+ * record_id_base (a chunk uploaded with chunk-local ids delivers the run's).  No peaks: 0 rows, nothing launched.
+ * sampling_rate 0 / NaN: WFA_E_INVALID "float division by zero".  The peak rows (wfa_find_peaks_fill still delivers
+ * them), pools, records and plan are untouched.  A records upload (or a pool upload, which drops the records) after
+ * the find_peaks pass voids its rows for this stage: WFA_E_STATE until the pass has run on the new table.
+ * Scratch (wfa_release_scratch frees it, wfa_scratch_bytes counts it; fill after a release: WFA_E_STATE):
+ *   36 B per record + 45 B per peak + 45 B per kept row.
+ * The keep flags and their scan reuse two per-candidate buffers of find_peaks, which that pass has finished with
+ * once its rows exist; they cost 12 B per peak and 8 B per 1024 peaks + 8 B only where a release has taken them. */
+#define WFA_S1S2_UNKNOWN 0
+#define WFA_S1S2_PREFER_S1 1
+#define WFA_S1S2_PREFER_S2 2
+int wfa_peak_chain_count(wfa_ctx* ctx, int width_source, int feature_source, double rise_low, double rise_high,
+                         double fall_high, double fall_low, double sampling_rate, int interpolation,
+                         int64_t height_start, int64_t height_end, int height_has_end, int64_t area_start,
+                         int64_t area_end, int area_has_end, int width_in_samples, const double* class_ranges,
+                         uint32_t range_bounds, int conflict_policy, int64_t record_id_base, int64_t* n_rows);
+int wfa_peak_chain_fill(wfa_ctx* ctx, void* out_rows, int64_t n_rows);
 
 /* ---- hit-table stages (device sort + scans; host columns in, host index tables out) ----------------------
  * K11 hit merge (reference: cpu/hit_merge.py:115-181 `_build_merged_clusters`, 256-322 `_emit_cluster`).

@@ -26,7 +26,8 @@ ST_SRC_HOST, ST_SRC_CSV, ST_SRC_ARENA, ST_SRC_POOL = 0, 1, 2, 3
 VIEW_WAVES, VIEW_WAVES_BASELINE, VIEW_SIGNALS = 0, 1, 2
 VIEW_U16, VIEW_F32, VIEW_F64 = 0, 1, 2
 DENSE_I16, DENSE_U16, DENSE_F32 = 0, 1, 2
-ABI_VERSION = 5
+S1S2_UNKNOWN, S1S2_PREFER_S1, S1S2_PREFER_S2 = 0, 1, 2
+ABI_VERSION = 6
 MAX_HIT_GROUPS = 8
 
 _p = C.c_void_p
@@ -79,6 +80,9 @@ SIGNATURES = {
     "wfa_find_hits_fill": (_int, [_p, _i64, _p, _p]),
     "wfa_waveform_width": (_int, [_p, _int, _i64, _p, _p, _i64, _i32, _f64, _f64, _f64, _f64, _f64, _int, _p, _p]),
     "wfa_waveform_width_records": (_int, [_p, _int, _i64, _p, _p, _f64, _f64, _f64, _f64, _f64, _int, _p, _p]),
+    "wfa_peak_chain_count": (_int, [_p, _int, _int, _f64, _f64, _f64, _f64, _f64, _int, _i64, _i64, _int, _i64, _i64, _int,
+                                    _int, _p, C.c_uint32, _int, _i64, C.POINTER(_i64)]),
+    "wfa_peak_chain_fill": (_int, [_p, _p, _i64]),
     "wfa_hit_merge_count": (_int, [_p, _i64] + [_p] * 7 + [_f64, _f64, C.POINTER(_i64)]),
     "wfa_hit_merge_fill": (_int, [_p, _i64, _i64, _p, _p]),
     "wfa_hit_merge_emit": (_int, [_p, _i64] + [_p] * 6 + [_i64, _p, _i64, _p] + [_p] * 6),

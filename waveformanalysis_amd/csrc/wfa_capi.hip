@@ -886,6 +886,7 @@ int wfa_release_scratch(wfa_ctx* c, int64_t* freed_bytes) {
     for (DevBuf* b : c->scratch) { freed += (int64_t)b->cap; b->release(); }  // (a count pass without its fill is void after this)
     c->ht_n = -1;
     c->ht_perm = nullptr;
+    c->n_chain = -1;
     c->csv_rows = -1;
     c->csv_samples = -1;
     c->csv_filled = false;
@@ -1905,8 +1906,8 @@ int wfa_find_peaks_count(wfa_ctx* c, int source, int signal_mode, int use_deriva
         return fail(WFA_E_INVALID, "height_method must be WFA_HEIGHT_MINMAX or WFA_HEIGHT_DIFF");
     if (signal_mode < WFA_PEAK_SIGNAL_RECORDS || signal_mode > WFA_PEAK_SIGNAL_ROWS_F64)
         return fail(WFA_E_INVALID, "signal_mode must be WFA_PEAK_SIGNAL_RECORDS, _ROWS or _ROWS_F64");
-    c->n_peaks = -1;
-    if (c->R == 0) { c->n_peaks = 0; *n_peaks = 0; return WFA_OK; }
+    c->n_peaks = c->n_chain = -1;
+    if (c->R == 0) { c->n_peaks = 0; c->peak_mode = signal_mode; c->peak_gen = c->records_gen; *n_peaks = 0; return WFA_OK; }
     if (c->rows_index == 2) c->rows_index = 0;  // rec_nhits / rec_out_start are this pass's from here on
     const int64_t R = c->R;
     if ((rc = c->rec_nhits.ensure(R * sizeof(int32_t)))) return rc;
@@ -2022,7 +2023,11 @@ int wfa_find_peaks_count(wfa_ctx* c, int source, int signal_mode, int use_deriva
     WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
     if (flag)  // numpy's message for np.max of the empty height window (peak_finding.py:606)
         return fail(WFA_E_INVALID, "zero-size array to reduction operation maximum which has no identity");
+    // peak_out holds the rows from here on: peak_accept and peak_row_start (like the other per-candidate buffers) have
+    // been read for the last time, and wfa_peak_chain_count takes them for its keep flags and their scan
     c->n_peaks = total;
+    c->peak_mode = signal_mode;
+    c->peak_gen = c->records_gen;
     *n_peaks = total;
     return WFA_OK;
 }
@@ -2199,6 +2204,103 @@ int wfa_waveform_width_records(wfa_ctx* c, int source, int64_t n_hits, const int
                                                                d_row, rise_low, rise_high, fall_high, fall_low,
                                                                sampling_rate, interpolation, d_out, d_valid);
                       });
+}
+
+int wfa_peak_chain_count(wfa_ctx* c, int width_source, int feature_source, double rise_low, double rise_high,
+                         double fall_high, double fall_low, double sampling_rate, int interpolation, int64_t h0,
+                         int64_t h1, int h_has_end, int64_t a0, int64_t a1, int a_has_end, int width_in_samples,
+                         const double* class_ranges, uint32_t range_bounds, int conflict_policy, int64_t record_id_base,
+                         int64_t* n_rows) {
+    int rc = use_device(c);
+    if (rc) return rc;
+    if (!n_rows) return fail(WFA_E_INVALID, "n_rows is null");
+    if ((width_source != WFA_SRC_RAW && width_source != WFA_SRC_F32) ||
+        (feature_source != WFA_SRC_RAW && feature_source != WFA_SRC_F32))
+        return fail(WFA_E_INVALID, "peak_chain reads stored samples: sources must be WFA_SRC_RAW or WFA_SRC_F32");
+    if (range_bounds >> 12) return fail(WFA_E_INVALID, "range_bounds has bits above the six ranges");
+    if (conflict_policy < WFA_S1S2_UNKNOWN || conflict_policy > WFA_S1S2_PREFER_S2)
+        return fail(WFA_E_INVALID, "conflict_policy must be WFA_S1S2_UNKNOWN, _PREFER_S1 or _PREFER_S2");
+    if (range_bounds && !class_ranges) return fail(WFA_E_INVALID, "class_ranges is null");
+    c->n_chain = -1;
+    if (c->n_peaks < 0) return fail(WFA_E_STATE, "no find_peaks pass has been run");
+    if (c->peak_mode != WFA_PEAK_SIGNAL_RECORDS)
+        return fail(WFA_E_STATE, "peak_chain needs the rows of a WFA_PEAK_SIGNAL_RECORDS find_peaks pass");
+    if (c->peak_gen != c->records_gen)
+        return fail(WFA_E_STATE, "the records have been replaced since the find_peaks pass: run it again");
+    if ((rc = need_source(c, width_source))) return rc;  // records (their slices were checked against the pool) + the pools
+    if ((rc = need_source(c, feature_source))) return rc;
+    const int64_t n = c->n_peaks;
+    if (n == 0) { c->n_chain = 0; *n_rows = 0; return WFA_OK; }
+    if (!(sampling_rate == sampling_rate) || sampling_rate == 0.0) return fail(WFA_E_INVALID, "float division by zero");
+    // scratch: feature rows, row slots, kept rows; keep flags and their scan in find_peaks' per-candidate buffers (the
+    // pass has read them for the last time: its rows are in peak_out)
+    if ((rc = c->pc_feat.ensure((size_t)c->R * 36))) return rc;
+    if ((rc = c->pc_rows.ensure((size_t)n * 45))) return rc;
+    if ((rc = c->peak_accept.ensure((size_t)n * sizeof(int32_t)))) return rc;
+    if ((rc = c->peak_row_start.ensure((size_t)n * sizeof(int64_t)))) return rc;
+    const int64_t nb = scan_blocks_for(n);
+    if ((rc = c->scan_blocks.ensure((nb + 1) * sizeof(int64_t)))) return rc;
+    FeatParams fp{};
+    fp.h0 = h0; fp.h1 = h1; fp.h_has_end = h_has_end;
+    fp.a0 = a0; fp.a1 = a1; fp.a_has_end = a_has_end;
+    fp.fixed_bl = nullptr;
+    {
+        LaunchTimer t(c);
+        hipError_t e = hipSuccess;
+        if (feature_source == WFA_SRC_RAW && launch_basic_features_wave(c, rec_view(c), fp, c->pc_feat.as<uint8_t>(), &e)) {
+            WFA_HIP_CHECK(e);
+            if ((rc = t.end("k_basic_features_leaf"))) return rc;
+        } else {
+            WFA_HIP_CHECK(launch_basic_features(c->stream, feature_source, pool_view(c), rec_view(c), sg_params(ctx_plan(c)), fp,
+                                                c->pc_feat.as<uint8_t>()));
+            if ((rc = t.end("k_basic_features"))) return rc;
+        }
+    }
+    ChainParams cp{};
+    for (int k = 0; k < 6; ++k) {
+        cp.lo[k] = (range_bounds >> (2 * k)) & 1u ? class_ranges[2 * k] : 0.0;
+        cp.hi[k] = (range_bounds >> (2 * k)) & 2u ? class_ranges[2 * k + 1] : 0.0;
+    }
+    cp.bounds = range_bounds;
+    cp.width_in_samples = width_in_samples ? 1 : 0;
+    cp.policy = conflict_policy;
+    cp.record_id_base = record_id_base;
+    int32_t* keep = c->peak_accept.as<int32_t>();
+    int64_t* start = c->peak_row_start.as<int64_t>();
+    {
+        LaunchTimer t(c);
+        WFA_HIP_CHECK(launch_peak_chain(c->stream, width_source, pool_view(c), rec_view(c), n, c->peak_out.as<uint8_t>(),
+                                        c->pc_feat.as<uint8_t>(), rise_low, rise_high, fall_high, fall_low, sampling_rate,
+                                        interpolation, cp, c->pc_rows.as<uint8_t>(), keep));
+        if ((rc = t.end("k_peak_chain"))) return rc;
+    }
+    int64_t kept = 0;
+    WFA_HIP_CHECK(launch_scan(c->stream, keep, n, c->scan_blocks.as<int64_t>(), start));
+    WFA_HIP_CHECK(hipMemcpyAsync(&kept, c->scan_blocks.as<int64_t>() + nb, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (kept < 0 || kept > n) return fail(WFA_E_HIP, "peak_chain kept %lld of %lld rows", (long long)kept, (long long)n);
+    if (kept > 0) {
+        if ((rc = c->pc_out.ensure((size_t)kept * 45))) return rc;
+        LaunchTimer t(c);
+        WFA_HIP_CHECK(launch_peak_chain_compact(c->stream, n, c->pc_rows.as<uint8_t>(), keep, start, c->pc_out.as<uint8_t>()));
+        if ((rc = t.end("k_peak_chain_compact"))) return rc;
+    }
+    c->n_chain = kept;
+    *n_rows = kept;
+    return WFA_OK;
+}
+
+int wfa_peak_chain_fill(wfa_ctx* c, void* out_rows, int64_t n_rows) {
+    int rc = use_device(c);
+    if (rc) return rc;
+    if (c->n_chain < 0) return fail(WFA_E_STATE, "no peak_chain pass has been run");
+    if (n_rows != c->n_chain)
+        return fail(WFA_E_INVALID, "caller expects %lld rows, the pass produced %lld", (long long)n_rows, (long long)c->n_chain);
+    if (n_rows == 0) return WFA_OK;
+    if (!out_rows) return fail(WFA_E_INVALID, "out_rows is null");
+    WFA_HIP_CHECK(hipMemcpyAsync(out_rows, c->pc_out.ptr, (size_t)n_rows * 45, hipMemcpyDeviceToHost, c->stream));
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return WFA_OK;
 }
 
 int wfa_width_integral(wfa_ctx* c, int source, double q_low, double q_high, double dt, void* out_rows) {

@@ -226,6 +226,13 @@ struct wfa_ctx {
     wfa::DevBuf fw_ties{scratch};  // width-integral records whose quantile positions are re-walked in numpy's order
     wfa::DevBuf peak_out;  // HIT_DTYPE rows of the last find_peaks pass
     int64_t n_peaks = -1;
+    int peak_mode = 0;      // WFA_PEAK_SIGNAL_* of the pass that wrote peak_out
+    // records_gen counts the records tables this context has held (every upload and every drop); peak_gen is its value
+    // when peak_out was written: the peak chain evaluates the rows only on the table they were found on
+    int64_t records_gen = 0, peak_gen = -1;
+    // peak chain (wfa_peak_chain_count): feature rows of the records, one row slot per peak, the kept rows
+    wfa::DevBuf pc_feat{scratch}, pc_rows{scratch}, pc_out{scratch};
+    int64_t n_chain = -1;   // kept rows of the last peak chain pass; -1: none, or its scratch was released
     int64_t n_legacy = -1;  // hits of the last wfa_find_hits_count pass
     wfa::DevBuf peak_cand_n{scratch}, peak_cand_pos{scratch}, peak_cand_val{scratch}, peak_cand_state{scratch};  // candidate lists of find_peaks
     wfa::DevBuf peak_slot_pos{scratch}, peak_slot_val{scratch};  // kPeakSlots candidates per record, written by the single walk
@@ -289,6 +296,7 @@ inline void pass_caches_dropped(wfa_ctx* c) { c->shadow_valid = c->bitmap_clean 
 // No records: the passes refuse until the next records upload, and what the old ones gave rise to goes with them.
 inline void records_dropped(wfa_ctx* c) {
     c->have_records = false;
+    c->records_gen += 1;
     c->layout = {};
     pass_caches_dropped(c);
 }
@@ -297,6 +305,7 @@ inline void records_dropped(wfa_ctx* c) {
 inline void records_replaced(wfa_ctx* c, int64_t R, int32_t max_len, int64_t bitmap_bytes, const UniformLayout& layout) {
     c->R = R; c->max_len = max_len; c->bitmap_bytes = bitmap_bytes; c->layout = layout;
     c->have_records = true;
+    c->records_gen += 1;
     pass_caches_dropped(c);
     c->len_host_valid = c->no_runs32 = false;
     c->n_hits = c->pw_plan_n = -1;

@@ -1989,25 +1989,21 @@ __device__ __forceinline__ PyNum py_div(const PyNum& a, double python_float) {
     return r;
 }
 
+// the float32 fields of one width row, as the reference rounds them into WAVEFORM_WIDTH_DTYPE
+struct WidthValues {
+    float rise_time, fall_time, total_width, rise_samples, fall_samples, total_samples, peak_height;
+};
+
+// Width of the peak at sample pos64 of row / record ri (waveform_width.py:205-374); false where the reference drops the
+// hit: no such row, position outside it, peak value <= 0.  Shared by k_waveform_width and k_peak_chain.
 template <int SRC, class Rows>
-__global__ __launch_bounds__(128) void k_waveform_width(PoolView pool, int64_t n_hits,
-                                                        const int64_t* __restrict__ position,
-                                                        const int64_t* __restrict__ row_index, Rows rows,
-                                                        WidthHitParams wp, uint8_t* __restrict__ out,
-                                                        uint8_t* __restrict__ valid) {
+__device__ __forceinline__ bool width_of_peak(const PoolView& pool, const Rows& rows, const WidthHitParams& wp, int64_t ri,
+                                              int64_t pos64, WidthValues* w) {
     using T = typename std::conditional<SRC == WFA_SRC_RAW, double, float>::type;
-    const int64_t h = (int64_t)blockIdx.x * 128 + threadIdx.x;
-    if (h >= n_hits) return;
-    uint32_t* row = reinterpret_cast<uint32_t*>(out + h * 56);
-#pragma unroll
-    for (int k = 0; k < 14; ++k) row[k] = 0u;
-    valid[h] = 0;
-    const int64_t ri = row_index[h];
-    const int64_t pos64 = position[h];
     int64_t base;
     int L;
-    if (!rows.locate(ri, &base, &L) || L <= 0) return;
-    if (pos64 >= L || pos64 < 0) return;  // waveform_width.py:252
+    if (!rows.locate(ri, &base, &L) || L <= 0) return false;
+    if (pos64 >= L || pos64 < 0) return false;  // waveform_width.py:252
     const int peak = (int)pos64;
     const uint16_t* xu = pool.u16 ? pool.u16 + base : nullptr;
     const float* xf = pool.f32 ? pool.f32 + base : nullptr;
@@ -2028,7 +2024,7 @@ __global__ __launch_bounds__(128) void k_waveform_width(PoolView pool, int64_t n
         return (T)(xf[i] - (float)baseline);
     };
     const T peak_value = at(peak);
-    if (!(peak_value > (T)0)) return;  // waveform_width.py:258 (NaN also compares false there -> kept; NaN is not produced)
+    if (!(peak_value > (T)0)) return false;  // waveform_width.py:258 (NaN also compares false there -> kept; NaN is not produced)
     const bool interp = wp.interpolation != 0;
     // python float options are weak: thresholds take the dtype of peak_value
     const T thr_rl = peak_value * (T)wp.rise_low, thr_rh = peak_value * (T)wp.rise_high;
@@ -2062,15 +2058,116 @@ __global__ __launch_bounds__(128) void k_waveform_width(PoolView pool, int64_t n
         }
         tot_t = py_div(tot_s, wp.sampling_rate);
     }
-    put_f32(row, 0, (float)rise_t.v);
-    put_f32(row, 1, (float)fall_t.v);
-    put_f32(row, 2, (float)tot_t.v);
-    put_f32(row, 3, (float)rise_s.v);
-    put_f32(row, 4, (float)fall_s.v);
-    put_f32(row, 5, (float)tot_s.v);
+    w->rise_time = (float)rise_t.v;
+    w->fall_time = (float)fall_t.v;
+    w->total_width = (float)tot_t.v;
+    w->rise_samples = (float)rise_s.v;
+    w->fall_samples = (float)fall_s.v;
+    w->total_samples = (float)tot_s.v;
+    w->peak_height = (float)peak_value;
+    return true;
+}
+
+template <int SRC, class Rows>
+__global__ __launch_bounds__(128) void k_waveform_width(PoolView pool, int64_t n_hits,
+                                                        const int64_t* __restrict__ position,
+                                                        const int64_t* __restrict__ row_index, Rows rows,
+                                                        WidthHitParams wp, uint8_t* __restrict__ out,
+                                                        uint8_t* __restrict__ valid) {
+    const int64_t h = (int64_t)blockIdx.x * 128 + threadIdx.x;
+    if (h >= n_hits) return;
+    uint32_t* row = reinterpret_cast<uint32_t*>(out + h * 56);
+#pragma unroll
+    for (int k = 0; k < 14; ++k) row[k] = 0u;
+    valid[h] = 0;
+    const int64_t pos64 = position[h];
+    WidthValues w;
+    if (!width_of_peak<SRC>(pool, rows, wp, row_index[h], pos64, &w)) return;
+    put_f32(row, 0, w.rise_time);
+    put_f32(row, 1, w.fall_time);
+    put_f32(row, 2, w.total_width);
+    put_f32(row, 3, w.rise_samples);
+    put_f32(row, 4, w.fall_samples);
+    put_f32(row, 5, w.total_samples);
     put_i64(row, 6, pos64);
-    put_f32(row, 8, (float)peak_value);
+    put_f32(row, 8, w.peak_height);
     valid[h] = 1;
+}
+
+// =============================================================================================
+// Peak chain: width + feature lookup + S1/S2 range cuts per resident find_peaks row
+// (waveform_width.py:205-374 on the record's slice, s1_s2_classifier.py:57-69,185-209)
+// =============================================================================================
+// One lane per HIT_DTYPE row of the last records-mode find_peaks pass.  The peak's record_id is the index of its
+// record and of its basic_features row (the feature table of this route has no record_id column).  Slot i of `rows`
+// receives the packed 45-byte S1_S2_CLASSIFIER_DTYPE row (label i1 @0, width_ns f4 @1, width_samples f4 @5, height f4
+// @9, area f4 @13, timestamp i8 @17, board i2 @25, channel i2 @27, record_id i8 @29, peak_position i8 @37) by byte
+// stores, keep[i] says whether the width stage keeps the peak.
+__device__ __forceinline__ void put_bytes(uint8_t* dst, uint64_t v, int n) {
+#pragma unroll
+    for (int k = 0; k < n; ++k) dst[k] = (uint8_t)(v >> (8 * k));
+}
+
+// s1_s2_classifier.py:57-69 on the float64 of a float32 value
+__device__ __forceinline__ bool chain_in_range(const ChainParams& cp, int k, double v) {
+    const uint32_t b = (cp.bounds >> (2 * k)) & 3u;
+    if (b == 0u) return true;
+    if (v != v) return false;
+    if ((b & 1u) && v < cp.lo[k]) return false;
+    if ((b & 2u) && v > cp.hi[k]) return false;
+    return true;
+}
+
+template <int SRC>
+__global__ __launch_bounds__(128) void k_peak_chain(PoolView pool, WidthRecordRows rec, int64_t n_peaks,
+                                                    const uint8_t* __restrict__ peaks,
+                                                    const uint8_t* __restrict__ features, WidthHitParams wp,
+                                                    ChainParams cp, uint8_t* __restrict__ rows,
+                                                    int32_t* __restrict__ keep) {
+    const int64_t i = (int64_t)blockIdx.x * 128 + threadIdx.x;
+    if (i >= n_peaks) return;
+    const uint32_t* hit = reinterpret_cast<const uint32_t*>(peaks + i * 48);  // 48-byte rows: dword aligned
+    const int64_t pos64 = (int64_t)((uint64_t)hit[0] | ((uint64_t)hit[1] << 32));
+    const uint64_t timestamp = (uint64_t)hit[7] | ((uint64_t)hit[8] << 32);
+    const uint32_t board_channel = hit[9];
+    const int64_t r = (int64_t)((uint64_t)hit[10] | ((uint64_t)hit[11] << 32));
+    WidthValues w;
+    const bool ok = width_of_peak<SRC>(pool, rec, wp, r, pos64, &w);
+    keep[i] = ok ? 1 : 0;
+    if (!ok) return;  // (the slot of a dropped peak is never read)
+    const uint32_t* feat = reinterpret_cast<const uint32_t*>(features + r * 36);  // 0 <= r < R: width_of_peak located it
+    const float height = __uint_as_float(feat[0]), area = __uint_as_float(feat[2]);
+    const double wv = (double)(cp.width_in_samples ? w.total_samples : w.total_width);
+    const double hv = (double)height, av = (double)area;
+    const bool s1_on = (cp.bounds & 0x03Fu) != 0u, s2_on = (cp.bounds & 0xFC0u) != 0u;
+    const bool s1 = s1_on && chain_in_range(cp, 0, wv) && chain_in_range(cp, 1, av) && chain_in_range(cp, 2, hv);
+    const bool s2 = s2_on && chain_in_range(cp, 3, wv) && chain_in_range(cp, 4, av) && chain_in_range(cp, 5, hv);
+    int label = 0;
+    if (s1 && !s2) label = 1;
+    else if (s2 && !s1) label = 2;
+    else if (s1 && s2) label = cp.policy == WFA_S1S2_PREFER_S1 ? 1 : cp.policy == WFA_S1S2_PREFER_S2 ? 2 : 0;
+    uint8_t* row = rows + i * 45;
+    row[0] = (uint8_t)label;
+    put_bytes(row + 1, __float_as_uint(w.total_width), 4);
+    put_bytes(row + 5, __float_as_uint(w.total_samples), 4);
+    put_bytes(row + 9, __float_as_uint(height), 4);
+    put_bytes(row + 13, __float_as_uint(area), 4);
+    put_bytes(row + 17, timestamp, 8);
+    put_bytes(row + 25, board_channel, 4);
+    put_bytes(row + 29, (uint64_t)(r + cp.record_id_base), 8);
+    put_bytes(row + 37, (uint64_t)pos64, 8);
+}
+
+// kept rows, in peak order, into the output table: one lane per byte of the slot table
+__global__ __launch_bounds__(256) void k_peak_chain_compact(int64_t n_peaks, const uint8_t* __restrict__ rows,
+                                                            const int32_t* __restrict__ keep,
+                                                            const int64_t* __restrict__ start,
+                                                            uint8_t* __restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_peaks * 45) return;
+    const int64_t i = t / 45;
+    if (!keep[i]) return;
+    out[start[i] * 45 + (t - i * 45)] = rows[t];
 }
 
 // =============================================================================================
@@ -3263,6 +3360,31 @@ hipError_t launch_waveform_width_records(hipStream_t st, int source, const PoolV
     return launch_width_rows(st, source, pool, n_hits, position, record_index, WidthRecordRows{rec.R, rec.off, rec.len},
                              WidthHitParams{rise_low, rise_high, fall_high, fall_low, sampling_rate, interpolation}, out,
                              valid);
+}
+
+hipError_t launch_peak_chain(hipStream_t st, int source, const PoolView& pool, const RecView& rec, int64_t n_peaks,
+                             const uint8_t* peaks, const uint8_t* features, double rise_low, double rise_high,
+                             double fall_high, double fall_low, double sampling_rate, int interpolation,
+                             const ChainParams& cp, uint8_t* rows, int32_t* keep) {
+    if (n_peaks == 0) return hipSuccess;
+    const unsigned grid = (unsigned)((n_peaks + 127) / 128);
+    const WidthRecordRows rr{rec.R, rec.off, rec.len};
+    const WidthHitParams wp{rise_low, rise_high, fall_high, fall_low, sampling_rate, interpolation};
+    if (source == WFA_SRC_RAW)
+        hipLaunchKernelGGL((k_peak_chain<WFA_SRC_RAW>), dim3(grid), dim3(128), 0, st, pool, rr, n_peaks, peaks, features, wp, cp, rows, keep);
+    else if (source == WFA_SRC_F32)
+        hipLaunchKernelGGL((k_peak_chain<WFA_SRC_F32>), dim3(grid), dim3(128), 0, st, pool, rr, n_peaks, peaks, features, wp, cp, rows, keep);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_peak_chain_compact(hipStream_t st, int64_t n_peaks, const uint8_t* rows, const int32_t* keep,
+                                     const int64_t* start, uint8_t* out) {
+    if (n_peaks == 0) return hipSuccess;
+    const unsigned grid = (unsigned)((n_peaks * 45 + 255) / 256);
+    hipLaunchKernelGGL(k_peak_chain_compact, dim3(grid), dim3(256), 0, st, n_peaks, rows, keep, start, out);
+    return hipGetLastError();
 }
 
 hipError_t launch_find_peaks(hipStream_t st, int source, bool fill, const PoolView& pool, const RecView& rec,

@@ -203,6 +203,22 @@ hipError_t launch_waveform_width_records(hipStream_t st, int source, const PoolV
                                          int64_t n_hits, const int64_t* position, const int64_t* record_index,
                                          double rise_low, double rise_high, double fall_high, double fall_low,
                                          double sampling_rate, int interpolation, uint8_t* out, uint8_t* valid);
+// peak chain: the S1/S2 range cuts (s1_s2_classifier.py:57-69) and the id shift of k_peak_chain
+struct ChainParams {
+    double lo[6], hi[6];   // s1 width, s1 area, s1 height, s2 width, s2 area, s2 height
+    uint32_t bounds;       // bit 2k: range k has a lower bound, bit 2k + 1: an upper bound; neither = range disabled
+    int width_in_samples;  // width_unit == "samples"
+    int policy;            // WFA_S1S2_UNKNOWN / _PREFER_S1 / _PREFER_S2
+    int64_t record_id_base;
+};
+// one lane per resident HIT_DTYPE row: 45-byte S1_S2_CLASSIFIER_DTYPE row into slot i of `rows`, keep[i] = 0 / 1
+hipError_t launch_peak_chain(hipStream_t st, int source, const PoolView& pool, const RecView& rec, int64_t n_peaks,
+                             const uint8_t* peaks, const uint8_t* features, double rise_low, double rise_high,
+                             double fall_high, double fall_low, double sampling_rate, int interpolation,
+                             const ChainParams& cp, uint8_t* rows, int32_t* keep);
+// kept slots, in order, to out[start[i]] (start = exclusive scan of keep)
+hipError_t launch_peak_chain_compact(hipStream_t st, int64_t n_peaks, const uint8_t* rows, const int32_t* keep,
+                                     const int64_t* start, uint8_t* out);
 // find_peaks: candidate scan per record (count / fill), distance selection per record, then per candidate
 hipError_t launch_find_peaks(hipStream_t st, int source, bool fill, const PoolView& pool, const RecView& rec,
                              const PeakParams& pp, int32_t* counts, const int64_t* out_start, int32_t* cand_pos,

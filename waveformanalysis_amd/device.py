@@ -19,6 +19,7 @@ from . import _lib
 from .dtypes import (
     BASIC_FEATURES_DTYPE,
     HIT_DTYPE,
+    S1_S2_CLASSIFIER_DTYPE,
     WAVEFORM_WIDTH_DTYPE,
     THRESHOLD_HIT_DTYPE,
     WAVEFORM_WIDTH_INTEGRAL_DTYPE,
@@ -599,6 +600,45 @@ class DeviceSession:
             self._h, int(source), len(pos), _ptr(pos), _ptr(rec), float(rise_low), float(rise_high), float(fall_high),
             float(fall_low), float(sampling_rate), int(bool(interpolation)), _ptr(out), _ptr(valid)))
         return out, valid.astype(bool)
+
+    CONFLICT_POLICIES = {"unknown": _lib.S1S2_UNKNOWN, "prefer_s1": _lib.S1S2_PREFER_S1, "prefer_s2": _lib.S1S2_PREFER_S2}
+
+    def peak_chain(self, width_source: int = _lib.SRC_RAW, feature_source: int = _lib.SRC_RAW, *, rise_low: float = 0.1,
+                   rise_high: float = 0.9, fall_high: float = 0.9, fall_low: float = 0.1, sampling_rate: float = 0.5,
+                   interpolation: bool = True, height_range=(40, 90), area_range=(0, None), width_unit: str = "ns",
+                   s1_width_range=None, s2_width_range=None, s1_area_range=None, s2_area_range=None,
+                   s1_height_range=None, s2_height_range=None, conflict_policy: str = "unknown", strict: bool = False,
+                   record_id_base: int = 0) -> np.ndarray:
+        """S1_S2_CLASSIFIER_DTYPE rows of the resident rows of the last find_peaks pass on the uploaded records: the
+        chain waveform_width (records route) -> s1_s2 with basic_features on the side, on the device
+        (wfa_peak_chain_count / _fill).  Keyword arguments are the plugins' options; a peak's record_id is the index of
+        its record, the rows carry record_id + record_id_base.  The peak rows stay (download_peaks still delivers
+        them)."""
+        from .plugins.s1_s2 import class_ranges  # (the plugins import this module)
+
+        ranges = class_ranges(s1_width_range=s1_width_range, s2_width_range=s2_width_range, s1_area_range=s1_area_range,
+                              s2_area_range=s2_area_range, s1_height_range=s1_height_range,
+                              s2_height_range=s2_height_range, strict=strict)
+        bounds = np.zeros(12, dtype=np.float64)
+        mask = 0
+        for k, r in enumerate(ranges):
+            for j in (0, 1):
+                if r is not None and r[j] is not None:
+                    bounds[2 * k + j] = r[j]
+                    mask |= 1 << (2 * k + j)
+        # (any other policy: both classes matched -> unknown, s1_s2_classifier.py:201-207)
+        policy = self.CONFLICT_POLICIES.get(conflict_policy, _lib.S1S2_UNKNOWN)
+        h0, h1 = height_range
+        a0, a1 = area_range
+        n = C.c_int64(0)
+        _lib.check(self._lib.wfa_peak_chain_count(
+            self._h, int(width_source), int(feature_source), float(rise_low), float(rise_high), float(fall_high),
+            float(fall_low), float(sampling_rate), int(bool(interpolation)), int(h0 or 0), int(h1 or 0),
+            int(h1 is not None), int(a0 or 0), int(a1 or 0), int(a1 is not None), int(width_unit == "samples"),
+            _ptr(bounds), mask, policy, int(record_id_base), C.byref(n)))
+        out = np.empty(int(n.value), dtype=S1_S2_CLASSIFIER_DTYPE)
+        _lib.check(self._lib.wfa_peak_chain_fill(self._h, _ptr(out), int(n.value)))
+        return out
 
     # ---- records builder -----------------------------------------------------------------------------------------
     def records_sort_order(self, timestamp, pid, board, channel) -> np.ndarray:

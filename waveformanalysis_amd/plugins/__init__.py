@@ -52,7 +52,17 @@ def hip_full():
     return hip_from_raw_files() + [HipDataFramePlugin(), HipGroupedEventsPlugin(), HipPairedEventsPlugin()]
 
 
-__all__ = ["HipWavePoolFilteredPlugin", "HipThresholdHitPlugin", "HipBasicFeaturesPlugin",
+def hip_streaming():
+    """The chunk streams: hit_threshold_stream, signal_peaks_stream and s1_s2_stream -- the counterpart of the
+    reference's placeholder streaming_default() (profiles.py: "not available yet").  Register them beside a profile
+    that provides records / wave_pool (and st_waveforms / filtered_waveforms for signal_peaks_stream)."""
+    from ..s1s2_stream import HipS1S2Stream  # (these modules import the plugins package)
+    from ..streaming import HipThresholdHitStream
+
+    return [HipThresholdHitStream(), HipSignalPeaksStreamPlugin(), HipS1S2Stream()]
+
+
+__all__ = ["hip_streaming", "HipWavePoolFilteredPlugin", "HipThresholdHitPlugin", "HipBasicFeaturesPlugin",
            "HipWaveformWidthIntegralPlugin", "HipHitGroupedPlugin", "HipHitFinderPlugin", "HipFilteredWaveformsPlugin",
            "HipWaveformWidthPlugin", "HipS1S2ClassifierPlugin", "HipHitMergeClustersPlugin",
            "HipHitMergePlugin", "HipHitMergedComponentsPlugin", "HipSignalPeaksStreamPlugin", "HipRecordsPlugin", "HipWavePoolPlugin",

@@ -44,16 +44,25 @@ def _in_range(values: np.ndarray, bounds) -> np.ndarray:
     return ok
 
 
+def class_ranges(*, s1_width_range=None, s2_width_range=None, s1_area_range=None, s2_area_range=None,
+                 s1_height_range=None, s2_height_range=None, strict=False):
+    """The six normalised ranges in the order (s1 width, s1 area, s1 height, s2 width, s2 area, s2 height) and the
+    `strict` check (s1_s2_classifier.py:139-152); shared by `classify` and DeviceSession.peak_chain."""
+    ranges = tuple(_normalize_range(r) for r in (s1_width_range, s1_area_range, s1_height_range,
+                                                 s2_width_range, s2_area_range, s2_height_range))
+    if strict and all(r is None for r in ranges):
+        raise ValueError("No S1/S2 criteria configured; set ranges or disable strict.")
+    return ranges
+
+
 def classify(widths: np.ndarray, features: np.ndarray, *, width_unit="ns", s1_width_range=None,
              s2_width_range=None, s1_area_range=None, s2_area_range=None, s1_height_range=None,
              s2_height_range=None, conflict_policy="unknown", strict=False) -> np.ndarray:
-    s1w, s2w = _normalize_range(s1_width_range), _normalize_range(s2_width_range)
-    s1a, s2a = _normalize_range(s1_area_range), _normalize_range(s2_area_range)
-    s1h, s2h = _normalize_range(s1_height_range), _normalize_range(s2_height_range)
+    s1w, s1a, s1h, s2w, s2a, s2h = class_ranges(
+        s1_width_range=s1_width_range, s2_width_range=s2_width_range, s1_area_range=s1_area_range,
+        s2_area_range=s2_area_range, s1_height_range=s1_height_range, s2_height_range=s2_height_range, strict=strict)
     s1_enabled = any(r is not None for r in (s1w, s1a, s1h))
     s2_enabled = any(r is not None for r in (s2w, s2a, s2h))
-    if strict and not s1_enabled and not s2_enabled:
-        raise ValueError("No S1/S2 criteria configured; set ranges or disable strict.")
     if not isinstance(widths, np.ndarray):
         raise ValueError("s1_s2 expects waveform_width as a single array")
     if not isinstance(features, np.ndarray):

@@ -387,7 +387,35 @@ class _RunPlan:
         return self._designs[g]
 
 
-class HipThresholdHitStream(HipStreamingPlugin):
+class _RecordsChunking:
+    """The chunk rule of the streams over the static `records` array (hit_threshold_stream, s1_s2_stream)."""
+
+    def _endtime_of(self, data: np.ndarray, time_field: str) -> np.ndarray:
+        # records: timestamp in ps, dt in ns per sample -> the end of a record in ps
+        return data[time_field].astype(np.int64) + data["dt"].astype(np.int64) * 1000 * data["event_length"].astype(np.int64)
+
+    def _data_to_chunks(self, data: Any, run_id: str):
+        """Records of different channels overlap in time, so time-range chunks (the base rule) share records at
+        their borders and every shared record's hits would come out twice.  Hits depend on their own record only:
+        a chunk is `chunk_size` consecutive records of a time segment, nothing is widened and nothing clipped
+        (no main_start / main_end in the metadata)."""
+        if not isinstance(data, np.ndarray) or data.dtype.names is None:
+            raise TypeError(f"{self.provides} chunks the structured `records` array")
+        if len(data) == 0:
+            return
+        if self.break_threshold_ps and self.break_threshold_ps > 0:
+            segments = [seg for seg, _info in split_by_breaks(
+                data, break_threshold_ps=self.break_threshold_ps, min_chunk_size=1, time_field="timestamp",
+                endtime_field=self.endtime_field, dt_field=self.dt_field, length_field=self.length_field, dt=self.dt)]
+        else:
+            segments = [data]
+        for seg_id, seg in enumerate(segments):
+            for ch in records_to_chunks(seg, self.chunk_size, run_id):
+                ch.metadata["segment_id"] = seg_id
+                yield ch
+
+
+class HipThresholdHitStream(_RecordsChunking, HipStreamingPlugin):
     """compute_chunk() = threshold hits of one chunk of records (fused SG filter optional).
 
     `compute(context, run_id)` streams over the static `records` array (breaks at 10^13 ps, 50 000 records per chunk);
@@ -528,30 +556,6 @@ class HipThresholdHitStream(HipStreamingPlugin):
                                  f"run ({longest})")
             return self.max_len
         return longest
-
-    def _endtime_of(self, data: np.ndarray, time_field: str) -> np.ndarray:
-        # records: timestamp in ps, dt in ns per sample -> the end of a record in ps
-        return data[time_field].astype(np.int64) + data["dt"].astype(np.int64) * 1000 * data["event_length"].astype(np.int64)
-
-    def _data_to_chunks(self, data: Any, run_id: str):
-        """Records of different channels overlap in time, so time-range chunks (the base rule) share records at
-        their borders and every shared record's hits would come out twice.  Hits depend on their own record only:
-        a chunk is `chunk_size` consecutive records of a time segment, nothing is widened and nothing clipped
-        (no main_start / main_end in the metadata)."""
-        if not isinstance(data, np.ndarray) or data.dtype.names is None:
-            raise TypeError("hit_threshold_stream chunks the structured `records` array")
-        if len(data) == 0:
-            return
-        if self.break_threshold_ps and self.break_threshold_ps > 0:
-            segments = [seg for seg, _info in split_by_breaks(
-                data, break_threshold_ps=self.break_threshold_ps, min_chunk_size=1, time_field="timestamp",
-                endtime_field=self.endtime_field, dt_field=self.dt_field, length_field=self.length_field, dt=self.dt)]
-        else:
-            segments = [data]
-        for seg_id, seg in enumerate(segments):
-            for ch in records_to_chunks(seg, self.chunk_size, run_id):
-                ch.metadata["segment_id"] = seg_id
-                yield ch
 
     def _empty(self, chunk: Chunk, run_id: str) -> Chunk:
         return Chunk(np.zeros(0, dtype=THRESHOLD_HIT_DTYPE), chunk.start, chunk.end, run_id, self.provides,
