@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define WFA_ABI_VERSION 6
+#define WFA_ABI_VERSION 7
 
 #define WFA_OK 0
 #define WFA_E_INVALID (-1)   /* bad argument / malformed records (maps to ValueError) */
@@ -434,6 +434,30 @@ int wfa_group_hit_windows_count(wfa_ctx* ctx, int64_t n_hits, const int64_t* tim
                                 int64_t* n_events);
 int wfa_group_hit_windows_fill(wfa_ctx* ctx, int64_t n_hits, int64_t n_events, int64_t* order, int64_t* event_start,
                                int64_t* t_min, int64_t* t_max);
+
+/* Event stream: K9 chunk by chunk, the hits of the events still open kept on the device between pushes.
+ * A horizon H is a float64 such that every hit not yet pushed has computed abs_start >= H.  A push appends its
+ * THRESHOLD_HIT_DTYPE rows (60 B, host memory; NULL with n_rows = 0 is a pure flush) behind the carried rows, runs the
+ * grouping pass of wfa_group_hit_windows_count over that table (sample window = edge_start / edge_end) and closes
+ * every event with max(abs_end) + time_window_ns * 1e3 < H, strictly: the closed events are a prefix of the table's
+ * events, no later hit can join or precede them, and their ids continue the count of the events closed before.  The
+ * hits of all other events stay on the device in their original row order (the carry) and are grouped again with the
+ * next push's rows; after the last rows a push with H = +inf closes everything.  All rows pushed, in any chunking,
+ * give the rows of the static pass over the whole table.
+ * _push reports the rows and events this push closed and the rows carried; _fill delivers those rows, 84 B packed
+ * (EVENT_HIT_DTYPE): event_id i8 @0, t_min i8 @8, t_max i8 @16 (truncated like the static pass), the hit's 60 bytes
+ * unchanged @24; one row per hit, events in order, inside an event the static pass's order.
+ * Refused with WFA_E_INVALID, the stream left as it was: a negative window (_begin); a pushed row with dt <= 0 or a
+ * negative edge_start / edge_end; a pushed row whose abs_start lies below the previous push's horizon; a horizon
+ * below the previous one, or NaN; carry + pushed rows >= 2^31.  _push without _begin, _fill before a push:
+ * WFA_E_STATE; _fill with another row count: WFA_E_INVALID.  _begin on an open stream starts over.
+ * The carry and the rows of the last push are state: wfa_release_scratch keeps them, wfa_scratch_bytes does not count
+ * them, _end frees them (60 B per carried row in each of two buffers, 84 B per row of the largest push). */
+int wfa_event_stream_begin(wfa_ctx* ctx, double time_window_ns);
+int wfa_event_stream_push(wfa_ctx* ctx, const void* hit_rows, int64_t n_rows, double horizon_ps, int64_t* n_out_rows,
+                          int64_t* n_out_events, int64_t* n_carry);
+int wfa_event_stream_fill(wfa_ctx* ctx, void* out_rows, int64_t n_out_rows);
+int wfa_event_stream_end(wfa_ctx* ctx);
 
 /* Legacy fixed-window grouping: group_multi_channel_hits (processing/event_grouping.py:98-283) with the boundary search of
  * _find_cluster_boundaries_numba (475-525).  The hits are ordered by timestamp (stable; pandas' default sort leaves the

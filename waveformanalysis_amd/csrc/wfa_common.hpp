@@ -256,6 +256,19 @@ struct wfa_ctx {
     // [0, arena_filled) has been written.  Not scratch: wfa_release_scratch keeps it, wfa_ctx_destroy frees it
     wfa::DevBuf csv_arena;
     int64_t arena_filled = 0;
+    // event stream (wfa_event_stream_*, wfa_hits.hip): the hits of the events still open after the last push, as 60-byte
+    // rows in their original order in es_carry[es.cur] (a push compacts them into the other buffer), and the 84-byte rows
+    // the last push closed.  State, not scratch: wfa_release_scratch keeps them, wfa_event_stream_end frees them
+    struct EventStream {
+        bool open = false;
+        double window_ns = 0.0;
+        double horizon = 0.0;     // horizon of the last accepted push (-inf before the first)
+        int64_t next_event = 0;   // events emitted so far = id of the next one
+        int64_t n_carry = 0;
+        int cur = 0;
+        int64_t out_rows = -1;    // rows of the last push waiting in es_out; -1: no push yet
+    } es;
+    wfa::DevBuf es_carry[2], es_out;
     wfa::DevBuf bw_scratch{scratch};  // float64 forward pass of sosfiltfilt, [sample][record-in-batch]
 
     // profiling: HIP events around every launch on the context's stream.  The pairs are only recorded while the

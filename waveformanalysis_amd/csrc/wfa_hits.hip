@@ -31,7 +31,7 @@ inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kTB - 1) / kTB); 
 enum Slot {
     S_TS, S_POS, S_START, S_END, S_DT, S_BOARD, S_CHAN, S_RID, S_HEIGHT, S_INTEGRAL,
     S_ABS0, S_ABS1, S_K0, S_K1, S_K2, S_K3, S_K4, S_KTMP0, S_KTMP1, S_PERM0, S_PERM1, S_CUB,
-    S_F0, S_F1, S_FLAG, S_ID, S_OUT0, S_OUT1, S_OUT2, S_OUT3, S_OUT4, S_OUT5, S_OUT6, S_OUT7, S_CNT, S_CNT2, S_SG, S_CSV, S_N
+    S_F0, S_F1, S_FLAG, S_ID, S_OUT0, S_OUT1, S_OUT2, S_OUT3, S_OUT4, S_OUT5, S_OUT6, S_OUT7, S_CNT, S_CNT2, S_SG, S_CSV, S_ES, S_EVHI, S_N
 };
 static_assert(S_N <= 40, "wfa_ctx::ht is too small");
 
@@ -312,7 +312,7 @@ __global__ void k_event_starts(int64_t n, const uint64_t* __restrict__ k_event, 
 __global__ void k_event_minmax(int64_t n_events, const int64_t* __restrict__ event_start,
                                const int64_t* __restrict__ perm, const double* __restrict__ abs0,
                                const double* __restrict__ abs1, int64_t* __restrict__ t_min,
-                               int64_t* __restrict__ t_max) {
+                               int64_t* __restrict__ t_max, double* __restrict__ ev_hi) {
     const int64_t ev = (int64_t)blockIdx.x * kTB + threadIdx.x;
     if (ev >= n_events) return;
     const int64_t a = event_start[ev], b = event_start[ev + 1];
@@ -324,6 +324,70 @@ __global__ void k_event_minmax(int64_t n_events, const int64_t* __restrict__ eve
     }
     t_min[ev] = (int64_t)lo;  // int(np.min(...)): truncation
     t_max[ev] = (int64_t)hi;
+    if (ev_hi) ev_hi[ev] = hi;  // the event stream compares the untruncated end with its horizon
+}
+
+// The grouping pass over a device table of n > 0 hits (the body of wfa_group_hit_windows_count; the event stream runs it
+// on carry ++ new rows): prep, lexsort, max-scan, flags, second sort, per-event tables.  Leaves, in scratch slots,
+// abs_start / abs_end per hit (S_ABS0 / S_ABS1), the event index of every hit (S_K1), *perm = the hits event-major in the
+// reference's order, event_start[n_ev + 1] (S_OUT0), t_min / t_max (S_OUT1 / S_OUT2) and, where ev_hi is given, the
+// untruncated max(abs_end) per event.  ev_hi must hold n entries (n_ev <= n is known only inside).  The launches are
+// queued on the context's stream; the last ones may still be running when this returns.
+int group_cols(wfa_ctx* c, int64_t n, const HitCols& h, const double* fix0, const double* fix1, double time_window_ns,
+               int64_t* n_events, int64_t** perm_out, double* ev_hi) {
+    int rc;
+    double *abs0, *abs1, *ends, *run_max;
+    uint64_t *k_abs, *k_dt, *k_ts, *k_rid, *k_chan, *k_ev;
+    int64_t *flag, *incl;
+    if ((rc = slot(c, S_ABS0, n, &abs0)) || (rc = slot(c, S_ABS1, n, &abs1)) || (rc = slot(c, S_K0, n, &k_abs)) ||
+        (rc = slot(c, S_K1, n, &k_dt)) || (rc = slot(c, S_K2, n, &k_ts)) || (rc = slot(c, S_K3, n, &k_rid)) ||
+        (rc = slot(c, S_K4, n, &k_chan)) || (rc = slot(c, S_F0, n, &ends)) || (rc = slot(c, S_F1, n, &run_max)) ||
+        (rc = slot(c, S_FLAG, n, &flag)) || (rc = slot(c, S_ID, n, &incl)))
+        return rc;
+    LaunchTimer t(c);
+    if ((rc = hit_prep(c, n, h, fix0, fix1, abs0, abs1, k_abs, k_dt, k_ts, k_rid, k_chan))) return rc;
+    int64_t* perm = nullptr;
+    {
+        const uint64_t* keys[4] = {k_abs, k_dt, k_ts, k_rid};  // np.lexsort((record_ids, timestamps, dt, abs_starts))
+        if ((rc = lexsort(c, n, keys, 4, &perm))) return rc;
+    }
+    hipLaunchKernelGGL(k_gather_f64, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, abs1, perm, ends);
+    size_t tb = 0;
+    WFA_HIP_CHECK(rocprim::inclusive_scan(nullptr, tb, ends, run_max, (size_t)n, MaxF64(), c->stream));
+    size_t tb2 = 0;
+    WFA_HIP_CHECK(rocprim::inclusive_scan(nullptr, tb2, flag, incl, (size_t)n, rocprim::plus<int64_t>(), c->stream));
+    if ((rc = c->ht[S_CUB].ensure(tb > tb2 ? tb : tb2))) return rc;
+    tb = c->ht[S_CUB].cap;
+    WFA_HIP_CHECK(rocprim::inclusive_scan(c->ht[S_CUB].ptr, tb, ends, run_max, (size_t)n, MaxF64(), c->stream));
+    hipLaunchKernelGGL(k_event_flags, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, abs0, perm, run_max,
+                       time_window_ns * 1e3, flag);
+    tb = c->ht[S_CUB].cap;
+    WFA_HIP_CHECK(rocprim::inclusive_scan(c->ht[S_CUB].ptr, tb, flag, incl, (size_t)n, rocprim::plus<int64_t>(), c->stream));
+    int64_t n_ev = 0;
+    WFA_HIP_CHECK(hipMemcpyAsync(&n_ev, incl + (n - 1), sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    // event id as the new primary key; k_dt's buffer is free again (k_chan carries dt)
+    k_ev = k_dt;
+    hipLaunchKernelGGL(k_event_keys, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, perm, incl, k_ev);
+    {
+        // np.lexsort((record_ids, timestamps, abs_starts, dt, channels, boards, event_id)).  The hits already stand in
+        // (abs_start, dt, timestamp, record_id) order: a stable sort of THAT order by (event, board, channel, dt) leaves
+        // every tie -- same event, channel and dt -- in (abs_start, timestamp, record_id) order, which is the reference's.
+        // Two narrow keys instead of five (17 radix passes -> 4).
+        const uint64_t* keys[2] = {k_ev, k_chan};
+        if ((rc = lexsort(c, n, keys, 2, &perm, perm))) return rc;
+    }
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    int64_t *ev_start, *t_min, *t_max;
+    if ((rc = slot(c, S_OUT0, n_ev + 1, &ev_start)) || (rc = slot(c, S_OUT1, n_ev, &t_min)) || (rc = slot(c, S_OUT2, n_ev, &t_max)))
+        return rc;
+    hipLaunchKernelGGL(k_event_starts, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, k_ev, perm, n_ev, ev_start);
+    hipLaunchKernelGGL(k_event_minmax, dim3(blocks_for(n_ev)), dim3(kTB), 0, c->stream, n_ev, ev_start, perm, abs0, abs1, t_min, t_max,
+                       ev_hi);
+    WFA_HIP_CHECK(hipGetLastError());
+    if ((rc = t.end("hit table: group_hit_windows (sort + scans)"))) return rc;
+    *n_events = n_ev;
+    *perm_out = perm;
+    return WFA_OK;
 }
 
 // ---- hit merge --------------------------------------------------------------------------------------------
@@ -824,6 +888,110 @@ __global__ __launch_bounds__(64) void k_csv_decode(int64_t n_rows, const uint8_t
     }
 }
 
+// ---- event stream (wfa_event_stream_*) -----------------------------------------------------------------------------
+// A push groups carry ++ new rows with group_cols, closes the events that end more than the window before the horizon
+// (a prefix of the table's events: no later hit can join or precede them), writes their hits as 84-byte rows and keeps
+// the hits of the open events, in their original row order, for the next push.
+constexpr int kEsBadDt = 1, kEsBadEdge = 2;
+struct EsCtl {
+    unsigned long long min_key;   // ord_f64 of the smallest abs_start among the pushed rows
+    unsigned long long n_closed;  // events of the closed prefix (starts at n_events, lowered to the first open event)
+    long long n_out;              // hits of the closed prefix
+    int flags, pad;
+};
+
+// the pushed rows [0, n) (columns and windows already offset past the carry): dt and edge checks, smallest abs_start
+__global__ __launch_bounds__(kTB) void k_es_check(int64_t n, const int32_t* __restrict__ dt, const int32_t* __restrict__ s,
+                                                  const int32_t* __restrict__ e, const double* __restrict__ abs0,
+                                                  EsCtl* __restrict__ ctl) {
+    unsigned long long lo = ~0ull;
+    int bad = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kTB + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTB) {
+        if (dt[i] <= 0) bad |= kEsBadDt;
+        if (s[i] < 0 || e[i] < 0) bad |= kEsBadEdge;
+        const unsigned long long k = ord_f64(abs0[i]);
+        lo = k < lo ? k : lo;
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned long long ol = __shfl_xor(lo, d);
+        lo = ol < lo ? ol : lo;
+        bad |= __shfl_xor(bad, d);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        atomicMin(&ctl->min_key, lo);
+        if (bad) atomicOr(&ctl->flags, bad);
+    }
+}
+
+// closed <=> max(abs_end) + gap < horizon, strictly; the first open event bounds the prefix
+__global__ void k_es_closed(int64_t n_events, const double* __restrict__ ev_hi, double gap_ps, double horizon,
+                            EsCtl* __restrict__ ctl) {
+    const int64_t ev = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (ev >= n_events) return;
+    if (ev_hi[ev] + gap_ps < horizon) return;
+    if (ev > 0 && !(ev_hi[ev - 1] + gap_ps < horizon)) return;  // not the first of its run of open events
+    atomicMin(&ctl->n_closed, (unsigned long long)ev);
+}
+__global__ void k_es_count(const int64_t* __restrict__ event_start, EsCtl* __restrict__ ctl) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctl->n_out = event_start[ctl->n_closed];
+}
+
+// 84-byte rows as 21 dwords: event_id, t_min, t_max (6 dwords), then the hit's 15 dwords; lanes over dwords
+__global__ __launch_bounds__(kTB) void k_es_rows(int64_t n_out, const int64_t* __restrict__ perm,
+                                                 const uint64_t* __restrict__ k_event, const int64_t* __restrict__ t_min,
+                                                 const int64_t* __restrict__ t_max, int64_t first_event,
+                                                 const uint32_t* __restrict__ rows, uint32_t* __restrict__ out) {
+    const int64_t d = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (d >= n_out * 21) return;
+    const int64_t j = d / 21;
+    const int w = (int)(d - j * 21);
+    const int64_t i = perm[j];
+    if (w >= 6) { out[d] = rows[i * 15 + (w - 6)]; return; }
+    const int64_t ev = (int64_t)k_event[i];
+    const int64_t v = w < 2 ? first_event + ev : (w < 4 ? t_min[ev] : t_max[ev]);
+    out[d] = (w & 1) ? (uint32_t)((uint64_t)v >> 32) : (uint32_t)(uint64_t)v;
+}
+
+__global__ void k_es_keep(int64_t n, const uint64_t* __restrict__ k_event, int64_t n_closed, int64_t* __restrict__ flag) {
+    const int64_t i = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (i < n) flag[i] = (int64_t)k_event[i] >= n_closed ? 1 : 0;
+}
+// the kept 60-byte rows, 15 dwords each, to their place in the other carry buffer (original row order)
+__global__ __launch_bounds__(kTB) void k_es_compact(int64_t n, const int64_t* __restrict__ flag,
+                                                    const int64_t* __restrict__ incl, const uint32_t* __restrict__ src,
+                                                    uint32_t* __restrict__ dst) {
+    const int64_t d = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (d >= n * 15) return;
+    const int64_t i = d / 15;
+    if (flag[i]) dst[(incl[i] - 1) * 15 + (d - i * 15)] = src[d];
+}
+
+// grow a carry buffer to `want` bytes and keep its first `used` bytes (DevBuf::ensure drops the contents)
+int es_grow(wfa_ctx* c, DevBuf& b, size_t used, size_t want) {
+    if (want <= b.cap) return WFA_OK;
+    if (used == 0) return b.ensure(want);
+    if (want < 2 * b.cap) want = 2 * b.cap;
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, want + 256);
+    if (e != hipSuccess) return fail(WFA_E_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
+    e = hipMemcpyAsync(p, b.ptr, used, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return fail(WFA_E_HIP, "growing the event stream's carry failed: %s", hipGetErrorString(e));
+    }
+    (void)hipFree(b.ptr);
+    b.ptr = p;
+    b.cap = want;
+    return WFA_OK;
+}
+
+inline uint64_t host_ord_f64(double v) {
+    uint64_t b;
+    memcpy(&b, &v, sizeof(b));
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
 }  // namespace
 }  // namespace wfa
 
@@ -869,54 +1037,9 @@ int wfa_group_hit_windows_count(wfa_ctx* c, int64_t n, const int64_t* timestamp,
     if ((abs_start_fix == nullptr) != (abs_end_fix == nullptr)) return fail(WFA_E_INVALID, "pass both abs_*_fix arrays or neither");
     double *fix0 = nullptr, *fix1 = nullptr;
     if (abs_start_fix && ((rc = upload(c, S_OUT6, abs_start_fix, n, &fix0)) || (rc = upload(c, S_OUT7, abs_end_fix, n, &fix1)))) return rc;
-    double *abs0, *abs1, *ends, *run_max;
-    uint64_t *k_abs, *k_dt, *k_ts, *k_rid, *k_chan, *k_ev;
-    int64_t *flag, *incl;
-    if ((rc = slot(c, S_ABS0, n, &abs0)) || (rc = slot(c, S_ABS1, n, &abs1)) || (rc = slot(c, S_K0, n, &k_abs)) ||
-        (rc = slot(c, S_K1, n, &k_dt)) || (rc = slot(c, S_K2, n, &k_ts)) || (rc = slot(c, S_K3, n, &k_rid)) ||
-        (rc = slot(c, S_K4, n, &k_chan)) || (rc = slot(c, S_F0, n, &ends)) || (rc = slot(c, S_F1, n, &run_max)) ||
-        (rc = slot(c, S_FLAG, n, &flag)) || (rc = slot(c, S_ID, n, &incl)))
-        return rc;
-    LaunchTimer t(c);
-    if ((rc = hit_prep(c, n, h, fix0, fix1, abs0, abs1, k_abs, k_dt, k_ts, k_rid, k_chan))) return rc;
-    int64_t* perm = nullptr;
-    {
-        const uint64_t* keys[4] = {k_abs, k_dt, k_ts, k_rid};  // np.lexsort((record_ids, timestamps, dt, abs_starts))
-        if ((rc = lexsort(c, n, keys, 4, &perm))) return rc;
-    }
-    hipLaunchKernelGGL(k_gather_f64, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, abs1, perm, ends);
-    size_t tb = 0;
-    WFA_HIP_CHECK(rocprim::inclusive_scan(nullptr, tb, ends, run_max, (size_t)n, MaxF64(), c->stream));
-    size_t tb2 = 0;
-    WFA_HIP_CHECK(rocprim::inclusive_scan(nullptr, tb2, flag, incl, (size_t)n, rocprim::plus<int64_t>(), c->stream));
-    if ((rc = c->ht[S_CUB].ensure(tb > tb2 ? tb : tb2))) return rc;
-    tb = c->ht[S_CUB].cap;
-    WFA_HIP_CHECK(rocprim::inclusive_scan(c->ht[S_CUB].ptr, tb, ends, run_max, (size_t)n, MaxF64(), c->stream));
-    hipLaunchKernelGGL(k_event_flags, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, abs0, perm, run_max,
-                       time_window_ns * 1e3, flag);
-    tb = c->ht[S_CUB].cap;
-    WFA_HIP_CHECK(rocprim::inclusive_scan(c->ht[S_CUB].ptr, tb, flag, incl, (size_t)n, rocprim::plus<int64_t>(), c->stream));
     int64_t n_ev = 0;
-    WFA_HIP_CHECK(hipMemcpyAsync(&n_ev, incl + (n - 1), sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    // event id as the new primary key; k_dt's buffer is free again (k_chan carries dt)
-    k_ev = k_dt;
-    hipLaunchKernelGGL(k_event_keys, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, perm, incl, k_ev);
-    {
-        // np.lexsort((record_ids, timestamps, abs_starts, dt, channels, boards, event_id)).  The hits already stand in
-        // (abs_start, dt, timestamp, record_id) order: a stable sort of THAT order by (event, board, channel, dt) leaves
-        // every tie -- same event, channel and dt -- in (abs_start, timestamp, record_id) order, which is the reference's.
-        // Two narrow keys instead of five (17 radix passes -> 4).
-        const uint64_t* keys[2] = {k_ev, k_chan};
-        if ((rc = lexsort(c, n, keys, 2, &perm, perm))) return rc;
-    }
-    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    int64_t *ev_start, *t_min, *t_max;
-    if ((rc = slot(c, S_OUT0, n_ev + 1, &ev_start)) || (rc = slot(c, S_OUT1, n_ev, &t_min)) || (rc = slot(c, S_OUT2, n_ev, &t_max)))
-        return rc;
-    hipLaunchKernelGGL(k_event_starts, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, k_ev, perm, n_ev, ev_start);
-    hipLaunchKernelGGL(k_event_minmax, dim3(blocks_for(n_ev)), dim3(kTB), 0, c->stream, n_ev, ev_start, perm, abs0, abs1, t_min, t_max);
-    WFA_HIP_CHECK(hipGetLastError());
-    if ((rc = t.end("hit table: group_hit_windows (sort + scans)"))) return rc;
+    int64_t* perm = nullptr;
+    if ((rc = group_cols(c, n, h, fix0, fix1, time_window_ns, &n_ev, &perm, nullptr))) return rc;
     WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
     c->ht_n = n; c->ht_groups = n_ev; c->ht_kind = 1; c->ht_perm = perm;
     *n_events = n_ev;
@@ -1172,6 +1295,153 @@ int wfa_records_sort(wfa_ctx* c, int64_t n, const int64_t* timestamp, const int3
     if ((rc = t.end("records: global sort order"))) return rc;
     WFA_HIP_CHECK(hipMemcpyAsync(order, perm, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
     WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return WFA_OK;
+}
+
+// ---- event stream -----------------------------------------------------------------------------------------------------
+int wfa_event_stream_begin(wfa_ctx* c, double time_window_ns) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (time_window_ns < 0) return fail(WFA_E_INVALID, "time_window_ns must be >= 0");
+    if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->es = wfa_ctx::EventStream{};  // (a stream left open starts over: empty carry, event id 0; the buffers are reused)
+    c->es.open = true;
+    c->es.window_ns = time_window_ns;
+    c->es.horizon = -HUGE_VAL;
+    return WFA_OK;
+}
+
+int wfa_event_stream_push(wfa_ctx* c, const void* hit_rows, int64_t n_rows, double horizon_ps, int64_t* n_out_rows,
+                          int64_t* n_out_events, int64_t* n_carry) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    wfa_ctx::EventStream& es = c->es;
+    if (!es.open) return fail(WFA_E_STATE, "no event stream is open (wfa_event_stream_begin first)");
+    if (n_rows < 0 || (n_rows > 0 && !hit_rows) || !n_out_rows || !n_out_events || !n_carry)
+        return fail(WFA_E_INVALID, "bad arguments");
+    if (horizon_ps != horizon_ps) return fail(WFA_E_INVALID, "the horizon is NaN");
+    if (horizon_ps < es.horizon)
+        return fail(WFA_E_INVALID, "the horizon (%.17g ps) lies below the previous push's (%.17g ps)", horizon_ps, es.horizon);
+    if (n_rows >= 0x80000000LL - es.n_carry)
+        return fail(WFA_E_INVALID, "carry (%lld rows) + pushed rows (%lld) reach the table limit of 2^31 rows",
+                    (long long)es.n_carry, (long long)n_rows);
+    const int64_t n = es.n_carry + n_rows;
+    if (n == 0) {  // nothing carried, nothing pushed: no launch
+        es.horizon = horizon_ps;
+        es.out_rows = 0;
+        *n_out_rows = *n_out_events = *n_carry = 0;
+        return WFA_OK;
+    }
+    c->ht_n = -1;  // the scratch slots a static count pass left for its fill are overwritten
+    DevBuf& table = c->es_carry[es.cur];
+    if ((rc = es_grow(c, table, (size_t)es.n_carry * 60, (size_t)n * 60))) return rc;
+    uint8_t* rows = table.as<uint8_t>();
+    // 1. the pushed rows behind the carry (a refused push leaves them there: they lie behind n_carry and are overwritten)
+    if (n_rows > 0 && (rc = h2d_copy(c, rows + (size_t)es.n_carry * 60, hit_rows, (size_t)n_rows * 60))) return rc;
+    int64_t *d_ts, *d_pos, *d_rid;
+    int32_t *d_s, *d_e, *d_dt;
+    int16_t *d_b, *d_c;
+    double* ev_hi;
+    EsCtl* d_ctl;
+    if ((rc = slot(c, S_TS, n, &d_ts)) || (rc = slot(c, S_POS, n, &d_pos)) || (rc = slot(c, S_START, n, &d_s)) ||
+        (rc = slot(c, S_END, n, &d_e)) || (rc = slot(c, S_DT, n, &d_dt)) || (rc = slot(c, S_BOARD, n, &d_b)) ||
+        (rc = slot(c, S_CHAN, n, &d_c)) || (rc = slot(c, S_RID, n, &d_rid)) || (rc = slot(c, S_EVHI, n, &ev_hi)) ||
+        (rc = slot(c, S_ES, 1, &d_ctl)))
+        return rc;
+    hipLaunchKernelGGL(k_unpack_hit_rows, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, rows, d_ts, d_pos, d_s, d_e, d_dt,
+                       d_b, d_c, d_rid);
+    // 2. the grouping pass of the static entry over the whole table
+    const HitCols h{d_ts, d_pos, d_s, d_e, d_dt, d_b, d_c, d_rid};
+    int64_t n_ev = 0;
+    int64_t* perm = nullptr;
+    if ((rc = group_cols(c, n, h, nullptr, nullptr, es.window_ns, &n_ev, &perm, ev_hi))) return rc;
+    if (n_ev < 1 || n_ev > n) return fail(WFA_E_HIP, "event stream: the grouping pass reported %lld events of %lld hits", (long long)n_ev, (long long)n);
+    // 3. the checks of the pushed rows and the closed prefix; one read of the control block
+    LaunchTimer t(c);
+    EsCtl ctl{~0ull, (unsigned long long)n_ev, 0, 0, 0};
+    WFA_HIP_CHECK(hipMemcpyAsync(d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
+    const double* abs0 = c->ht[S_ABS0].as<double>();
+    if (n_rows > 0) {
+        const unsigned cb = blocks_for(n_rows) < 1024u ? blocks_for(n_rows) : 1024u;
+        hipLaunchKernelGGL(k_es_check, dim3(cb), dim3(kTB), 0, c->stream, n_rows, d_dt + es.n_carry, d_s + es.n_carry,
+                           d_e + es.n_carry, abs0 + es.n_carry, d_ctl);
+    }
+    const int64_t* ev_start = c->ht[S_OUT0].as<int64_t>();
+    hipLaunchKernelGGL(k_es_closed, dim3(blocks_for(n_ev)), dim3(kTB), 0, c->stream, n_ev, ev_hi, es.window_ns * 1e3, horizon_ps,
+                       d_ctl);
+    hipLaunchKernelGGL(k_es_count, dim3(1), dim3(64), 0, c->stream, ev_start, d_ctl);
+    WFA_HIP_CHECK(hipGetLastError());
+    WFA_HIP_CHECK(hipMemcpyAsync(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (ctl.flags & kEsBadDt) return fail(WFA_E_INVALID, "hit dt must be positive for every row");
+    if (ctl.flags & kEsBadEdge)
+        return fail(WFA_E_INVALID, "a pushed row has a negative edge_start / edge_end (merged hits that span records are "
+                                   "outside the event stream)");
+    if (n_rows > 0 && ctl.min_key < host_ord_f64(es.horizon))
+        return fail(WFA_E_INVALID, "a pushed row starts below the previous push's horizon (%.17g ps)", es.horizon);
+    const int64_t n_closed = (int64_t)ctl.n_closed, n_out = (int64_t)ctl.n_out, n_keep = n - n_out;
+    if (n_closed < 0 || n_closed > n_ev || n_out < 0 || n_out > n) return fail(WFA_E_HIP, "event stream: inconsistent counts");
+    // 4. the rows of the closed events
+    const uint64_t* k_ev = c->ht[S_K1].as<uint64_t>();
+    if (n_out > 0) {
+        if ((rc = c->es_out.ensure((size_t)n_out * 84))) return rc;
+        hipLaunchKernelGGL(k_es_rows, dim3(blocks_for(n_out * 21)), dim3(kTB), 0, c->stream, n_out, perm, k_ev,
+                           c->ht[S_OUT1].as<int64_t>(), c->ht[S_OUT2].as<int64_t>(), es.next_event,
+                           reinterpret_cast<const uint32_t*>(rows), c->es_out.as<uint32_t>());
+    }
+    // 5. the hits of the open events, in row order, into the other carry buffer (all open: the table is the carry)
+    if (n_keep > 0 && n_out > 0) {
+        DevBuf& other = c->es_carry[es.cur ^ 1];
+        if ((rc = other.ensure((size_t)n_keep * 60))) return rc;
+        int64_t* flag = c->ht[S_FLAG].as<int64_t>();
+        int64_t* incl = c->ht[S_ID].as<int64_t>();
+        hipLaunchKernelGGL(k_es_keep, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, k_ev, n_closed, flag);
+        size_t tb = c->ht[S_CUB].cap;  // (sized by group_cols for this very scan)
+        WFA_HIP_CHECK(rocprim::inclusive_scan(c->ht[S_CUB].ptr, tb, flag, incl, (size_t)n, rocprim::plus<int64_t>(), c->stream));
+        hipLaunchKernelGGL(k_es_compact, dim3(blocks_for(n * 15)), dim3(kTB), 0, c->stream, n, flag, incl,
+                           reinterpret_cast<const uint32_t*>(rows), other.as<uint32_t>());
+    }
+    WFA_HIP_CHECK(hipGetLastError());
+    if ((rc = t.end("event stream: closed prefix, rows, carry"))) return rc;
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (n_keep > 0 && n_out > 0) es.cur ^= 1;
+    es.n_carry = n_keep;
+    es.next_event += n_closed;
+    es.horizon = horizon_ps;
+    es.out_rows = n_out;
+    *n_out_rows = n_out;
+    *n_out_events = n_closed;
+    *n_carry = n_keep;
+    return WFA_OK;
+}
+
+int wfa_event_stream_fill(wfa_ctx* c, void* out_rows, int64_t n_out_rows) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (!c->es.open || c->es.out_rows < 0) return fail(WFA_E_STATE, "no event stream push has been made");
+    if (n_out_rows != c->es.out_rows)
+        return fail(WFA_E_INVALID, "caller expects %lld rows, the last push closed %lld", (long long)n_out_rows,
+                    (long long)c->es.out_rows);
+    if (n_out_rows == 0) return WFA_OK;
+    if (!out_rows) return fail(WFA_E_INVALID, "out_rows is null");
+    const size_t bytes = (size_t)n_out_rows * 84;
+    if (bytes >= (4u << 20)) {  // large: through the pinned staging ring
+        if ((rc = d2h_staged(c, out_rows, c->es_out.ptr, bytes, nullptr, nullptr))) return rc;
+    } else {
+        WFA_HIP_CHECK(hipMemcpyAsync(out_rows, c->es_out.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return WFA_OK;
+}
+
+int wfa_event_stream_end(wfa_ctx* c) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->es_carry[0].release();
+    c->es_carry[1].release();
+    c->es_out.release();
+    c->es = wfa_ctx::EventStream{};
     return WFA_OK;
 }
 

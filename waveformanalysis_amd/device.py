@@ -18,6 +18,7 @@ import numpy as np
 from . import _lib
 from .dtypes import (
     BASIC_FEATURES_DTYPE,
+    EVENT_HIT_DTYPE,
     HIT_DTYPE,
     S1_S2_CLASSIFIER_DTYPE,
     WAVEFORM_WIDTH_DTYPE,
@@ -943,6 +944,31 @@ class DeviceSession:
         _lib.check(self._lib.wfa_group_hit_windows_fill(self._h, int(n), k, _ptr(out["order"]), _ptr(out["event_start"]),
                                                         _ptr(out["t_min"]), _ptr(out["t_max"])))
         return out
+
+    # ---- event stream: group_hit_windows chunk by chunk, the open events' hits resident between pushes ----------------
+    def event_stream_begin(self, time_window_ns: float) -> None:
+        """Open the session's event stream (wfa_event_stream_begin): empty carry, next event id 0."""
+        _lib.check(self._lib.wfa_event_stream_begin(self._h, float(time_window_ns)))
+
+    def event_stream_push(self, rows: np.ndarray | None, horizon: float) -> tuple[np.ndarray, int]:
+        """Push THRESHOLD_HIT_DTYPE rows (None / empty: a pure flush) with the horizon (ps, float64) below which no
+        later hit starts -> (EVENT_HIT_DTYPE rows of the events this push closed, rows carried on the device)."""
+        n = 0 if rows is None else len(rows)
+        src = None
+        if n:
+            if rows.dtype != THRESHOLD_HIT_DTYPE:
+                raise ValueError("event_stream_push takes THRESHOLD_HIT_DTYPE rows")
+            src = np.ascontiguousarray(rows)
+        n_out, n_ev, n_carry = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _lib.check(self._lib.wfa_event_stream_push(self._h, _ptr(src), n, float(horizon), C.byref(n_out), C.byref(n_ev),
+                                                   C.byref(n_carry)))
+        out = np.empty(int(n_out.value), dtype=EVENT_HIT_DTYPE)
+        _lib.check(self._lib.wfa_event_stream_fill(self._h, _ptr(out), int(n_out.value)))
+        return out, int(n_carry.value)
+
+    def event_stream_end(self) -> None:
+        """Free the carry and close the stream (wfa_event_stream_end)."""
+        _lib.check(self._lib.wfa_event_stream_end(self._h))
 
     def hit_merge_clusters_resident(self, n: int, merge_gap_ns: float, max_total_width_ns: float):
         """hit_merge_clusters on the n resident rows: (order, cluster_offset)."""

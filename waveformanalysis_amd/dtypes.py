@@ -52,6 +52,10 @@ THRESHOLD_HIT_DTYPE = np.dtype(
     ]
 )
 
+# one row per hit of a closed event (event stream, wfa_event_stream_fill; 84 B): the event's id and extent, then the
+# THRESHOLD_HIT_DTYPE row unchanged
+EVENT_HIT_DTYPE = np.dtype([("event_id", "i8"), ("t_min", "i8"), ("t_max", "i8")] + THRESHOLD_HIT_DTYPE.descr)
+
 BASIC_FEATURES_DTYPE = np.dtype(
     [
         ("height", "f4"),
@@ -201,12 +205,14 @@ assert S1_S2_CLASSIFIER_DTYPE.itemsize == 45
 assert HIT_MERGED_DTYPE.itemsize == 72
 assert RECORDS_DTYPE.itemsize == 102
 assert THRESHOLD_HIT_DTYPE.itemsize == 60
+assert EVENT_HIT_DTYPE.itemsize == 84 and EVENT_HIT_DTYPE.fields["position"][1] == 24
 assert BASIC_FEATURES_DTYPE.itemsize == 36
 assert WAVEFORM_WIDTH_INTEGRAL_DTYPE.itemsize == 52
 
 __all__ = [
     "RECORDS_DTYPE",
     "THRESHOLD_HIT_DTYPE",
+    "EVENT_HIT_DTYPE",
     "BASIC_FEATURES_DTYPE",
     "WAVEFORM_WIDTH_INTEGRAL_DTYPE",
     "HIT_DTYPE",

@@ -1,0 +1,311 @@
+"""HipHitGroupedStream -- `hit_grouped` chunk by chunk: the coincidence events of the records stream, with the hits of the
+events still open kept on the device between chunks.
+
+The reference groups the run's whole hit table at once (processing/event_grouping.py:286-471) and has no streaming form
+of it (profiles.py names streaming_default() as not available yet).  The static rule: after a global sort by abs_start a
+hit opens a new event iff abs_start > running max(abs_end) + gap.  An event can therefore be emitted as soon as no later
+hit can reach it.  A horizon H is a float64 such that every hit not yet seen has computed abs_start >= H; an event of the
+table at hand is closed iff max(abs_end) + gap < H, strictly.  The closed events are a prefix of the table's events, no
+later hit can join or precede them, so they are final; the hits of all other events (the carry) are grouped again together
+with the next chunk's hits.  After the last chunk H = +inf closes everything.  Holding back more than necessary only
+delays rows, it never changes them: all chunks together give the static table, whatever the chunk size.
+
+The device part is wfa_event_stream_* (DeviceSession.event_stream_begin / _push / _end): the carry stays in HBM, a push
+runs the grouping pass of the static entry over carry ++ new rows and returns EVENT_HIT_DTYPE rows, one per hit of the
+events it closed.
+"""
+
+from __future__ import annotations
+
+import math
+from types import SimpleNamespace
+from typing import Any
+
+import numpy as np
+
+from .chunk import Chunk
+from .device import DevicePool
+from .dtypes import EVENT_HIT_DTYPE, THRESHOLD_HIT_DTYPE
+from .event_grouping import EVENT_COLUMNS
+from .plugins import _common as K
+from .plugins.hit_grouped import HipHitGroupedPlugin
+from .streaming import _UNSET, HipStreamingPlugin, HipThresholdHitStream, _RecordsChunking
+
+HIT_OPTION_NAMES = tuple(HipThresholdHitStream.options)
+EXACT_LIMIT_PS = 2**53   # below it every int64 ps value, and so every abs window, is exact in float64
+
+
+def abs_windows(rows: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """(abs_start, abs_end) in float64 ps, rounded as the device and the reference round them:
+    float(ts) + (float(edge) - float(position)) * (float(dt) * 1e3)."""
+    t = rows["timestamp"].astype(np.float64)
+    p = rows["position"].astype(np.float64)
+    dps = rows["dt"].astype(np.float64) * 1e3
+    return t + (rows["edge_start"].astype(np.float64) - p) * dps, t + (rows["edge_end"].astype(np.float64) - p) * dps
+
+
+def horizon_margin(magnitude_ps: float) -> float:
+    """What to subtract from float(minimum later record timestamp) so that it is a horizon, given the largest magnitude
+    (ps) any timestamp, record end or record span of the run reaches.  Below 2^53 ps everything is exact: 0.  Beyond it
+    four roundings stand between the integer bound and a later hit's computed abs_start -- float(minimum) itself,
+    float(hit timestamp), the product (edge - position) * (dt * 1e3) and the final sum -- each at most half an ulp of a
+    value whose magnitude the argument bounds: two ulps of it."""
+    m = abs(float(magnitude_ps))
+    if m < EXACT_LIMIT_PS:
+        return 0.0
+    return 2.0 * float(np.spacing(m))
+
+
+def run_magnitude(records: np.ndarray) -> int:
+    """Largest |value| in ps among the records' timestamps, their ends and their spans (Python ints: no overflow)."""
+    if len(records) == 0:
+        return 0
+    ts = records["timestamp"].astype(np.int64)
+    # (a hit's position may lie in the padding up to the run's longest record: the widest span at the largest dt)
+    lo, hi = int(ts.min()), int(ts.max())
+    width = int(records["dt"].max()) * 1000 * int(records["event_length"].max())
+    return max(abs(lo), abs(hi), abs(lo) + width, abs(hi) + width)
+
+
+def horizon_of(min_later_timestamp: int | None, margin: float) -> float:
+    """The horizon of a push after which only records with timestamp >= min_later_timestamp follow (None: nothing
+    follows)."""
+    if min_later_timestamp is None:
+        return math.inf
+    h = float(min_later_timestamp)
+    if margin > 0.0:
+        h = float(np.nextafter(h - margin, -np.inf))   # (the subtraction rounds to nearest: one more step down)
+    return h
+
+
+def chunk_horizons(chunks: list) -> list[float]:
+    """One horizon per records chunk: the minimum record timestamp over all records of LATER chunks (a suffix minimum,
+    taken once per run; correct for unsorted runs as well), as float64 less the run's margin; +inf for the last chunk.
+    A threshold hit has edge_start >= 0 and timestamp = record timestamp + position * dt * 1e3, so its abs_start is at
+    least its record's timestamp."""
+    nonempty = [c.data for c in chunks if len(c.data)]
+    margin = horizon_margin(max((run_magnitude(d) for d in nonempty), default=0))
+    out: list[float] = [math.inf] * len(chunks)
+    later = None
+    for k in range(len(chunks) - 1, -1, -1):
+        out[k] = horizon_of(later, margin)
+        if len(chunks[k].data):
+            first = int(chunks[k].data["timestamp"].min())
+            later = first if later is None else min(later, first)
+    return out
+
+
+def event_rows(hits: np.ndarray, flat: dict, first_event: int = 0) -> np.ndarray:
+    """EVENT_HIT_DTYPE rows from the flat form of the static pass (event_grouping.group_hit_windows_flat)."""
+    order, es = np.asarray(flat["order"], dtype=np.int64), np.asarray(flat["event_start"], dtype=np.int64)
+    counts = np.diff(es)
+    out = np.zeros(len(order), dtype=EVENT_HIT_DTYPE)
+    out["event_id"] = np.repeat(first_event + np.arange(len(counts), dtype=np.int64), counts)
+    out["t_min"] = np.repeat(np.asarray(flat["t_min"], dtype=np.int64), counts)
+    out["t_max"] = np.repeat(np.asarray(flat["t_max"], dtype=np.int64), counts)
+    picked = hits[order]
+    for name in THRESHOLD_HIT_DTYPE.names:
+        out[name] = picked[name]
+    return out
+
+
+def events_frame(rows: np.ndarray):
+    """The reference's hit_grouped DataFrame (EVENT_COLUMNS) from EVENT_HIT_DTYPE rows: one frame row per run of equal
+    event_id, n_hits = the run's length, the per-hit columns as arrays in row order."""
+    import pandas as pd
+
+    if len(rows) == 0:
+        return pd.DataFrame(columns=EVENT_COLUMNS)
+    ids = rows["event_id"]
+    starts = np.concatenate([[0], np.flatnonzero(ids[1:] != ids[:-1]) + 1, [len(rows)]])
+    cols = {"dt": ("dt", np.int32), "boards": ("board", np.int16), "channels": ("channel", np.int16),
+            "heights": ("height", np.float32), "integrals": ("integral", np.float32), "timestamps": ("timestamp", np.int64),
+            "record_ids": ("record_id", np.int64), "sample_starts": ("edge_start", np.int32),
+            "sample_ends": ("edge_end", np.int32)}
+    flat = {k: np.ascontiguousarray(rows[f], dtype=t) for k, (f, t) in cols.items()}
+    out = []
+    for a, b in zip(starts[:-1].tolist(), starts[1:].tolist()):
+        t_min, t_max = int(rows["t_min"][a]), int(rows["t_max"][a])
+        row = {"event_id": int(ids[a]), "t_min": t_min, "t_max": t_max, "dt/ns": (t_max - t_min) / 1e3, "n_hits": b - a}
+        for k, v in flat.items():
+            row[k] = v[a:b].copy()
+        out.append(row)
+    return pd.DataFrame(out, columns=EVENT_COLUMNS)
+
+
+class HipHitGroupedStream(_RecordsChunking, HipStreamingPlugin):
+    """compute() = the events of the records stream, delivered as they close.
+
+    The records are chunked like hit_threshold_stream; an inner HipThresholdHitStream (same options, same ring of two
+    sessions per device, same overlap of upload and kernels) finds every chunk's hits.  Each chunk's rows go, in order,
+    to ONE more session borrowed for the whole run, with the chunk's horizon (`chunk_horizons`); after the last chunk one
+    push with +inf.  A result chunk holds the EVENT_HIT_DTYPE rows of the events one push closed, with bounds
+    [min t_min, max t_max + 1); a push that closes nothing yields nothing.  `events_frame(all rows)` is the DataFrame of
+    HipHitGroupedPlugin on HipThresholdHitPlugin's rows under the same configuration.
+
+    Stateful (the carry lives on the device between chunks) and not reset at a time break: an event may span one.
+    Options: those of hit_threshold_stream, and `time_window_ns` / `dt` with hit_grouped's names and defaults; a value
+    given to the constructor wins over the Context.  The stream's rows always carry dt (the records'), so `dt` is read
+    for parity only, as the static plugin ignores it when its hits have the column.
+
+    The rows travel device -> host -> device once more than necessary: the ring's sessions download a chunk's 60-byte
+    rows (the hit stream's product), and the push uploads them to the grouping session.
+
+    Refused on the host, before any upload: a Context whose configuration sets merge_gap_ns > 0 for hit_merged (the
+    static plugin would then group merged hits, which the stream does not build), and a device pool with fewer than three
+    sessions (two for the ring, one for the grouping)."""
+
+    provides = "hit_grouped_stream"
+    depends_on = ["records", "wave_pool"]
+    description = "Coincidence events of the records stream, delivered as they close (HIP, gfx950)."
+    version = "0.1.0+hip1"
+    output_dtype = EVENT_HIT_DTYPE
+    save_when = "never"
+    chunk_size = 50_000
+    length_field = "event_length"
+    output_data_kind = "events"
+    output_time_field = "t_min"
+    output_endtime_field = "t_max"
+    is_stateful = True
+    reset_on_break = False
+    profile_pushes = False   # measurement: kernel timers on the grouping session, their report in stats["profile"]
+
+    options = {**HipThresholdHitStream.options, **HipHitGroupedPlugin.options}
+
+    def __init__(self, device_pool: DevicePool | None = None, max_len: int = 0, **given):
+        super().__init__()
+        unknown = sorted(set(given) - set(self.options))
+        if unknown:
+            raise TypeError(f"hit_grouped_stream: unknown options {unknown}")
+        self._given = {k: v for k, v in given.items() if v is not _UNSET}
+        self.device_pool = device_pool
+        self.max_len = int(max_len)
+        self.stats: dict = {}
+        self._configure(None)
+
+    def _configure(self, context: Any) -> dict:
+        """Constructor argument > Context configuration > option default."""
+        def value(name):
+            if name in self._given:
+                return self._given[name]
+            if context is not None and hasattr(context, "get_config"):
+                v = context.get_config(self, name)
+                if v is not None:
+                    return v
+            return self.options[name].default
+
+        cfg = {name: value(name) for name in self.options}
+        cfg["time_window_ns"] = float(cfg["time_window_ns"])
+        if cfg["time_window_ns"] < 0:
+            raise ValueError("time_window_ns must be >= 0")
+        self.cfg = cfg
+        return cfg
+
+    def _inner(self, cfg: dict, pool: DevicePool) -> HipThresholdHitStream:
+        """The hit stream with this stream's resolved options as its constructor values (so they win in its own
+        _configure) and this stream's chunking knobs."""
+        given = {name: cfg[name] for name in HIT_OPTION_NAMES}
+        if str(given["filter_source"]) == "wave_pool_filtered":  # (that plugin's filter settings: none of our own)
+            given.pop("sg_window_size"), given.pop("sg_poly_order")
+        inner = HipThresholdHitStream(max_len=self.max_len, device_pool=pool, **given)
+        inner.chunk_size, inner.break_threshold_ps = self.chunk_size, self.break_threshold_ps
+        return inner
+
+    @staticmethod
+    def _check_scope(context: Any) -> None:
+        if not isinstance(getattr(context, "config", None), dict):
+            return
+        gap = K.raw_config(context, SimpleNamespace(provides="hit_merged"), "merge_gap_ns")
+        if gap is not None and float(gap) > 0:
+            raise ValueError(f"hit_grouped_stream: the configuration sets merge_gap_ns = {gap!r} for hit_merged; the static "
+                             "hit_grouped would group merged hits, the stream groups threshold hits only")
+
+    @staticmethod
+    def _check_pool(pool: DevicePool) -> None:
+        if int(pool.max_sessions) < 3:
+            raise ValueError(f"hit_grouped_stream needs a device pool with max_sessions >= 3 (two sessions for the hit "
+                             f"ring, one for the grouping), got {pool.max_sessions}")
+
+    def compute_chunk(self, chunk: Chunk, context: Any, run_id: str, **_kw):
+        raise NotImplementedError("hit_grouped_stream is stateful across chunks: drive it through compute() / run_chunks()")
+
+    def compute(self, context: Any, run_id: str, **kwargs):
+        self._apply_streaming_config(kwargs.pop("streaming_config", None))
+        records = context.get_data(run_id, "records")
+        if not isinstance(records, np.ndarray) or records.dtype.names is None:
+            raise TypeError(f"{self.provides} chunks the structured `records` array")
+        # (refusals first: the chunk list is only cut once the run is known to start)
+        cfg = self._configure(context)
+        self._check_scope(context)
+        self._check_pool(self._pool(context))
+        del cfg
+        workers = (kwargs.get("executor_config") or {}).get("max_workers") or self.max_workers
+        yield from self.run_chunks(list(self._data_to_chunks(records, run_id)), context, run_id, max_workers=workers)
+
+    def run_chunks(self, chunks: list, context: Any, run_id: str, max_workers: int | None = None,
+                   first_event_time: list | None = None):
+        """Generator over the result chunks of ready-made records chunks (what compute() cuts).  `first_event_time`
+        (optional list) receives time.perf_counter() when the first rows are delivered."""
+        import time
+
+        cfg = self._configure(context)
+        self._check_scope(context)
+        pool = self._pool(context)
+        self._check_pool(pool)
+        inner = self._inner(cfg, pool)
+        horizons = chunk_horizons(chunks)
+        stats = self.stats = {"pushes": 0, "rows_in": 0, "rows_out": 0, "events": 0, "max_carry": 0}
+        serial = not self.parallel or (max_workers is not None and int(max_workers) <= 1)
+        if serial:
+            inner._configure(context)
+            width, plan = inner._run_width(context, run_id, chunks), inner._run_plan(context, run_id, chunks)
+            hits = ((c, inner._compute_one(c, context, run_id, width, plan)) for c in chunks)
+        else:
+            # the grouping session is borrowed first and for the whole run: the ring may take what is left, no more
+            ring = int(pool.max_sessions) - 1
+            hits = inner._pipeline(chunks, context, run_id, max_workers=min(ring, int(max_workers)) if max_workers else ring)
+        with pool.borrow() as sess:
+            if self.profile_pushes:
+                sess.profile(True)
+            sess.event_stream_begin(cfg["time_window_ns"])
+            try:
+                k = -1
+                for k, (_chunk, raw) in enumerate(hits):
+                    out = self._push(sess, raw.data, horizons[k], run_id, stats)
+                    if out is not None:
+                        if first_event_time is not None and not first_event_time:
+                            first_event_time.append(time.perf_counter())
+                        yield out
+                if k + 1 != len(chunks):
+                    raise RuntimeError(f"hit_grouped_stream: {k + 1} results for {len(chunks)} chunks")
+                out = self._push(sess, None, math.inf, run_id, stats)
+                if out is not None:
+                    if first_event_time is not None and not first_event_time:
+                        first_event_time.append(time.perf_counter())
+                    yield out
+            finally:
+                if hasattr(hits, "close"):
+                    hits.close()   # (gives the ring's sessions back before ours)
+                if self.profile_pushes:
+                    stats["profile"] = sess.profile_report()
+                    sess.profile(False)
+                sess.event_stream_end()
+
+    def _push(self, sess, rows, horizon: float, run_id: str, stats: dict):
+        out, n_carry = sess.event_stream_push(rows, horizon)
+        stats["pushes"] += 1
+        stats["rows_in"] += 0 if rows is None else len(rows)
+        stats["rows_out"] += len(out)
+        stats["max_carry"] = max(stats["max_carry"], int(n_carry))
+        if len(out) == 0:
+            return None
+        stats["events"] = int(out["event_id"][-1]) + 1
+        result = Chunk(out, int(out["t_min"].min()), int(out["t_max"].max()) + 1, run_id, self.provides,
+                       data_kind=self.output_data_kind, time_field="t_min", endtime_field="t_max",
+                       metadata={"first_event": int(out["event_id"][0]), "n_carry": int(n_carry)})
+        self._validate_chunk(result)
+        return result
+
+
+__all__ = ["HipHitGroupedStream", "events_frame", "event_rows", "chunk_horizons", "horizon_of", "horizon_margin",
+           "run_magnitude", "abs_windows", "EVENT_HIT_DTYPE"]

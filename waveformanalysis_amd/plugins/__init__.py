@@ -62,7 +62,14 @@ def hip_streaming():
     return [HipThresholdHitStream(), HipSignalPeaksStreamPlugin(), HipS1S2Stream()]
 
 
-__all__ = ["hip_streaming", "HipWavePoolFilteredPlugin", "HipThresholdHitPlugin", "HipBasicFeaturesPlugin",
+def hip_streaming_events():
+    """hip_streaming() plus hit_grouped_stream: the coincidence events of the records stream, delivered as they close."""
+    from ..event_stream import HipHitGroupedStream
+
+    return hip_streaming() + [HipHitGroupedStream()]
+
+
+__all__ = ["hip_streaming", "hip_streaming_events", "HipWavePoolFilteredPlugin", "HipThresholdHitPlugin", "HipBasicFeaturesPlugin",
            "HipWaveformWidthIntegralPlugin", "HipHitGroupedPlugin", "HipHitFinderPlugin", "HipFilteredWaveformsPlugin",
            "HipWaveformWidthPlugin", "HipS1S2ClassifierPlugin", "HipHitMergeClustersPlugin",
            "HipHitMergePlugin", "HipHitMergedComponentsPlugin", "HipSignalPeaksStreamPlugin", "HipRecordsPlugin", "HipWavePoolPlugin",
