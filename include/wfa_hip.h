@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define WFA_ABI_VERSION 7
+#define WFA_ABI_VERSION 8
 
 #define WFA_OK 0
 #define WFA_E_INVALID (-1)   /* bad argument / malformed records (maps to ValueError) */
@@ -458,6 +458,41 @@ int wfa_event_stream_push(wfa_ctx* ctx, const void* hit_rows, int64_t n_rows, do
                           int64_t* n_out_events, int64_t* n_carry);
 int wfa_event_stream_fill(wfa_ctx* ctx, void* out_rows, int64_t n_out_rows);
 int wfa_event_stream_end(wfa_ctx* ctx);
+
+/* Merge stream: K11 chunk by chunk, the hits of the clusters still open kept on the device between pushes.
+ * A horizon H is as for the event stream.  A push appends its THRESHOLD_HIT_DTYPE rows (60 B, host memory; NULL with
+ * n_rows = 0 is a pure flush) behind the carried rows -- the carry keeps its original row order, so ties of the stable
+ * sort fall where the whole table would put them -- and runs the sort and chain of wfa_hit_merge_count over that table.
+ * In a channel's sorted table let F be the number of rows with abs_start < H, strictly.  A cluster at sorted positions
+ * [a, b) is closed iff b <= F and one of: b < F (the hit that broke the chain is final); merge_gap_ns <= 0 (nothing ever
+ * joins); H - cluster_end > merge_gap_ns * 1e3 in float64 (no later hit can join: its abs_start is >= H and float
+ * subtraction is monotone).  Closed clusters are a prefix of every channel's clusters and final; the hits of all others
+ * stay on the device (the carry) and are chained again with the next push's rows, which reproduces them because a chain
+ * restarted at a cluster head gives the rest.  After the last rows a push with H = +inf closes everything.
+ * _push reports the clusters closed, their members, the rows carried and open_start = the smallest abs_start among the
+ * carried rows (+inf: none): below min(H, open_start) no merged row will start any more.  _fill delivers
+ *   merged_rows: 72 B packed (HIT_MERGED_DTYPE), one per closed cluster, ordered by (board, channel), then chain order:
+ *                the fields of wfa_hit_merge_emit's cluster on its anchor hit, a cluster of one hit being that hit;
+ *                component_count as in the static table; component_offset = the offset of the cluster's members in the
+ *                stream's own component sequence, cumulative over all pushes since _begin;
+ *   hit_index:   one int64 per member, clusters in the order of the merged rows, members in chain order: the row's
+ *                position in the sequence of all rows pushed since _begin.
+ * Stably sorted by (board, channel), with component_offset rewritten as the running sum of component_count and the
+ * members moved with their clusters, all pushes together give the static hit_merged, hit_merge_clusters.hit_index and
+ * hit_merged_components of the whole table, in any chunking.
+ * Refused with WFA_E_INVALID, the stream left as it was: a negative or NaN gap or width (_begin); a pushed row with
+ * dt <= 0 or a negative edge_start / edge_end; a pushed row whose abs_start lies below the previous push's horizon; a
+ * horizon below the previous one, or NaN; carry + pushed rows >= 2^31.  _push without _begin, _fill before a push:
+ * WFA_E_STATE; _fill with other counts: WFA_E_INVALID.  _begin on an open stream starts over.  A context may hold an open
+ * event stream and an open merge stream at once.
+ * The carry and the output of the last push are state: wfa_release_scratch keeps them, wfa_scratch_bytes does not count
+ * them, _end frees them (68 B per carried row in each of two buffers, 72 B per cluster and 8 B per member of the largest
+ * push). */
+int wfa_merge_stream_begin(wfa_ctx* ctx, double merge_gap_ns, double max_total_width_ns);
+int wfa_merge_stream_push(wfa_ctx* ctx, const void* hit_rows, int64_t n_rows, double horizon_ps, int64_t* n_merged,
+                          int64_t* n_components, int64_t* n_carry, double* open_start_ps);
+int wfa_merge_stream_fill(wfa_ctx* ctx, void* merged_rows, int64_t* hit_index, int64_t n_merged, int64_t n_components);
+int wfa_merge_stream_end(wfa_ctx* ctx);
 
 /* Legacy fixed-window grouping: group_multi_channel_hits (processing/event_grouping.py:98-283) with the boundary search of
  * _find_cluster_boundaries_numba (475-525).  The hits are ordered by timestamp (stable; pandas' default sort leaves the

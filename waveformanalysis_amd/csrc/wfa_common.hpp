@@ -239,7 +239,7 @@ struct wfa_ctx {
     wfa::DevBuf peak_cand_rec{scratch}, peak_accept{scratch}, peak_ips{scratch}, peak_row_start{scratch};
     wfa::DevBuf wh_pos{scratch}, wh_row{scratch}, wh_valid{scratch};  // per-hit inputs of k_waveform_width
     // hit-table stages (wfa_hits.hip): scratch slots and the state of the last count pass
-    wfa::DevBuf ht[40];
+    wfa::DevBuf ht[48];
     int ht_src = 1;            // wfa_hit_rows_source: 1 = rows of the last hit pass, 2 = rows of the last gather
     wfa::DevBuf gathered;      // rows the last wfa_rccl_gather_rows left on the root
     int64_t gathered_n = -1;
@@ -269,6 +269,21 @@ struct wfa_ctx {
         int64_t out_rows = -1;    // rows of the last push waiting in es_out; -1: no push yet
     } es;
     wfa::DevBuf es_carry[2], es_out;
+    // merge stream (wfa_merge_stream_*, wfa_hits.hip): the hits of the clusters still open after the last push, as 60-byte
+    // rows in their original order in ms_carry[ms.cur], each row's index in the sequence of all pushed rows beside it in
+    // ms_index[ms.cur], and what the last push closed: 72-byte merged rows and their members' indices.  State like the
+    // event stream's: wfa_release_scratch keeps it, wfa_merge_stream_end frees it
+    struct MergeStream {
+        bool open = false;
+        double gap_ns = 0.0, width_ns = 0.0;
+        double horizon = 0.0;       // horizon of the last accepted push (-inf before the first)
+        int64_t next_hit = 0;       // rows pushed so far = index of the next pushed row
+        int64_t next_component = 0; // component rows emitted so far = component_offset of the next cluster
+        int64_t n_carry = 0;
+        int cur = 0;
+        int64_t out_merged = -1, out_components = 0;  // of the last push, waiting in ms_out / ms_out_index; -1: no push yet
+    } ms;
+    wfa::DevBuf ms_carry[2], ms_index[2], ms_out, ms_out_index;
     wfa::DevBuf bw_scratch{scratch};  // float64 forward pass of sosfiltfilt, [sample][record-in-batch]
 
     // profiling: HIP events around every launch on the context's stream.  The pairs are only recorded while the

@@ -31,9 +31,10 @@ inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kTB - 1) / kTB); 
 enum Slot {
     S_TS, S_POS, S_START, S_END, S_DT, S_BOARD, S_CHAN, S_RID, S_HEIGHT, S_INTEGRAL,
     S_ABS0, S_ABS1, S_K0, S_K1, S_K2, S_K3, S_K4, S_KTMP0, S_KTMP1, S_PERM0, S_PERM1, S_CUB,
-    S_F0, S_F1, S_FLAG, S_ID, S_OUT0, S_OUT1, S_OUT2, S_OUT3, S_OUT4, S_OUT5, S_OUT6, S_OUT7, S_CNT, S_CNT2, S_SG, S_CSV, S_ES, S_EVHI, S_N
+    S_F0, S_F1, S_FLAG, S_ID, S_OUT0, S_OUT1, S_OUT2, S_OUT3, S_OUT4, S_OUT5, S_OUT6, S_OUT7, S_CNT, S_CNT2, S_SG, S_CSV, S_ES, S_EVHI,
+    S_MS0, S_MS1, S_MS2, S_MS3, S_MS4, S_MS5, S_MS6, S_N
 };
-static_assert(S_N <= 40, "wfa_ctx::ht is too small");
+static_assert(S_N <= 48, "wfa_ctx::ht is too small");
 
 template <typename T>
 int slot(wfa_ctx* c, int s, int64_t n, T** out) {
@@ -522,14 +523,17 @@ __global__ void k_cluster_offsets(int64_t n, const int64_t* __restrict__ flag, c
     if (j == n - 1) offset[n_clusters] = n;
 }
 
-// _emit_cluster (hit_merge.py:256-322) for every cluster; singles are flagged and copied on the host
+// _emit_cluster (hit_merge.py:256-322) for every cluster, or for the n_clusters clusters `list` names (results indexed
+// like the list); singles are flagged and copied on the host, or by k_ms_rows
 __global__ void k_merge_emit(int64_t n_clusters, const int64_t* __restrict__ offset, const int64_t* __restrict__ perm,
                              HitCols h, const float* __restrict__ height, const float* __restrict__ integral,
                              int64_t* __restrict__ anchor, float* __restrict__ out_h, float* __restrict__ out_int,
-                             int32_t* __restrict__ out_s, int32_t* __restrict__ out_e, float* __restrict__ out_w) {
+                             int32_t* __restrict__ out_s, int32_t* __restrict__ out_e, float* __restrict__ out_w,
+                             const int64_t* __restrict__ list = nullptr) {
     __shared__ double s_pw[kPairwiseLevels][kTB];
-    const int64_t cl = (int64_t)blockIdx.x * kTB + threadIdx.x;
-    if (cl >= n_clusters) return;
+    const int64_t r = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (r >= n_clusters) return;
+    const int64_t cl = list ? list[r] : r;
     const int64_t a = offset[cl], b = offset[cl + 1];
     int64_t best = perm[a];
     double max_h = (double)height[best];
@@ -559,12 +563,12 @@ __global__ void k_merge_emit(int64_t n_clusters, const int64_t* __restrict__ off
     if (smin < 0 || emax < 0) w = -1.0;
     const double total = np_pairwise_sum([&](int q) { return (double)integral[perm[a + q]]; }, 0, (int)(b - a),
                                          &s_pw[0][threadIdx.x], kTB);
-    anchor[cl] = best;
-    out_h[cl] = (float)max_h;
-    out_int[cl] = (float)total;
-    out_s[cl] = smin;
-    out_e[cl] = emax;
-    out_w[cl] = (float)w;
+    anchor[r] = best;
+    out_h[r] = (float)max_h;
+    out_int[r] = (float)total;
+    out_s[r] = smin;
+    out_e[r] = emax;
+    out_w[r] = (float)w;
 }
 
 // ---- records builder: global order + pool packing (records_builder.py:115-120, 164-209, 869-945) --------------
@@ -900,10 +904,12 @@ struct EsCtl {
     int flags, pad;
 };
 
-// the pushed rows [0, n) (columns and windows already offset past the carry): dt and edge checks, smallest abs_start
+// the pushed rows [0, n) (columns and windows already offset past the carry): dt and edge checks, smallest abs_start;
+// Ctl = the control block of the event stream or of the merge stream
+template <typename Ctl>
 __global__ __launch_bounds__(kTB) void k_es_check(int64_t n, const int32_t* __restrict__ dt, const int32_t* __restrict__ s,
                                                   const int32_t* __restrict__ e, const double* __restrict__ abs0,
-                                                  EsCtl* __restrict__ ctl) {
+                                                  Ctl* __restrict__ ctl) {
     unsigned long long lo = ~0ull;
     int bad = 0;
     for (int64_t i = (int64_t)blockIdx.x * kTB + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTB) {
@@ -956,14 +962,15 @@ __global__ void k_es_keep(int64_t n, const uint64_t* __restrict__ k_event, int64
     const int64_t i = (int64_t)blockIdx.x * kTB + threadIdx.x;
     if (i < n) flag[i] = (int64_t)k_event[i] >= n_closed ? 1 : 0;
 }
-// the kept 60-byte rows, 15 dwords each, to their place in the other carry buffer (original row order)
+// the kept rows, W dwords each (15: a 60-byte hit row), to their place in the other carry buffer (original row order)
+template <int W>
 __global__ __launch_bounds__(kTB) void k_es_compact(int64_t n, const int64_t* __restrict__ flag,
                                                     const int64_t* __restrict__ incl, const uint32_t* __restrict__ src,
                                                     uint32_t* __restrict__ dst) {
     const int64_t d = (int64_t)blockIdx.x * kTB + threadIdx.x;
-    if (d >= n * 15) return;
-    const int64_t i = d / 15;
-    if (flag[i]) dst[(incl[i] - 1) * 15 + (d - i * 15)] = src[d];
+    if (d >= n * W) return;
+    const int64_t i = d / W;
+    if (flag[i]) dst[(incl[i] - 1) * W + (d - i * W)] = src[d];
 }
 
 // grow a carry buffer to `want` bytes and keep its first `used` bytes (DevBuf::ensure drops the contents)
@@ -978,7 +985,7 @@ int es_grow(wfa_ctx* c, DevBuf& b, size_t used, size_t want) {
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         (void)hipFree(p);
-        return fail(WFA_E_HIP, "growing the event stream's carry failed: %s", hipGetErrorString(e));
+        return fail(WFA_E_HIP, "growing a stream's carry failed: %s", hipGetErrorString(e));
     }
     (void)hipFree(b.ptr);
     b.ptr = p;
@@ -990,6 +997,199 @@ inline uint64_t host_ord_f64(double v) {
     uint64_t b;
     memcpy(&b, &v, sizeof(b));
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+// The merge pass over a device table of n > 0 hits (the body of wfa_hit_merge_count; the merge stream runs it on
+// carry ++ new rows): prep, sort per hardware channel, segmented max-scan, greedy chain, cluster offsets.  Leaves, in
+// scratch slots, abs_start / abs_end per hit (S_ABS0 / S_ABS1), the sorted columns s0 / s1 / dt / channel key (S_F0 / S_F1 /
+// S_K1 / S_SG), the head flag of every sorted position and its inclusive scan = cluster index + 1 (S_FLAG / S_ID),
+// cluster_offset[n_clusters + 1] (S_OUT0) and *perm_out = the hits channel-major in chain order.  The launches are queued
+// on the context's stream; the last one may still be running when this returns.
+int merge_cols(wfa_ctx* c, int64_t n, const HitCols& h, double merge_gap_ns, double max_total_width_ns, int64_t* n_clusters,
+               int64_t** perm_out) {
+    int rc;
+    double *abs0, *abs1, *s0, *s1;
+    uint64_t *k_abs, *k_chan, *sg;
+    int32_t* sdt;
+    int64_t *flag, *incl;
+    if ((rc = slot(c, S_ABS0, n, &abs0)) || (rc = slot(c, S_ABS1, n, &abs1)) || (rc = slot(c, S_K0, n, &k_abs)) ||
+        (rc = slot(c, S_K4, n, &k_chan)) || (rc = slot(c, S_F0, n, &s0)) || (rc = slot(c, S_F1, n, &s1)) ||
+        (rc = slot(c, S_K1, n, &sdt)) || (rc = slot(c, S_SG, n, &sg)) || (rc = slot(c, S_FLAG, n, &flag)) ||
+        (rc = slot(c, S_ID, n, &incl)))
+        return rc;
+    LaunchTimer t(c);
+    if ((rc = hit_prep(c, n, h, nullptr, nullptr, abs0, abs1, k_abs, nullptr, nullptr, nullptr, k_chan))) return rc;
+    int64_t* perm = nullptr;
+    {
+        // per hardware channel (ascending board, channel), stable by abs_start (hit_merge.py:137-149)
+        const uint64_t* keys[2] = {k_chan, k_abs};
+        if ((rc = lexsort(c, n, keys, 2, &perm))) return rc;
+    }
+    hipLaunchKernelGGL(k_merge_gather, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, perm, abs0, abs1, h.dt, k_chan, s0, s1, sdt, sg);
+    SegMax *seg_in, *seg_run;
+    if ((rc = slot(c, S_OUT1, n, &seg_in)) || (rc = slot(c, S_OUT2, n, &seg_run))) return rc;
+    const int do_merge = merge_gap_ns > 0 ? 1 : 0;
+    const double gap_ps = merge_gap_ns * 1e3;
+    hipLaunchKernelGGL(k_merge_segin, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, s1, sg, seg_in);
+    size_t tb = 0, tb_seg = 0;
+    WFA_HIP_CHECK(rocprim::inclusive_scan(nullptr, tb_seg, seg_in, seg_run, (size_t)n, SegMaxOp(), c->stream));
+    WFA_HIP_CHECK(rocprim::inclusive_scan(nullptr, tb, flag, incl, (size_t)n, rocprim::plus<int64_t>(), c->stream));
+    if ((rc = c->ht[S_CUB].ensure(tb > tb_seg ? tb : tb_seg))) return rc;
+    tb_seg = c->ht[S_CUB].cap;
+    WFA_HIP_CHECK(rocprim::inclusive_scan(c->ht[S_CUB].ptr, tb_seg, seg_in, seg_run, (size_t)n, SegMaxOp(), c->stream));
+    hipLaunchKernelGGL(k_merge_chain, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, s0, s1, sdt, sg, seg_run, do_merge,
+                       gap_ps, max_total_width_ns * 1e3, flag);
+    tb = c->ht[S_CUB].cap;
+    WFA_HIP_CHECK(rocprim::inclusive_scan(c->ht[S_CUB].ptr, tb, flag, incl, (size_t)n, rocprim::plus<int64_t>(), c->stream));
+    int64_t n_cl = 0;
+    WFA_HIP_CHECK(hipMemcpyAsync(&n_cl, incl + (n - 1), sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    int64_t* offset;
+    if ((rc = slot(c, S_OUT0, n_cl + 1, &offset))) return rc;
+    hipLaunchKernelGGL(k_cluster_offsets, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, flag, incl, n_cl, offset);
+    WFA_HIP_CHECK(hipGetLastError());
+    if ((rc = t.end("hit table: hit_merge clusters (sort + chain)"))) return rc;
+    *n_clusters = n_cl;
+    *perm_out = perm;
+    return WFA_OK;
+}
+
+
+// ---- merge stream (wfa_merge_stream_*) ------------------------------------------------------------------------------
+// A push chains carry ++ new rows with merge_cols and closes, per hardware channel, the clusters no later hit can precede
+// or join.  With F = the rows of the channel that start below the horizon H, strictly, a cluster at sorted positions
+// [a, b) is closed iff b <= F and (b < F, or nothing merges, or H - cluster_end > gap): a prefix of the channel's clusters.
+// Their merged rows and member indices go out; the hits of all other clusters stay, in original row order, for the next push.
+struct MsCtl {
+    unsigned long long min_key;   // ord_f64 of the smallest abs_start among the pushed rows
+    unsigned long long open_key;  // ord_f64 of the smallest abs_start among the rows that stay carried; ~0: none stay
+    long long n_closed;           // closed clusters
+    long long n_comp;             // their members
+    int flags, pad;
+};
+
+// the pushed rows' indices in the sequence of all rows pushed since _begin
+__global__ void k_ms_number(int64_t n, int64_t base, int64_t* __restrict__ index) {
+    const int64_t i = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (i < n) index[i] = base + i;
+}
+
+// height / integral columns of 60-byte rows (dwords 2 and 3) for k_merge_emit
+__global__ void k_ms_cols(int64_t n, const uint32_t* __restrict__ rows, float* __restrict__ height,
+                          float* __restrict__ integral) {
+    const int64_t i = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (i >= n) return;
+    height[i] = __uint_as_float(rows[i * 15 + 2]);
+    integral[i] = __uint_as_float(rows[i * 15 + 3]);
+}
+
+// closed flag and member count (0 for an open cluster) per cluster.  s0 ascends inside a channel, so b <= F is
+// s0[b - 1] < H and b < F is "the next row belongs to the channel and starts below H"; cluster_end = max(abs_end).
+__global__ void k_ms_closed(int64_t n_clusters, int64_t n, const int64_t* __restrict__ offset, const double* __restrict__ s0,
+                            const double* __restrict__ s1, const uint64_t* __restrict__ sg, int do_merge, double gap_ps,
+                            double horizon, int64_t* __restrict__ closed, int64_t* __restrict__ count) {
+    const int64_t cl = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (cl >= n_clusters) return;
+    const int64_t a = offset[cl], b = offset[cl + 1];
+    bool done = s0[b - 1] < horizon;
+    if (done && do_merge && !(b < n && sg[b] == sg[a] && s0[b] < horizon)) {
+        double c_end = s1[a];
+        for (int64_t j = a + 1; j < b; ++j) c_end = s1[j] > c_end ? s1[j] : c_end;
+        done = horizon - c_end > gap_ps;
+    }
+    closed[cl] = done ? 1 : 0;
+    count[cl] = done ? b - a : 0;
+}
+
+// keep flag per table row (1: its cluster stays open), the smallest abs_start among the kept rows, and, from one lane,
+// the totals of the two scans
+__global__ __launch_bounds__(kTB) void k_ms_keep(int64_t n, int64_t n_clusters, const int64_t* __restrict__ perm,
+                                                 const int64_t* __restrict__ cluster_incl, const int64_t* __restrict__ closed,
+                                                 const int64_t* __restrict__ closed_incl, const int64_t* __restrict__ comp_incl,
+                                                 const double* __restrict__ s0, int64_t* __restrict__ keep,
+                                                 MsCtl* __restrict__ ctl) {
+    const int64_t j = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    unsigned long long lo = ~0ull;
+    if (j < n) {
+        const bool open = !closed[cluster_incl[j] - 1];
+        keep[perm[j]] = open ? 1 : 0;
+        if (open) lo = ord_f64(s0[j]);
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned long long ol = __shfl_xor(lo, d);
+        lo = ol < lo ? ol : lo;
+    }
+    if ((threadIdx.x & 63) == 0 && lo != ~0ull) atomicMin(&ctl->open_key, lo);
+    if (j == 0) {
+        ctl->n_closed = closed_incl[n_clusters - 1];
+        ctl->n_comp = comp_incl[n_clusters - 1];
+    }
+}
+
+// list[r] = the r-th closed cluster
+__global__ void k_ms_list(int64_t n_clusters, const int64_t* __restrict__ closed, const int64_t* __restrict__ closed_incl,
+                          int64_t* __restrict__ list) {
+    const int64_t cl = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (cl < n_clusters && closed[cl]) list[closed_incl[cl] - 1] = cl;
+}
+
+// 72-byte HIT_MERGED_DTYPE rows as 18 dwords, lanes over dwords: the anchor hit's 15 dwords with height, integral,
+// sample_start, sample_end, width (dwords 2..6) replaced by the cluster's reductions -- a cluster of one hit keeps the
+// hit's own (hit_merge.py:266-284) -- then component_offset (i8) and component_count (i4)
+__global__ __launch_bounds__(kTB) void k_ms_rows(int64_t n_out, const int64_t* __restrict__ list,
+                                                 const int64_t* __restrict__ offset, const int64_t* __restrict__ comp_incl,
+                                                 int64_t first_component, const int64_t* __restrict__ anchor,
+                                                 const float* __restrict__ red_h, const float* __restrict__ red_int,
+                                                 const int32_t* __restrict__ red_s, const int32_t* __restrict__ red_e,
+                                                 const float* __restrict__ red_w, const uint32_t* __restrict__ rows,
+                                                 uint32_t* __restrict__ out) {
+    const int64_t d = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (d >= n_out * 18) return;
+    const int64_t r = d / 18;
+    const int w = (int)(d - r * 18);
+    const int64_t cl = list[r];
+    const int64_t count = offset[cl + 1] - offset[cl];
+    uint32_t v;
+    if (w >= 15) {
+        const int64_t first = first_component + comp_incl[cl] - count;
+        v = w == 15 ? (uint32_t)(uint64_t)first : (w == 16 ? (uint32_t)((uint64_t)first >> 32) : (uint32_t)count);
+    } else if (count == 1 || w < 2 || w > 6) {
+        v = rows[anchor[r] * 15 + w];
+    } else {
+        v = w == 2 ? __float_as_uint(red_h[r]) : w == 3 ? __float_as_uint(red_int[r]) : w == 4 ? (uint32_t)red_s[r]
+          : w == 5 ? (uint32_t)red_e[r] : __float_as_uint(red_w[r]);
+    }
+    out[d] = v;
+}
+
+// hit_index of the closed clusters' members: clusters in the order of the merged rows, members in chain order
+__global__ void k_ms_members(int64_t n, const int64_t* __restrict__ perm, const int64_t* __restrict__ cluster_incl,
+                             const int64_t* __restrict__ closed, const int64_t* __restrict__ offset,
+                             const int64_t* __restrict__ comp_incl, const int64_t* __restrict__ index,
+                             int64_t* __restrict__ hit_index) {
+    const int64_t j = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (j >= n) return;
+    const int64_t cl = cluster_incl[j] - 1;
+    if (!closed[cl]) return;
+    const int64_t a = offset[cl];
+    hit_index[comp_incl[cl] - (offset[cl + 1] - a) + (j - a)] = index[perm[j]];
+}
+
+inline double host_unord_f64(uint64_t k) {
+    const uint64_t b = (k >> 63) ? (k ^ 0x8000000000000000ull) : ~k;
+    double v;
+    memcpy(&v, &b, sizeof(v));
+    return v;
+}
+
+int plus_scan(wfa_ctx* c, const int64_t* in, int64_t* out, int64_t n) {
+    int rc;
+    size_t tb = 0;
+    WFA_HIP_CHECK(rocprim::inclusive_scan(nullptr, tb, in, out, (size_t)n, rocprim::plus<int64_t>(), c->stream));
+    if ((rc = c->ht[S_CUB].ensure(tb))) return rc;
+    tb = c->ht[S_CUB].cap;
+    WFA_HIP_CHECK(rocprim::inclusive_scan(c->ht[S_CUB].ptr, tb, in, out, (size_t)n, rocprim::plus<int64_t>(), c->stream));
+    return WFA_OK;
 }
 
 }  // namespace
@@ -1160,47 +1360,9 @@ int wfa_hit_merge_count(wfa_ctx* c, int64_t n, const int64_t* timestamp, const i
             return fail(WFA_E_INVALID, "null column");
         if ((rc = upload_cols(c, n, timestamp, position, edge_start, edge_end, dt, board, channel, timestamp, &h))) return rc;
     }
-    double *abs0, *abs1, *s0, *s1;
-    uint64_t *k_abs, *k_chan, *sg;
-    int32_t* sdt;
-    int64_t *flag, *incl;
-    if ((rc = slot(c, S_ABS0, n, &abs0)) || (rc = slot(c, S_ABS1, n, &abs1)) || (rc = slot(c, S_K0, n, &k_abs)) ||
-        (rc = slot(c, S_K4, n, &k_chan)) || (rc = slot(c, S_F0, n, &s0)) || (rc = slot(c, S_F1, n, &s1)) ||
-        (rc = slot(c, S_K1, n, &sdt)) || (rc = slot(c, S_SG, n, &sg)) || (rc = slot(c, S_FLAG, n, &flag)) ||
-        (rc = slot(c, S_ID, n, &incl)))
-        return rc;
-    LaunchTimer t(c);
-    if ((rc = hit_prep(c, n, h, nullptr, nullptr, abs0, abs1, k_abs, nullptr, nullptr, nullptr, k_chan))) return rc;
-    int64_t* perm = nullptr;
-    {
-        // per hardware channel (ascending board, channel), stable by abs_start (hit_merge.py:137-149)
-        const uint64_t* keys[2] = {k_chan, k_abs};
-        if ((rc = lexsort(c, n, keys, 2, &perm))) return rc;
-    }
-    hipLaunchKernelGGL(k_merge_gather, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, perm, abs0, abs1, h.dt, k_chan, s0, s1, sdt, sg);
-    SegMax *seg_in, *seg_run;
-    if ((rc = slot(c, S_OUT1, n, &seg_in)) || (rc = slot(c, S_OUT2, n, &seg_run))) return rc;
-    const int do_merge = merge_gap_ns > 0 ? 1 : 0;
-    const double gap_ps = merge_gap_ns * 1e3;
-    hipLaunchKernelGGL(k_merge_segin, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, s1, sg, seg_in);
-    size_t tb = 0, tb_seg = 0;
-    WFA_HIP_CHECK(rocprim::inclusive_scan(nullptr, tb_seg, seg_in, seg_run, (size_t)n, SegMaxOp(), c->stream));
-    WFA_HIP_CHECK(rocprim::inclusive_scan(nullptr, tb, flag, incl, (size_t)n, rocprim::plus<int64_t>(), c->stream));
-    if ((rc = c->ht[S_CUB].ensure(tb > tb_seg ? tb : tb_seg))) return rc;
-    tb_seg = c->ht[S_CUB].cap;
-    WFA_HIP_CHECK(rocprim::inclusive_scan(c->ht[S_CUB].ptr, tb_seg, seg_in, seg_run, (size_t)n, SegMaxOp(), c->stream));
-    hipLaunchKernelGGL(k_merge_chain, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, s0, s1, sdt, sg, seg_run, do_merge,
-                       gap_ps, max_total_width_ns * 1e3, flag);
-    tb = c->ht[S_CUB].cap;
-    WFA_HIP_CHECK(rocprim::inclusive_scan(c->ht[S_CUB].ptr, tb, flag, incl, (size_t)n, rocprim::plus<int64_t>(), c->stream));
     int64_t n_cl = 0;
-    WFA_HIP_CHECK(hipMemcpyAsync(&n_cl, incl + (n - 1), sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    int64_t* offset;
-    if ((rc = slot(c, S_OUT0, n_cl + 1, &offset))) return rc;
-    hipLaunchKernelGGL(k_cluster_offsets, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, flag, incl, n_cl, offset);
-    WFA_HIP_CHECK(hipGetLastError());
-    if ((rc = t.end("hit table: hit_merge clusters (sort + chain)"))) return rc;
+    int64_t* perm = nullptr;
+    if ((rc = merge_cols(c, n, h, merge_gap_ns, max_total_width_ns, &n_cl, &perm))) return rc;
     WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
     c->ht_n = n; c->ht_groups = n_cl; c->ht_kind = 2; c->ht_perm = perm;
     *n_clusters = n_cl;
@@ -1363,7 +1525,7 @@ int wfa_event_stream_push(wfa_ctx* c, const void* hit_rows, int64_t n_rows, doub
     const double* abs0 = c->ht[S_ABS0].as<double>();
     if (n_rows > 0) {
         const unsigned cb = blocks_for(n_rows) < 1024u ? blocks_for(n_rows) : 1024u;
-        hipLaunchKernelGGL(k_es_check, dim3(cb), dim3(kTB), 0, c->stream, n_rows, d_dt + es.n_carry, d_s + es.n_carry,
+        hipLaunchKernelGGL(k_es_check<EsCtl>, dim3(cb), dim3(kTB), 0, c->stream, n_rows, d_dt + es.n_carry, d_s + es.n_carry,
                            d_e + es.n_carry, abs0 + es.n_carry, d_ctl);
     }
     const int64_t* ev_start = c->ht[S_OUT0].as<int64_t>();
@@ -1398,7 +1560,7 @@ int wfa_event_stream_push(wfa_ctx* c, const void* hit_rows, int64_t n_rows, doub
         hipLaunchKernelGGL(k_es_keep, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, k_ev, n_closed, flag);
         size_t tb = c->ht[S_CUB].cap;  // (sized by group_cols for this very scan)
         WFA_HIP_CHECK(rocprim::inclusive_scan(c->ht[S_CUB].ptr, tb, flag, incl, (size_t)n, rocprim::plus<int64_t>(), c->stream));
-        hipLaunchKernelGGL(k_es_compact, dim3(blocks_for(n * 15)), dim3(kTB), 0, c->stream, n, flag, incl,
+        hipLaunchKernelGGL(k_es_compact<15>, dim3(blocks_for(n * 15)), dim3(kTB), 0, c->stream, n, flag, incl,
                            reinterpret_cast<const uint32_t*>(rows), other.as<uint32_t>());
     }
     WFA_HIP_CHECK(hipGetLastError());
@@ -1442,6 +1604,188 @@ int wfa_event_stream_end(wfa_ctx* c) {
     c->es_carry[1].release();
     c->es_out.release();
     c->es = wfa_ctx::EventStream{};
+    return WFA_OK;
+}
+
+// ---- merge stream -----------------------------------------------------------------------------------------------------
+int wfa_merge_stream_begin(wfa_ctx* c, double merge_gap_ns, double max_total_width_ns) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (!(merge_gap_ns >= 0)) return fail(WFA_E_INVALID, "merge_gap_ns must be >= 0");
+    if (!(max_total_width_ns >= 0)) return fail(WFA_E_INVALID, "max_total_width_ns must be >= 0");
+    if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->ms = wfa_ctx::MergeStream{};  // (a stream left open starts over: empty carry, index 0; the buffers are reused)
+    c->ms.open = true;
+    c->ms.gap_ns = merge_gap_ns;
+    c->ms.width_ns = max_total_width_ns;
+    c->ms.horizon = -HUGE_VAL;
+    return WFA_OK;
+}
+
+int wfa_merge_stream_push(wfa_ctx* c, const void* hit_rows, int64_t n_rows, double horizon_ps, int64_t* n_merged,
+                          int64_t* n_components, int64_t* n_carry, double* open_start_ps) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    wfa_ctx::MergeStream& ms = c->ms;
+    if (!ms.open) return fail(WFA_E_STATE, "no merge stream is open (wfa_merge_stream_begin first)");
+    if (n_rows < 0 || (n_rows > 0 && !hit_rows) || !n_merged || !n_components || !n_carry || !open_start_ps)
+        return fail(WFA_E_INVALID, "bad arguments");
+    if (horizon_ps != horizon_ps) return fail(WFA_E_INVALID, "the horizon is NaN");
+    if (horizon_ps < ms.horizon)
+        return fail(WFA_E_INVALID, "the horizon (%.17g ps) lies below the previous push's (%.17g ps)", horizon_ps, ms.horizon);
+    if (n_rows >= 0x80000000LL - ms.n_carry)
+        return fail(WFA_E_INVALID, "carry (%lld rows) + pushed rows (%lld) reach the table limit of 2^31 rows",
+                    (long long)ms.n_carry, (long long)n_rows);
+    const int64_t n = ms.n_carry + n_rows;
+    if (n == 0) {  // nothing carried, nothing pushed: no launch
+        ms.horizon = horizon_ps;
+        ms.out_merged = ms.out_components = 0;
+        *n_merged = *n_components = *n_carry = 0;
+        *open_start_ps = HUGE_VAL;
+        return WFA_OK;
+    }
+    c->ht_n = -1;  // the scratch slots a static count pass left for its fill are overwritten
+    DevBuf& table = c->ms_carry[ms.cur];
+    DevBuf& table_index = c->ms_index[ms.cur];
+    if ((rc = es_grow(c, table, (size_t)ms.n_carry * 60, (size_t)n * 60)) ||
+        (rc = es_grow(c, table_index, (size_t)ms.n_carry * 8, (size_t)n * 8)))
+        return rc;
+    uint8_t* rows = table.as<uint8_t>();
+    int64_t* index = table_index.as<int64_t>();
+    // 1. the pushed rows and their indices behind the carry (a refused push leaves them there: they lie behind n_carry and
+    //    are overwritten)
+    if (n_rows > 0) {
+        if ((rc = h2d_copy(c, rows + (size_t)ms.n_carry * 60, hit_rows, (size_t)n_rows * 60))) return rc;
+        hipLaunchKernelGGL(k_ms_number, dim3(blocks_for(n_rows)), dim3(kTB), 0, c->stream, n_rows, ms.next_hit,
+                           index + ms.n_carry);
+    }
+    int64_t *d_ts, *d_pos, *d_rid;
+    int32_t *d_s, *d_e, *d_dt;
+    int16_t *d_b, *d_c;
+    if ((rc = slot(c, S_TS, n, &d_ts)) || (rc = slot(c, S_POS, n, &d_pos)) || (rc = slot(c, S_START, n, &d_s)) ||
+        (rc = slot(c, S_END, n, &d_e)) || (rc = slot(c, S_DT, n, &d_dt)) || (rc = slot(c, S_BOARD, n, &d_b)) ||
+        (rc = slot(c, S_CHAN, n, &d_c)) || (rc = slot(c, S_RID, n, &d_rid)))
+        return rc;
+    hipLaunchKernelGGL(k_unpack_hit_rows, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, rows, d_ts, d_pos, d_s, d_e, d_dt,
+                       d_b, d_c, d_rid);
+    // 2. the sort and chain of the static entry over the whole table
+    const HitCols h{d_ts, d_pos, d_s, d_e, d_dt, d_b, d_c, d_rid};
+    int64_t n_cl = 0;
+    int64_t* perm = nullptr;
+    if ((rc = merge_cols(c, n, h, ms.gap_ns, ms.width_ns, &n_cl, &perm))) return rc;
+    if (n_cl < 1 || n_cl > n) return fail(WFA_E_HIP, "merge stream: the chain reported %lld clusters of %lld hits", (long long)n_cl, (long long)n);
+    // 3. the checks of the pushed rows, the closed clusters, the rows that stay; one read of the control block
+    int64_t *closed, *closed_incl, *count, *comp_incl, *list, *keep, *keep_incl;
+    MsCtl* d_ctl;
+    if ((rc = slot(c, S_MS0, n_cl, &closed)) || (rc = slot(c, S_MS1, n_cl, &closed_incl)) || (rc = slot(c, S_MS2, n_cl, &count)) ||
+        (rc = slot(c, S_MS3, n_cl, &comp_incl)) || (rc = slot(c, S_MS4, n_cl, &list)) || (rc = slot(c, S_K2, n, &keep)) ||
+        (rc = slot(c, S_K3, n, &keep_incl)) || (rc = slot(c, S_MS5, 1, &d_ctl)))
+        return rc;
+    LaunchTimer t(c);
+    MsCtl ctl{~0ull, ~0ull, 0, 0, 0, 0};
+    WFA_HIP_CHECK(hipMemcpyAsync(d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
+    if (n_rows > 0) {
+        const unsigned cb = blocks_for(n_rows) < 1024u ? blocks_for(n_rows) : 1024u;
+        hipLaunchKernelGGL(k_es_check<MsCtl>, dim3(cb), dim3(kTB), 0, c->stream, n_rows, d_dt + ms.n_carry, d_s + ms.n_carry,
+                           d_e + ms.n_carry, c->ht[S_ABS0].as<double>() + ms.n_carry, d_ctl);
+    }
+    const int64_t* offset = c->ht[S_OUT0].as<int64_t>();
+    const int64_t* cluster_incl = c->ht[S_ID].as<int64_t>();
+    const double* s0 = c->ht[S_F0].as<double>();
+    hipLaunchKernelGGL(k_ms_closed, dim3(blocks_for(n_cl)), dim3(kTB), 0, c->stream, n_cl, n, offset, s0, c->ht[S_F1].as<double>(),
+                       c->ht[S_SG].as<uint64_t>(), ms.gap_ns > 0 ? 1 : 0, ms.gap_ns * 1e3, horizon_ps, closed, count);
+    if ((rc = plus_scan(c, closed, closed_incl, n_cl)) || (rc = plus_scan(c, count, comp_incl, n_cl))) return rc;
+    hipLaunchKernelGGL(k_ms_keep, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, n_cl, perm, cluster_incl, closed, closed_incl,
+                       comp_incl, s0, keep, d_ctl);
+    WFA_HIP_CHECK(hipGetLastError());
+    WFA_HIP_CHECK(hipMemcpyAsync(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (ctl.flags & kEsBadDt) return fail(WFA_E_INVALID, "hit dt must be positive for every row");
+    if (ctl.flags & kEsBadEdge) return fail(WFA_E_INVALID, "a pushed row has a negative edge_start / edge_end");
+    if (n_rows > 0 && ctl.min_key < host_ord_f64(ms.horizon))
+        return fail(WFA_E_INVALID, "a pushed row starts below the previous push's horizon (%.17g ps)", ms.horizon);
+    const int64_t n_closed = (int64_t)ctl.n_closed, n_comp = (int64_t)ctl.n_comp, n_keep = n - n_comp;
+    if (n_closed < 0 || n_closed > n_cl || n_comp < n_closed || n_comp > n || (n_keep > 0) != (ctl.open_key != ~0ull))
+        return fail(WFA_E_HIP, "merge stream: inconsistent counts");
+    // 4. the merged rows and member indices of the closed clusters
+    if (n_closed > 0) {
+        float *height, *integral, *red_h, *red_int, *red_w;
+        int32_t *red_s, *red_e;
+        int64_t* anchor;
+        if ((rc = slot(c, S_HEIGHT, n, &height)) || (rc = slot(c, S_INTEGRAL, n, &integral)) || (rc = slot(c, S_OUT3, n_closed, &anchor)) ||
+            (rc = slot(c, S_OUT4, n_closed, &red_h)) || (rc = slot(c, S_OUT5, n_closed, &red_int)) || (rc = slot(c, S_OUT6, n_closed, &red_s)) ||
+            (rc = slot(c, S_OUT7, n_closed, &red_e)) || (rc = slot(c, S_MS6, n_closed, &red_w)) ||
+            (rc = c->ms_out.ensure((size_t)n_closed * 72)) || (rc = c->ms_out_index.ensure((size_t)n_comp * 8)))
+            return rc;
+        const uint32_t* words = reinterpret_cast<const uint32_t*>(rows);
+        hipLaunchKernelGGL(k_ms_cols, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, words, height, integral);
+        hipLaunchKernelGGL(k_ms_list, dim3(blocks_for(n_cl)), dim3(kTB), 0, c->stream, n_cl, closed, closed_incl, list);
+        hipLaunchKernelGGL(k_merge_emit, dim3(blocks_for(n_closed)), dim3(kTB), 0, c->stream, n_closed, offset, perm, h, height,
+                           integral, anchor, red_h, red_int, red_s, red_e, red_w, list);
+        hipLaunchKernelGGL(k_ms_rows, dim3(blocks_for(n_closed * 18)), dim3(kTB), 0, c->stream, n_closed, list, offset, comp_incl,
+                           ms.next_component, anchor, red_h, red_int, red_s, red_e, red_w, words, c->ms_out.as<uint32_t>());
+        hipLaunchKernelGGL(k_ms_members, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, perm, cluster_incl, closed, offset,
+                           comp_incl, index, c->ms_out_index.as<int64_t>());
+    }
+    // 5. the hits of the open clusters and their indices, in row order, into the other buffers (all open: the table is
+    //    the carry)
+    if (n_keep > 0 && n_closed > 0) {
+        DevBuf& other = c->ms_carry[ms.cur ^ 1];
+        DevBuf& other_index = c->ms_index[ms.cur ^ 1];
+        if ((rc = other.ensure((size_t)n_keep * 60)) || (rc = other_index.ensure((size_t)n_keep * 8))) return rc;
+        if ((rc = plus_scan(c, keep, keep_incl, n))) return rc;
+        hipLaunchKernelGGL(k_es_compact<15>, dim3(blocks_for(n * 15)), dim3(kTB), 0, c->stream, n, keep, keep_incl,
+                           reinterpret_cast<const uint32_t*>(rows), other.as<uint32_t>());
+        hipLaunchKernelGGL(k_es_compact<2>, dim3(blocks_for(n * 2)), dim3(kTB), 0, c->stream, n, keep, keep_incl,
+                           reinterpret_cast<const uint32_t*>(index), other_index.as<uint32_t>());
+    }
+    WFA_HIP_CHECK(hipGetLastError());
+    if ((rc = t.end("merge stream: closed clusters, rows, carry"))) return rc;
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (n_keep > 0 && n_closed > 0) ms.cur ^= 1;
+    ms.n_carry = n_keep;
+    ms.next_hit += n_rows;
+    ms.next_component += n_comp;
+    ms.horizon = horizon_ps;
+    ms.out_merged = n_closed;
+    ms.out_components = n_comp;
+    *n_merged = n_closed;
+    *n_components = n_comp;
+    *n_carry = n_keep;
+    *open_start_ps = n_keep > 0 ? host_unord_f64(ctl.open_key) : HUGE_VAL;
+    return WFA_OK;
+}
+
+int wfa_merge_stream_fill(wfa_ctx* c, void* merged_rows, int64_t* hit_index, int64_t n_merged, int64_t n_components) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (!c->ms.open || c->ms.out_merged < 0) return fail(WFA_E_STATE, "no merge stream push has been made");
+    if (n_merged != c->ms.out_merged || n_components != c->ms.out_components)
+        return fail(WFA_E_INVALID, "caller expects %lld rows / %lld components, the last push closed %lld / %lld",
+                    (long long)n_merged, (long long)n_components, (long long)c->ms.out_merged, (long long)c->ms.out_components);
+    if (n_merged == 0) return WFA_OK;
+    if (!merged_rows || !hit_index) return fail(WFA_E_INVALID, "null output");
+    const size_t bytes = (size_t)n_merged * 72, index_bytes = (size_t)n_components * 8;
+    if (bytes >= (4u << 20)) {  // large: through the pinned staging ring
+        if ((rc = d2h_staged(c, merged_rows, c->ms_out.ptr, bytes, nullptr, nullptr))) return rc;
+    } else {
+        WFA_HIP_CHECK(hipMemcpyAsync(merged_rows, c->ms_out.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (index_bytes >= (4u << 20)) {
+        if ((rc = d2h_staged(c, hit_index, c->ms_out_index.ptr, index_bytes, nullptr, nullptr))) return rc;
+    } else {
+        WFA_HIP_CHECK(hipMemcpyAsync(hit_index, c->ms_out_index.ptr, index_bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return WFA_OK;
+}
+
+int wfa_merge_stream_end(wfa_ctx* c) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    for (DevBuf* b : {&c->ms_carry[0], &c->ms_carry[1], &c->ms_index[0], &c->ms_index[1], &c->ms_out, &c->ms_out_index}) b->release();
+    c->ms = wfa_ctx::MergeStream{};
     return WFA_OK;
 }
 

@@ -20,6 +20,7 @@ from .dtypes import (
     BASIC_FEATURES_DTYPE,
     EVENT_HIT_DTYPE,
     HIT_DTYPE,
+    HIT_MERGED_DTYPE,
     S1_S2_CLASSIFIER_DTYPE,
     WAVEFORM_WIDTH_DTYPE,
     THRESHOLD_HIT_DTYPE,
@@ -969,6 +970,33 @@ class DeviceSession:
     def event_stream_end(self) -> None:
         """Free the carry and close the stream (wfa_event_stream_end)."""
         _lib.check(self._lib.wfa_event_stream_end(self._h))
+
+    # ---- merge stream: the per-channel hit merge chunk by chunk, the open clusters' hits resident between pushes --------
+    def merge_stream_begin(self, merge_gap_ns: float, max_total_width_ns: float) -> None:
+        """Open the session's merge stream (wfa_merge_stream_begin): empty carry, hit and component index 0."""
+        _lib.check(self._lib.wfa_merge_stream_begin(self._h, float(merge_gap_ns), float(max_total_width_ns)))
+
+    def merge_stream_push(self, rows: np.ndarray | None, horizon: float) -> tuple[np.ndarray, np.ndarray, int, float]:
+        """Push THRESHOLD_HIT_DTYPE rows (None / empty: a pure flush) with the horizon (ps, float64) below which no
+        later hit starts -> (HIT_MERGED_DTYPE rows of the clusters this push closed, int64 hit_index of their members,
+        rows carried on the device, smallest abs_start among the carried rows or +inf)."""
+        n = 0 if rows is None else len(rows)
+        src = None
+        if n:
+            if rows.dtype != THRESHOLD_HIT_DTYPE:
+                raise ValueError("merge_stream_push takes THRESHOLD_HIT_DTYPE rows")
+            src = np.ascontiguousarray(rows)
+        n_merged, n_comp, n_carry, open_start = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_double(0.0)
+        _lib.check(self._lib.wfa_merge_stream_push(self._h, _ptr(src), n, float(horizon), C.byref(n_merged), C.byref(n_comp),
+                                                   C.byref(n_carry), C.byref(open_start)))
+        merged = np.empty(int(n_merged.value), dtype=HIT_MERGED_DTYPE)
+        hit_index = np.empty(int(n_comp.value), dtype=np.int64)
+        _lib.check(self._lib.wfa_merge_stream_fill(self._h, _ptr(merged), _ptr(hit_index), len(merged), len(hit_index)))
+        return merged, hit_index, int(n_carry.value), float(open_start.value)
+
+    def merge_stream_end(self) -> None:
+        """Free the carry and close the stream (wfa_merge_stream_end)."""
+        _lib.check(self._lib.wfa_merge_stream_end(self._h))
 
     def hit_merge_clusters_resident(self, n: int, merge_gap_ns: float, max_total_width_ns: float):
         """hit_merge_clusters on the n resident rows: (order, cluster_offset)."""

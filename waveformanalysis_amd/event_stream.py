@@ -133,50 +133,37 @@ def events_frame(rows: np.ndarray):
     return pd.DataFrame(out, columns=EVENT_COLUMNS)
 
 
-class HipHitGroupedStream(_RecordsChunking, HipStreamingPlugin):
-    """compute() = the events of the records stream, delivered as they close.
+class HitPushStream(_RecordsChunking, HipStreamingPlugin):
+    """What the streams that push the hit stream's rows to one more session share (hit_grouped_stream here,
+    hit_merged_stream in merge_stream.py): option resolution, the inner hit stream, the refusals and the push loop.
 
     The records are chunked like hit_threshold_stream; an inner HipThresholdHitStream (same options, same ring of two
-    sessions per device, same overlap of upload and kernels) finds every chunk's hits.  Each chunk's rows go, in order,
-    to ONE more session borrowed for the whole run, with the chunk's horizon (`chunk_horizons`); after the last chunk one
-    push with +inf.  A result chunk holds the EVENT_HIT_DTYPE rows of the events one push closed, with bounds
-    [min t_min, max t_max + 1); a push that closes nothing yields nothing.  `events_frame(all rows)` is the DataFrame of
-    HipHitGroupedPlugin on HipThresholdHitPlugin's rows under the same configuration.
+    sessions per device, same overlap of upload and kernels) finds every chunk's hits.  Each chunk's rows, empty ones
+    included, go in order to ONE more session borrowed for the whole run, with the chunk's horizon (`chunk_horizons`);
+    after the last chunk one push with +inf.  A subclass opens and closes the device stream (`_begin` / `_end`), turns one
+    push into a result chunk or None (`_push`) and names its counters (`_new_stats`).
 
-    Stateful (the carry lives on the device between chunks) and not reset at a time break: an event may span one.
-    Options: those of hit_threshold_stream, and `time_window_ns` / `dt` with hit_grouped's names and defaults; a value
-    given to the constructor wins over the Context.  The stream's rows always carry dt (the records'), so `dt` is read
-    for parity only, as the static plugin ignores it when its hits have the column.
+    Stateful (the carry lives on the device between chunks) and not reset at a time break: what is open may span one.
+    A value given to the constructor wins over the Context, the Context over the option's default.
 
     The rows travel device -> host -> device once more than necessary: the ring's sessions download a chunk's 60-byte
-    rows (the hit stream's product), and the push uploads them to the grouping session.
+    rows (the hit stream's product), and the push uploads them to the borrowed session."""
 
-    Refused on the host, before any upload: a Context whose configuration sets merge_gap_ns > 0 for hit_merged (the
-    static plugin would then group merged hits, which the stream does not build), and a device pool with fewer than three
-    sessions (two for the ring, one for the grouping)."""
-
-    provides = "hit_grouped_stream"
     depends_on = ["records", "wave_pool"]
-    description = "Coincidence events of the records stream, delivered as they close (HIP, gfx950)."
     version = "0.1.0+hip1"
-    output_dtype = EVENT_HIT_DTYPE
     save_when = "never"
     chunk_size = 50_000
     length_field = "event_length"
-    output_data_kind = "events"
-    output_time_field = "t_min"
-    output_endtime_field = "t_max"
     is_stateful = True
     reset_on_break = False
-    profile_pushes = False   # measurement: kernel timers on the grouping session, their report in stats["profile"]
-
-    options = {**HipThresholdHitStream.options, **HipHitGroupedPlugin.options}
+    profile_pushes = False   # measurement: kernel timers on the borrowed session, their report in stats["profile"]
+    role = "push"            # what the third session does, for the pool refusal
 
     def __init__(self, device_pool: DevicePool | None = None, max_len: int = 0, **given):
         super().__init__()
         unknown = sorted(set(given) - set(self.options))
         if unknown:
-            raise TypeError(f"hit_grouped_stream: unknown options {unknown}")
+            raise TypeError(f"{self.provides}: unknown options {unknown}")
         self._given = {k: v for k, v in given.items() if v is not _UNSET}
         self.device_pool = device_pool
         self.max_len = int(max_len)
@@ -195,11 +182,12 @@ class HipHitGroupedStream(_RecordsChunking, HipStreamingPlugin):
             return self.options[name].default
 
         cfg = {name: value(name) for name in self.options}
-        cfg["time_window_ns"] = float(cfg["time_window_ns"])
-        if cfg["time_window_ns"] < 0:
-            raise ValueError("time_window_ns must be >= 0")
+        self._check_cfg(cfg)
         self.cfg = cfg
         return cfg
+
+    def _check_cfg(self, cfg: dict) -> None:
+        """Convert and refuse the subclass's own options, in place."""
 
     def _inner(self, cfg: dict, pool: DevicePool) -> HipThresholdHitStream:
         """The hit stream with this stream's resolved options as its constructor values (so they win in its own
@@ -211,23 +199,16 @@ class HipHitGroupedStream(_RecordsChunking, HipStreamingPlugin):
         inner.chunk_size, inner.break_threshold_ps = self.chunk_size, self.break_threshold_ps
         return inner
 
-    @staticmethod
-    def _check_scope(context: Any) -> None:
-        if not isinstance(getattr(context, "config", None), dict):
-            return
-        gap = K.raw_config(context, SimpleNamespace(provides="hit_merged"), "merge_gap_ns")
-        if gap is not None and float(gap) > 0:
-            raise ValueError(f"hit_grouped_stream: the configuration sets merge_gap_ns = {gap!r} for hit_merged; the static "
-                             "hit_grouped would group merged hits, the stream groups threshold hits only")
+    def _check_scope(self, context: Any) -> None:
+        """Refuse a Context the stream does not cover (before any upload)."""
 
-    @staticmethod
-    def _check_pool(pool: DevicePool) -> None:
+    def _check_pool(self, pool: DevicePool) -> None:
         if int(pool.max_sessions) < 3:
-            raise ValueError(f"hit_grouped_stream needs a device pool with max_sessions >= 3 (two sessions for the hit "
-                             f"ring, one for the grouping), got {pool.max_sessions}")
+            raise ValueError(f"{self.provides} needs a device pool with max_sessions >= 3 (two sessions for the hit "
+                             f"ring, one for the {self.role}), got {pool.max_sessions}")
 
     def compute_chunk(self, chunk: Chunk, context: Any, run_id: str, **_kw):
-        raise NotImplementedError("hit_grouped_stream is stateful across chunks: drive it through compute() / run_chunks()")
+        raise NotImplementedError(f"{self.provides} is stateful across chunks: drive it through compute() / run_chunks()")
 
     def compute(self, context: Any, run_id: str, **kwargs):
         self._apply_streaming_config(kwargs.pop("streaming_config", None))
@@ -235,10 +216,9 @@ class HipHitGroupedStream(_RecordsChunking, HipStreamingPlugin):
         if not isinstance(records, np.ndarray) or records.dtype.names is None:
             raise TypeError(f"{self.provides} chunks the structured `records` array")
         # (refusals first: the chunk list is only cut once the run is known to start)
-        cfg = self._configure(context)
+        self._configure(context)
         self._check_scope(context)
         self._check_pool(self._pool(context))
-        del cfg
         workers = (kwargs.get("executor_config") or {}).get("max_workers") or self.max_workers
         yield from self.run_chunks(list(self._data_to_chunks(records, run_id)), context, run_id, max_workers=workers)
 
@@ -254,20 +234,20 @@ class HipHitGroupedStream(_RecordsChunking, HipStreamingPlugin):
         self._check_pool(pool)
         inner = self._inner(cfg, pool)
         horizons = chunk_horizons(chunks)
-        stats = self.stats = {"pushes": 0, "rows_in": 0, "rows_out": 0, "events": 0, "max_carry": 0}
+        stats = self.stats = self._new_stats()
         serial = not self.parallel or (max_workers is not None and int(max_workers) <= 1)
         if serial:
             inner._configure(context)
             width, plan = inner._run_width(context, run_id, chunks), inner._run_plan(context, run_id, chunks)
             hits = ((c, inner._compute_one(c, context, run_id, width, plan)) for c in chunks)
         else:
-            # the grouping session is borrowed first and for the whole run: the ring may take what is left, no more
+            # the push session is borrowed first and for the whole run: the ring may take what is left, no more
             ring = int(pool.max_sessions) - 1
             hits = inner._pipeline(chunks, context, run_id, max_workers=min(ring, int(max_workers)) if max_workers else ring)
         with pool.borrow() as sess:
             if self.profile_pushes:
                 sess.profile(True)
-            sess.event_stream_begin(cfg["time_window_ns"])
+            self._begin(sess, cfg)
             try:
                 k = -1
                 for k, (_chunk, raw) in enumerate(hits):
@@ -277,7 +257,7 @@ class HipHitGroupedStream(_RecordsChunking, HipStreamingPlugin):
                             first_event_time.append(time.perf_counter())
                         yield out
                 if k + 1 != len(chunks):
-                    raise RuntimeError(f"hit_grouped_stream: {k + 1} results for {len(chunks)} chunks")
+                    raise RuntimeError(f"{self.provides}: {k + 1} results for {len(chunks)} chunks")
                 out = self._push(sess, None, math.inf, run_id, stats)
                 if out is not None:
                     if first_event_time is not None and not first_event_time:
@@ -289,7 +269,55 @@ class HipHitGroupedStream(_RecordsChunking, HipStreamingPlugin):
                 if self.profile_pushes:
                     stats["profile"] = sess.profile_report()
                     sess.profile(False)
-                sess.event_stream_end()
+                self._end(sess)
+
+
+class HipHitGroupedStream(HitPushStream):
+    """compute() = the events of the records stream, delivered as they close (HitPushStream with wfa_event_stream_*).
+
+    A result chunk holds the EVENT_HIT_DTYPE rows of the events one push closed, with bounds
+    [min t_min, max t_max + 1); a push that closes nothing yields nothing.  `events_frame(all rows)` is the DataFrame of
+    HipHitGroupedPlugin on HipThresholdHitPlugin's rows under the same configuration.
+
+    Options: those of hit_threshold_stream, and `time_window_ns` / `dt` with hit_grouped's names and defaults.  The
+    stream's rows always carry dt (the records'), so `dt` is read for parity only, as the static plugin ignores it when
+    its hits have the column.
+
+    Refused on the host, before any upload: a Context whose configuration sets merge_gap_ns > 0 for hit_merged (the
+    static plugin would then group merged hits, which the stream does not build), and a device pool with fewer than three
+    sessions (two for the ring, one for the grouping)."""
+
+    provides = "hit_grouped_stream"
+    description = "Coincidence events of the records stream, delivered as they close (HIP, gfx950)."
+    output_dtype = EVENT_HIT_DTYPE
+    output_data_kind = "events"
+    output_time_field = "t_min"
+    output_endtime_field = "t_max"
+    role = "grouping"
+
+    options = {**HipThresholdHitStream.options, **HipHitGroupedPlugin.options}
+
+    def _check_cfg(self, cfg: dict) -> None:
+        cfg["time_window_ns"] = float(cfg["time_window_ns"])
+        if cfg["time_window_ns"] < 0:
+            raise ValueError("time_window_ns must be >= 0")
+
+    def _check_scope(self, context: Any) -> None:
+        if not isinstance(getattr(context, "config", None), dict):
+            return
+        gap = K.raw_config(context, SimpleNamespace(provides="hit_merged"), "merge_gap_ns")
+        if gap is not None and float(gap) > 0:
+            raise ValueError(f"hit_grouped_stream: the configuration sets merge_gap_ns = {gap!r} for hit_merged; the static "
+                             "hit_grouped would group merged hits, the stream groups threshold hits only")
+
+    def _new_stats(self) -> dict:
+        return {"pushes": 0, "rows_in": 0, "rows_out": 0, "events": 0, "max_carry": 0}
+
+    def _begin(self, sess, cfg: dict) -> None:
+        sess.event_stream_begin(cfg["time_window_ns"])
+
+    def _end(self, sess) -> None:
+        sess.event_stream_end()
 
     def _push(self, sess, rows, horizon: float, run_id: str, stats: dict):
         out, n_carry = sess.event_stream_push(rows, horizon)
@@ -307,5 +335,5 @@ class HipHitGroupedStream(_RecordsChunking, HipStreamingPlugin):
         return result
 
 
-__all__ = ["HipHitGroupedStream", "events_frame", "event_rows", "chunk_horizons", "horizon_of", "horizon_margin",
+__all__ = ["HipHitGroupedStream", "HitPushStream", "events_frame", "event_rows", "chunk_horizons", "horizon_of", "horizon_margin",
            "run_magnitude", "abs_windows", "EVENT_HIT_DTYPE"]

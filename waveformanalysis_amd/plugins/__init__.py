@@ -69,7 +69,15 @@ def hip_streaming_events():
     return hip_streaming() + [HipHitGroupedStream()]
 
 
-__all__ = ["hip_streaming", "hip_streaming_events", "HipWavePoolFilteredPlugin", "HipThresholdHitPlugin", "HipBasicFeaturesPlugin",
+def hip_streaming_merged():
+    """hip_streaming_events() plus hit_merged_stream: the per-channel merged hits of the records stream, delivered as
+    their clusters close."""
+    from ..merge_stream import HipHitMergedStream
+
+    return hip_streaming_events() + [HipHitMergedStream()]
+
+
+__all__ = ["hip_streaming", "hip_streaming_events", "hip_streaming_merged", "HipWavePoolFilteredPlugin", "HipThresholdHitPlugin", "HipBasicFeaturesPlugin",
            "HipWaveformWidthIntegralPlugin", "HipHitGroupedPlugin", "HipHitFinderPlugin", "HipFilteredWaveformsPlugin",
            "HipWaveformWidthPlugin", "HipS1S2ClassifierPlugin", "HipHitMergeClustersPlugin",
            "HipHitMergePlugin", "HipHitMergedComponentsPlugin", "HipSignalPeaksStreamPlugin", "HipRecordsPlugin", "HipWavePoolPlugin",
