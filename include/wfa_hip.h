@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define WFA_ABI_VERSION 8
+#define WFA_ABI_VERSION 9
 
 #define WFA_OK 0
 #define WFA_E_INVALID (-1)   /* bad argument / malformed records (maps to ValueError) */
@@ -493,6 +493,47 @@ int wfa_merge_stream_push(wfa_ctx* ctx, const void* hit_rows, int64_t n_rows, do
                           int64_t* n_components, int64_t* n_carry, double* open_start_ps);
 int wfa_merge_stream_fill(wfa_ctx* ctx, void* merged_rows, int64_t* hit_index, int64_t n_merged, int64_t n_components);
 int wfa_merge_stream_end(wfa_ctx* ctx);
+
+/* Merged-event stream: K9 over the rows of K11, chunk by chunk; the merged rows never visit the host.  One push
+ * (THRESHOLD_HIT_DTYPE rows, H) does two steps on a state of its own (neither the event stream's nor the merge stream's;
+ * all three may be open on one context):
+ *  1. the merge step: the rule of wfa_merge_stream_push -- clusters close, the hits of the open ones stay in row order,
+ *     open_start = the smallest computed abs_start still carried;
+ *  2. the group step: the merged rows of the clusters just closed go behind the event carry, in the merge step's delivery
+ *     order ((board, channel), then chain order), and the grouping pass of wfa_group_hit_windows_count runs over carry ++
+ *     new rows.  A merged row with sample_start >= 0 and sample_end >= 0 takes the anchor formula; any other (its cluster
+ *     spans records) takes min abs_start / max abs_end of its member hits, computed when the cluster closes and carried
+ *     with the row (the abs_start_fix / abs_end_fix of the static pass).  An event closes iff
+ *     max(abs_end) + time_window_ns * 1e3 < G, strictly, under the grouping horizon
+ *         G = max(G of the previous push, min(H, open_start'))
+ *     with open_start' = open_start where horizon_margin_ps == 0 and nextafter(open_start - 1.5 * horizon_margin_ps, -inf)
+ *     otherwise: every merged row still to come starts at a carried hit or at a hit not yet pushed.  horizon_margin_ps is
+ *     the run's margin as event_stream.horizon_margin gives it (2 ulp of the run's magnitude beyond 2^53 ps, else 0); the
+ *     bound is 3 ulp because a computed member window and a computed anchor window each lie within 1.5 ulp of the exact
+ *     start.  Below 2^53 ps min(H, open_start) never falls and the outer max changes nothing.
+ *     Precondition: the hits of one record share timestamp - position * dt * 1e3 (threshold hits do), so that the anchor
+ *     window of a one-record cluster starts where its first member does.  A violation is refused, never a wrong table.
+ * All pushes together give the static K9 on the static K11 rows of the whole table (components included), in any chunking.
+ * _push reports: rows and events the group step closed; clusters and members the merge step closed; hits carried by the
+ * merge step and merged rows carried by the group step; G.  _fill delivers
+ *   out_rows:  96 B packed (EVENT_MERGED_HIT_DTYPE): event_id i8 @0, t_min i8 @8, t_max i8 @16, then the 72 bytes of the
+ *              HIT_MERGED_DTYPE row @24, component_offset counting through the stream's own component sequence;
+ *   hit_index: one int64 per member of the clusters the MERGE step closed in this push (not: of the rows delivered), in
+ *              the merge stream's order; concatenated over all pushes it is the sequence component_offset addresses.
+ * Refused with WFA_E_INVALID, both carries and all counters left as they were: a negative or NaN gap, width or window, a
+ * negative, NaN or infinite margin (_begin); a pushed row with dt <= 0 or a negative edge_start / edge_end (merged rows
+ * with -1, -1 are legitimate inside); a pushed row below the previous push's H; a merged row below the previous push's G;
+ * an H below the previous one, or NaN; either table reaching 2^31 rows.  _push without _begin, _fill before a push or
+ * after a refused one: WFA_E_STATE; _fill with other counts: WFA_E_INVALID.  _begin on an open stream starts over.
+ * State, not scratch: 68 B per carried hit and 88 B per carried merged row in each of two buffers, 96 B per row and 8 B
+ * per member of the largest push; wfa_release_scratch keeps them, _end frees them. */
+int wfa_merged_event_stream_begin(wfa_ctx* ctx, double merge_gap_ns, double max_total_width_ns, double time_window_ns,
+                                  double horizon_margin_ps);
+int wfa_merged_event_stream_push(wfa_ctx* ctx, const void* hit_rows, int64_t n_rows, double horizon_ps, int64_t* n_out_rows,
+                                 int64_t* n_out_events, int64_t* n_clusters, int64_t* n_components, int64_t* n_merge_carry,
+                                 int64_t* n_event_carry, double* group_horizon_ps);
+int wfa_merged_event_stream_fill(wfa_ctx* ctx, void* out_rows, int64_t* hit_index, int64_t n_out_rows, int64_t n_components);
+int wfa_merged_event_stream_end(wfa_ctx* ctx);
 
 /* Legacy fixed-window grouping: group_multi_channel_hits (processing/event_grouping.py:98-283) with the boundary search of
  * _find_cluster_boundaries_numba (475-525).  The hits are ordered by timestamp (stable; pandas' default sort leaves the

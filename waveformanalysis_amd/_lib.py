@@ -27,7 +27,7 @@ VIEW_WAVES, VIEW_WAVES_BASELINE, VIEW_SIGNALS = 0, 1, 2
 VIEW_U16, VIEW_F32, VIEW_F64 = 0, 1, 2
 DENSE_I16, DENSE_U16, DENSE_F32 = 0, 1, 2
 S1S2_UNKNOWN, S1S2_PREFER_S1, S1S2_PREFER_S2 = 0, 1, 2
-ABI_VERSION = 8
+ABI_VERSION = 9
 MAX_HIT_GROUPS = 8
 
 _p = C.c_void_p
@@ -96,6 +96,10 @@ SIGNATURES = {
     "wfa_merge_stream_push": (_int, [_p, _p, _i64, _f64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_f64)]),
     "wfa_merge_stream_fill": (_int, [_p, _p, _p, _i64, _i64]),
     "wfa_merge_stream_end": (_int, [_p]),
+    "wfa_merged_event_stream_begin": (_int, [_p, _f64, _f64, _f64, _f64]),
+    "wfa_merged_event_stream_push": (_int, [_p, _p, _i64, _f64] + [C.POINTER(_i64)] * 6 + [C.POINTER(_f64)]),
+    "wfa_merged_event_stream_fill": (_int, [_p, _p, _p, _i64, _i64]),
+    "wfa_merged_event_stream_end": (_int, [_p]),
     "wfa_group_multi_channel_count": (_int, [_p, _i64, _p, _p, _f64, C.POINTER(_i64)]),
     "wfa_group_multi_channel_fill": (_int, [_p, _i64, _i64, _p, _p]),
     "wfa_v1725_index": (_int, [_p, _i64, _i64, _p, _p, _p, _p, _p, _p, C.POINTER(_i64)]),

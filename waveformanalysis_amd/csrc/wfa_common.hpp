@@ -284,6 +284,18 @@ struct wfa_ctx {
         int64_t out_merged = -1, out_components = 0;  // of the last push, waiting in ms_out / ms_out_index; -1: no push yet
     } ms;
     wfa::DevBuf ms_carry[2], ms_index[2], ms_out, ms_out_index;
+    // merged-event stream (wfa_merged_event_stream_*, wfa_hits.hip): a merge step and a group step per push, each with the
+    // state of the stream it is the body of -- `m` and the mes_m* buffers like ms / ms_*, `e` and mes_carry like es /
+    // es_carry, but with 88-byte entries (a 72-byte merged row, then its abs_start_fix / abs_end_fix) -- and the 96-byte
+    // rows and the member indices of the last push.  e.horizon is the grouping horizon G of the last push.  State of its
+    // own: a context may hold it open beside es and ms; wfa_release_scratch keeps it, wfa_merged_event_stream_end frees it
+    struct MergedEventStream {
+        bool open = false;
+        double margin_ps = 0.0;   // the run's horizon margin (2 ulp of its magnitude; 0 below 2^53 ps)
+        MergeStream m;
+        EventStream e;
+    } mes;
+    wfa::DevBuf mes_mcarry[2], mes_mindex[2], mes_mindex_out, mes_carry[2], mes_out;
     wfa::DevBuf bw_scratch{scratch};  // float64 forward pass of sosfiltfilt, [sample][record-in-batch]
 
     // profiling: HIP events around every launch on the context's stream.  The pairs are only recorded while the

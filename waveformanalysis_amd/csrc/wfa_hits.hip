@@ -240,14 +240,16 @@ int upload_cols(wfa_ctx* c, int64_t n, const int64_t* ts, const int64_t* pos, co
 
 // Columns out of device-resident THRESHOLD_HIT_DTYPE rows (60 B packed: position i8 @0, edge_start i4 @16, edge_end i4
 // @20, dt i4 @28, timestamp i8 @40, board i2 @48, channel i2 @50, record_id i8 @52; cpu/hit_finder.py:33-49): the rows
-// of the last hit pass or of the last RCCL gather feed the hit-table stages without a host round trip.
-__global__ void k_unpack_hit_rows(int64_t n, const uint8_t* __restrict__ rows, int64_t* __restrict__ ts,
+// of the last hit pass or of the last RCCL gather feed the hit-table stages without a host round trip.  `stride` = bytes
+// from row to row (a multiple of 4): 60 for packed hit rows; the first 60 bytes of a HIT_MERGED_DTYPE row have the same
+// layout (sample_start / sample_end where the edges stand), so the merged-event stream reads its 88-byte carry entries here.
+__global__ void k_unpack_hit_rows(int64_t n, const uint8_t* __restrict__ rows, int64_t stride, int64_t* __restrict__ ts,
                                   int64_t* __restrict__ pos, int32_t* __restrict__ s, int32_t* __restrict__ e,
                                   int32_t* __restrict__ dt, int16_t* __restrict__ board, int16_t* __restrict__ chan,
                                   int64_t* __restrict__ rid) {
     const int64_t i = (int64_t)blockIdx.x * kTB + threadIdx.x;
     if (i >= n) return;
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(rows + i * 60);
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(rows + i * stride);
     pos[i] = (int64_t)(((uint64_t)w[1] << 32) | w[0]);
     s[i] = (int32_t)w[4];
     e[i] = (int32_t)w[5];
@@ -274,7 +276,7 @@ int resident_cols(wfa_ctx* c, int64_t n, HitCols* h) {
         (rc = slot(c, S_END, n, &d_e)) || (rc = slot(c, S_DT, n, &d_dt)) || (rc = slot(c, S_BOARD, n, &d_b)) ||
         (rc = slot(c, S_CHAN, n, &d_c)) || (rc = slot(c, S_RID, n, &d_rid)))
         return rc;
-    hipLaunchKernelGGL(k_unpack_hit_rows, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, rows, d_ts, d_pos, d_s, d_e, d_dt,
+    hipLaunchKernelGGL(k_unpack_hit_rows, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, rows, (int64_t)60, d_ts, d_pos, d_s, d_e, d_dt,
                        d_b, d_c, d_rid);
     *h = HitCols{d_ts, d_pos, d_s, d_e, d_dt, d_b, d_c, d_rid};
     return WFA_OK;
@@ -942,17 +944,19 @@ __global__ void k_es_count(const int64_t* __restrict__ event_start, EsCtl* __res
     if (blockIdx.x == 0 && threadIdx.x == 0) ctl->n_out = event_start[ctl->n_closed];
 }
 
-// 84-byte rows as 21 dwords: event_id, t_min, t_max (6 dwords), then the hit's 15 dwords; lanes over dwords
+// 84-byte rows as 21 dwords: event_id, t_min, t_max (6 dwords), then the hit's 15 dwords; lanes over dwords.  In general
+// the first W dwords of table entries of S dwords (W = 18, S = 22: a 72-byte merged row out of an 88-byte entry, 96-byte rows)
+template <int W, int S>
 __global__ __launch_bounds__(kTB) void k_es_rows(int64_t n_out, const int64_t* __restrict__ perm,
                                                  const uint64_t* __restrict__ k_event, const int64_t* __restrict__ t_min,
                                                  const int64_t* __restrict__ t_max, int64_t first_event,
                                                  const uint32_t* __restrict__ rows, uint32_t* __restrict__ out) {
     const int64_t d = (int64_t)blockIdx.x * kTB + threadIdx.x;
-    if (d >= n_out * 21) return;
-    const int64_t j = d / 21;
-    const int w = (int)(d - j * 21);
+    if (d >= n_out * (6 + W)) return;
+    const int64_t j = d / (6 + W);
+    const int w = (int)(d - j * (6 + W));
     const int64_t i = perm[j];
-    if (w >= 6) { out[d] = rows[i * 15 + (w - 6)]; return; }
+    if (w >= 6) { out[d] = rows[i * S + (w - 6)]; return; }
     const int64_t ev = (int64_t)k_event[i];
     const int64_t v = w < 2 ? first_event + ev : (w < 4 ? t_min[ev] : t_max[ev]);
     out[d] = (w & 1) ? (uint32_t)((uint64_t)v >> 32) : (uint32_t)(uint64_t)v;
@@ -1135,14 +1139,15 @@ __global__ void k_ms_list(int64_t n_clusters, const int64_t* __restrict__ closed
 
 // 72-byte HIT_MERGED_DTYPE rows as 18 dwords, lanes over dwords: the anchor hit's 15 dwords with height, integral,
 // sample_start, sample_end, width (dwords 2..6) replaced by the cluster's reductions -- a cluster of one hit keeps the
-// hit's own (hit_merge.py:266-284) -- then component_offset (i8) and component_count (i4)
+// hit's own (hit_merge.py:266-284) -- then component_offset (i8) and component_count (i4).  Row r goes to out + r * out_words
+// (18: packed rows; 22: the merged-event stream's carry entries, whose last 4 dwords k_mes_fix writes)
 __global__ __launch_bounds__(kTB) void k_ms_rows(int64_t n_out, const int64_t* __restrict__ list,
                                                  const int64_t* __restrict__ offset, const int64_t* __restrict__ comp_incl,
                                                  int64_t first_component, const int64_t* __restrict__ anchor,
                                                  const float* __restrict__ red_h, const float* __restrict__ red_int,
                                                  const int32_t* __restrict__ red_s, const int32_t* __restrict__ red_e,
                                                  const float* __restrict__ red_w, const uint32_t* __restrict__ rows,
-                                                 uint32_t* __restrict__ out) {
+                                                 uint32_t* __restrict__ out, int out_words) {
     const int64_t d = (int64_t)blockIdx.x * kTB + threadIdx.x;
     if (d >= n_out * 18) return;
     const int64_t r = d / 18;
@@ -1159,7 +1164,37 @@ __global__ __launch_bounds__(kTB) void k_ms_rows(int64_t n_out, const int64_t* _
         v = w == 2 ? __float_as_uint(red_h[r]) : w == 3 ? __float_as_uint(red_int[r]) : w == 4 ? (uint32_t)red_s[r]
           : w == 5 ? (uint32_t)red_e[r] : __float_as_uint(red_w[r]);
     }
-    out[d] = v;
+    out[r * out_words + w] = v;
+}
+
+// abs_start_fix / abs_end_fix of the closed clusters (event_grouping.py:369-416) into dwords 18..21 of their 22-dword
+// entries: where the merged row has no sample window (its cluster spans records: -1, -1) the extent of the member hits,
+// min abs_start and max abs_end over the sorted positions [a, b); NaN for every other cluster (the anchor formula holds)
+__global__ void k_mes_fix(int64_t n_out, const int64_t* __restrict__ list, const int64_t* __restrict__ offset,
+                          const double* __restrict__ s0, const double* __restrict__ s1, const int32_t* __restrict__ red_s,
+                          const int32_t* __restrict__ red_e, double* __restrict__ entries) {
+    const int64_t r = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (r >= n_out) return;
+    double lo = __longlong_as_double(0x7ff8000000000000ll), hi = lo;
+    if (red_s[r] < 0 || red_e[r] < 0) {
+        const int64_t cl = list[r];
+        const int64_t a = offset[cl], b = offset[cl + 1];
+        lo = s0[a]; hi = s1[a];
+        for (int64_t j = a + 1; j < b; ++j) {
+            lo = s0[j] < lo ? s0[j] : lo;
+            hi = s1[j] > hi ? s1[j] : hi;
+        }
+    }
+    entries[r * 11 + 9] = lo;
+    entries[r * 11 + 10] = hi;
+}
+// ... and back out of the n entries of a table as the two columns group_cols takes
+__global__ void k_mes_fixcols(int64_t n, const double* __restrict__ entries, double* __restrict__ fix0,
+                              double* __restrict__ fix1) {
+    const int64_t i = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (i >= n) return;
+    fix0[i] = entries[i * 11 + 9];
+    fix1[i] = entries[i * 11 + 10];
 }
 
 // hit_index of the closed clusters' members: clusters in the order of the merged rows, members in chain order
@@ -1189,6 +1224,276 @@ int plus_scan(wfa_ctx* c, const int64_t* in, int64_t* out, int64_t n) {
     if ((rc = c->ht[S_CUB].ensure(tb))) return rc;
     tb = c->ht[S_CUB].cap;
     WFA_HIP_CHECK(rocprim::inclusive_scan(c->ht[S_CUB].ptr, tb, in, out, (size_t)n, rocprim::plus<int64_t>(), c->stream));
+    return WFA_OK;
+}
+
+// ---- the two steps of a push ----------------------------------------------------------------------------------------
+// wfa_merge_stream_push is the merge step on c->ms, wfa_event_stream_push the group step on c->es; a push of the
+// merged-event stream is one after the other on a state of its own, the merged rows handed over in HBM.  A step reads its
+// stream's state and changes none of it: what it decides comes back in *r and the caller commits (merge_commit /
+// group_commit) once the whole push has succeeded, so a refused push leaves every carry as it was.
+
+// the merge step's buffers: carried rows and their indices (two each), member indices of the closed clusters, and the
+// merged rows: n_closed entries of out_words dwords behind the first out_used entries of `out`, which are kept
+struct MergeIo {
+    DevBuf* carry[2];
+    DevBuf* index[2];
+    DevBuf* out_index;
+    DevBuf* out;
+    int out_words;      // 18: HIT_MERGED_DTYPE rows; 22: with the fix windows behind each row (k_mes_fix)
+    int64_t out_used;
+};
+struct MergeStepOut {
+    int64_t n_closed = 0, n_comp = 0, n_keep = 0;
+    double open_start = HUGE_VAL;
+    bool flip = false;  // the carry went to the other pair of buffers
+};
+
+int merge_step(wfa_ctx* c, const wfa_ctx::MergeStream& ms, const MergeIo& io, const void* hit_rows, int64_t n_rows,
+               double horizon_ps, MergeStepOut* r) {
+    int rc;
+    *r = MergeStepOut{};
+    if (horizon_ps != horizon_ps) return fail(WFA_E_INVALID, "the horizon is NaN");
+    if (horizon_ps < ms.horizon)
+        return fail(WFA_E_INVALID, "the horizon (%.17g ps) lies below the previous push's (%.17g ps)", horizon_ps, ms.horizon);
+    if (n_rows >= 0x80000000LL - ms.n_carry)
+        return fail(WFA_E_INVALID, "carry (%lld rows) + pushed rows (%lld) reach the table limit of 2^31 rows",
+                    (long long)ms.n_carry, (long long)n_rows);
+    const int64_t n = ms.n_carry + n_rows;
+    if (n == 0) return WFA_OK;  // nothing carried, nothing pushed: no launch
+    c->ht_n = -1;  // the scratch slots a static count pass left for its fill are overwritten
+    DevBuf& table = *io.carry[ms.cur];
+    DevBuf& table_index = *io.index[ms.cur];
+    if ((rc = es_grow(c, table, (size_t)ms.n_carry * 60, (size_t)n * 60)) ||
+        (rc = es_grow(c, table_index, (size_t)ms.n_carry * 8, (size_t)n * 8)))
+        return rc;
+    uint8_t* rows = table.as<uint8_t>();
+    int64_t* index = table_index.as<int64_t>();
+    // 1. the pushed rows and their indices behind the carry (a refused push leaves them there: they lie behind n_carry and
+    //    are overwritten)
+    if (n_rows > 0) {
+        if ((rc = h2d_copy(c, rows + (size_t)ms.n_carry * 60, hit_rows, (size_t)n_rows * 60))) return rc;
+        hipLaunchKernelGGL(k_ms_number, dim3(blocks_for(n_rows)), dim3(kTB), 0, c->stream, n_rows, ms.next_hit,
+                           index + ms.n_carry);
+    }
+    int64_t *d_ts, *d_pos, *d_rid;
+    int32_t *d_s, *d_e, *d_dt;
+    int16_t *d_b, *d_c;
+    if ((rc = slot(c, S_TS, n, &d_ts)) || (rc = slot(c, S_POS, n, &d_pos)) || (rc = slot(c, S_START, n, &d_s)) ||
+        (rc = slot(c, S_END, n, &d_e)) || (rc = slot(c, S_DT, n, &d_dt)) || (rc = slot(c, S_BOARD, n, &d_b)) ||
+        (rc = slot(c, S_CHAN, n, &d_c)) || (rc = slot(c, S_RID, n, &d_rid)))
+        return rc;
+    hipLaunchKernelGGL(k_unpack_hit_rows, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, rows, (int64_t)60, d_ts, d_pos, d_s,
+                       d_e, d_dt, d_b, d_c, d_rid);
+    // 2. the sort and chain of the static entry over the whole table
+    const HitCols h{d_ts, d_pos, d_s, d_e, d_dt, d_b, d_c, d_rid};
+    int64_t n_cl = 0;
+    int64_t* perm = nullptr;
+    if ((rc = merge_cols(c, n, h, ms.gap_ns, ms.width_ns, &n_cl, &perm))) return rc;
+    if (n_cl < 1 || n_cl > n) return fail(WFA_E_HIP, "merge stream: the chain reported %lld clusters of %lld hits", (long long)n_cl, (long long)n);
+    // 3. the checks of the pushed rows, the closed clusters, the rows that stay; one read of the control block
+    int64_t *closed, *closed_incl, *count, *comp_incl, *list, *keep, *keep_incl;
+    MsCtl* d_ctl;
+    if ((rc = slot(c, S_MS0, n_cl, &closed)) || (rc = slot(c, S_MS1, n_cl, &closed_incl)) || (rc = slot(c, S_MS2, n_cl, &count)) ||
+        (rc = slot(c, S_MS3, n_cl, &comp_incl)) || (rc = slot(c, S_MS4, n_cl, &list)) || (rc = slot(c, S_K2, n, &keep)) ||
+        (rc = slot(c, S_K3, n, &keep_incl)) || (rc = slot(c, S_MS5, 1, &d_ctl)))
+        return rc;
+    LaunchTimer t(c);
+    MsCtl ctl{~0ull, ~0ull, 0, 0, 0, 0};
+    WFA_HIP_CHECK(hipMemcpyAsync(d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
+    if (n_rows > 0) {
+        const unsigned cb = blocks_for(n_rows) < 1024u ? blocks_for(n_rows) : 1024u;
+        hipLaunchKernelGGL(k_es_check<MsCtl>, dim3(cb), dim3(kTB), 0, c->stream, n_rows, d_dt + ms.n_carry, d_s + ms.n_carry,
+                           d_e + ms.n_carry, c->ht[S_ABS0].as<double>() + ms.n_carry, d_ctl);
+    }
+    const int64_t* offset = c->ht[S_OUT0].as<int64_t>();
+    const int64_t* cluster_incl = c->ht[S_ID].as<int64_t>();
+    const double* s0 = c->ht[S_F0].as<double>();
+    const double* s1 = c->ht[S_F1].as<double>();
+    hipLaunchKernelGGL(k_ms_closed, dim3(blocks_for(n_cl)), dim3(kTB), 0, c->stream, n_cl, n, offset, s0, s1,
+                       c->ht[S_SG].as<uint64_t>(), ms.gap_ns > 0 ? 1 : 0, ms.gap_ns * 1e3, horizon_ps, closed, count);
+    if ((rc = plus_scan(c, closed, closed_incl, n_cl)) || (rc = plus_scan(c, count, comp_incl, n_cl))) return rc;
+    hipLaunchKernelGGL(k_ms_keep, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, n_cl, perm, cluster_incl, closed, closed_incl,
+                       comp_incl, s0, keep, d_ctl);
+    WFA_HIP_CHECK(hipGetLastError());
+    WFA_HIP_CHECK(hipMemcpyAsync(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (ctl.flags & kEsBadDt) return fail(WFA_E_INVALID, "hit dt must be positive for every row");
+    if (ctl.flags & kEsBadEdge) return fail(WFA_E_INVALID, "a pushed row has a negative edge_start / edge_end");
+    if (n_rows > 0 && ctl.min_key < host_ord_f64(ms.horizon))
+        return fail(WFA_E_INVALID, "a pushed row starts below the previous push's horizon (%.17g ps)", ms.horizon);
+    const int64_t n_closed = (int64_t)ctl.n_closed, n_comp = (int64_t)ctl.n_comp, n_keep = n - n_comp;
+    if (n_closed < 0 || n_closed > n_cl || n_comp < n_closed || n_comp > n || (n_keep > 0) != (ctl.open_key != ~0ull))
+        return fail(WFA_E_HIP, "merge stream: inconsistent counts");
+    if (n_closed >= 0x80000000LL - io.out_used)
+        return fail(WFA_E_INVALID, "carried merged rows (%lld) + closed clusters (%lld) reach the table limit of 2^31 rows",
+                    (long long)io.out_used, (long long)n_closed);
+    // 4. the merged rows and member indices of the closed clusters
+    if (n_closed > 0) {
+        float *height, *integral, *red_h, *red_int, *red_w;
+        int32_t *red_s, *red_e;
+        int64_t* anchor;
+        const size_t entry = (size_t)io.out_words * 4;
+        if ((rc = slot(c, S_HEIGHT, n, &height)) || (rc = slot(c, S_INTEGRAL, n, &integral)) || (rc = slot(c, S_OUT3, n_closed, &anchor)) ||
+            (rc = slot(c, S_OUT4, n_closed, &red_h)) || (rc = slot(c, S_OUT5, n_closed, &red_int)) || (rc = slot(c, S_OUT6, n_closed, &red_s)) ||
+            (rc = slot(c, S_OUT7, n_closed, &red_e)) || (rc = slot(c, S_MS6, n_closed, &red_w)) ||
+            (rc = es_grow(c, *io.out, (size_t)io.out_used * entry, (size_t)(io.out_used + n_closed) * entry)) ||
+            (rc = io.out_index->ensure((size_t)n_comp * 8)))
+            return rc;
+        const uint32_t* words = reinterpret_cast<const uint32_t*>(rows);
+        uint32_t* out = io.out->as<uint32_t>() + (size_t)io.out_used * io.out_words;
+        hipLaunchKernelGGL(k_ms_cols, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, words, height, integral);
+        hipLaunchKernelGGL(k_ms_list, dim3(blocks_for(n_cl)), dim3(kTB), 0, c->stream, n_cl, closed, closed_incl, list);
+        hipLaunchKernelGGL(k_merge_emit, dim3(blocks_for(n_closed)), dim3(kTB), 0, c->stream, n_closed, offset, perm, h, height,
+                           integral, anchor, red_h, red_int, red_s, red_e, red_w, list);
+        hipLaunchKernelGGL(k_ms_rows, dim3(blocks_for(n_closed * 18)), dim3(kTB), 0, c->stream, n_closed, list, offset, comp_incl,
+                           ms.next_component, anchor, red_h, red_int, red_s, red_e, red_w, words, out, io.out_words);
+        if (io.out_words == 22)
+            hipLaunchKernelGGL(k_mes_fix, dim3(blocks_for(n_closed)), dim3(kTB), 0, c->stream, n_closed, list, offset, s0, s1, red_s,
+                               red_e, reinterpret_cast<double*>(out));
+        hipLaunchKernelGGL(k_ms_members, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, perm, cluster_incl, closed, offset,
+                           comp_incl, index, io.out_index->as<int64_t>());
+    }
+    // 5. the hits of the open clusters and their indices, in row order, into the other buffers (all open: the table is
+    //    the carry)
+    if (n_keep > 0 && n_closed > 0) {
+        DevBuf& other = *io.carry[ms.cur ^ 1];
+        DevBuf& other_index = *io.index[ms.cur ^ 1];
+        if ((rc = other.ensure((size_t)n_keep * 60)) || (rc = other_index.ensure((size_t)n_keep * 8))) return rc;
+        if ((rc = plus_scan(c, keep, keep_incl, n))) return rc;
+        hipLaunchKernelGGL(k_es_compact<15>, dim3(blocks_for(n * 15)), dim3(kTB), 0, c->stream, n, keep, keep_incl,
+                           reinterpret_cast<const uint32_t*>(rows), other.as<uint32_t>());
+        hipLaunchKernelGGL(k_es_compact<2>, dim3(blocks_for(n * 2)), dim3(kTB), 0, c->stream, n, keep, keep_incl,
+                           reinterpret_cast<const uint32_t*>(index), other_index.as<uint32_t>());
+    }
+    WFA_HIP_CHECK(hipGetLastError());
+    if ((rc = t.end("merge stream: closed clusters, rows, carry"))) return rc;
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    r->n_closed = n_closed;
+    r->n_comp = n_comp;
+    r->n_keep = n_keep;
+    r->open_start = n_keep > 0 ? host_unord_f64(ctl.open_key) : HUGE_VAL;
+    r->flip = n_keep > 0 && n_closed > 0;
+    return WFA_OK;
+}
+
+void merge_commit(wfa_ctx::MergeStream& ms, const MergeStepOut& r, int64_t n_rows, double horizon_ps) {
+    if (r.flip) ms.cur ^= 1;
+    ms.n_carry = r.n_keep;
+    ms.next_hit += n_rows;
+    ms.next_component += r.n_comp;
+    ms.horizon = horizon_ps;
+    ms.out_merged = r.n_closed;
+    ms.out_components = r.n_comp;
+}
+
+struct GroupStepOut {
+    int64_t n_out = 0, n_closed = 0, n_keep = 0;
+    bool flip = false;  // the carry went to the other buffer
+};
+
+// The group step over the table in carry[es.cur]: es.n_carry carried entries, then n_new new ones, already in place
+// (n = both > 0; the caller has checked the horizon).  An entry is S dwords; its first W are the row that goes out behind
+// the three event fields, and where S > W it ends with the row's abs_start_fix / abs_end_fix (S = 22, W = 18: a merged
+// row, whose edges may be -1, -1; S = W = 15: a threshold hit, whose edges may not).
+template <int W, int S>
+int group_step(wfa_ctx* c, const wfa_ctx::EventStream& es, DevBuf* const carry[2], DevBuf& out_buf, int64_t n_new,
+               double horizon_ps, GroupStepOut* r) {
+    int rc;
+    *r = GroupStepOut{};
+    const int64_t n = es.n_carry + n_new;
+    c->ht_n = -1;  // the scratch slots a static count pass left for its fill are overwritten
+    uint8_t* rows = carry[es.cur]->as<uint8_t>();
+    int64_t *d_ts, *d_pos, *d_rid;
+    int32_t *d_s, *d_e, *d_dt;
+    int16_t *d_b, *d_c;
+    double *ev_hi, *fix0 = nullptr, *fix1 = nullptr;
+    EsCtl* d_ctl;
+    if ((rc = slot(c, S_TS, n, &d_ts)) || (rc = slot(c, S_POS, n, &d_pos)) || (rc = slot(c, S_START, n, &d_s)) ||
+        (rc = slot(c, S_END, n, &d_e)) || (rc = slot(c, S_DT, n, &d_dt)) || (rc = slot(c, S_BOARD, n, &d_b)) ||
+        (rc = slot(c, S_CHAN, n, &d_c)) || (rc = slot(c, S_RID, n, &d_rid)) || (rc = slot(c, S_EVHI, n, &ev_hi)) ||
+        (rc = slot(c, S_ES, 1, &d_ctl)))
+        return rc;
+    hipLaunchKernelGGL(k_unpack_hit_rows, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, rows, (int64_t)(S * 4), d_ts, d_pos,
+                       d_s, d_e, d_dt, d_b, d_c, d_rid);
+    if (S > W) {
+        if ((rc = slot(c, S_OUT6, n, &fix0)) || (rc = slot(c, S_OUT7, n, &fix1))) return rc;
+        hipLaunchKernelGGL(k_mes_fixcols, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, reinterpret_cast<const double*>(rows),
+                           fix0, fix1);
+    }
+    // the grouping pass of the static entry over the whole table
+    const HitCols h{d_ts, d_pos, d_s, d_e, d_dt, d_b, d_c, d_rid};
+    int64_t n_ev = 0;
+    int64_t* perm = nullptr;
+    if ((rc = group_cols(c, n, h, fix0, fix1, es.window_ns, &n_ev, &perm, ev_hi))) return rc;
+    if (n_ev < 1 || n_ev > n) return fail(WFA_E_HIP, "event stream: the grouping pass reported %lld events of %lld hits", (long long)n_ev, (long long)n);
+    // the checks of the new rows and the closed prefix; one read of the control block
+    LaunchTimer t(c);
+    EsCtl ctl{~0ull, (unsigned long long)n_ev, 0, 0, 0};
+    WFA_HIP_CHECK(hipMemcpyAsync(d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
+    const double* abs0 = c->ht[S_ABS0].as<double>();
+    if (n_new > 0) {
+        const unsigned cb = blocks_for(n_new) < 1024u ? blocks_for(n_new) : 1024u;
+        hipLaunchKernelGGL(k_es_check<EsCtl>, dim3(cb), dim3(kTB), 0, c->stream, n_new, d_dt + es.n_carry, d_s + es.n_carry,
+                           d_e + es.n_carry, abs0 + es.n_carry, d_ctl);
+    }
+    const int64_t* ev_start = c->ht[S_OUT0].as<int64_t>();
+    hipLaunchKernelGGL(k_es_closed, dim3(blocks_for(n_ev)), dim3(kTB), 0, c->stream, n_ev, ev_hi, es.window_ns * 1e3, horizon_ps,
+                       d_ctl);
+    hipLaunchKernelGGL(k_es_count, dim3(1), dim3(64), 0, c->stream, ev_start, d_ctl);
+    WFA_HIP_CHECK(hipGetLastError());
+    WFA_HIP_CHECK(hipMemcpyAsync(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (ctl.flags & kEsBadDt) return fail(WFA_E_INVALID, "hit dt must be positive for every row");
+    if (S == W && (ctl.flags & kEsBadEdge))  // (merged rows come from the merge step, which has checked the hits' edges)
+        return fail(WFA_E_INVALID, "a pushed row has a negative edge_start / edge_end (merged hits that span records are "
+                                   "outside the event stream)");
+    if (n_new > 0 && ctl.min_key < host_ord_f64(es.horizon))
+        return fail(WFA_E_INVALID, "a pushed row starts below the previous push's horizon (%.17g ps)", es.horizon);
+    const int64_t n_closed = (int64_t)ctl.n_closed, n_out = (int64_t)ctl.n_out, n_keep = n - n_out;
+    if (n_closed < 0 || n_closed > n_ev || n_out < 0 || n_out > n) return fail(WFA_E_HIP, "event stream: inconsistent counts");
+    // the rows of the closed events
+    const uint64_t* k_ev = c->ht[S_K1].as<uint64_t>();
+    if (n_out > 0) {
+        if ((rc = out_buf.ensure((size_t)n_out * (6 + W) * 4))) return rc;
+        hipLaunchKernelGGL((k_es_rows<W, S>), dim3(blocks_for(n_out * (6 + W))), dim3(kTB), 0, c->stream, n_out, perm, k_ev,
+                           c->ht[S_OUT1].as<int64_t>(), c->ht[S_OUT2].as<int64_t>(), es.next_event,
+                           reinterpret_cast<const uint32_t*>(rows), out_buf.as<uint32_t>());
+    }
+    // the entries of the open events, in row order, into the other carry buffer (all open: the table is the carry)
+    if (n_keep > 0 && n_out > 0) {
+        DevBuf& other = *carry[es.cur ^ 1];
+        if ((rc = other.ensure((size_t)n_keep * S * 4))) return rc;
+        int64_t* flag = c->ht[S_FLAG].as<int64_t>();
+        int64_t* incl = c->ht[S_ID].as<int64_t>();
+        hipLaunchKernelGGL(k_es_keep, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, k_ev, n_closed, flag);
+        size_t tb = c->ht[S_CUB].cap;  // (sized by group_cols for this very scan)
+        WFA_HIP_CHECK(rocprim::inclusive_scan(c->ht[S_CUB].ptr, tb, flag, incl, (size_t)n, rocprim::plus<int64_t>(), c->stream));
+        hipLaunchKernelGGL(k_es_compact<S>, dim3(blocks_for(n * S)), dim3(kTB), 0, c->stream, n, flag, incl,
+                           reinterpret_cast<const uint32_t*>(rows), other.as<uint32_t>());
+    }
+    WFA_HIP_CHECK(hipGetLastError());
+    if ((rc = t.end("event stream: closed prefix, rows, carry"))) return rc;
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    r->n_out = n_out;
+    r->n_closed = n_closed;
+    r->n_keep = n_keep;
+    r->flip = n_keep > 0 && n_out > 0;
+    return WFA_OK;
+}
+
+void group_commit(wfa_ctx::EventStream& es, const GroupStepOut& r, double horizon_ps) {
+    if (r.flip) es.cur ^= 1;
+    es.n_carry = r.n_keep;
+    es.next_event += r.n_closed;
+    es.horizon = horizon_ps;
+    es.out_rows = r.n_out;
+}
+
+// rows of a finished push to the host (large ones through the pinned staging ring); the caller synchronises
+int stream_d2h(wfa_ctx* c, void* dst, const void* src, size_t bytes) {
+    if (bytes >= (4u << 20)) return d2h_staged(c, dst, src, bytes, nullptr, nullptr);
+    WFA_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
     return WFA_OK;
 }
 
@@ -1487,93 +1792,19 @@ int wfa_event_stream_push(wfa_ctx* c, const void* hit_rows, int64_t n_rows, doub
     if (n_rows >= 0x80000000LL - es.n_carry)
         return fail(WFA_E_INVALID, "carry (%lld rows) + pushed rows (%lld) reach the table limit of 2^31 rows",
                     (long long)es.n_carry, (long long)n_rows);
-    const int64_t n = es.n_carry + n_rows;
-    if (n == 0) {  // nothing carried, nothing pushed: no launch
-        es.horizon = horizon_ps;
-        es.out_rows = 0;
-        *n_out_rows = *n_out_events = *n_carry = 0;
-        return WFA_OK;
+    GroupStepOut r;
+    if (es.n_carry + n_rows > 0) {  // (nothing carried, nothing pushed: no launch)
+        DevBuf& table = c->es_carry[es.cur];
+        if ((rc = es_grow(c, table, (size_t)es.n_carry * 60, (size_t)(es.n_carry + n_rows) * 60))) return rc;
+        // the pushed rows behind the carry (a refused push leaves them there: they lie behind n_carry and are overwritten)
+        if (n_rows > 0 && (rc = h2d_copy(c, table.as<uint8_t>() + (size_t)es.n_carry * 60, hit_rows, (size_t)n_rows * 60))) return rc;
+        DevBuf* const carry[2] = {&c->es_carry[0], &c->es_carry[1]};
+        if ((rc = group_step<15, 15>(c, es, carry, c->es_out, n_rows, horizon_ps, &r))) return rc;
     }
-    c->ht_n = -1;  // the scratch slots a static count pass left for its fill are overwritten
-    DevBuf& table = c->es_carry[es.cur];
-    if ((rc = es_grow(c, table, (size_t)es.n_carry * 60, (size_t)n * 60))) return rc;
-    uint8_t* rows = table.as<uint8_t>();
-    // 1. the pushed rows behind the carry (a refused push leaves them there: they lie behind n_carry and are overwritten)
-    if (n_rows > 0 && (rc = h2d_copy(c, rows + (size_t)es.n_carry * 60, hit_rows, (size_t)n_rows * 60))) return rc;
-    int64_t *d_ts, *d_pos, *d_rid;
-    int32_t *d_s, *d_e, *d_dt;
-    int16_t *d_b, *d_c;
-    double* ev_hi;
-    EsCtl* d_ctl;
-    if ((rc = slot(c, S_TS, n, &d_ts)) || (rc = slot(c, S_POS, n, &d_pos)) || (rc = slot(c, S_START, n, &d_s)) ||
-        (rc = slot(c, S_END, n, &d_e)) || (rc = slot(c, S_DT, n, &d_dt)) || (rc = slot(c, S_BOARD, n, &d_b)) ||
-        (rc = slot(c, S_CHAN, n, &d_c)) || (rc = slot(c, S_RID, n, &d_rid)) || (rc = slot(c, S_EVHI, n, &ev_hi)) ||
-        (rc = slot(c, S_ES, 1, &d_ctl)))
-        return rc;
-    hipLaunchKernelGGL(k_unpack_hit_rows, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, rows, d_ts, d_pos, d_s, d_e, d_dt,
-                       d_b, d_c, d_rid);
-    // 2. the grouping pass of the static entry over the whole table
-    const HitCols h{d_ts, d_pos, d_s, d_e, d_dt, d_b, d_c, d_rid};
-    int64_t n_ev = 0;
-    int64_t* perm = nullptr;
-    if ((rc = group_cols(c, n, h, nullptr, nullptr, es.window_ns, &n_ev, &perm, ev_hi))) return rc;
-    if (n_ev < 1 || n_ev > n) return fail(WFA_E_HIP, "event stream: the grouping pass reported %lld events of %lld hits", (long long)n_ev, (long long)n);
-    // 3. the checks of the pushed rows and the closed prefix; one read of the control block
-    LaunchTimer t(c);
-    EsCtl ctl{~0ull, (unsigned long long)n_ev, 0, 0, 0};
-    WFA_HIP_CHECK(hipMemcpyAsync(d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
-    const double* abs0 = c->ht[S_ABS0].as<double>();
-    if (n_rows > 0) {
-        const unsigned cb = blocks_for(n_rows) < 1024u ? blocks_for(n_rows) : 1024u;
-        hipLaunchKernelGGL(k_es_check<EsCtl>, dim3(cb), dim3(kTB), 0, c->stream, n_rows, d_dt + es.n_carry, d_s + es.n_carry,
-                           d_e + es.n_carry, abs0 + es.n_carry, d_ctl);
-    }
-    const int64_t* ev_start = c->ht[S_OUT0].as<int64_t>();
-    hipLaunchKernelGGL(k_es_closed, dim3(blocks_for(n_ev)), dim3(kTB), 0, c->stream, n_ev, ev_hi, es.window_ns * 1e3, horizon_ps,
-                       d_ctl);
-    hipLaunchKernelGGL(k_es_count, dim3(1), dim3(64), 0, c->stream, ev_start, d_ctl);
-    WFA_HIP_CHECK(hipGetLastError());
-    WFA_HIP_CHECK(hipMemcpyAsync(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
-    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (ctl.flags & kEsBadDt) return fail(WFA_E_INVALID, "hit dt must be positive for every row");
-    if (ctl.flags & kEsBadEdge)
-        return fail(WFA_E_INVALID, "a pushed row has a negative edge_start / edge_end (merged hits that span records are "
-                                   "outside the event stream)");
-    if (n_rows > 0 && ctl.min_key < host_ord_f64(es.horizon))
-        return fail(WFA_E_INVALID, "a pushed row starts below the previous push's horizon (%.17g ps)", es.horizon);
-    const int64_t n_closed = (int64_t)ctl.n_closed, n_out = (int64_t)ctl.n_out, n_keep = n - n_out;
-    if (n_closed < 0 || n_closed > n_ev || n_out < 0 || n_out > n) return fail(WFA_E_HIP, "event stream: inconsistent counts");
-    // 4. the rows of the closed events
-    const uint64_t* k_ev = c->ht[S_K1].as<uint64_t>();
-    if (n_out > 0) {
-        if ((rc = c->es_out.ensure((size_t)n_out * 84))) return rc;
-        hipLaunchKernelGGL(k_es_rows, dim3(blocks_for(n_out * 21)), dim3(kTB), 0, c->stream, n_out, perm, k_ev,
-                           c->ht[S_OUT1].as<int64_t>(), c->ht[S_OUT2].as<int64_t>(), es.next_event,
-                           reinterpret_cast<const uint32_t*>(rows), c->es_out.as<uint32_t>());
-    }
-    // 5. the hits of the open events, in row order, into the other carry buffer (all open: the table is the carry)
-    if (n_keep > 0 && n_out > 0) {
-        DevBuf& other = c->es_carry[es.cur ^ 1];
-        if ((rc = other.ensure((size_t)n_keep * 60))) return rc;
-        int64_t* flag = c->ht[S_FLAG].as<int64_t>();
-        int64_t* incl = c->ht[S_ID].as<int64_t>();
-        hipLaunchKernelGGL(k_es_keep, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, k_ev, n_closed, flag);
-        size_t tb = c->ht[S_CUB].cap;  // (sized by group_cols for this very scan)
-        WFA_HIP_CHECK(rocprim::inclusive_scan(c->ht[S_CUB].ptr, tb, flag, incl, (size_t)n, rocprim::plus<int64_t>(), c->stream));
-        hipLaunchKernelGGL(k_es_compact<15>, dim3(blocks_for(n * 15)), dim3(kTB), 0, c->stream, n, flag, incl,
-                           reinterpret_cast<const uint32_t*>(rows), other.as<uint32_t>());
-    }
-    WFA_HIP_CHECK(hipGetLastError());
-    if ((rc = t.end("event stream: closed prefix, rows, carry"))) return rc;
-    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (n_keep > 0 && n_out > 0) es.cur ^= 1;
-    es.n_carry = n_keep;
-    es.next_event += n_closed;
-    es.horizon = horizon_ps;
-    es.out_rows = n_out;
-    *n_out_rows = n_out;
-    *n_out_events = n_closed;
-    *n_carry = n_keep;
+    group_commit(es, r, horizon_ps);
+    *n_out_rows = r.n_out;
+    *n_out_events = r.n_closed;
+    *n_carry = r.n_keep;
     return WFA_OK;
 }
 
@@ -1630,129 +1861,14 @@ int wfa_merge_stream_push(wfa_ctx* c, const void* hit_rows, int64_t n_rows, doub
     if (!ms.open) return fail(WFA_E_STATE, "no merge stream is open (wfa_merge_stream_begin first)");
     if (n_rows < 0 || (n_rows > 0 && !hit_rows) || !n_merged || !n_components || !n_carry || !open_start_ps)
         return fail(WFA_E_INVALID, "bad arguments");
-    if (horizon_ps != horizon_ps) return fail(WFA_E_INVALID, "the horizon is NaN");
-    if (horizon_ps < ms.horizon)
-        return fail(WFA_E_INVALID, "the horizon (%.17g ps) lies below the previous push's (%.17g ps)", horizon_ps, ms.horizon);
-    if (n_rows >= 0x80000000LL - ms.n_carry)
-        return fail(WFA_E_INVALID, "carry (%lld rows) + pushed rows (%lld) reach the table limit of 2^31 rows",
-                    (long long)ms.n_carry, (long long)n_rows);
-    const int64_t n = ms.n_carry + n_rows;
-    if (n == 0) {  // nothing carried, nothing pushed: no launch
-        ms.horizon = horizon_ps;
-        ms.out_merged = ms.out_components = 0;
-        *n_merged = *n_components = *n_carry = 0;
-        *open_start_ps = HUGE_VAL;
-        return WFA_OK;
-    }
-    c->ht_n = -1;  // the scratch slots a static count pass left for its fill are overwritten
-    DevBuf& table = c->ms_carry[ms.cur];
-    DevBuf& table_index = c->ms_index[ms.cur];
-    if ((rc = es_grow(c, table, (size_t)ms.n_carry * 60, (size_t)n * 60)) ||
-        (rc = es_grow(c, table_index, (size_t)ms.n_carry * 8, (size_t)n * 8)))
-        return rc;
-    uint8_t* rows = table.as<uint8_t>();
-    int64_t* index = table_index.as<int64_t>();
-    // 1. the pushed rows and their indices behind the carry (a refused push leaves them there: they lie behind n_carry and
-    //    are overwritten)
-    if (n_rows > 0) {
-        if ((rc = h2d_copy(c, rows + (size_t)ms.n_carry * 60, hit_rows, (size_t)n_rows * 60))) return rc;
-        hipLaunchKernelGGL(k_ms_number, dim3(blocks_for(n_rows)), dim3(kTB), 0, c->stream, n_rows, ms.next_hit,
-                           index + ms.n_carry);
-    }
-    int64_t *d_ts, *d_pos, *d_rid;
-    int32_t *d_s, *d_e, *d_dt;
-    int16_t *d_b, *d_c;
-    if ((rc = slot(c, S_TS, n, &d_ts)) || (rc = slot(c, S_POS, n, &d_pos)) || (rc = slot(c, S_START, n, &d_s)) ||
-        (rc = slot(c, S_END, n, &d_e)) || (rc = slot(c, S_DT, n, &d_dt)) || (rc = slot(c, S_BOARD, n, &d_b)) ||
-        (rc = slot(c, S_CHAN, n, &d_c)) || (rc = slot(c, S_RID, n, &d_rid)))
-        return rc;
-    hipLaunchKernelGGL(k_unpack_hit_rows, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, rows, d_ts, d_pos, d_s, d_e, d_dt,
-                       d_b, d_c, d_rid);
-    // 2. the sort and chain of the static entry over the whole table
-    const HitCols h{d_ts, d_pos, d_s, d_e, d_dt, d_b, d_c, d_rid};
-    int64_t n_cl = 0;
-    int64_t* perm = nullptr;
-    if ((rc = merge_cols(c, n, h, ms.gap_ns, ms.width_ns, &n_cl, &perm))) return rc;
-    if (n_cl < 1 || n_cl > n) return fail(WFA_E_HIP, "merge stream: the chain reported %lld clusters of %lld hits", (long long)n_cl, (long long)n);
-    // 3. the checks of the pushed rows, the closed clusters, the rows that stay; one read of the control block
-    int64_t *closed, *closed_incl, *count, *comp_incl, *list, *keep, *keep_incl;
-    MsCtl* d_ctl;
-    if ((rc = slot(c, S_MS0, n_cl, &closed)) || (rc = slot(c, S_MS1, n_cl, &closed_incl)) || (rc = slot(c, S_MS2, n_cl, &count)) ||
-        (rc = slot(c, S_MS3, n_cl, &comp_incl)) || (rc = slot(c, S_MS4, n_cl, &list)) || (rc = slot(c, S_K2, n, &keep)) ||
-        (rc = slot(c, S_K3, n, &keep_incl)) || (rc = slot(c, S_MS5, 1, &d_ctl)))
-        return rc;
-    LaunchTimer t(c);
-    MsCtl ctl{~0ull, ~0ull, 0, 0, 0, 0};
-    WFA_HIP_CHECK(hipMemcpyAsync(d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
-    if (n_rows > 0) {
-        const unsigned cb = blocks_for(n_rows) < 1024u ? blocks_for(n_rows) : 1024u;
-        hipLaunchKernelGGL(k_es_check<MsCtl>, dim3(cb), dim3(kTB), 0, c->stream, n_rows, d_dt + ms.n_carry, d_s + ms.n_carry,
-                           d_e + ms.n_carry, c->ht[S_ABS0].as<double>() + ms.n_carry, d_ctl);
-    }
-    const int64_t* offset = c->ht[S_OUT0].as<int64_t>();
-    const int64_t* cluster_incl = c->ht[S_ID].as<int64_t>();
-    const double* s0 = c->ht[S_F0].as<double>();
-    hipLaunchKernelGGL(k_ms_closed, dim3(blocks_for(n_cl)), dim3(kTB), 0, c->stream, n_cl, n, offset, s0, c->ht[S_F1].as<double>(),
-                       c->ht[S_SG].as<uint64_t>(), ms.gap_ns > 0 ? 1 : 0, ms.gap_ns * 1e3, horizon_ps, closed, count);
-    if ((rc = plus_scan(c, closed, closed_incl, n_cl)) || (rc = plus_scan(c, count, comp_incl, n_cl))) return rc;
-    hipLaunchKernelGGL(k_ms_keep, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, n_cl, perm, cluster_incl, closed, closed_incl,
-                       comp_incl, s0, keep, d_ctl);
-    WFA_HIP_CHECK(hipGetLastError());
-    WFA_HIP_CHECK(hipMemcpyAsync(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
-    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (ctl.flags & kEsBadDt) return fail(WFA_E_INVALID, "hit dt must be positive for every row");
-    if (ctl.flags & kEsBadEdge) return fail(WFA_E_INVALID, "a pushed row has a negative edge_start / edge_end");
-    if (n_rows > 0 && ctl.min_key < host_ord_f64(ms.horizon))
-        return fail(WFA_E_INVALID, "a pushed row starts below the previous push's horizon (%.17g ps)", ms.horizon);
-    const int64_t n_closed = (int64_t)ctl.n_closed, n_comp = (int64_t)ctl.n_comp, n_keep = n - n_comp;
-    if (n_closed < 0 || n_closed > n_cl || n_comp < n_closed || n_comp > n || (n_keep > 0) != (ctl.open_key != ~0ull))
-        return fail(WFA_E_HIP, "merge stream: inconsistent counts");
-    // 4. the merged rows and member indices of the closed clusters
-    if (n_closed > 0) {
-        float *height, *integral, *red_h, *red_int, *red_w;
-        int32_t *red_s, *red_e;
-        int64_t* anchor;
-        if ((rc = slot(c, S_HEIGHT, n, &height)) || (rc = slot(c, S_INTEGRAL, n, &integral)) || (rc = slot(c, S_OUT3, n_closed, &anchor)) ||
-            (rc = slot(c, S_OUT4, n_closed, &red_h)) || (rc = slot(c, S_OUT5, n_closed, &red_int)) || (rc = slot(c, S_OUT6, n_closed, &red_s)) ||
-            (rc = slot(c, S_OUT7, n_closed, &red_e)) || (rc = slot(c, S_MS6, n_closed, &red_w)) ||
-            (rc = c->ms_out.ensure((size_t)n_closed * 72)) || (rc = c->ms_out_index.ensure((size_t)n_comp * 8)))
-            return rc;
-        const uint32_t* words = reinterpret_cast<const uint32_t*>(rows);
-        hipLaunchKernelGGL(k_ms_cols, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, words, height, integral);
-        hipLaunchKernelGGL(k_ms_list, dim3(blocks_for(n_cl)), dim3(kTB), 0, c->stream, n_cl, closed, closed_incl, list);
-        hipLaunchKernelGGL(k_merge_emit, dim3(blocks_for(n_closed)), dim3(kTB), 0, c->stream, n_closed, offset, perm, h, height,
-                           integral, anchor, red_h, red_int, red_s, red_e, red_w, list);
-        hipLaunchKernelGGL(k_ms_rows, dim3(blocks_for(n_closed * 18)), dim3(kTB), 0, c->stream, n_closed, list, offset, comp_incl,
-                           ms.next_component, anchor, red_h, red_int, red_s, red_e, red_w, words, c->ms_out.as<uint32_t>());
-        hipLaunchKernelGGL(k_ms_members, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, perm, cluster_incl, closed, offset,
-                           comp_incl, index, c->ms_out_index.as<int64_t>());
-    }
-    // 5. the hits of the open clusters and their indices, in row order, into the other buffers (all open: the table is
-    //    the carry)
-    if (n_keep > 0 && n_closed > 0) {
-        DevBuf& other = c->ms_carry[ms.cur ^ 1];
-        DevBuf& other_index = c->ms_index[ms.cur ^ 1];
-        if ((rc = other.ensure((size_t)n_keep * 60)) || (rc = other_index.ensure((size_t)n_keep * 8))) return rc;
-        if ((rc = plus_scan(c, keep, keep_incl, n))) return rc;
-        hipLaunchKernelGGL(k_es_compact<15>, dim3(blocks_for(n * 15)), dim3(kTB), 0, c->stream, n, keep, keep_incl,
-                           reinterpret_cast<const uint32_t*>(rows), other.as<uint32_t>());
-        hipLaunchKernelGGL(k_es_compact<2>, dim3(blocks_for(n * 2)), dim3(kTB), 0, c->stream, n, keep, keep_incl,
-                           reinterpret_cast<const uint32_t*>(index), other_index.as<uint32_t>());
-    }
-    WFA_HIP_CHECK(hipGetLastError());
-    if ((rc = t.end("merge stream: closed clusters, rows, carry"))) return rc;
-    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (n_keep > 0 && n_closed > 0) ms.cur ^= 1;
-    ms.n_carry = n_keep;
-    ms.next_hit += n_rows;
-    ms.next_component += n_comp;
-    ms.horizon = horizon_ps;
-    ms.out_merged = n_closed;
-    ms.out_components = n_comp;
-    *n_merged = n_closed;
-    *n_components = n_comp;
-    *n_carry = n_keep;
-    *open_start_ps = n_keep > 0 ? host_unord_f64(ctl.open_key) : HUGE_VAL;
+    const MergeIo io{{&c->ms_carry[0], &c->ms_carry[1]}, {&c->ms_index[0], &c->ms_index[1]}, &c->ms_out_index, &c->ms_out, 18, 0};
+    MergeStepOut r;
+    if ((rc = merge_step(c, ms, io, hit_rows, n_rows, horizon_ps, &r))) return rc;
+    merge_commit(ms, r, n_rows, horizon_ps);
+    *n_merged = r.n_closed;
+    *n_components = r.n_comp;
+    *n_carry = r.n_keep;
+    *open_start_ps = r.open_start;
     return WFA_OK;
 }
 
@@ -1786,6 +1902,95 @@ int wfa_merge_stream_end(wfa_ctx* c) {
     if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
     for (DevBuf* b : {&c->ms_carry[0], &c->ms_carry[1], &c->ms_index[0], &c->ms_index[1], &c->ms_out, &c->ms_out_index}) b->release();
     c->ms = wfa_ctx::MergeStream{};
+    return WFA_OK;
+}
+
+// ---- merged-event stream ----------------------------------------------------------------------------------------------
+int wfa_merged_event_stream_begin(wfa_ctx* c, double merge_gap_ns, double max_total_width_ns, double time_window_ns,
+                                  double horizon_margin_ps) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (!(merge_gap_ns >= 0)) return fail(WFA_E_INVALID, "merge_gap_ns must be >= 0");
+    if (!(max_total_width_ns >= 0)) return fail(WFA_E_INVALID, "max_total_width_ns must be >= 0");
+    if (!(time_window_ns >= 0)) return fail(WFA_E_INVALID, "time_window_ns must be >= 0");
+    if (!(horizon_margin_ps >= 0) || horizon_margin_ps == HUGE_VAL)
+        return fail(WFA_E_INVALID, "horizon_margin_ps must be >= 0 and finite");
+    if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->mes = wfa_ctx::MergedEventStream{};  // (a stream left open starts over: empty carries, ids 0; the buffers are reused)
+    c->mes.open = true;
+    c->mes.margin_ps = horizon_margin_ps;
+    c->mes.m.gap_ns = merge_gap_ns;
+    c->mes.m.width_ns = max_total_width_ns;
+    c->mes.m.horizon = -HUGE_VAL;
+    c->mes.e.window_ns = time_window_ns;
+    c->mes.e.horizon = -HUGE_VAL;
+    return WFA_OK;
+}
+
+int wfa_merged_event_stream_push(wfa_ctx* c, const void* hit_rows, int64_t n_rows, double horizon_ps, int64_t* n_out_rows,
+                                 int64_t* n_out_events, int64_t* n_clusters, int64_t* n_components, int64_t* n_merge_carry,
+                                 int64_t* n_event_carry, double* group_horizon_ps) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    wfa_ctx::MergedEventStream& st = c->mes;
+    if (!st.open) return fail(WFA_E_STATE, "no merged-event stream is open (wfa_merged_event_stream_begin first)");
+    if (n_rows < 0 || (n_rows > 0 && !hit_rows) || !n_out_rows || !n_out_events || !n_clusters || !n_components ||
+        !n_merge_carry || !n_event_carry || !group_horizon_ps)
+        return fail(WFA_E_INVALID, "bad arguments");
+    // 1. the merge step; its rows go behind the event carry as 88-byte entries, with their fix windows
+    const MergeIo io{{&c->mes_mcarry[0], &c->mes_mcarry[1]}, {&c->mes_mindex[0], &c->mes_mindex[1]}, &c->mes_mindex_out,
+                     &c->mes_carry[st.e.cur], 22, st.e.n_carry};
+    MergeStepOut m;
+    if ((rc = merge_step(c, st.m, io, hit_rows, n_rows, horizon_ps, &m))) return rc;
+    // 2. the grouping horizon: no merged row still to come starts below min(H, open_start'), nor below an earlier G
+    double open = m.open_start;
+    if (st.margin_ps > 0 && open != HUGE_VAL) open = nextafter(open - 1.5 * st.margin_ps, -HUGE_VAL);
+    double g = horizon_ps < open ? horizon_ps : open;
+    if (g < st.e.horizon) g = st.e.horizon;
+    // 3. the group step over event carry ++ the new merged rows
+    GroupStepOut e;
+    if (st.e.n_carry + m.n_closed > 0) {
+        DevBuf* const carry[2] = {&c->mes_carry[0], &c->mes_carry[1]};
+        if ((rc = group_step<18, 22>(c, st.e, carry, c->mes_out, m.n_closed, g, &e))) {
+            st.e.out_rows = -1;  // (the merge step has overwritten the member indices of the last push: nothing to fill)
+            return rc;
+        }
+    }
+    merge_commit(st.m, m, n_rows, horizon_ps);
+    group_commit(st.e, e, g);
+    *n_out_rows = e.n_out;
+    *n_out_events = e.n_closed;
+    *n_clusters = m.n_closed;
+    *n_components = m.n_comp;
+    *n_merge_carry = m.n_keep;
+    *n_event_carry = e.n_keep;
+    *group_horizon_ps = g;
+    return WFA_OK;
+}
+
+int wfa_merged_event_stream_fill(wfa_ctx* c, void* out_rows, int64_t* hit_index, int64_t n_out_rows, int64_t n_components) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    const wfa_ctx::MergedEventStream& st = c->mes;
+    if (!st.open || st.e.out_rows < 0) return fail(WFA_E_STATE, "no merged-event stream push has been made");
+    if (n_out_rows != st.e.out_rows || n_components != st.m.out_components)
+        return fail(WFA_E_INVALID, "caller expects %lld rows / %lld components, the last push closed %lld / %lld",
+                    (long long)n_out_rows, (long long)n_components, (long long)st.e.out_rows, (long long)st.m.out_components);
+    if ((n_out_rows > 0 && !out_rows) || (n_components > 0 && !hit_index)) return fail(WFA_E_INVALID, "null output");
+    if (n_out_rows > 0 && (rc = stream_d2h(c, out_rows, c->mes_out.ptr, (size_t)n_out_rows * 96))) return rc;
+    if (n_components > 0 && (rc = stream_d2h(c, hit_index, c->mes_mindex_out.ptr, (size_t)n_components * 8))) return rc;
+    if (n_out_rows > 0 || n_components > 0) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return WFA_OK;
+}
+
+int wfa_merged_event_stream_end(wfa_ctx* c) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    for (DevBuf* b : {&c->mes_mcarry[0], &c->mes_mcarry[1], &c->mes_mindex[0], &c->mes_mindex[1], &c->mes_mindex_out,
+                      &c->mes_carry[0], &c->mes_carry[1], &c->mes_out})
+        b->release();
+    c->mes = wfa_ctx::MergedEventStream{};
     return WFA_OK;
 }
 

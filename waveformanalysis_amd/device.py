@@ -19,6 +19,7 @@ from . import _lib
 from .dtypes import (
     BASIC_FEATURES_DTYPE,
     EVENT_HIT_DTYPE,
+    EVENT_MERGED_HIT_DTYPE,
     HIT_DTYPE,
     HIT_MERGED_DTYPE,
     S1_S2_CLASSIFIER_DTYPE,
@@ -997,6 +998,39 @@ class DeviceSession:
     def merge_stream_end(self) -> None:
         """Free the carry and close the stream (wfa_merge_stream_end)."""
         _lib.check(self._lib.wfa_merge_stream_end(self._h))
+
+    # ---- merged-event stream: merge step and group step in one push, the merged rows handed over on the device ----------
+    def merged_event_stream_begin(self, merge_gap_ns: float, max_total_width_ns: float, time_window_ns: float,
+                                  horizon_margin_ps: float = 0.0) -> None:
+        """Open the session's merged-event stream (wfa_merged_event_stream_begin): empty carries, hit, component and event
+        index 0.  `horizon_margin_ps` is the run's margin (event_stream.horizon_margin; 0 below 2^53 ps)."""
+        _lib.check(self._lib.wfa_merged_event_stream_begin(self._h, float(merge_gap_ns), float(max_total_width_ns),
+                                                           float(time_window_ns), float(horizon_margin_ps)))
+
+    def merged_event_stream_push(self, rows: np.ndarray | None, horizon: float):
+        """Push THRESHOLD_HIT_DTYPE rows (None / empty: a pure flush) with the horizon (ps, float64) below which no later
+        hit starts -> (EVENT_MERGED_HIT_DTYPE rows of the events this push closed, int64 hit_index of the members of the
+        clusters its merge step closed, hits carried by the merge step, merged rows carried by the group step, the
+        grouping horizon G)."""
+        n = 0 if rows is None else len(rows)
+        src = None
+        if n:
+            if rows.dtype != THRESHOLD_HIT_DTYPE:
+                raise ValueError("merged_event_stream_push takes THRESHOLD_HIT_DTYPE rows")
+            src = np.ascontiguousarray(rows)
+        n_out, n_ev, n_cl, n_comp, n_mc, n_ec = (C.c_int64(0) for _ in range(6))
+        g = C.c_double(0.0)
+        _lib.check(self._lib.wfa_merged_event_stream_push(self._h, _ptr(src), n, float(horizon), C.byref(n_out), C.byref(n_ev),
+                                                          C.byref(n_cl), C.byref(n_comp), C.byref(n_mc), C.byref(n_ec),
+                                                          C.byref(g)))
+        out = np.empty(int(n_out.value), dtype=EVENT_MERGED_HIT_DTYPE)
+        hit_index = np.empty(int(n_comp.value), dtype=np.int64)
+        _lib.check(self._lib.wfa_merged_event_stream_fill(self._h, _ptr(out), _ptr(hit_index), len(out), len(hit_index)))
+        return out, hit_index, int(n_mc.value), int(n_ec.value), float(g.value)
+
+    def merged_event_stream_end(self) -> None:
+        """Free both carries and close the stream (wfa_merged_event_stream_end)."""
+        _lib.check(self._lib.wfa_merged_event_stream_end(self._h))
 
     def hit_merge_clusters_resident(self, n: int, merge_gap_ns: float, max_total_width_ns: float):
         """hit_merge_clusters on the n resident rows: (order, cluster_offset)."""

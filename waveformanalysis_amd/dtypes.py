@@ -155,6 +155,10 @@ HIT_MERGED_DTYPE = np.dtype(
         ("component_count", "i4"),
     ]
 )
+
+# one row per merged hit of a closed event (merged-event stream, wfa_merged_event_stream_fill; 96 B): the event's id and
+# extent, then the HIT_MERGED_DTYPE row unchanged
+EVENT_MERGED_HIT_DTYPE = np.dtype([("event_id", "i8"), ("t_min", "i8"), ("t_max", "i8")] + HIT_MERGED_DTYPE.descr)
 HIT_MERGED_COMPONENTS_DTYPE = np.dtype([("merged_index", "i8"), ("hit_index", "i8")])
 HIT_MERGE_CLUSTERS_DTYPE = np.dtype([("cluster_index", "i8"), ("hit_index", "i8")])
 
@@ -203,6 +207,7 @@ assert HIT_DTYPE.itemsize == 48
 assert WAVEFORM_WIDTH_DTYPE.itemsize == 56
 assert S1_S2_CLASSIFIER_DTYPE.itemsize == 45
 assert HIT_MERGED_DTYPE.itemsize == 72
+assert EVENT_MERGED_HIT_DTYPE.itemsize == 96 and EVENT_MERGED_HIT_DTYPE.fields["position"][1] == 24
 assert RECORDS_DTYPE.itemsize == 102
 assert THRESHOLD_HIT_DTYPE.itemsize == 60
 assert EVENT_HIT_DTYPE.itemsize == 84 and EVENT_HIT_DTYPE.fields["position"][1] == 24
@@ -219,6 +224,7 @@ __all__ = [
     "WAVEFORM_WIDTH_DTYPE",
     "S1_S2_CLASSIFIER_DTYPE",
     "HIT_MERGED_DTYPE",
+    "EVENT_MERGED_HIT_DTYPE",
     "HIT_MERGED_COMPONENTS_DTYPE",
     "HIT_MERGE_CLUSTERS_DTYPE",
     "PEAK_DTYPE",

@@ -78,13 +78,19 @@ def horizon_of(min_later_timestamp: int | None, margin: float) -> float:
     return h
 
 
-def chunk_horizons(chunks: list) -> list[float]:
+def run_margin(chunks: list) -> float:
+    """horizon_margin of the run the records chunks make up."""
+    return horizon_margin(max((run_magnitude(c.data) for c in chunks if len(c.data)), default=0))
+
+
+def chunk_horizons(chunks: list, margin: float | None = None) -> list[float]:
     """One horizon per records chunk: the minimum record timestamp over all records of LATER chunks (a suffix minimum,
-    taken once per run; correct for unsorted runs as well), as float64 less the run's margin; +inf for the last chunk.
+    taken once per run; correct for unsorted runs as well), as float64 less the run's margin (`run_margin`, taken here
+    unless given); +inf for the last chunk.
     A threshold hit has edge_start >= 0 and timestamp = record timestamp + position * dt * 1e3, so its abs_start is at
     least its record's timestamp."""
-    nonempty = [c.data for c in chunks if len(c.data)]
-    margin = horizon_margin(max((run_magnitude(d) for d in nonempty), default=0))
+    if margin is None:
+        margin = run_margin(chunks)
     out: list[float] = [math.inf] * len(chunks)
     later = None
     for k in range(len(chunks) - 1, -1, -1):
@@ -109,9 +115,10 @@ def event_rows(hits: np.ndarray, flat: dict, first_event: int = 0) -> np.ndarray
     return out
 
 
-def events_frame(rows: np.ndarray):
+def events_frame(rows: np.ndarray, window_fields: tuple[str, str] = ("edge_start", "edge_end")):
     """The reference's hit_grouped DataFrame (EVENT_COLUMNS) from EVENT_HIT_DTYPE rows: one frame row per run of equal
-    event_id, n_hits = the run's length, the per-hit columns as arrays in row order."""
+    event_id, n_hits = the run's length, the per-hit columns as arrays in row order.  `window_fields` names the rows'
+    sample window (merged rows call it sample_start / sample_end: merged_event_stream.merged_events_frame)."""
     import pandas as pd
 
     if len(rows) == 0:
@@ -120,8 +127,8 @@ def events_frame(rows: np.ndarray):
     starts = np.concatenate([[0], np.flatnonzero(ids[1:] != ids[:-1]) + 1, [len(rows)]])
     cols = {"dt": ("dt", np.int32), "boards": ("board", np.int16), "channels": ("channel", np.int16),
             "heights": ("height", np.float32), "integrals": ("integral", np.float32), "timestamps": ("timestamp", np.int64),
-            "record_ids": ("record_id", np.int64), "sample_starts": ("edge_start", np.int32),
-            "sample_ends": ("edge_end", np.int32)}
+            "record_ids": ("record_id", np.int64), "sample_starts": (window_fields[0], np.int32),
+            "sample_ends": (window_fields[1], np.int32)}
     flat = {k: np.ascontiguousarray(rows[f], dtype=t) for k, (f, t) in cols.items()}
     out = []
     for a, b in zip(starts[:-1].tolist(), starts[1:].tolist()):
@@ -202,6 +209,9 @@ class HitPushStream(_RecordsChunking, HipStreamingPlugin):
     def _check_scope(self, context: Any) -> None:
         """Refuse a Context the stream does not cover (before any upload)."""
 
+    def _run_margin(self, margin: float) -> None:
+        """Told the run's horizon margin (ps; `run_margin`) before `_begin`, for a device stream that takes it."""
+
     def _check_pool(self, pool: DevicePool) -> None:
         if int(pool.max_sessions) < 3:
             raise ValueError(f"{self.provides} needs a device pool with max_sessions >= 3 (two sessions for the hit "
@@ -233,7 +243,9 @@ class HitPushStream(_RecordsChunking, HipStreamingPlugin):
         pool = self._pool(context)
         self._check_pool(pool)
         inner = self._inner(cfg, pool)
-        horizons = chunk_horizons(chunks)
+        margin = run_margin(chunks)
+        horizons = chunk_horizons(chunks, margin)
+        self._run_margin(margin)
         stats = self.stats = self._new_stats()
         serial = not self.parallel or (max_workers is not None and int(max_workers) <= 1)
         if serial:
@@ -285,7 +297,9 @@ class HipHitGroupedStream(HitPushStream):
 
     Refused on the host, before any upload: a Context whose configuration sets merge_gap_ns > 0 for hit_merged (the
     static plugin would then group merged hits, which the stream does not build), and a device pool with fewer than three
-    sessions (two for the ring, one for the grouping)."""
+    sessions (two for the ring, one for the grouping).  The stream that does group merged hits is hit_merged_grouped_stream
+    (merged_event_stream.py); this one keeps its refusal, so that a configuration with merging never silently gets events
+    of unmerged hits."""
 
     provides = "hit_grouped_stream"
     description = "Coincidence events of the records stream, delivered as they close (HIP, gfx950)."
@@ -336,4 +350,4 @@ class HipHitGroupedStream(HitPushStream):
 
 
 __all__ = ["HipHitGroupedStream", "HitPushStream", "events_frame", "event_rows", "chunk_horizons", "horizon_of", "horizon_margin",
-           "run_magnitude", "abs_windows", "EVENT_HIT_DTYPE"]
+           "run_magnitude", "run_margin", "abs_windows", "EVENT_HIT_DTYPE"]

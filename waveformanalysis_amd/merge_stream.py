@@ -21,10 +21,11 @@ order: the result equals hit_merged, hit_merge_clusters and hit_merged_component
 
 The device part is wfa_merge_stream_* (DeviceSession.merge_stream_begin / _push / _end).
 
-Not built here: feeding these rows to hit_grouped_stream -- its kernels take 60-byte rows, and it would need the grouping
-horizon min(H, open_start); `open_start` (the smallest abs_start still carried) is reported with every chunk for that
-purpose, and hit_grouped_stream keeps refusing merge_gap_ns > 0.  Nor a device-to-device hand-over of the hit rows, nor
-several merging devices.
+The events of these rows come from hit_merged_grouped_stream (merged_event_stream.py): one push there is this stream's
+merge step followed by the grouping step on the same session, the merged rows handed over in HBM, under the grouping
+horizon min(H, open_start) -- `open_start` (the smallest abs_start still carried) is what this stream reports with every
+chunk.  hit_grouped_stream itself keeps refusing merge_gap_ns > 0.  Not built: a device-to-device hand-over of the hit
+rows, several merging devices.
 """
 
 from __future__ import annotations

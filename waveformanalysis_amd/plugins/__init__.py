@@ -77,7 +77,15 @@ def hip_streaming_merged():
     return hip_streaming_events() + [HipHitMergedStream()]
 
 
-__all__ = ["hip_streaming", "hip_streaming_events", "hip_streaming_merged", "HipWavePoolFilteredPlugin", "HipThresholdHitPlugin", "HipBasicFeaturesPlugin",
+def hip_streaming_merged_events():
+    """hip_streaming_merged() plus hit_merged_grouped_stream: the coincidence events of the merged hits, delivered as
+    they close -- the streamed form of hit_grouped whenever merging is on."""
+    from ..merged_event_stream import HipHitMergedGroupedStream
+
+    return hip_streaming_merged() + [HipHitMergedGroupedStream()]
+
+
+__all__ = ["hip_streaming", "hip_streaming_events", "hip_streaming_merged", "hip_streaming_merged_events", "HipWavePoolFilteredPlugin", "HipThresholdHitPlugin", "HipBasicFeaturesPlugin",
            "HipWaveformWidthIntegralPlugin", "HipHitGroupedPlugin", "HipHitFinderPlugin", "HipFilteredWaveformsPlugin",
            "HipWaveformWidthPlugin", "HipS1S2ClassifierPlugin", "HipHitMergeClustersPlugin",
            "HipHitMergePlugin", "HipHitMergedComponentsPlugin", "HipSignalPeaksStreamPlugin", "HipRecordsPlugin", "HipWavePoolPlugin",
