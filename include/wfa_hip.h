@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define WFA_ABI_VERSION 9
+#define WFA_ABI_VERSION 10
 
 #define WFA_OK 0
 #define WFA_E_INVALID (-1)   /* bad argument / malformed records (maps to ValueError) */
@@ -253,6 +253,18 @@ int wfa_hits_wait(wfa_ctx* ctx, int64_t* n_hits);
  * record stand.  It writes those records' slices of the float32 twin and nothing else (a twin that did not exist is
  * zeroed first), downloads nothing and does not wait for the device.
  *
+ * wfa_savgol_group is its Savitzky-Golay twin: wfa_savgol under the plan kept in `slot` (wfa_sg_plan_store), restricted
+ * to the records r with group_of_record[r] == group, over the uploaded table.  It writes those records' slices of the
+ * float32 twin and nothing else (a twin that did not exist is zeroed first), downloads nothing, does not wait for the
+ * device and waits out a pending queued hit pass first; the plan of wfa_set_sg_plan is untouched.  The route is the one
+ * wfa_savgol takes for the uploaded table (k_savgol_span on uniform records, padded or not, k_savgol on ragged ones); a
+ * record that is not a member is neither loaded nor stored.  The written samples are byte-identical to wfa_savgol on
+ * a table that holds only the member records, records shorter than the window included.  So a chunk whose channels
+ * resolve to several filter settings gets its float32 twin from one call per setting, with the whole chunk's table
+ * resident for the stages behind (wfa_find_peaks_count, wfa_peak_chain_count).
+ * WFA_E_INVALID: slot out of range, group_of_record NULL with records uploaded.  WFA_E_STATE: no records or no
+ * wave_pool uploaded, a slot without a stored plan.
+ *
  * wfa_hits_enqueue_groups queues, on the context's stream, the table of n_groups passes over the uploaded records.
  * The table: group g (in order) contributes the rows of one hit pass under the plan of groups[g].plan_slot
  * (WFA_SRC_SG_FUSED) or from the float32 twin (WFA_SRC_F32), in which only the records with group_of_record[r] == g can
@@ -295,6 +307,7 @@ int wfa_sg_plan_store(wfa_ctx* ctx, int slot, int window, int polyorder, const d
                       int int_ok, const int32_t* itab, int32_t den, int32_t den_edge, int64_t guard, int64_t guard_edge);
 int wfa_sosfiltfilt_group(wfa_ctx* ctx, int n_sections, const double* sos, const double* zi, int32_t padlen,
                           const int32_t* group_of_record, int32_t group);
+int wfa_savgol_group(wfa_ctx* ctx, int slot, const int32_t* group_of_record, int32_t group);
 int wfa_hits_enqueue_groups(wfa_ctx* ctx, int n_groups, const wfa_hit_group* groups, const int32_t* group_of_record,
                             int32_t bl_start, int32_t bl_end, int32_t left_extension, int32_t right_extension,
                             int32_t max_len);
@@ -369,8 +382,9 @@ int wfa_waveform_width_records(wfa_ctx* ctx, int source, int64_t n_hits, const i
  * cpu/basic_features.py:108-195, cpu/s1_s2_classifier.py:57-69,133-228).  Two-phase like the other row stages.
  * Needs uploaded records, the pool(s) of the two sources, and a wfa_find_peaks_count pass in signal mode
  * WFA_PEAK_SIGNAL_RECORDS whose rows are still resident (WFA_E_STATE otherwise).  count, on the context's stream:
- *  1. basic_features of the uploaded records (feature_source, height / area ranges as for wfa_basic_features, no
- *     fixed baseline) into a buffer of the stage -- the leaf kernel where wfa_basic_features would take it;
+ *  1. basic_features of the uploaded records (feature_source, height / area ranges as for wfa_basic_features; no
+ *     fixed baseline in wfa_peak_chain_count, the column `fixed_baseline` in wfa_peak_chain_count_fixed) into a buffer
+ *     of the stage -- the leaf kernel where wfa_basic_features would take it;
  *  2. k_peak_chain, one lane per peak row: the width of wfa_waveform_width_records (width_source) at (record_id,
  *     position) of the row, record_id being the INDEX of the record and of its feature row; a peak that call would mark
  *     valid = 0 is dropped.  Range cuts on float64(width), float64(area), float64(height): class_ranges = 6 x (lo, hi)
@@ -388,7 +402,13 @@ int wfa_waveform_width_records(wfa_ctx* ctx, int source, int64_t n_hits, const i
  * Scratch (wfa_release_scratch frees it, wfa_scratch_bytes counts it; fill after a release: WFA_E_STATE):
  *   36 B per record + 45 B per peak + 45 B per kept row.
  * The keep flags and their scan reuse two per-candidate buffers of find_peaks, which that pass has finished with
- * once its rows exist; they cost 12 B per peak and 8 B per 1024 peaks + 8 B only where a release has taken them. */
+ * once its rows exist; they cost 12 B per peak and 8 B per 1024 peaks + 8 B only where a release has taken them.
+ *
+ * wfa_peak_chain_count_fixed takes the arguments of wfa_peak_chain_count, then fixed_baseline (one float64 per uploaded
+ * record, NaN = none: the override of wfa_basic_features, basic_features.py:143-146), then n_rows.  Step 1 is then
+ * wfa_basic_features with that column: the feature rows in the stage's buffer equal that call's rows byte for byte.
+ * The column is an argument of the call, not state of the context.  fixed_baseline = NULL is wfa_peak_chain_count
+ * exactly, and wfa_peak_chain_count is that case of this entry. */
 #define WFA_S1S2_UNKNOWN 0
 #define WFA_S1S2_PREFER_S1 1
 #define WFA_S1S2_PREFER_S2 2
@@ -397,6 +417,12 @@ int wfa_peak_chain_count(wfa_ctx* ctx, int width_source, int feature_source, dou
                          int64_t height_start, int64_t height_end, int height_has_end, int64_t area_start,
                          int64_t area_end, int area_has_end, int width_in_samples, const double* class_ranges,
                          uint32_t range_bounds, int conflict_policy, int64_t record_id_base, int64_t* n_rows);
+int wfa_peak_chain_count_fixed(wfa_ctx* ctx, int width_source, int feature_source, double rise_low, double rise_high,
+                               double fall_high, double fall_low, double sampling_rate, int interpolation,
+                               int64_t height_start, int64_t height_end, int height_has_end, int64_t area_start,
+                               int64_t area_end, int area_has_end, int width_in_samples, const double* class_ranges,
+                               uint32_t range_bounds, int conflict_policy, int64_t record_id_base,
+                               const double* fixed_baseline, int64_t* n_rows);
 int wfa_peak_chain_fill(wfa_ctx* ctx, void* out_rows, int64_t n_rows);
 
 /* ---- hit-table stages (device sort + scans; host columns in, host index tables out) ----------------------

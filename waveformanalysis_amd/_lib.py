@@ -27,7 +27,7 @@ VIEW_WAVES, VIEW_WAVES_BASELINE, VIEW_SIGNALS = 0, 1, 2
 VIEW_U16, VIEW_F32, VIEW_F64 = 0, 1, 2
 DENSE_I16, DENSE_U16, DENSE_F32 = 0, 1, 2
 S1S2_UNKNOWN, S1S2_PREFER_S1, S1S2_PREFER_S2 = 0, 1, 2
-ABI_VERSION = 9
+ABI_VERSION = 10
 MAX_HIT_GROUPS = 8
 
 _p = C.c_void_p
@@ -65,6 +65,7 @@ SIGNATURES = {
     "wfa_hits_wait": (_int, [_p, C.POINTER(_i64)]),
     "wfa_sg_plan_store": (_int, [_p, _int, _int, _int, _p, _p, _int, _p, _i32, _i32, _i64, _i64]),
     "wfa_sosfiltfilt_group": (_int, [_p, _int, _p, _p, _i32, _p, _i32]),
+    "wfa_savgol_group": (_int, [_p, _int, _p, _i32]),
     "wfa_hits_enqueue_groups": (_int, [_p, _int, _p, _p, _i32, _i32, _i32, _i32, _i32]),
     "wfa_hits_pending": (_int, [_p, C.POINTER(_int)]),
     "wfa_find_peaks_count": (_int, [_p, _int, _int, _int, _f64, _int, _f64, _i32, _f64, _f64, _int, _i32, C.POINTER(_i64)]),
@@ -82,6 +83,8 @@ SIGNATURES = {
     "wfa_waveform_width_records": (_int, [_p, _int, _i64, _p, _p, _f64, _f64, _f64, _f64, _f64, _int, _p, _p]),
     "wfa_peak_chain_count": (_int, [_p, _int, _int, _f64, _f64, _f64, _f64, _f64, _int, _i64, _i64, _int, _i64, _i64, _int,
                                     _int, _p, C.c_uint32, _int, _i64, C.POINTER(_i64)]),
+    "wfa_peak_chain_count_fixed": (_int, [_p, _int, _int, _f64, _f64, _f64, _f64, _f64, _int, _i64, _i64, _int, _i64, _i64,
+                                          _int, _int, _p, C.c_uint32, _int, _i64, _p, C.POINTER(_i64)]),
     "wfa_peak_chain_fill": (_int, [_p, _p, _i64]),
     "wfa_hit_merge_count": (_int, [_p, _i64] + [_p] * 7 + [_f64, _f64, C.POINTER(_i64)]),
     "wfa_hit_merge_fill": (_int, [_p, _i64, _i64, _p, _p]),

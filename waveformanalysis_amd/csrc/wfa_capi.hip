@@ -1308,6 +1308,34 @@ int wfa_download_pool_f32_range(wfa_ctx* c, float* out, int64_t start, int64_t n
     return WFA_OK;
 }
 
+// K2 over the uploaded records (c->R > 0) under `plan`, into the float32 pool: the span kernel on uniform records, else
+// one wave per record.  sel (device, one int32 per record) != nullptr: only the records r with sel[r] == group
+// (wfa_savgol_group); the route is chosen from the layout of the whole table either way.
+static int savgol_launch(wfa_ctx* c, const SgPlanDev* plan, const int32_t* sel, int32_t group) {
+    int rc;
+    const SgParams sp0 = sg_params(plan);
+    const UniformLayout& u = c->layout;
+    const bool fast = sg_mask_supported(sp0) && !c->opt.no_fast;
+    // uniform records, L % 16 != 0: the span kernel reads the padded shadow and writes the packed pool
+    const bool padded = u.pad && u.L >= sp0.W && fast && !c->opt.no_pad;
+    LayoutView v;
+    if ((rc = layout_view(c, c->thr.as<double>(), padded, &v))) return rc;
+    LaunchTimer t(c);
+    if (padded || (u.span && u.L >= 16 && u.L >= sp0.W && fast)) {
+        SpanParams sp{};
+        sp.off0 = v.off0; sp.L = v.L; sp.positive = 0;
+        if (padded) { sp.S = v.S; sp.out_off0 = u.off0; }
+        sp.rs = 64;
+        sp.n_spans = (c->R + sp.rs - 1) / sp.rs;
+        // (the records as uploaded: their offsets address the output)
+        WFA_HIP_CHECK(launch_savgol_span(c->stream, v.pool, rec_view(c), sp0, sp, c->pool_f32.as<float>(), sel, group));
+        if (sel) return t.end(padded ? "k_savgol_span<padded, group>" : "k_savgol_span<group>");
+        return t.end(padded ? "k_savgol_span<padded>" : "k_savgol_span");
+    }
+    WFA_HIP_CHECK(launch_savgol(c->stream, v.pool, v.rec, sp0, c->pool_f32.as<float>(), sel, group));
+    return t.end(sel ? "k_savgol<group>" : "k_savgol");
+}
+
 int wfa_savgol(wfa_ctx* c, float* out) {
     int rc = use_device(c);
     if (rc) return rc;
@@ -1315,29 +1343,7 @@ int wfa_savgol(wfa_ctx* c, float* out) {
     if ((rc = c->pool_f32.ensure((size_t)c->pool_n * sizeof(float)))) return rc;
     // gaps between records stay 0.0 (records.py:382)
     if (!c->filter_keep) WFA_HIP_CHECK(hipMemsetAsync(c->pool_f32.ptr, 0, (size_t)c->pool_n * sizeof(float), c->stream));
-    if (c->R > 0) {
-        const SgParams sp0 = sg_params(ctx_plan(c));
-        const UniformLayout& u = c->layout;
-        const bool fast = sg_mask_supported(sp0) && !c->opt.no_fast;
-        // uniform records, L % 16 != 0: the span kernel reads the padded shadow and writes the packed pool
-        const bool padded = u.pad && u.L >= sp0.W && fast && !c->opt.no_pad;
-        LayoutView v;
-        if ((rc = layout_view(c, c->thr.as<double>(), padded, &v))) return rc;
-        LaunchTimer t(c);
-        if (padded || (u.span && u.L >= 16 && u.L >= sp0.W && fast)) {
-            SpanParams sp{};
-            sp.off0 = v.off0; sp.L = v.L; sp.positive = 0;
-            if (padded) { sp.S = v.S; sp.out_off0 = u.off0; }
-            sp.rs = 64;
-            sp.n_spans = (c->R + sp.rs - 1) / sp.rs;
-            // (the records as uploaded: their offsets address the output)
-            WFA_HIP_CHECK(launch_savgol_span(c->stream, v.pool, rec_view(c), sp0, sp, c->pool_f32.as<float>()));
-            if ((rc = t.end(padded ? "k_savgol_span<padded>" : "k_savgol_span"))) return rc;
-        } else {
-            WFA_HIP_CHECK(launch_savgol(c->stream, v.pool, v.rec, sp0, c->pool_f32.as<float>()));
-            if ((rc = t.end("k_savgol"))) return rc;
-        }
-    }
+    if (c->R > 0 && (rc = savgol_launch(c, ctx_plan(c), nullptr, 0))) return rc;
     c->have_f32 = true;
     if (out)
         WFA_HIP_CHECK(hipMemcpyAsync(out, c->pool_f32.ptr, (size_t)c->pool_n * sizeof(float),
@@ -1828,6 +1834,32 @@ int wfa_sosfiltfilt_group(wfa_ctx* c, int n_sections, const double* sos, const d
     return WFA_OK;
 }
 
+int wfa_savgol_group(wfa_ctx* c, int slot, const int32_t* group_of_record, int32_t group) {
+    int rc = use_device(c);
+    if (rc) return rc;
+    if (slot < 0 || slot >= WFA_MAX_HIT_GROUPS)
+        return fail(WFA_E_INVALID, "plan slot must be in [0, %d), got %d", WFA_MAX_HIT_GROUPS, slot);
+    if (!c->have_records) return fail(WFA_E_STATE, "records not uploaded");
+    if (!c->have_u16) return fail(WFA_E_STATE, "wave_pool (uint16) not uploaded");
+    if (!c->have_slot[slot]) return fail(WFA_E_STATE, "plan slot %d holds no plan (wfa_sg_plan_store)", slot);
+    if (c->R > 0 && !group_of_record) return fail(WFA_E_INVALID, "group_of_record is null");
+    if (c->pending) {  // a queued pass may read the twin
+        int64_t n = 0;
+        if ((rc = wfa_hits_wait(c, &n))) return rc;
+    }
+    const bool fresh = !c->have_f32 || c->pool_f32.cap < (size_t)c->pool_n * sizeof(float);
+    if ((rc = c->pool_f32.ensure((size_t)c->pool_n * sizeof(float)))) return rc;
+    // a twin that did not exist: gaps and the other groups' records read 0.0 until their own filter call
+    if (fresh) WFA_HIP_CHECK(hipMemsetAsync(c->pool_f32.ptr, 0, (size_t)c->pool_n * sizeof(float), c->stream));
+    if (c->R > 0) {
+        if ((rc = c->grp_gor.ensure((size_t)c->R * sizeof(int32_t)))) return rc;
+        if ((rc = h2d_copy(c, c->grp_gor.ptr, group_of_record, (size_t)c->R * sizeof(int32_t)))) return rc;
+        if ((rc = savgol_launch(c, &c->sg_slot[slot], c->grp_gor.as<int32_t>(), group))) return rc;
+    }
+    c->have_f32 = true;
+    return WFA_OK;
+}
+
 int wfa_hits_enqueue_groups(wfa_ctx* c, int n_groups, const wfa_hit_group* groups, const int32_t* group_of_record,
                             int32_t bl_start, int32_t bl_end, int32_t le, int32_t re, int32_t max_len) {
     int rc = use_device(c);
@@ -2212,6 +2244,16 @@ int wfa_peak_chain_count(wfa_ctx* c, int width_source, int feature_source, doubl
                          int64_t h1, int h_has_end, int64_t a0, int64_t a1, int a_has_end, int width_in_samples,
                          const double* class_ranges, uint32_t range_bounds, int conflict_policy, int64_t record_id_base,
                          int64_t* n_rows) {
+    return wfa_peak_chain_count_fixed(c, width_source, feature_source, rise_low, rise_high, fall_high, fall_low,
+                                      sampling_rate, interpolation, h0, h1, h_has_end, a0, a1, a_has_end, width_in_samples,
+                                      class_ranges, range_bounds, conflict_policy, record_id_base, nullptr, n_rows);
+}
+
+int wfa_peak_chain_count_fixed(wfa_ctx* c, int width_source, int feature_source, double rise_low, double rise_high,
+                               double fall_high, double fall_low, double sampling_rate, int interpolation, int64_t h0,
+                               int64_t h1, int h_has_end, int64_t a0, int64_t a1, int a_has_end, int width_in_samples,
+                               const double* class_ranges, uint32_t range_bounds, int conflict_policy,
+                               int64_t record_id_base, const double* fixed_baseline, int64_t* n_rows) {
     int rc = use_device(c);
     if (rc) return rc;
     if (!n_rows) return fail(WFA_E_INVALID, "n_rows is null");
@@ -2245,6 +2287,10 @@ int wfa_peak_chain_count(wfa_ctx* c, int width_source, int feature_source, doubl
     fp.h0 = h0; fp.h1 = h1; fp.h_has_end = h_has_end;
     fp.a0 = a0; fp.a1 = a1; fp.a_has_end = a_has_end;
     fp.fixed_bl = nullptr;
+    if (fixed_baseline) {  // per record, NaN = none: the column of wfa_basic_features
+        if ((rc = h2d(c, c->fixed_bl, fixed_baseline, (size_t)c->R * sizeof(double)))) return rc;
+        fp.fixed_bl = c->fixed_bl.as<double>();
+    }
     {
         LaunchTimer t(c);
         hipError_t e = hipSuccess;

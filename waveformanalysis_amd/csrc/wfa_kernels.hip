@@ -43,12 +43,16 @@ __global__ __launch_bounds__(kBlock) void k_baseline_mean(PoolView pool, RecView
 // =============================================================================================
 // K2: wave_pool_filtered materialisation  (records.py:368-438, filtering.py:377-407)
 // =============================================================================================
+// Record selection (wfa_savgol_group): with `sel` only the records r with sel[r] == sel_group are filtered, the waves of
+// the others move on at once and their slices of the output stay as they are.
 __global__ __launch_bounds__(kBlock) void k_savgol(PoolView pool, RecView rec, SgParams sg,
-                                                   float* __restrict__ out) {
+                                                   float* __restrict__ out, const int32_t* __restrict__ sel,
+                                                   int32_t sel_group) {
     const int lane = lane_id();
     const int64_t wave0 = (int64_t)blockIdx.x * kWavesPerBlock + wave_in_block();
     const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
     for (int64_t r = wave0; r < rec.R; r += nwaves) {
+        if (sel && sel[r] != sel_group) continue;
         const int L = rec.len[r];
         if (L <= 0) continue;
         const int64_t off = rec.off[r];
@@ -842,9 +846,16 @@ __global__ __launch_bounds__(kBlock, WFA_SPAN_WAVES) void k_sg_mask_span16(PoolV
 // (integer projection rows, literal below their guard) use the float64 code of k_savgol.
 // PADDED: input = the padded shadow pool (record stride S = roundup16(L), see wfa_capi: ensure_shadow), output = the
 // packed float32 pool (record stride L)
-template <int W, bool PADDED = false>
+// GROUPED (wfa_savgol_group): only the records r with sel[r] == sel_group are filtered.  A span's members are one
+// ballot word; a span without a member is skipped, in a mixed span a lane whose 8-sample chunk lies in another record
+// loads nothing (its registers read 0) and stores nothing.  A chunk never straddles two records (S % 8 == 0), and every
+// value that reads a neighbouring record's samples is one of the 2H edge values, which come from the record's own
+// samples (s_edge): a member's values are those of the ungrouped kernel.  Stores go out per lane, not through s_out,
+// whose two store instructions write other lanes' values.
+template <int W, bool PADDED = false, bool GROUPED = false>
 __global__ __launch_bounds__(kBlock) void k_savgol_span(PoolView pool, RecView rec, SgParams sg, SpanParams sp,
-                                                        float* __restrict__ out) {
+                                                        float* __restrict__ out, const int32_t* __restrict__ sel,
+                                                        int32_t sel_group) {
     constexpr int H = W / 2;
     constexpr int NP = H + 1;
     __shared__ float s_edge[kWavesPerBlock][kWave][2 * H];
@@ -878,8 +889,13 @@ __global__ __launch_bounds__(kBlock) void k_savgol_span(PoolView pool, RecView r
         const int nrec = (int)((rec.R - r0) < sp.rs ? (rec.R - r0) : sp.rs);
         const int64_t g_base = sp.off0 + r0 * S;                   // input
         const int64_t g_out = PADDED ? sp.out_off0 + r0 * L : g_base;  // output
+        uint64_t members = ~0ull;  // bit k: record r0 + k is filtered
+        if (GROUPED) {
+            members = __ballot(lane < nrec && sel[r0 + (lane < nrec ? lane : 0)] == sel_group);
+            if (members == 0) continue;
+        }
         // ---- edges: lane = record ----
-        if (lane < nrec) {
+        if (lane < nrec && (!GROUPED || ((members >> lane) & 1))) {
             const uint4* __restrict__ p = reinterpret_cast<const uint4*>(pool.u16) + ((g_base + (int64_t)lane * S) >> 3);
             WaveSrc<WFA_SRC_SG_FUSED> src = make_src<WFA_SRC_SG_FUSED>(pool, sg, g_base + (int64_t)lane * S, L);
 #pragma unroll 1
@@ -934,8 +950,12 @@ __global__ __launch_bounds__(kBlock) void k_savgol_span(PoolView pool, RecView r
         auto tile_at = [&](int t) {
             int pos = t * 512 + lane * 8;
             pos = pos < last_chunk_pos ? pos : last_chunk_pos;
-            const uint4 v = *reinterpret_cast<const uint4*>(span_ptr + pos);
             Tile x;
+            if (GROUPED && !((members >> (pos / S)) & 1)) {  // (pos / S < nrec <= 64)
+                x.d[0] = x.d[1] = x.d[2] = x.d[3] = 0;
+                return x;
+            }
+            const uint4 v = *reinterpret_cast<const uint4*>(span_ptr + pos);
             x.d[0] = v.x; x.d[1] = v.y; x.d[2] = v.z; x.d[3] = v.w;
             return x;
         };
@@ -944,7 +964,8 @@ __global__ __launch_bounds__(kBlock) void k_savgol_span(PoolView pool, RecView r
         uint32_t p0 = fillb, p1 = fillb, p2 = fillb, p3 = fillb;
         auto do_tile = [&](int t, const Tile& cur, const Tile& nxt) {
             const int pos = t * 512 + lane * 8;
-            const bool in_span = pos < span_samples;
+            // in the span, and (GROUPED) in a record of the group
+            const bool in_span = pos < span_samples && (!GROUPED || ((members >> (rl & 63)) & 1));
             uint32_t E[12];
 #pragma unroll
             for (int k = 0; k < 4; ++k) E[4 + k] = cur.d[k] ^ 0x80008000u;
@@ -997,7 +1018,7 @@ __global__ __launch_bounds__(kBlock) void k_savgol_span(PoolView pool, RecView r
                 }
             }
             if (!PADDED) {
-                if (t * 512 + 512 <= span_samples) {  // whole tile inside the span (wave-uniform)
+                if (!GROUPED && t * 512 + 512 <= span_samples) {  // whole tile inside the span (wave-uniform)
                     float4* stage = reinterpret_cast<float4*>(&s_out[wv][0]);
                     stage[2 * lane] = make_float4(y[0], y[1], y[2], y[3]);
                     stage[2 * lane + 1] = make_float4(y[4], y[5], y[6], y[7]);
@@ -3205,8 +3226,9 @@ hipError_t launch_baseline_mean(hipStream_t st, const PoolView& pool, const RecV
 }
 
 hipError_t launch_savgol(hipStream_t st, const PoolView& pool, const RecView& rec,
-                         const SgParams& sg, float* out) {
-    hipLaunchKernelGGL(k_savgol, dim3(grid_for_records(rec.R)), dim3(kBlock), 0, st, pool, rec, sg, out);
+                         const SgParams& sg, float* out, const int32_t* group_of_record, int32_t group) {
+    hipLaunchKernelGGL(k_savgol, dim3(grid_for_records(rec.R)), dim3(kBlock), 0, st, pool, rec, sg, out, group_of_record,
+                       group);
     return hipGetLastError();
 }
 
@@ -3546,15 +3568,21 @@ hipError_t launch_sg_mask(hipStream_t st, bool fused_baseline, int max_len, cons
 }
 
 hipError_t launch_savgol_span(hipStream_t st, const PoolView& pool, const RecView& rec, const SgParams& sg,
-                              const SpanParams& sp, float* out) {
+                              const SpanParams& sp, float* out, const int32_t* group_of_record, int32_t group) {
     int64_t g = (sp.n_spans + kWavesPerBlock - 1) / kWavesPerBlock;
     if (g < 1) g = 1;
     if (g > 1024) g = 1024;
     const int grid = (int)g;
+#define WFA_SVS2(WW, PAD, GRP)                                                                                        \
+    hipLaunchKernelGGL((k_savgol_span<WW, PAD, GRP>), dim3(grid), dim3(kBlock), 0, st, pool, rec, sg, sp, out,           \
+                       group_of_record, group)
 #define WFA_SVS(WW)                                                                                                  \
     case WW:                                                                                                         \
-        if (sp.S > sp.L) hipLaunchKernelGGL((k_savgol_span<WW, true>), dim3(grid), dim3(kBlock), 0, st, pool, rec, sg, sp, out); \
-        else hipLaunchKernelGGL((k_savgol_span<WW, false>), dim3(grid), dim3(kBlock), 0, st, pool, rec, sg, sp, out);   \
+        if (group_of_record) {                                                                                       \
+            if (sp.S > sp.L) WFA_SVS2(WW, true, true); else WFA_SVS2(WW, false, true);                                \
+        } else {                                                                                                     \
+            if (sp.S > sp.L) WFA_SVS2(WW, true, false); else WFA_SVS2(WW, false, false);                              \
+        }                                                                                                            \
         break;
     switch (sg.W) {
         WFA_SVS(5)
@@ -3566,6 +3594,7 @@ hipError_t launch_savgol_span(hipStream_t st, const PoolView& pool, const RecVie
         default: return hipErrorInvalidValue;
     }
 #undef WFA_SVS
+#undef WFA_SVS2
     return hipGetLastError();
 }
 

@@ -176,8 +176,10 @@ struct WidthParams {
 
 hipError_t launch_baseline_mean(hipStream_t st, const PoolView& pool, const RecView& rec,
                                 int32_t start, int32_t end, double* out);
+// group_of_record != nullptr (here, in launch_sosfiltfilt and in launch_savgol_span): only the records r with
+// group_of_record[r] == group
 hipError_t launch_savgol(hipStream_t st, const PoolView& pool, const RecView& rec,
-                         const SgParams& sg, float* out);
+                         const SgParams& sg, float* out, const int32_t* group_of_record = nullptr, int32_t group = 0);
 int hits_grid(int64_t R);
 int hits_waves(int64_t R);
 hipError_t launch_hits(hipStream_t st, int source, bool fused_baseline, const PoolView& pool,
@@ -251,7 +253,8 @@ hipError_t launch_pad_rows(hipStream_t st, const uint16_t* src, int64_t off0, in
 hipError_t launch_sg_mask(hipStream_t st, bool fused_baseline, int max_len, const PoolView& pool,
                           const RecView& rec, const SgParams& sg, const MaskParams& mp);
 hipError_t launch_savgol_span(hipStream_t st, const PoolView& pool, const RecView& rec, const SgParams& sg,
-                              const SpanParams& sp, float* out);
+                              const SpanParams& sp, float* out, const int32_t* group_of_record = nullptr,
+                              int32_t group = 0);
 bool sg_mask_span16_supported(const SgParams& sg, int L);
 hipError_t launch_sg_mask_span16(hipStream_t st, bool fused_baseline, const PoolView& pool, const RecView& rec,
                                  const SgParams& sg, const MaskParams& mp, const SpanParams& sp);

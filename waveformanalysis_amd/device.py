@@ -504,6 +504,15 @@ class DeviceSession:
                                                    int(group)))
         self._keep.append(gor)
 
+    def savgol_group(self, slot: int, group_of_record, group: int) -> None:
+        """The Savitzky-Golay filter of plan slot `slot` (store_sg_plan) over the uploaded records table, restricted to
+        the records of `group`, into the device float32 twin (wfa_savgol_group): no records upload, nothing downloaded,
+        nothing waited for."""
+        gor = self._group_column(group_of_record)
+        self._drop_f32_tags()  # the device float32 pool is this filter's output now
+        _lib.check(self._lib.wfa_savgol_group(self._h, int(slot), _ptr(gor), int(group)))
+        self._keep.append(gor)
+
     def hits_enqueue_groups(self, groups, group_of_record, left_extension: int = 2, right_extension: int = 2,
                             max_len: int = 0, baseline_window: tuple[int, int] = (0, 0)) -> None:
         """Queue the grouped hit pass (wfa_hits_enqueue_groups): groups = [(source, plan slot)], group_of_record = one
@@ -611,12 +620,13 @@ class DeviceSession:
                    interpolation: bool = True, height_range=(40, 90), area_range=(0, None), width_unit: str = "ns",
                    s1_width_range=None, s2_width_range=None, s1_area_range=None, s2_area_range=None,
                    s1_height_range=None, s2_height_range=None, conflict_policy: str = "unknown", strict: bool = False,
-                   record_id_base: int = 0) -> np.ndarray:
+                   record_id_base: int = 0, fixed_baseline: np.ndarray | None = None) -> np.ndarray:
         """S1_S2_CLASSIFIER_DTYPE rows of the resident rows of the last find_peaks pass on the uploaded records: the
         chain waveform_width (records route) -> s1_s2 with basic_features on the side, on the device
         (wfa_peak_chain_count / _fill).  Keyword arguments are the plugins' options; a peak's record_id is the index of
         its record, the rows carry record_id + record_id_base.  The peak rows stay (download_peaks still delivers
-        them)."""
+        them).  fixed_baseline: basic_features' per-record override (one float64 per uploaded record, NaN = none), handed
+        to the device only when given (wfa_peak_chain_count_fixed)."""
         from .plugins.s1_s2 import class_ranges  # (the plugins import this module)
 
         ranges = class_ranges(s1_width_range=s1_width_range, s2_width_range=s2_width_range, s1_area_range=s1_area_range,
@@ -634,11 +644,20 @@ class DeviceSession:
         h0, h1 = height_range
         a0, a1 = area_range
         n = C.c_int64(0)
-        _lib.check(self._lib.wfa_peak_chain_count(
-            self._h, int(width_source), int(feature_source), float(rise_low), float(rise_high), float(fall_high),
-            float(fall_low), float(sampling_rate), int(bool(interpolation)), int(h0 or 0), int(h1 or 0),
-            int(h1 is not None), int(a0 or 0), int(a1 or 0), int(a1 is not None), int(width_unit == "samples"),
-            _ptr(bounds), mask, policy, int(record_id_base), C.byref(n)))
+        args = (self._h, int(width_source), int(feature_source), float(rise_low), float(rise_high), float(fall_high),
+                float(fall_low), float(sampling_rate), int(bool(interpolation)), int(h0 or 0), int(h1 or 0),
+                int(h1 is not None), int(a0 or 0), int(a1 or 0), int(a1 is not None), int(width_unit == "samples"),
+                _ptr(bounds), mask, policy, int(record_id_base))
+        if fixed_baseline is None:
+            _lib.check(self._lib.wfa_peak_chain_count(*args, C.byref(n)))
+        else:
+            fb = np.ascontiguousarray(fixed_baseline, dtype=np.float64)
+            if fb.shape != (self.n_records,):
+                raise ValueError("fixed_baseline must have one entry per record")
+            _lib.check(self._lib.wfa_peak_chain_count_fixed(*args, _ptr(fb), C.byref(n)))
+        # a count that found rows has waited for the stream: the group columns of the filter calls before it are copied
+        if self._keep and n.value > 0 and not self.hits_pending():
+            self._keep.clear()
         out = np.empty(int(n.value), dtype=S1_S2_CLASSIFIER_DTYPE)
         _lib.check(self._lib.wfa_peak_chain_fill(self._h, _ptr(out), int(n.value)))
         return out
