@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define WFA_ABI_VERSION 10
+#define WFA_ABI_VERSION 11
 
 #define WFA_OK 0
 #define WFA_E_INVALID (-1)   /* bad argument / malformed records (maps to ValueError) */
@@ -570,6 +570,41 @@ int wfa_merged_event_stream_end(wfa_ctx* ctx);
 int wfa_group_multi_channel_count(wfa_ctx* ctx, int64_t n_hits, const int64_t* timestamp, const int64_t* channel,
                                   double time_window_ps, int64_t* n_events);
 int wfa_group_multi_channel_fill(wfa_ctx* ctx, int64_t n_hits, int64_t n_events, int64_t* order, int64_t* bounds);
+
+/* df_events stream: the fixed-window grouping above chunk by chunk, the rows of the events still open kept on the device
+ * between pushes.  Input rows are 40 B (DF_ROW_DTYPE, host memory): timestamp i8 @0, record_id i8 @8, area f4 @16,
+ * height f4 @20, amp f4 @24, max_abs_diff f4 @28, board i2 @32, channel i2 @34, reserved u4 @36 (must be 0).
+ * A horizon H is an int64 such that every row not yet pushed has timestamp >= H.  A push appends its rows (NULL with
+ * n_rows = 0 is a pure flush) behind the carried rows -- the carry keeps its original row order, so ties of the stable
+ * sort fall where the whole table would put them -- and runs the sort and chain of wfa_group_multi_channel_count over
+ * that table.  An event with anchor (first row's) timestamp a is closed iff (double)H > (double)a + time_window_ps,
+ * strictly, in float64, or if the push is final (final != 0).  Anchors do not decrease and the conversion int64 ->
+ * float64 is monotone: the closed events are a prefix of the chain, and a later row has
+ * (double)ts >= (double)H > (double)a + time_window_ps >= (double) of every member, so it can neither join nor precede
+ * them.  The rows of all other events stay on the device in row order (the carry) and are chained again with the next
+ * push's rows.  All rows pushed, in any chunking, give the rows of the static pass over the whole table.
+ * _push reports the rows and events this push closed and the rows carried; _fill delivers those rows, 64 B
+ * (DF_EVENT_ROW_DTYPE): event_id i8 @0 (continuing the count of the events closed before), t_min i8 @8, t_max i8 @16 (the
+ * timestamps of the event's first and last row after the channel sort, as the static pass: not the extremes),
+ * timestamp i8 @24, record_id i8 @32, area f4 @40, height f4 @44, amp f4 @48, max_abs_diff f4 @52, n_hits i4 @56,
+ * board i2 @60, channel i2 @62; one row per member, events in chain order, inside an event the static pass's order.
+ * time_window_ps = time_window_ns * 1e3, formed by the caller as for the static pass.
+ * Host waits of a push: one for the counts (the control block), as in wfa_event_stream_push, and, because the static
+ * pass's radix sort is reused as it is, one per sort for its key ranges (two sorts: the table by timestamp, the closed
+ * prefix by (event, channel)), one when the push ends, and one more in a push that has to grow the carry buffer; _fill
+ * waits for its copy.
+ * Refused with WFA_E_INVALID, the stream left as it was: a negative or NaN window (_begin); a pushed row whose timestamp
+ * lies below the previous push's horizon; a horizon below the previous one; a pushed row with reserved != 0; carry +
+ * pushed rows >= 2^31.  _push without _begin, _fill before a push or after a refused one: WFA_E_STATE; _fill with another
+ * row count: WFA_E_INVALID.  _begin on an open stream starts over.  A context may hold this stream open beside the event,
+ * merge and merged-event streams.
+ * The carry and the rows of the last push are state: wfa_release_scratch keeps them, wfa_scratch_bytes does not count
+ * them, _end frees them (40 B per carried row in each of two buffers, 64 B per row of the largest push). */
+int wfa_df_event_stream_begin(wfa_ctx* ctx, double time_window_ps);
+int wfa_df_event_stream_push(wfa_ctx* ctx, const void* rows, int64_t n_rows, int64_t horizon_ts, int final,
+                             int64_t* n_out_rows, int64_t* n_out_events, int64_t* n_carry);
+int wfa_df_event_stream_fill(wfa_ctx* ctx, void* out_rows, int64_t n_out_rows);
+int wfa_df_event_stream_end(wfa_ctx* ctx);
 
 /* ---- records builder (reference: processing/records_builder.py) -------------------------------------------------
  * K12 global record order: np.lexsort((seq, channel, board, pid, timestamp)) (records_builder.py:115-120), i.e. the

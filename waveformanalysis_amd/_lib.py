@@ -27,7 +27,7 @@ VIEW_WAVES, VIEW_WAVES_BASELINE, VIEW_SIGNALS = 0, 1, 2
 VIEW_U16, VIEW_F32, VIEW_F64 = 0, 1, 2
 DENSE_I16, DENSE_U16, DENSE_F32 = 0, 1, 2
 S1S2_UNKNOWN, S1S2_PREFER_S1, S1S2_PREFER_S2 = 0, 1, 2
-ABI_VERSION = 10
+ABI_VERSION = 11
 MAX_HIT_GROUPS = 8
 
 _p = C.c_void_p
@@ -105,6 +105,10 @@ SIGNATURES = {
     "wfa_merged_event_stream_end": (_int, [_p]),
     "wfa_group_multi_channel_count": (_int, [_p, _i64, _p, _p, _f64, C.POINTER(_i64)]),
     "wfa_group_multi_channel_fill": (_int, [_p, _i64, _i64, _p, _p]),
+    "wfa_df_event_stream_begin": (_int, [_p, _f64]),
+    "wfa_df_event_stream_push": (_int, [_p, _p, _i64, _i64, _int, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "wfa_df_event_stream_fill": (_int, [_p, _p, _i64]),
+    "wfa_df_event_stream_end": (_int, [_p]),
     "wfa_v1725_index": (_int, [_p, _i64, _i64, _p, _p, _p, _p, _p, _p, C.POINTER(_i64)]),
     "wfa_records_sort": (_int, [_p, _i64, _p, _p, _p, _p, _p]),
     "wfa_pool_gather": (_int, [_p, _i64, _p, _p, _p, _i64, _p, _p, _i64]),

@@ -879,8 +879,9 @@ int wfa_release_scratch(wfa_ctx* c, int64_t* freed_bytes) {
     if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
     // what a later call rebuilds by itself.  Kept: the resident pools, the records columns, the filter plan, the rows of the
     // last passes (hit_out / hit_desc / peak_out / out_rows / gathered: *_fill and the resident hit-table stages read them),
-    // the CSV sample arena (source of wfa_csv_arena_gather), the carry and the last rows of an open event stream (state
-    // between pushes, freed by wfa_event_stream_end), the pinned staging ring and the small control blocks.  The
+    // the CSV sample arena (source of wfa_csv_arena_gather), the carry and the last rows of an open event, merge,
+    // merged-event or df_events stream (state between pushes, freed by the stream's _end), the pinned staging ring and the
+    // small control blocks.  The
     // samples of the last wfa_csv_decode_fill live in a scratch slot: they go, and wfa_pool_gather(src_pool = NULL) refuses
     // until the next decode.
     int64_t freed = 0;

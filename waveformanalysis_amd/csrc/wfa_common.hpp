@@ -296,6 +296,20 @@ struct wfa_ctx {
         EventStream e;
     } mes;
     wfa::DevBuf mes_mcarry[2], mes_mindex[2], mes_mindex_out, mes_carry[2], mes_out;
+    // df_events stream (wfa_df_event_stream_*, wfa_hits.hip): the fixed-window grouping chunk by chunk.  The rows of the
+    // events still open after the last push, as 40-byte DF_ROW_DTYPE rows in their original order in ds_carry[ds.cur] (a
+    // push compacts them into the other buffer), and the 64-byte rows the last push closed.  State of its own beside es,
+    // ms and mes: wfa_release_scratch keeps it, wfa_df_event_stream_end frees it
+    struct DfEventStream {
+        bool open = false;
+        double window_ps = 0.0;
+        int64_t horizon = INT64_MIN;  // horizon of the last accepted push (the smallest int64 before the first)
+        int64_t next_event = 0;       // events emitted so far = id of the next one
+        int64_t n_carry = 0;
+        int cur = 0;
+        int64_t out_rows = -1;        // rows of the last push waiting in ds_out; -1: no push yet, or the last was refused
+    } ds;
+    wfa::DevBuf ds_carry[2], ds_out;
     wfa::DevBuf bw_scratch{scratch};  // float64 forward pass of sosfiltfilt, [sample][record-in-batch]
 
     // profiling: HIP events around every launch on the context's stream.  The pairs are only recorded while the

@@ -1497,6 +1497,213 @@ int stream_d2h(wfa_ctx* c, void* dst, const void* src, size_t bytes) {
     return WFA_OK;
 }
 
+// ---- df_events stream (wfa_df_event_stream_*) -------------------------------------------------------------------------
+// The fixed-window grouping chunk by chunk.  A push chains carry ++ new rows like wfa_group_multi_channel_count (stable
+// sort by timestamp, next search, pointer jumping) and closes the events whose anchor a has (double)H > (double)a + window,
+// strictly, or all of them when the push is final.  Anchors ascend and the float64 sum is monotone, so the closed events
+// are a prefix of the chain, and since an event is a run of the timestamp order, their rows are the sorted positions
+// [0, n_out) with n_out = the position of the first open anchor: one number says which events close, which rows go out
+// and which stay.  Only that prefix is sorted again by (event, channel).
+constexpr int kDfsBadReserved = 1;
+struct DfsCtl {
+    unsigned long long min_key;     // ord_i64 of the smallest timestamp among the pushed rows
+    unsigned long long first_open;  // sorted position of the first open event's anchor; n: every event closes
+    long long n_closed;             // events of the closed prefix
+    int flags, pad;
+};
+
+// 40-byte rows as 5 qwords: timestamp @0, record_id @1, area | height @2, amp | max_abs_diff @3, board | channel | reserved @4.
+// The timestamp and channel columns of the whole table for the chain; of the pushed rows [n_carry, n) the smallest
+// timestamp and the reserved check
+__global__ __launch_bounds__(kTB) void k_dfs_cols(int64_t n, int64_t n_carry, const int64_t* __restrict__ rows,
+                                                  int64_t* __restrict__ ts, int64_t* __restrict__ ch,
+                                                  DfsCtl* __restrict__ ctl) {
+    const int64_t i = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    unsigned long long lo = ~0ull;
+    int bad = 0;
+    if (i < n) {
+        const int64_t t = rows[i * 5];
+        const uint64_t tail = (uint64_t)rows[i * 5 + 4];
+        ts[i] = t;
+        ch[i] = (int64_t)(int16_t)(uint16_t)(tail >> 16);
+        if (i >= n_carry) {
+            lo = ord_i64(t);
+            if (tail >> 32) bad = kDfsBadReserved;
+        }
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned long long ol = __shfl_xor(lo, d);
+        lo = ol < lo ? ol : lo;
+        bad |= __shfl_xor(bad, d);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (lo != ~0ull) atomicMin(&ctl->min_key, lo);
+        if (bad) atomicOr(&ctl->flags, bad);
+    }
+}
+
+// the close rule over the anchors (the marked sorted positions): open <=> not final and not (double)H > anchor + window
+__global__ __launch_bounds__(kTB) void k_dfs_closed(int64_t n, const int64_t* __restrict__ mark,
+                                                    const double* __restrict__ ts_f, double window_ps, double horizon,
+                                                    int final, DfsCtl* __restrict__ ctl) {
+    const int64_t j = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    unsigned long long lo = ~0ull;
+    if (j < n && !final && mark[j] && !(horizon > ts_f[j] + window_ps)) lo = (unsigned long long)j;
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned long long ol = __shfl_xor(lo, d);
+        lo = ol < lo ? ol : lo;
+    }
+    if ((threadIdx.x & 63) == 0 && lo != ~0ull) atomicMin(&ctl->first_open, lo);
+}
+// events before the first open anchor (incl = the inclusive scan of the marks)
+__global__ void k_dfs_count(int64_t n, const int64_t* __restrict__ incl, DfsCtl* __restrict__ ctl) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const unsigned long long fo = ctl->first_open;
+    ctl->n_closed = fo >= (unsigned long long)n ? incl[n - 1] : incl[fo] - 1;
+}
+
+// one key for the (event, channel) order of the closed prefix [0, n_out) of the timestamp order: the event index above
+// the 16 bits of the int16 channel
+__global__ void k_dfs_keys(int64_t n_out, const int64_t* __restrict__ perm, const int64_t* __restrict__ incl,
+                           const int64_t* __restrict__ ch, uint64_t* __restrict__ key) {
+    const int64_t j = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (j < n_out) key[j] = ((uint64_t)(incl[j] - 1) << 16) | ((uint64_t)(ch[perm[j]] + 32768) & 0xffffu);
+}
+
+// 64-byte rows as 16 dwords, lanes over dwords: event_id, t_min, t_max (6 dwords), the input row's first 8 dwords
+// (timestamp .. max_abs_diff), n_hits, board | channel.  Output row p is sorted position order[p] = table row
+// perm[order[p]]; event e holds the output rows [bounds[e], bounds[e + 1]) and t_min / t_max are the timestamps of its
+// first and last output row (after the channel sort: not the extremes)
+__global__ __launch_bounds__(kTB) void k_dfs_rows(int64_t n_out, const int64_t* __restrict__ order,
+                                                  const int64_t* __restrict__ perm, const int64_t* __restrict__ incl,
+                                                  const int64_t* __restrict__ bounds, int64_t first_event,
+                                                  const uint32_t* __restrict__ rows, uint32_t* __restrict__ out) {
+    const int64_t d = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (d >= n_out * 16) return;
+    const int64_t p = d >> 4;
+    const int w = (int)(d & 15);
+    const int64_t q = order[p];
+    const int64_t i = perm[q];
+    if (w >= 6 && w < 14) { out[d] = rows[i * 10 + (w - 6)]; return; }
+    if (w == 15) { out[d] = rows[i * 10 + 8]; return; }
+    const int64_t ev = incl[q] - 1;
+    const int64_t a = bounds[ev], b = bounds[ev + 1];
+    if (w == 14) { out[d] = (uint32_t)(b - a); return; }
+    const int64_t edge = perm[order[w < 4 ? a : b - 1]];
+    const uint32_t* src = rows + edge * 10;
+    const int64_t v = w < 2 ? first_event + ev : (int64_t)((uint64_t)src[0] | ((uint64_t)src[1] << 32));
+    out[d] = (w & 1) ? (uint32_t)((uint64_t)v >> 32) : (uint32_t)(uint64_t)v;
+}
+
+// keep flag per table row: 1 where its sorted position lies behind the closed prefix
+__global__ void k_dfs_keep(int64_t n, int64_t n_out, const int64_t* __restrict__ perm, int64_t* __restrict__ flag) {
+    const int64_t j = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (j < n) flag[perm[j]] = j >= n_out ? 1 : 0;
+}
+
+struct DfsStepOut {
+    int64_t n_out = 0, n_closed = 0, n_keep = 0;
+    bool flip = false;  // the carry went to the other buffer
+};
+
+// One push over the table in ds_carry[ds.cur]: ds.n_carry carried rows, then the pushed ones.  Reads the stream's state
+// and changes none of it; the caller commits.
+int dfs_step(wfa_ctx* c, const wfa_ctx::DfEventStream& ds, const void* rows_in, int64_t n_rows, int64_t horizon_ts, int final,
+             DfsStepOut* r) {
+    int rc;
+    *r = DfsStepOut{};
+    const int64_t n = ds.n_carry + n_rows;
+    if (n == 0) return WFA_OK;  // nothing carried, nothing pushed: no launch
+    c->ht_n = -1;  // the scratch slots a static count pass left for its fill are overwritten
+    DevBuf& table = c->ds_carry[ds.cur];
+    if ((rc = es_grow(c, table, (size_t)ds.n_carry * 40, (size_t)n * 40))) return rc;
+    // the pushed rows behind the carry (a refused push leaves them there: they lie behind n_carry and are overwritten)
+    if (n_rows > 0 && (rc = h2d_copy(c, table.as<uint8_t>() + (size_t)ds.n_carry * 40, rows_in, (size_t)n_rows * 40))) return rc;
+    int levels = 1;
+    while ((1ll << levels) < n) ++levels;  // next^(2^levels) of any row is n
+    int64_t *ts, *ch, *mark, *incl;
+    uint64_t *k_ts, *k_ch;
+    double* ts_f;
+    int32_t* jump;  // two levels, J_k and J_(k+1), used in turn
+    DfsCtl* d_ctl;
+    if ((rc = slot(c, S_TS, n, &ts)) || (rc = slot(c, S_POS, n, &ch)) || (rc = slot(c, S_K0, n, &k_ts)) ||
+        (rc = slot(c, S_K1, n, &k_ch)) || (rc = slot(c, S_ABS0, n, &ts_f)) || (rc = slot(c, S_FLAG, n, &mark)) ||
+        (rc = slot(c, S_ID, n, &incl)) || (rc = slot(c, S_OUT3, 2 * (n + 1), &jump)) || (rc = slot(c, S_ES, 1, &d_ctl)))
+        return rc;
+    LaunchTimer t(c);
+    DfsCtl ctl{~0ull, (unsigned long long)n, 0, 0, 0};
+    WFA_HIP_CHECK(hipMemcpyAsync(d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_dfs_cols, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, ds.n_carry, table.as<int64_t>(), ts, ch, d_ctl);
+    // the chain of the static pass over the whole table (k_mc_keys as the static pass launches it: its channel key is not
+    // read here, the closed prefix gets a key of its own below)
+    hipLaunchKernelGGL(k_mc_keys, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, ts, ch, k_ts, k_ch);
+    int64_t* perm = nullptr;
+    {
+        const uint64_t* keys[1] = {k_ts};  // stable: the carry stands in front of the pushed rows, as in the whole table
+        if ((rc = lexsort(c, n, keys, 1, &perm))) return rc;  // (its wait covers the upload of `ctl`)
+    }
+    hipLaunchKernelGGL(k_mc_sorted_ts, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, ts, perm, ts_f);
+    hipLaunchKernelGGL(k_mc_next, dim3(blocks_for(n + 1)), dim3(kTB), 0, c->stream, n, ts_f, ds.window_ps, jump);
+    WFA_HIP_CHECK(hipMemsetAsync(mark, 0, (size_t)n * sizeof(int64_t), c->stream));
+    static const int64_t one = 1;
+    WFA_HIP_CHECK(hipMemcpyAsync(mark, &one, sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    for (int k = 0; k < levels; ++k)
+        hipLaunchKernelGGL(k_mc_mark_jump, dim3(blocks_for(n + 1)), dim3(kTB), 0, c->stream, n, jump + (int64_t)(k & 1) * (n + 1),
+                           jump + (int64_t)((k + 1) & 1) * (n + 1), mark);
+    if ((rc = plus_scan(c, mark, incl, n))) return rc;
+    // the close rule, the prefix count, the checks of the pushed rows; one read of the control block
+    hipLaunchKernelGGL(k_dfs_closed, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, mark, ts_f, ds.window_ps, (double)horizon_ts,
+                       final ? 1 : 0, d_ctl);
+    hipLaunchKernelGGL(k_dfs_count, dim3(1), dim3(64), 0, c->stream, n, incl, d_ctl);
+    WFA_HIP_CHECK(hipGetLastError());
+    WFA_HIP_CHECK(hipMemcpyAsync(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (ctl.flags & kDfsBadReserved) return fail(WFA_E_INVALID, "a pushed row has reserved != 0");
+    if (n_rows > 0 && ctl.min_key < ((uint64_t)ds.horizon ^ 0x8000000000000000ull))
+        return fail(WFA_E_INVALID, "a pushed row's timestamp lies below the previous push's horizon (%lld ps)", (long long)ds.horizon);
+    const int64_t n_out = ctl.first_open < (unsigned long long)n ? (int64_t)ctl.first_open : n;
+    const int64_t n_closed = (int64_t)ctl.n_closed, n_keep = n - n_out;
+    if (n_closed < 0 || n_closed > n_out || (n_closed == 0) != (n_out == 0))
+        return fail(WFA_E_HIP, "df_events stream: inconsistent counts");
+    if (n_out > 0) {
+        // the (event, channel) order of the closed prefix (the second sort takes lexsort's buffers: the timestamp order
+        // moves out of them first), the events' bounds in it, the rows
+        int64_t *perm_ts, *bounds, *order = nullptr;
+        uint64_t* key;
+        if ((rc = slot(c, S_OUT1, n, &perm_ts)) || (rc = slot(c, S_K2, n_out, &key)) || (rc = slot(c, S_OUT0, n_closed + 1, &bounds)) ||
+            (rc = c->ds_out.ensure((size_t)n_out * 64)))
+            return rc;
+        WFA_HIP_CHECK(hipMemcpyAsync(perm_ts, perm, (size_t)n * 8, hipMemcpyDeviceToDevice, c->stream));
+        hipLaunchKernelGGL(k_dfs_keys, dim3(blocks_for(n_out)), dim3(kTB), 0, c->stream, n_out, perm_ts, incl, ch, key);
+        {
+            const uint64_t* keys[1] = {key};
+            if ((rc = lexsort(c, n_out, keys, 1, &order))) return rc;
+        }
+        hipLaunchKernelGGL(k_mc_bounds, dim3(blocks_for(n_out)), dim3(kTB), 0, c->stream, n_out, mark, incl, n_closed, bounds);
+        hipLaunchKernelGGL(k_dfs_rows, dim3(blocks_for(n_out * 16)), dim3(kTB), 0, c->stream, n_out, order, perm_ts, incl, bounds,
+                           ds.next_event, table.as<uint32_t>(), c->ds_out.as<uint32_t>());
+        // the rows of the open events, in row order, into the other carry buffer (all open: the table is the carry)
+        if (n_keep > 0) {
+            DevBuf& other = c->ds_carry[ds.cur ^ 1];
+            int64_t *keep, *keep_incl;
+            if ((rc = other.ensure((size_t)n_keep * 40)) || (rc = slot(c, S_K3, n, &keep)) || (rc = slot(c, S_K4, n, &keep_incl)))
+                return rc;
+            hipLaunchKernelGGL(k_dfs_keep, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, n_out, perm_ts, keep);
+            if ((rc = plus_scan(c, keep, keep_incl, n))) return rc;
+            hipLaunchKernelGGL(k_es_compact<10>, dim3(blocks_for(n * 10)), dim3(kTB), 0, c->stream, n, keep, keep_incl,
+                               table.as<uint32_t>(), other.as<uint32_t>());
+        }
+    }
+    WFA_HIP_CHECK(hipGetLastError());
+    if ((rc = t.end("df_events stream: chain, closed prefix, rows, carry"))) return rc;
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    r->n_out = n_out;
+    r->n_closed = n_closed;
+    r->n_keep = n_keep;
+    r->flip = n_keep > 0 && n_out > 0;
+    return WFA_OK;
+}
+
 }  // namespace
 }  // namespace wfa
 
@@ -1991,6 +2198,68 @@ int wfa_merged_event_stream_end(wfa_ctx* c) {
                       &c->mes_carry[0], &c->mes_carry[1], &c->mes_out})
         b->release();
     c->mes = wfa_ctx::MergedEventStream{};
+    return WFA_OK;
+}
+
+// ---- df_events stream -------------------------------------------------------------------------------------------------
+int wfa_df_event_stream_begin(wfa_ctx* c, double time_window_ps) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (!(time_window_ps >= 0)) return fail(WFA_E_INVALID, "time_window_ps must be >= 0");
+    if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->ds = wfa_ctx::DfEventStream{};  // (a stream left open starts over: empty carry, event id 0; the buffers are reused)
+    c->ds.open = true;
+    c->ds.window_ps = time_window_ps;
+    return WFA_OK;
+}
+
+int wfa_df_event_stream_push(wfa_ctx* c, const void* rows, int64_t n_rows, int64_t horizon_ts, int final, int64_t* n_out_rows,
+                             int64_t* n_out_events, int64_t* n_carry) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    wfa_ctx::DfEventStream& ds = c->ds;
+    if (!ds.open) return fail(WFA_E_STATE, "no df_events stream is open (wfa_df_event_stream_begin first)");
+    ds.out_rows = -1;  // (nothing to fill after a refused push)
+    if (n_rows < 0 || (n_rows > 0 && !rows) || !n_out_rows || !n_out_events || !n_carry) return fail(WFA_E_INVALID, "bad arguments");
+    if (horizon_ts < ds.horizon)
+        return fail(WFA_E_INVALID, "the horizon (%lld ps) lies below the previous push's (%lld ps)", (long long)horizon_ts,
+                    (long long)ds.horizon);
+    if (n_rows >= 0x80000000LL - ds.n_carry)
+        return fail(WFA_E_INVALID, "carry (%lld rows) + pushed rows (%lld) reach the table limit of 2^31 rows",
+                    (long long)ds.n_carry, (long long)n_rows);
+    DfsStepOut r;
+    if ((rc = dfs_step(c, ds, rows, n_rows, horizon_ts, final, &r))) return rc;
+    if (r.flip) ds.cur ^= 1;
+    ds.n_carry = r.n_keep;
+    ds.next_event += r.n_closed;
+    ds.horizon = horizon_ts;
+    ds.out_rows = r.n_out;
+    *n_out_rows = r.n_out;
+    *n_out_events = r.n_closed;
+    *n_carry = r.n_keep;
+    return WFA_OK;
+}
+
+int wfa_df_event_stream_fill(wfa_ctx* c, void* out_rows, int64_t n_out_rows) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (!c->ds.open || c->ds.out_rows < 0) return fail(WFA_E_STATE, "no df_events stream push has been made");
+    if (n_out_rows != c->ds.out_rows)
+        return fail(WFA_E_INVALID, "caller expects %lld rows, the last push closed %lld", (long long)n_out_rows,
+                    (long long)c->ds.out_rows);
+    if (n_out_rows == 0) return WFA_OK;
+    if (!out_rows) return fail(WFA_E_INVALID, "out_rows is null");
+    if ((rc = stream_d2h(c, out_rows, c->ds_out.ptr, (size_t)n_out_rows * 64))) return rc;
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return WFA_OK;
+}
+
+int wfa_df_event_stream_end(wfa_ctx* c) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    for (DevBuf* b : {&c->ds_carry[0], &c->ds_carry[1], &c->ds_out}) b->release();
+    c->ds = wfa_ctx::DfEventStream{};
     return WFA_OK;
 }
 

@@ -18,6 +18,8 @@ import numpy as np
 from . import _lib
 from .dtypes import (
     BASIC_FEATURES_DTYPE,
+    DF_EVENT_ROW_DTYPE,
+    DF_ROW_DTYPE,
     EVENT_HIT_DTYPE,
     EVENT_MERGED_HIT_DTYPE,
     HIT_DTYPE,
@@ -1050,6 +1052,33 @@ class DeviceSession:
     def merged_event_stream_end(self) -> None:
         """Free both carries and close the stream (wfa_merged_event_stream_end)."""
         _lib.check(self._lib.wfa_merged_event_stream_end(self._h))
+
+    # ---- df_events stream: the fixed-window grouping chunk by chunk, the open events' rows resident between pushes -------
+    def df_event_stream_begin(self, time_window_ns: float) -> None:
+        """Open the session's df_events stream (wfa_df_event_stream_begin): empty carry, next event id 0.  The window goes
+        down as time_window_ns * 1e3 ps, formed here as the static pass forms it."""
+        _lib.check(self._lib.wfa_df_event_stream_begin(self._h, float(time_window_ns) * 1e3))
+
+    def df_event_stream_push(self, rows: np.ndarray | None, horizon_ts: int, final: bool = False) -> tuple[np.ndarray, int]:
+        """Push DF_ROW_DTYPE rows (None / empty: a pure flush) with the horizon (ps, int64) below which no later row's
+        timestamp lies; `final` closes every event -> (DF_EVENT_ROW_DTYPE rows of the events this push closed, rows carried
+        on the device)."""
+        n = 0 if rows is None else len(rows)
+        src = None
+        if n:
+            if rows.dtype != DF_ROW_DTYPE:
+                raise ValueError("df_event_stream_push takes DF_ROW_DTYPE rows")
+            src = np.ascontiguousarray(rows)
+        n_out, n_ev, n_carry = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _lib.check(self._lib.wfa_df_event_stream_push(self._h, _ptr(src), n, int(horizon_ts), int(bool(final)), C.byref(n_out),
+                                                      C.byref(n_ev), C.byref(n_carry)))
+        out = np.empty(int(n_out.value), dtype=DF_EVENT_ROW_DTYPE)
+        _lib.check(self._lib.wfa_df_event_stream_fill(self._h, _ptr(out), int(n_out.value)))
+        return out, int(n_carry.value)
+
+    def df_event_stream_end(self) -> None:
+        """Free the carry and close the stream (wfa_df_event_stream_end)."""
+        _lib.check(self._lib.wfa_df_event_stream_end(self._h))
 
     def hit_merge_clusters_resident(self, n: int, merge_gap_ns: float, max_total_width_ns: float):
         """hit_merge_clusters on the n resident rows: (order, cluster_offset)."""

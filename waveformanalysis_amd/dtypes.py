@@ -162,6 +162,17 @@ EVENT_MERGED_HIT_DTYPE = np.dtype([("event_id", "i8"), ("t_min", "i8"), ("t_max"
 HIT_MERGED_COMPONENTS_DTYPE = np.dtype([("merged_index", "i8"), ("hit_index", "i8")])
 HIT_MERGE_CLUSTERS_DTYPE = np.dtype([("cluster_index", "i8"), ("hit_index", "i8")])
 
+# df_events stream (wfa_df_event_stream_*): one df row as it is pushed (40 B; reserved must be 0), and one row per member
+# of a closed event as it comes back (64 B): the event's id, t_min / t_max, the df row, the event's size
+DF_ROW_DTYPE = np.dtype(
+    [("timestamp", "i8"), ("record_id", "i8"), ("area", "f4"), ("height", "f4"), ("amp", "f4"), ("max_abs_diff", "f4"),
+     ("board", "i2"), ("channel", "i2"), ("reserved", "u4")]
+)
+DF_EVENT_ROW_DTYPE = np.dtype(
+    [("event_id", "i8"), ("t_min", "i8"), ("t_max", "i8"), ("timestamp", "i8"), ("record_id", "i8"), ("area", "f4"),
+     ("height", "f4"), ("amp", "f4"), ("max_abs_diff", "f4"), ("n_hits", "i4"), ("board", "i2"), ("channel", "i2")]
+)
+
 
 # PEAK_DTYPE of the legacy helpers (reference: processing/dtypes.py:67-77, 30 B)
 PEAK_DTYPE = np.dtype(
@@ -213,6 +224,8 @@ assert THRESHOLD_HIT_DTYPE.itemsize == 60
 assert EVENT_HIT_DTYPE.itemsize == 84 and EVENT_HIT_DTYPE.fields["position"][1] == 24
 assert BASIC_FEATURES_DTYPE.itemsize == 36
 assert WAVEFORM_WIDTH_INTEGRAL_DTYPE.itemsize == 52
+assert DF_ROW_DTYPE.itemsize == 40 and DF_ROW_DTYPE.fields["board"][1] == 32
+assert DF_EVENT_ROW_DTYPE.itemsize == 64 and DF_EVENT_ROW_DTYPE.fields["n_hits"][1] == 56
 
 __all__ = [
     "RECORDS_DTYPE",
@@ -227,6 +240,8 @@ __all__ = [
     "EVENT_MERGED_HIT_DTYPE",
     "HIT_MERGED_COMPONENTS_DTYPE",
     "HIT_MERGE_CLUSTERS_DTYPE",
+    "DF_ROW_DTYPE",
+    "DF_EVENT_ROW_DTYPE",
     "PEAK_DTYPE",
     "create_record_dtype",
     "create_filtered_waveform_dtype",

@@ -236,8 +236,6 @@ class HitPushStream(_RecordsChunking, HipStreamingPlugin):
                    first_event_time: list | None = None):
         """Generator over the result chunks of ready-made records chunks (what compute() cuts).  `first_event_time`
         (optional list) receives time.perf_counter() when the first rows are delivered."""
-        import time
-
         cfg = self._configure(context)
         self._check_scope(context)
         pool = self._pool(context)
@@ -256,28 +254,40 @@ class HitPushStream(_RecordsChunking, HipStreamingPlugin):
             # the push session is borrowed first and for the whole run: the ring may take what is left, no more
             ring = int(pool.max_sessions) - 1
             hits = inner._pipeline(chunks, context, run_id, max_workers=min(ring, int(max_workers)) if max_workers else ring)
+        yield from self._push_loop(pool, cfg, hits, len(chunks), lambda k, _chunk, raw: (raw.data, horizons[k]),
+                                   (None, math.inf), run_id, stats, first_event_time)
+
+    def _push_loop(self, pool: DevicePool, cfg: dict, results, n_chunks: int, push_args, flush_args, run_id: str,
+                   stats: dict, first_event_time: list | None = None):
+        """The push loop: one session borrowed for the whole run, `_begin`, one `_push(sess, *push_args(k, chunk, raw),
+        run_id, stats)` per (chunk, raw result) of `results` in order, then one with `flush_args` (None: the last chunk's
+        push has closed everything), `_end`.  Yields what the pushes return, Nones dropped."""
+        import time
+
+        def deliver(out):
+            if first_event_time is not None and not first_event_time:
+                first_event_time.append(time.perf_counter())
+            return out
+
         with pool.borrow() as sess:
             if self.profile_pushes:
                 sess.profile(True)
             self._begin(sess, cfg)
             try:
                 k = -1
-                for k, (_chunk, raw) in enumerate(hits):
-                    out = self._push(sess, raw.data, horizons[k], run_id, stats)
+                for k, (chunk, raw) in enumerate(results):
+                    out = self._push(sess, *push_args(k, chunk, raw), run_id, stats)
                     if out is not None:
-                        if first_event_time is not None and not first_event_time:
-                            first_event_time.append(time.perf_counter())
-                        yield out
-                if k + 1 != len(chunks):
-                    raise RuntimeError(f"{self.provides}: {k + 1} results for {len(chunks)} chunks")
-                out = self._push(sess, None, math.inf, run_id, stats)
-                if out is not None:
-                    if first_event_time is not None and not first_event_time:
-                        first_event_time.append(time.perf_counter())
-                    yield out
+                        yield deliver(out)
+                if k + 1 != n_chunks:
+                    raise RuntimeError(f"{self.provides}: {k + 1} results for {n_chunks} chunks")
+                if flush_args is not None:
+                    out = self._push(sess, *flush_args, run_id, stats)
+                    if out is not None:
+                        yield deliver(out)
             finally:
-                if hasattr(hits, "close"):
-                    hits.close()   # (gives the ring's sessions back before ours)
+                if hasattr(results, "close"):
+                    results.close()   # (gives the ring's sessions back before ours)
                 if self.profile_pushes:
                     stats["profile"] = sess.profile_report()
                     sess.profile(False)

@@ -85,7 +85,16 @@ def hip_streaming_merged_events():
     return hip_streaming_merged() + [HipHitMergedGroupedStream()]
 
 
-__all__ = ["hip_streaming", "hip_streaming_events", "hip_streaming_merged", "hip_streaming_merged_events", "HipWavePoolFilteredPlugin", "HipThresholdHitPlugin", "HipBasicFeaturesPlugin",
+def hip_streaming_df_events():
+    """hip_streaming() plus basic_features_stream and df_events_stream: the features and the fixed-window coincidence
+    events of the default chain (basic_features -> df -> df_events), delivered as the events close."""
+    from ..df_event_stream import HipGroupedEventsStream
+    from ..features_stream import HipBasicFeaturesStream
+
+    return hip_streaming() + [HipBasicFeaturesStream(), HipGroupedEventsStream()]
+
+
+__all__ = ["hip_streaming", "hip_streaming_events", "hip_streaming_df_events", "hip_streaming_merged", "hip_streaming_merged_events", "HipWavePoolFilteredPlugin", "HipThresholdHitPlugin", "HipBasicFeaturesPlugin",
            "HipWaveformWidthIntegralPlugin", "HipHitGroupedPlugin", "HipHitFinderPlugin", "HipFilteredWaveformsPlugin",
            "HipWaveformWidthPlugin", "HipS1S2ClassifierPlugin", "HipHitMergeClustersPlugin",
            "HipHitMergePlugin", "HipHitMergedComponentsPlugin", "HipSignalPeaksStreamPlugin", "HipRecordsPlugin", "HipWavePoolPlugin",
