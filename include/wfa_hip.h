@@ -475,8 +475,8 @@ int wfa_group_hit_windows_fill(wfa_ctx* ctx, int64_t n_hits, int64_t n_events, i
  * unchanged @24; one row per hit, events in order, inside an event the static pass's order.
  * Refused with WFA_E_INVALID, the stream left as it was: a negative window (_begin); a pushed row with dt <= 0 or a
  * negative edge_start / edge_end; a pushed row whose abs_start lies below the previous push's horizon; a horizon
- * below the previous one, or NaN; carry + pushed rows >= 2^31.  _push without _begin, _fill before a push:
- * WFA_E_STATE; _fill with another row count: WFA_E_INVALID.  _begin on an open stream starts over.
+ * below the previous one, or NaN; carry + pushed rows >= 2^31.  _push without _begin, _fill before a push or after a
+ * refused one: WFA_E_STATE; _fill with another row count: WFA_E_INVALID.  _begin on an open stream starts over.
  * The carry and the rows of the last push are state: wfa_release_scratch keeps them, wfa_scratch_bytes does not count
  * them, _end frees them (60 B per carried row in each of two buffers, 84 B per row of the largest push). */
 int wfa_event_stream_begin(wfa_ctx* ctx, double time_window_ns);
@@ -508,9 +508,9 @@ int wfa_event_stream_end(wfa_ctx* ctx);
  * hit_merged_components of the whole table, in any chunking.
  * Refused with WFA_E_INVALID, the stream left as it was: a negative or NaN gap or width (_begin); a pushed row with
  * dt <= 0 or a negative edge_start / edge_end; a pushed row whose abs_start lies below the previous push's horizon; a
- * horizon below the previous one, or NaN; carry + pushed rows >= 2^31.  _push without _begin, _fill before a push:
- * WFA_E_STATE; _fill with other counts: WFA_E_INVALID.  _begin on an open stream starts over.  A context may hold an open
- * event stream and an open merge stream at once.
+ * horizon below the previous one, or NaN; carry + pushed rows >= 2^31.  _push without _begin, _fill before a push or
+ * after a refused one: WFA_E_STATE; _fill with other counts: WFA_E_INVALID.  _begin on an open stream starts over.  A
+ * context may hold an open event stream and an open merge stream at once.
  * The carry and the output of the last push are state: wfa_release_scratch keeps them, wfa_scratch_bytes does not count
  * them, _end frees them (68 B per carried row in each of two buffers, 72 B per cluster and 8 B per member of the largest
  * push). */

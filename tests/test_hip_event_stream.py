@@ -217,21 +217,34 @@ def test_refusals_leave_the_stream_untouched(sess, static_sess):
         want, want_carry = rule.push(a, 400_000.0)
         assert (got.tobytes(), carry) == (want.tobytes(), want_carry) and carry == 2
         assert lib.wfa_event_stream_fill(sess._h, out.ctypes.data_as(C.c_void_p), 4) == _lib.WFA_E_INVALID  # another count
+        accepted = len(got)
+        assert 0 < accepted <= len(out)
+
+        def nothing_to_fill():      # after a refused push: not with the last accepted push's count, not with 0
+            return all(lib.wfa_event_stream_fill(sess._h, out.ctypes.data_as(C.c_void_p), count) == _lib.WFA_E_STATE
+                       for count in (accepted, 0))
+
         bad = b.copy()
         bad["dt"][1] = 0
         _assert_invalid(lambda: sess.event_stream_push(bad, 900_000.0), "dt must be positive")
+        assert nothing_to_fill()
         for field in ("edge_start", "edge_end"):
             bad = b.copy()
             bad[field][0] = -1
             _assert_invalid(lambda: sess.event_stream_push(bad, 900_000.0), "negative edge_start / edge_end")
+            assert nothing_to_fill()
         bad = b.copy()
         bad["timestamp"][0] = 399_999                                        # starts below the previous horizon
         _assert_invalid(lambda: sess.event_stream_push(bad, 900_000.0), "below the previous push's horizon")
+        assert nothing_to_fill()
         _assert_invalid(lambda: sess.event_stream_push(b, 399_999.0), "lies below the previous push's")
+        assert nothing_to_fill()
         _assert_invalid(lambda: sess.event_stream_push(b, math.nan), "NaN")
+        assert nothing_to_fill()
         rc = lib.wfa_event_stream_push(sess._h, b.ctypes.data_as(C.c_void_p), 2**31 - 2, 900_000.0, C.byref(n), C.byref(n),
                                        C.byref(n))                           # carry (2) + rows = 2^31: refused unread
         assert rc == _lib.WFA_E_INVALID and "table limit" in _lib.last_error()
+        assert nothing_to_fill()
         # the carry is intact: the valid push gives what the rule gives without the refused ones
         got, carry = sess.event_stream_push(b, 900_000.0)
         want, want_carry = rule.push(b, 900_000.0)

@@ -320,20 +320,32 @@ def test_refusals_leave_the_stream_untouched(sess):
         assert (got[0].tobytes(), got[1].tolist(), got[2:]) == (want[0].tobytes(), want[1].tolist(), want[2:])
         assert got[2:] == (2, 400_000.0)
         assert lib.wfa_merge_stream_fill(sess._h, *ptrs, 2, 1) == _lib.WFA_E_INVALID            # other counts
+        accepted = (len(got[0]), len(got[1]))
+        assert 0 < accepted[0] <= len(out) and 0 < accepted[1] <= len(idx)
+
+        def nothing_to_fill():      # after a refused push: not with the last accepted push's counts, not with 0
+            return all(lib.wfa_merge_stream_fill(sess._h, *ptrs, *c) == _lib.WFA_E_STATE for c in (accepted, (0, 0)))
+
         bad = b.copy()
         bad["dt"][1] = 0
         _assert_invalid(lambda: sess.merge_stream_push(bad, 900_000.0), "dt must be positive")
+        assert nothing_to_fill()
         for field in ("edge_start", "edge_end"):
             bad = b.copy()
             bad[field][0] = -1
             _assert_invalid(lambda: sess.merge_stream_push(bad, 900_000.0), "negative edge_start / edge_end")
+            assert nothing_to_fill()
         bad = b.copy()
         bad["timestamp"][0] = 399_999                                        # starts below the previous horizon
         _assert_invalid(lambda: sess.merge_stream_push(bad, 900_000.0), "below the previous push's horizon")
+        assert nothing_to_fill()
         _assert_invalid(lambda: sess.merge_stream_push(b, 399_999.0), "lies below the previous push's")
+        assert nothing_to_fill()
         _assert_invalid(lambda: sess.merge_stream_push(b, math.nan), "NaN")
+        assert nothing_to_fill()
         rc = lib.wfa_merge_stream_push(sess._h, b.ctypes.data_as(C.c_void_p), 2**31 - 2, 900_000.0, *counts)
         assert rc == _lib.WFA_E_INVALID and "table limit" in _lib.last_error()   # carry (2) + rows = 2^31: refused unread
+        assert nothing_to_fill()
         # carry, hit and component counters are intact: the valid push gives what the rule gives without the refused ones
         got, want = sess.merge_stream_push(b, 900_000.0), rule.push(b, 900_000.0)
         assert (got[0].tobytes(), got[1].tolist(), got[2:]) == (want[0].tobytes(), want[1].tolist(), want[2:])

@@ -327,12 +327,17 @@ def test_refusals_leave_the_stream_untouched(sess):
         idx = np.zeros(4, dtype=np.int64)
         ptrs = (out.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p))
         assert lib.wfa_merged_event_stream_fill(sess._h, *ptrs, 0, 0) == _lib.WFA_E_STATE          # before a push
-        assert _same(sess.merged_event_stream_push(a, 400_000.0), rule.push(a, 400_000.0))
+        got = sess.merged_event_stream_push(a, 400_000.0)
+        assert _same(got, rule.push(a, 400_000.0))
         assert lib.wfa_merged_event_stream_fill(sess._h, *ptrs, 2, 1) == _lib.WFA_E_INVALID         # other counts
         assert lib.wfa_merged_event_stream_fill(sess._h, *ptrs, 1, 2) == _lib.WFA_E_INVALID
+        accepted = (len(got[0]), len(got[1]))
+        assert accepted[0] <= len(out) and 0 < accepted[1] <= len(idx)
         bad = b.copy()
-        bad["dt"][1] = 0
+        bad["dt"][1] = 0                                                     # (refused by the MERGE step)
         _assert_invalid(lambda: sess.merged_event_stream_push(bad, 900_000.0), "dt must be positive")
+        for c in (accepted, (0, 0)):                                         # nothing to fill after a refused push
+            assert lib.wfa_merged_event_stream_fill(sess._h, *ptrs, *c) == _lib.WFA_E_STATE
         for field in ("edge_start", "edge_end"):
             bad = b.copy()
             bad[field][0] = -1

@@ -54,6 +54,27 @@ struct DevBuf {
     }
 };
 
+// A stream's carry: a table of fixed-size rows in one of two buffers.  The first n rows of table() were left by the last
+// accepted push; a push puts its rows behind them (reserve, upload), works on the whole table and compacts the rows that
+// stay into the other buffer.  None of that touches cur or n: the caller commits once the whole push has succeeded, so a
+// refused push leaves the carry as it was.  State, not scratch: wfa_release_scratch keeps the buffers (wfa_hits.hip)
+struct Carry {
+    DevBuf buf[2];
+    int cur = 0;
+    int64_t n = 0;   // rows carried
+    const int row;   // bytes per row: 8, 40, 60 or 88
+    explicit Carry(int row_bytes) : row(row_bytes) {}
+    DevBuf& table() { return buf[cur]; }
+    int reserve(wfa_ctx* c, int64_t n_new);                   // room for n + n_new rows, the carried ones kept
+    int upload(wfa_ctx* c, const void* rows, int64_t n_new);  // host rows behind the carry (room reserved)
+    // the flagged rows of the n_table rows of table(), n_keep of them (incl = the inclusive scan of flag), into the other
+    // buffer in row order
+    int compact(wfa_ctx* c, int64_t n_table, const int64_t* flag, const int64_t* incl, int64_t n_keep);
+    void commit(int64_t n_keep, bool flip) { cur ^= flip ? 1 : 0; n = n_keep; }
+    void clear() { cur = 0; n = 0; }  // an empty carry; the buffers are reused
+    void release() { buf[0].release(); buf[1].release(); clear(); }
+};
+
 struct ProfEntry {
     std::string name;
     double total_ms = 0.0;
@@ -256,60 +277,67 @@ struct wfa_ctx {
     // [0, arena_filled) has been written.  Not scratch: wfa_release_scratch keeps it, wfa_ctx_destroy frees it
     wfa::DevBuf csv_arena;
     int64_t arena_filled = 0;
-    // event stream (wfa_event_stream_*, wfa_hits.hip): the hits of the events still open after the last push, as 60-byte
-    // rows in their original order in es_carry[es.cur] (a push compacts them into the other buffer), and the 84-byte rows
-    // the last push closed.  State, not scratch: wfa_release_scratch keeps them, wfa_event_stream_end frees them
-    struct EventStream {
+    // The carry streams (wfa_*_stream_*, wfa_hits.hip).  Each is a run's settings and counters (a `Run`, which _begin starts
+    // over), the rows still open after the last accepted push in a wfa::Carry, and what that push closed in an output
+    // buffer until _fill takes it.  out_* < 0: nothing to fill (no push yet, or the last one was refused).  A context may
+    // hold all four open side by side.  State, not scratch: wfa_release_scratch keeps the buffers, _end releases them.
+    template <typename Run>
+    struct GroupStream : Run {  // one carry, one output table: the event stream and the df_events stream
+        wfa::Carry carry;
+        wfa::DevBuf out;
+        explicit GroupStream(int entry_bytes) : carry(entry_bytes) {}
+        void restart() { Run::operator=(Run{}); carry.clear(); }  // (the buffers are reused)
+        void release() { restart(); carry.release(); out.release(); }
+    };
+    // event stream: the hits of the open events as 60-byte rows; a push closes 84-byte rows
+    struct EventRun {
         bool open = false;
         double window_ns = 0.0;
         double horizon = 0.0;     // horizon of the last accepted push (-inf before the first)
         int64_t next_event = 0;   // events emitted so far = id of the next one
-        int64_t n_carry = 0;
-        int cur = 0;
-        int64_t out_rows = -1;    // rows of the last push waiting in es_out; -1: no push yet
-    } es;
-    wfa::DevBuf es_carry[2], es_out;
-    // merge stream (wfa_merge_stream_*, wfa_hits.hip): the hits of the clusters still open after the last push, as 60-byte
-    // rows in their original order in ms_carry[ms.cur], each row's index in the sequence of all pushed rows beside it in
-    // ms_index[ms.cur], and what the last push closed: 72-byte merged rows and their members' indices.  State like the
-    // event stream's: wfa_release_scratch keeps it, wfa_merge_stream_end frees it
-    struct MergeStream {
+        int64_t out_rows = -1;    // rows of the last push waiting in `out`
+    };
+    using EventStream = GroupStream<EventRun>;
+    EventStream es{60};
+    // merge stream: the hits of the open clusters as 60-byte rows, each row's index in the sequence of all pushed rows
+    // beside it in a second carry compacted under the same flag; a push closes 72-byte merged rows and their members' indices
+    struct MergeRun {
         bool open = false;
         double gap_ns = 0.0, width_ns = 0.0;
         double horizon = 0.0;       // horizon of the last accepted push (-inf before the first)
         int64_t next_hit = 0;       // rows pushed so far = index of the next pushed row
         int64_t next_component = 0; // component rows emitted so far = component_offset of the next cluster
-        int64_t n_carry = 0;
-        int cur = 0;
-        int64_t out_merged = -1, out_components = 0;  // of the last push, waiting in ms_out / ms_out_index; -1: no push yet
+        int64_t out_merged = -1, out_components = 0;  // of the last push, waiting in out / out_index
+    };
+    struct MergeStream : MergeRun {
+        wfa::Carry carry{60}, index{8};
+        wfa::DevBuf out, out_index;
+        void restart() { MergeRun::operator=(MergeRun{}); carry.clear(); index.clear(); }
+        void release() { restart(); carry.release(); index.release(); out.release(); out_index.release(); }
     } ms;
-    wfa::DevBuf ms_carry[2], ms_index[2], ms_out, ms_out_index;
-    // merged-event stream (wfa_merged_event_stream_*, wfa_hits.hip): a merge step and a group step per push, each with the
-    // state of the stream it is the body of -- `m` and the mes_m* buffers like ms / ms_*, `e` and mes_carry like es /
-    // es_carry, but with 88-byte entries (a 72-byte merged row, then its abs_start_fix / abs_end_fix) -- and the 96-byte
-    // rows and the member indices of the last push.  e.horizon is the grouping horizon G of the last push.  State of its
-    // own: a context may hold it open beside es and ms; wfa_release_scratch keeps it, wfa_merged_event_stream_end frees it
+    // merged-event stream: a merge step and a group step per push, each on the state of the stream it is the body of.  The
+    // merged rows go straight behind the event carry (m.out stays empty), whose entries are 88 bytes: a 72-byte merged row,
+    // then its abs_start_fix / abs_end_fix.  A push closes 96-byte rows (e.out) and member indices (m.out_index), both
+    // waiting while e.out_rows >= 0.  e.horizon is the grouping horizon G of the last push
     struct MergedEventStream {
         bool open = false;
         double margin_ps = 0.0;   // the run's horizon margin (2 ulp of its magnitude; 0 below 2^53 ps)
         MergeStream m;
-        EventStream e;
+        EventStream e{88};
+        void restart() { open = false; margin_ps = 0.0; m.restart(); e.restart(); }
+        void release() { restart(); m.release(); e.release(); }
     } mes;
-    wfa::DevBuf mes_mcarry[2], mes_mindex[2], mes_mindex_out, mes_carry[2], mes_out;
-    // df_events stream (wfa_df_event_stream_*, wfa_hits.hip): the fixed-window grouping chunk by chunk.  The rows of the
-    // events still open after the last push, as 40-byte DF_ROW_DTYPE rows in their original order in ds_carry[ds.cur] (a
-    // push compacts them into the other buffer), and the 64-byte rows the last push closed.  State of its own beside es,
-    // ms and mes: wfa_release_scratch keeps it, wfa_df_event_stream_end frees it
-    struct DfEventStream {
+    // df_events stream: the fixed-window grouping chunk by chunk.  The rows of the open events as 40-byte DF_ROW_DTYPE
+    // rows; a push closes 64-byte rows
+    struct DfEventRun {
         bool open = false;
         double window_ps = 0.0;
         int64_t horizon = INT64_MIN;  // horizon of the last accepted push (the smallest int64 before the first)
         int64_t next_event = 0;       // events emitted so far = id of the next one
-        int64_t n_carry = 0;
-        int cur = 0;
-        int64_t out_rows = -1;        // rows of the last push waiting in ds_out; -1: no push yet, or the last was refused
-    } ds;
-    wfa::DevBuf ds_carry[2], ds_out;
+        int64_t out_rows = -1;        // rows of the last push waiting in `out`
+    };
+    using DfEventStream = GroupStream<DfEventRun>;
+    DfEventStream ds{40};
     wfa::DevBuf bw_scratch{scratch};  // float64 forward pass of sosfiltfilt, [sample][record-in-batch]
 
     // profiling: HIP events around every launch on the context's stream.  The pairs are only recorded while the

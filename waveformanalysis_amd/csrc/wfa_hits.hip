@@ -997,6 +997,35 @@ int es_grow(wfa_ctx* c, DevBuf& b, size_t used, size_t want) {
     return WFA_OK;
 }
 
+}  // namespace
+
+int Carry::reserve(wfa_ctx* c, int64_t n_new) { return es_grow(c, table(), (size_t)n * row, (size_t)(n + n_new) * row); }
+
+// (a refused push leaves its rows there: they lie behind n and the next push overwrites them)
+int Carry::upload(wfa_ctx* c, const void* rows, int64_t n_new) {
+    return n_new > 0 ? h2d_copy(c, table().as<uint8_t>() + (size_t)n * row, rows, (size_t)n_new * row) : WFA_OK;
+}
+
+int Carry::compact(wfa_ctx* c, int64_t n_table, const int64_t* flag, const int64_t* incl, int64_t n_keep) {
+    DevBuf& other = buf[cur ^ 1];
+    const int rc = other.ensure((size_t)n_keep * row);
+    if (rc) return rc;
+    const int words = row / 4;
+    const dim3 grid(blocks_for(n_table * words));
+    const uint32_t* src = table().as<uint32_t>();
+    uint32_t* dst = other.as<uint32_t>();
+    switch (words) {
+    case 2: hipLaunchKernelGGL(k_es_compact<2>, grid, dim3(kTB), 0, c->stream, n_table, flag, incl, src, dst); break;
+    case 10: hipLaunchKernelGGL(k_es_compact<10>, grid, dim3(kTB), 0, c->stream, n_table, flag, incl, src, dst); break;
+    case 15: hipLaunchKernelGGL(k_es_compact<15>, grid, dim3(kTB), 0, c->stream, n_table, flag, incl, src, dst); break;
+    case 22: hipLaunchKernelGGL(k_es_compact<22>, grid, dim3(kTB), 0, c->stream, n_table, flag, incl, src, dst); break;
+    default: return fail(WFA_E_INVALID, "no carry of %d-byte rows", row);
+    }
+    return WFA_OK;
+}
+
+namespace {
+
 inline uint64_t host_ord_f64(double v) {
     uint64_t b;
     memcpy(&b, &v, sizeof(b));
@@ -1230,15 +1259,38 @@ int plus_scan(wfa_ctx* c, const int64_t* in, int64_t* out, int64_t n) {
 // ---- the two steps of a push ----------------------------------------------------------------------------------------
 // wfa_merge_stream_push is the merge step on c->ms, wfa_event_stream_push the group step on c->es; a push of the
 // merged-event stream is one after the other on a state of its own, the merged rows handed over in HBM.  A step reads its
-// stream's state and changes none of it: what it decides comes back in *r and the caller commits (merge_commit /
-// group_commit) once the whole push has succeeded, so a refused push leaves every carry as it was.
+// stream's counters and changes none of them -- it only fills buffers behind what the carries hold: what it decides comes
+// back in *r and the caller commits (merge_commit / group_commit) once the whole push has succeeded, so a refused push
+// leaves every carry as it was.
 
-// the merge step's buffers: carried rows and their indices (two each), member indices of the closed clusters, and the
-// merged rows: n_closed entries of out_words dwords behind the first out_used entries of `out`, which are kept
+// The checks every push makes before it touches the device: stream open, argument pointers, horizon not NaN and not below
+// the previous push's, carry + pushed rows below 2^31.  The output of the previous push is void from here on (*out_count =
+// -1): a push that is refused leaves nothing to fill.  H: double (ps) or int64_t (the df_events stream's timestamps)
+inline bool horizon_nan(double h) { return h != h; }
+inline bool horizon_nan(int64_t) { return false; }
+inline int horizon_below(double h, double prev) {
+    return fail(WFA_E_INVALID, "the horizon (%.17g ps) lies below the previous push's (%.17g ps)", h, prev);
+}
+inline int horizon_below(int64_t h, int64_t prev) {
+    return fail(WFA_E_INVALID, "the horizon (%lld ps) lies below the previous push's (%lld ps)", (long long)h, (long long)prev);
+}
+template <typename H>
+int push_checks(bool open, const char* what, const char* begin, int64_t* out_count, bool args_ok, H horizon, H previous,
+                int64_t n_carry, int64_t n_rows) {
+    if (!open) return fail(WFA_E_STATE, "no %s stream is open (%s first)", what, begin);
+    *out_count = -1;
+    if (!args_ok) return fail(WFA_E_INVALID, "bad arguments");
+    if (horizon_nan(horizon)) return fail(WFA_E_INVALID, "the horizon is NaN");
+    if (horizon < previous) return horizon_below(horizon, previous);
+    if (n_rows >= 0x80000000LL - n_carry)
+        return fail(WFA_E_INVALID, "carry (%lld rows) + pushed rows (%lld) reach the table limit of 2^31 rows",
+                    (long long)n_carry, (long long)n_rows);
+    return WFA_OK;
+}
+
+// where the merge step's merged rows go: n_closed entries of out_words dwords behind the first out_used entries of `out`,
+// which are kept
 struct MergeIo {
-    DevBuf* carry[2];
-    DevBuf* index[2];
-    DevBuf* out_index;
     DevBuf* out;
     int out_words;      // 18: HIT_MERGED_DTYPE rows; 22: with the fix windows behind each row (k_mes_fix)
     int64_t out_used;
@@ -1246,35 +1298,23 @@ struct MergeIo {
 struct MergeStepOut {
     int64_t n_closed = 0, n_comp = 0, n_keep = 0;
     double open_start = HUGE_VAL;
-    bool flip = false;  // the carry went to the other pair of buffers
+    bool flip = false;  // the carries went to their other buffers
 };
 
-int merge_step(wfa_ctx* c, const wfa_ctx::MergeStream& ms, const MergeIo& io, const void* hit_rows, int64_t n_rows,
+int merge_step(wfa_ctx* c, wfa_ctx::MergeStream& ms, const MergeIo& io, const void* hit_rows, int64_t n_rows,
                double horizon_ps, MergeStepOut* r) {
     int rc;
     *r = MergeStepOut{};
-    if (horizon_ps != horizon_ps) return fail(WFA_E_INVALID, "the horizon is NaN");
-    if (horizon_ps < ms.horizon)
-        return fail(WFA_E_INVALID, "the horizon (%.17g ps) lies below the previous push's (%.17g ps)", horizon_ps, ms.horizon);
-    if (n_rows >= 0x80000000LL - ms.n_carry)
-        return fail(WFA_E_INVALID, "carry (%lld rows) + pushed rows (%lld) reach the table limit of 2^31 rows",
-                    (long long)ms.n_carry, (long long)n_rows);
-    const int64_t n = ms.n_carry + n_rows;
+    const int64_t n_carry = ms.carry.n, n = n_carry + n_rows;
     if (n == 0) return WFA_OK;  // nothing carried, nothing pushed: no launch
     c->ht_n = -1;  // the scratch slots a static count pass left for its fill are overwritten
-    DevBuf& table = *io.carry[ms.cur];
-    DevBuf& table_index = *io.index[ms.cur];
-    if ((rc = es_grow(c, table, (size_t)ms.n_carry * 60, (size_t)n * 60)) ||
-        (rc = es_grow(c, table_index, (size_t)ms.n_carry * 8, (size_t)n * 8)))
-        return rc;
-    uint8_t* rows = table.as<uint8_t>();
-    int64_t* index = table_index.as<int64_t>();
-    // 1. the pushed rows and their indices behind the carry (a refused push leaves them there: they lie behind n_carry and
-    //    are overwritten)
+    if ((rc = ms.carry.reserve(c, n_rows)) || (rc = ms.index.reserve(c, n_rows))) return rc;
+    uint8_t* rows = ms.carry.table().as<uint8_t>();
+    int64_t* index = ms.index.table().as<int64_t>();
+    // 1. the pushed rows and their indices behind the carry
     if (n_rows > 0) {
-        if ((rc = h2d_copy(c, rows + (size_t)ms.n_carry * 60, hit_rows, (size_t)n_rows * 60))) return rc;
-        hipLaunchKernelGGL(k_ms_number, dim3(blocks_for(n_rows)), dim3(kTB), 0, c->stream, n_rows, ms.next_hit,
-                           index + ms.n_carry);
+        if ((rc = ms.carry.upload(c, hit_rows, n_rows))) return rc;
+        hipLaunchKernelGGL(k_ms_number, dim3(blocks_for(n_rows)), dim3(kTB), 0, c->stream, n_rows, ms.next_hit, index + n_carry);
     }
     int64_t *d_ts, *d_pos, *d_rid;
     int32_t *d_s, *d_e, *d_dt;
@@ -1303,8 +1343,8 @@ int merge_step(wfa_ctx* c, const wfa_ctx::MergeStream& ms, const MergeIo& io, co
     WFA_HIP_CHECK(hipMemcpyAsync(d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
     if (n_rows > 0) {
         const unsigned cb = blocks_for(n_rows) < 1024u ? blocks_for(n_rows) : 1024u;
-        hipLaunchKernelGGL(k_es_check<MsCtl>, dim3(cb), dim3(kTB), 0, c->stream, n_rows, d_dt + ms.n_carry, d_s + ms.n_carry,
-                           d_e + ms.n_carry, c->ht[S_ABS0].as<double>() + ms.n_carry, d_ctl);
+        hipLaunchKernelGGL(k_es_check<MsCtl>, dim3(cb), dim3(kTB), 0, c->stream, n_rows, d_dt + n_carry, d_s + n_carry,
+                           d_e + n_carry, c->ht[S_ABS0].as<double>() + n_carry, d_ctl);
     }
     const int64_t* offset = c->ht[S_OUT0].as<int64_t>();
     const int64_t* cluster_incl = c->ht[S_ID].as<int64_t>();
@@ -1338,7 +1378,7 @@ int merge_step(wfa_ctx* c, const wfa_ctx::MergeStream& ms, const MergeIo& io, co
             (rc = slot(c, S_OUT4, n_closed, &red_h)) || (rc = slot(c, S_OUT5, n_closed, &red_int)) || (rc = slot(c, S_OUT6, n_closed, &red_s)) ||
             (rc = slot(c, S_OUT7, n_closed, &red_e)) || (rc = slot(c, S_MS6, n_closed, &red_w)) ||
             (rc = es_grow(c, *io.out, (size_t)io.out_used * entry, (size_t)(io.out_used + n_closed) * entry)) ||
-            (rc = io.out_index->ensure((size_t)n_comp * 8)))
+            (rc = ms.out_index.ensure((size_t)n_comp * 8)))
             return rc;
         const uint32_t* words = reinterpret_cast<const uint32_t*>(rows);
         uint32_t* out = io.out->as<uint32_t>() + (size_t)io.out_used * io.out_words;
@@ -1352,20 +1392,14 @@ int merge_step(wfa_ctx* c, const wfa_ctx::MergeStream& ms, const MergeIo& io, co
             hipLaunchKernelGGL(k_mes_fix, dim3(blocks_for(n_closed)), dim3(kTB), 0, c->stream, n_closed, list, offset, s0, s1, red_s,
                                red_e, reinterpret_cast<double*>(out));
         hipLaunchKernelGGL(k_ms_members, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, perm, cluster_incl, closed, offset,
-                           comp_incl, index, io.out_index->as<int64_t>());
+                           comp_incl, index, ms.out_index.as<int64_t>());
     }
     // 5. the hits of the open clusters and their indices, in row order, into the other buffers (all open: the table is
     //    the carry)
-    if (n_keep > 0 && n_closed > 0) {
-        DevBuf& other = *io.carry[ms.cur ^ 1];
-        DevBuf& other_index = *io.index[ms.cur ^ 1];
-        if ((rc = other.ensure((size_t)n_keep * 60)) || (rc = other_index.ensure((size_t)n_keep * 8))) return rc;
-        if ((rc = plus_scan(c, keep, keep_incl, n))) return rc;
-        hipLaunchKernelGGL(k_es_compact<15>, dim3(blocks_for(n * 15)), dim3(kTB), 0, c->stream, n, keep, keep_incl,
-                           reinterpret_cast<const uint32_t*>(rows), other.as<uint32_t>());
-        hipLaunchKernelGGL(k_es_compact<2>, dim3(blocks_for(n * 2)), dim3(kTB), 0, c->stream, n, keep, keep_incl,
-                           reinterpret_cast<const uint32_t*>(index), other_index.as<uint32_t>());
-    }
+    if (n_keep > 0 && n_closed > 0 &&
+        ((rc = plus_scan(c, keep, keep_incl, n)) || (rc = ms.carry.compact(c, n, keep, keep_incl, n_keep)) ||
+         (rc = ms.index.compact(c, n, keep, keep_incl, n_keep))))
+        return rc;
     WFA_HIP_CHECK(hipGetLastError());
     if ((rc = t.end("merge stream: closed clusters, rows, carry"))) return rc;
     WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -1378,8 +1412,8 @@ int merge_step(wfa_ctx* c, const wfa_ctx::MergeStream& ms, const MergeIo& io, co
 }
 
 void merge_commit(wfa_ctx::MergeStream& ms, const MergeStepOut& r, int64_t n_rows, double horizon_ps) {
-    if (r.flip) ms.cur ^= 1;
-    ms.n_carry = r.n_keep;
+    ms.carry.commit(r.n_keep, r.flip);
+    ms.index.commit(r.n_keep, r.flip);
     ms.next_hit += n_rows;
     ms.next_component += r.n_comp;
     ms.horizon = horizon_ps;
@@ -1387,23 +1421,24 @@ void merge_commit(wfa_ctx::MergeStream& ms, const MergeStepOut& r, int64_t n_row
     ms.out_components = r.n_comp;
 }
 
+// what the group step and the df step decide
 struct GroupStepOut {
     int64_t n_out = 0, n_closed = 0, n_keep = 0;
     bool flip = false;  // the carry went to the other buffer
 };
 
-// The group step over the table in carry[es.cur]: es.n_carry carried entries, then n_new new ones, already in place
-// (n = both > 0; the caller has checked the horizon).  An entry is S dwords; its first W are the row that goes out behind
+// The group step over the table of es.carry: the carried entries, then n_new new ones, already in place (n = both > 0;
+// the caller has checked the horizon).  An entry is S dwords; its first W are the row that goes out behind
 // the three event fields, and where S > W it ends with the row's abs_start_fix / abs_end_fix (S = 22, W = 18: a merged
 // row, whose edges may be -1, -1; S = W = 15: a threshold hit, whose edges may not).
 template <int W, int S>
-int group_step(wfa_ctx* c, const wfa_ctx::EventStream& es, DevBuf* const carry[2], DevBuf& out_buf, int64_t n_new,
-               double horizon_ps, GroupStepOut* r) {
+int group_step(wfa_ctx* c, wfa_ctx::EventStream& es, int64_t n_new, double horizon_ps, GroupStepOut* r) {
     int rc;
     *r = GroupStepOut{};
-    const int64_t n = es.n_carry + n_new;
+    if (es.carry.row != S * 4) return fail(WFA_E_INVALID, "group step: %d-dword entries on a carry of %d-byte rows", S, es.carry.row);
+    const int64_t n_carry = es.carry.n, n = n_carry + n_new;
     c->ht_n = -1;  // the scratch slots a static count pass left for its fill are overwritten
-    uint8_t* rows = carry[es.cur]->as<uint8_t>();
+    uint8_t* rows = es.carry.table().as<uint8_t>();
     int64_t *d_ts, *d_pos, *d_rid;
     int32_t *d_s, *d_e, *d_dt;
     int16_t *d_b, *d_c;
@@ -1434,8 +1469,8 @@ int group_step(wfa_ctx* c, const wfa_ctx::EventStream& es, DevBuf* const carry[2
     const double* abs0 = c->ht[S_ABS0].as<double>();
     if (n_new > 0) {
         const unsigned cb = blocks_for(n_new) < 1024u ? blocks_for(n_new) : 1024u;
-        hipLaunchKernelGGL(k_es_check<EsCtl>, dim3(cb), dim3(kTB), 0, c->stream, n_new, d_dt + es.n_carry, d_s + es.n_carry,
-                           d_e + es.n_carry, abs0 + es.n_carry, d_ctl);
+        hipLaunchKernelGGL(k_es_check<EsCtl>, dim3(cb), dim3(kTB), 0, c->stream, n_new, d_dt + n_carry, d_s + n_carry,
+                           d_e + n_carry, abs0 + n_carry, d_ctl);
     }
     const int64_t* ev_start = c->ht[S_OUT0].as<int64_t>();
     hipLaunchKernelGGL(k_es_closed, dim3(blocks_for(n_ev)), dim3(kTB), 0, c->stream, n_ev, ev_hi, es.window_ns * 1e3, horizon_ps,
@@ -1455,22 +1490,19 @@ int group_step(wfa_ctx* c, const wfa_ctx::EventStream& es, DevBuf* const carry[2
     // the rows of the closed events
     const uint64_t* k_ev = c->ht[S_K1].as<uint64_t>();
     if (n_out > 0) {
-        if ((rc = out_buf.ensure((size_t)n_out * (6 + W) * 4))) return rc;
+        if ((rc = es.out.ensure((size_t)n_out * (6 + W) * 4))) return rc;
         hipLaunchKernelGGL((k_es_rows<W, S>), dim3(blocks_for(n_out * (6 + W))), dim3(kTB), 0, c->stream, n_out, perm, k_ev,
                            c->ht[S_OUT1].as<int64_t>(), c->ht[S_OUT2].as<int64_t>(), es.next_event,
-                           reinterpret_cast<const uint32_t*>(rows), out_buf.as<uint32_t>());
+                           reinterpret_cast<const uint32_t*>(rows), es.out.as<uint32_t>());
     }
     // the entries of the open events, in row order, into the other carry buffer (all open: the table is the carry)
     if (n_keep > 0 && n_out > 0) {
-        DevBuf& other = *carry[es.cur ^ 1];
-        if ((rc = other.ensure((size_t)n_keep * S * 4))) return rc;
         int64_t* flag = c->ht[S_FLAG].as<int64_t>();
         int64_t* incl = c->ht[S_ID].as<int64_t>();
         hipLaunchKernelGGL(k_es_keep, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, k_ev, n_closed, flag);
         size_t tb = c->ht[S_CUB].cap;  // (sized by group_cols for this very scan)
         WFA_HIP_CHECK(rocprim::inclusive_scan(c->ht[S_CUB].ptr, tb, flag, incl, (size_t)n, rocprim::plus<int64_t>(), c->stream));
-        hipLaunchKernelGGL(k_es_compact<S>, dim3(blocks_for(n * S)), dim3(kTB), 0, c->stream, n, flag, incl,
-                           reinterpret_cast<const uint32_t*>(rows), other.as<uint32_t>());
+        if ((rc = es.carry.compact(c, n, flag, incl, n_keep))) return rc;
     }
     WFA_HIP_CHECK(hipGetLastError());
     if ((rc = t.end("event stream: closed prefix, rows, carry"))) return rc;
@@ -1482,12 +1514,13 @@ int group_step(wfa_ctx* c, const wfa_ctx::EventStream& es, DevBuf* const carry[2
     return WFA_OK;
 }
 
-void group_commit(wfa_ctx::EventStream& es, const GroupStepOut& r, double horizon_ps) {
-    if (r.flip) es.cur ^= 1;
-    es.n_carry = r.n_keep;
-    es.next_event += r.n_closed;
-    es.horizon = horizon_ps;
-    es.out_rows = r.n_out;
+// (Stream: the event stream's state or the df_events stream's, H its horizon type)
+template <typename Stream, typename H>
+void group_commit(Stream& st, const GroupStepOut& r, H horizon) {
+    st.carry.commit(r.n_keep, r.flip);
+    st.next_event += r.n_closed;
+    st.horizon = horizon;
+    st.out_rows = r.n_out;
 }
 
 // rows of a finished push to the host (large ones through the pinned staging ring); the caller synchronises
@@ -1601,24 +1634,17 @@ __global__ void k_dfs_keep(int64_t n, int64_t n_out, const int64_t* __restrict__
     if (j < n) flag[perm[j]] = j >= n_out ? 1 : 0;
 }
 
-struct DfsStepOut {
-    int64_t n_out = 0, n_closed = 0, n_keep = 0;
-    bool flip = false;  // the carry went to the other buffer
-};
-
-// One push over the table in ds_carry[ds.cur]: ds.n_carry carried rows, then the pushed ones.  Reads the stream's state
-// and changes none of it; the caller commits.
-int dfs_step(wfa_ctx* c, const wfa_ctx::DfEventStream& ds, const void* rows_in, int64_t n_rows, int64_t horizon_ts, int final,
-             DfsStepOut* r) {
+// One push over the table of ds.carry: the carried rows, then the pushed ones.  Reads the stream's counters and changes
+// none of them; the caller commits.
+int dfs_step(wfa_ctx* c, wfa_ctx::DfEventStream& ds, const void* rows_in, int64_t n_rows, int64_t horizon_ts, int final,
+             GroupStepOut* r) {
     int rc;
-    *r = DfsStepOut{};
-    const int64_t n = ds.n_carry + n_rows;
+    *r = GroupStepOut{};
+    const int64_t n = ds.carry.n + n_rows;
     if (n == 0) return WFA_OK;  // nothing carried, nothing pushed: no launch
     c->ht_n = -1;  // the scratch slots a static count pass left for its fill are overwritten
-    DevBuf& table = c->ds_carry[ds.cur];
-    if ((rc = es_grow(c, table, (size_t)ds.n_carry * 40, (size_t)n * 40))) return rc;
-    // the pushed rows behind the carry (a refused push leaves them there: they lie behind n_carry and are overwritten)
-    if (n_rows > 0 && (rc = h2d_copy(c, table.as<uint8_t>() + (size_t)ds.n_carry * 40, rows_in, (size_t)n_rows * 40))) return rc;
+    if ((rc = ds.carry.reserve(c, n_rows)) || (rc = ds.carry.upload(c, rows_in, n_rows))) return rc;
+    const DevBuf& table = ds.carry.table();
     int levels = 1;
     while ((1ll << levels) < n) ++levels;  // next^(2^levels) of any row is n
     int64_t *ts, *ch, *mark, *incl;
@@ -1633,7 +1659,7 @@ int dfs_step(wfa_ctx* c, const wfa_ctx::DfEventStream& ds, const void* rows_in, 
     LaunchTimer t(c);
     DfsCtl ctl{~0ull, (unsigned long long)n, 0, 0, 0};
     WFA_HIP_CHECK(hipMemcpyAsync(d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_dfs_cols, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, ds.n_carry, table.as<int64_t>(), ts, ch, d_ctl);
+    hipLaunchKernelGGL(k_dfs_cols, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, ds.carry.n, table.as<int64_t>(), ts, ch, d_ctl);
     // the chain of the static pass over the whole table (k_mc_keys as the static pass launches it: its channel key is not
     // read here, the closed prefix gets a key of its own below)
     hipLaunchKernelGGL(k_mc_keys, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, ts, ch, k_ts, k_ch);
@@ -1671,7 +1697,7 @@ int dfs_step(wfa_ctx* c, const wfa_ctx::DfEventStream& ds, const void* rows_in, 
         int64_t *perm_ts, *bounds, *order = nullptr;
         uint64_t* key;
         if ((rc = slot(c, S_OUT1, n, &perm_ts)) || (rc = slot(c, S_K2, n_out, &key)) || (rc = slot(c, S_OUT0, n_closed + 1, &bounds)) ||
-            (rc = c->ds_out.ensure((size_t)n_out * 64)))
+            (rc = ds.out.ensure((size_t)n_out * 64)))
             return rc;
         WFA_HIP_CHECK(hipMemcpyAsync(perm_ts, perm, (size_t)n * 8, hipMemcpyDeviceToDevice, c->stream));
         hipLaunchKernelGGL(k_dfs_keys, dim3(blocks_for(n_out)), dim3(kTB), 0, c->stream, n_out, perm_ts, incl, ch, key);
@@ -1681,17 +1707,13 @@ int dfs_step(wfa_ctx* c, const wfa_ctx::DfEventStream& ds, const void* rows_in, 
         }
         hipLaunchKernelGGL(k_mc_bounds, dim3(blocks_for(n_out)), dim3(kTB), 0, c->stream, n_out, mark, incl, n_closed, bounds);
         hipLaunchKernelGGL(k_dfs_rows, dim3(blocks_for(n_out * 16)), dim3(kTB), 0, c->stream, n_out, order, perm_ts, incl, bounds,
-                           ds.next_event, table.as<uint32_t>(), c->ds_out.as<uint32_t>());
+                           ds.next_event, table.as<uint32_t>(), ds.out.as<uint32_t>());
         // the rows of the open events, in row order, into the other carry buffer (all open: the table is the carry)
         if (n_keep > 0) {
-            DevBuf& other = c->ds_carry[ds.cur ^ 1];
             int64_t *keep, *keep_incl;
-            if ((rc = other.ensure((size_t)n_keep * 40)) || (rc = slot(c, S_K3, n, &keep)) || (rc = slot(c, S_K4, n, &keep_incl)))
-                return rc;
+            if ((rc = slot(c, S_K3, n, &keep)) || (rc = slot(c, S_K4, n, &keep_incl))) return rc;
             hipLaunchKernelGGL(k_dfs_keep, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, n_out, perm_ts, keep);
-            if ((rc = plus_scan(c, keep, keep_incl, n))) return rc;
-            hipLaunchKernelGGL(k_es_compact<10>, dim3(blocks_for(n * 10)), dim3(kTB), 0, c->stream, n, keep, keep_incl,
-                               table.as<uint32_t>(), other.as<uint32_t>());
+            if ((rc = plus_scan(c, keep, keep_incl, n)) || (rc = ds.carry.compact(c, n, keep, keep_incl, n_keep))) return rc;
         }
     }
     WFA_HIP_CHECK(hipGetLastError());
@@ -1978,7 +2000,7 @@ int wfa_event_stream_begin(wfa_ctx* c, double time_window_ns) {
     if (rc) return rc;
     if (time_window_ns < 0) return fail(WFA_E_INVALID, "time_window_ns must be >= 0");
     if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    c->es = wfa_ctx::EventStream{};  // (a stream left open starts over: empty carry, event id 0; the buffers are reused)
+    c->es.restart();
     c->es.open = true;
     c->es.window_ns = time_window_ns;
     c->es.horizon = -HUGE_VAL;
@@ -1990,24 +2012,15 @@ int wfa_event_stream_push(wfa_ctx* c, const void* hit_rows, int64_t n_rows, doub
     int rc = use_device_ht(c);
     if (rc) return rc;
     wfa_ctx::EventStream& es = c->es;
-    if (!es.open) return fail(WFA_E_STATE, "no event stream is open (wfa_event_stream_begin first)");
-    if (n_rows < 0 || (n_rows > 0 && !hit_rows) || !n_out_rows || !n_out_events || !n_carry)
-        return fail(WFA_E_INVALID, "bad arguments");
-    if (horizon_ps != horizon_ps) return fail(WFA_E_INVALID, "the horizon is NaN");
-    if (horizon_ps < es.horizon)
-        return fail(WFA_E_INVALID, "the horizon (%.17g ps) lies below the previous push's (%.17g ps)", horizon_ps, es.horizon);
-    if (n_rows >= 0x80000000LL - es.n_carry)
-        return fail(WFA_E_INVALID, "carry (%lld rows) + pushed rows (%lld) reach the table limit of 2^31 rows",
-                    (long long)es.n_carry, (long long)n_rows);
+    if ((rc = push_checks(es.open, "event", "wfa_event_stream_begin", &es.out_rows,
+                          n_rows >= 0 && (n_rows == 0 || hit_rows) && n_out_rows && n_out_events && n_carry, horizon_ps,
+                          es.horizon, es.carry.n, n_rows)))
+        return rc;
     GroupStepOut r;
-    if (es.n_carry + n_rows > 0) {  // (nothing carried, nothing pushed: no launch)
-        DevBuf& table = c->es_carry[es.cur];
-        if ((rc = es_grow(c, table, (size_t)es.n_carry * 60, (size_t)(es.n_carry + n_rows) * 60))) return rc;
-        // the pushed rows behind the carry (a refused push leaves them there: they lie behind n_carry and are overwritten)
-        if (n_rows > 0 && (rc = h2d_copy(c, table.as<uint8_t>() + (size_t)es.n_carry * 60, hit_rows, (size_t)n_rows * 60))) return rc;
-        DevBuf* const carry[2] = {&c->es_carry[0], &c->es_carry[1]};
-        if ((rc = group_step<15, 15>(c, es, carry, c->es_out, n_rows, horizon_ps, &r))) return rc;
-    }
+    if (es.carry.n + n_rows > 0 &&  // (nothing carried, nothing pushed: no launch)
+        ((rc = es.carry.reserve(c, n_rows)) || (rc = es.carry.upload(c, hit_rows, n_rows)) ||
+         (rc = group_step<15, 15>(c, es, n_rows, horizon_ps, &r))))
+        return rc;
     group_commit(es, r, horizon_ps);
     *n_out_rows = r.n_out;
     *n_out_events = r.n_closed;
@@ -2024,12 +2037,7 @@ int wfa_event_stream_fill(wfa_ctx* c, void* out_rows, int64_t n_out_rows) {
                     (long long)c->es.out_rows);
     if (n_out_rows == 0) return WFA_OK;
     if (!out_rows) return fail(WFA_E_INVALID, "out_rows is null");
-    const size_t bytes = (size_t)n_out_rows * 84;
-    if (bytes >= (4u << 20)) {  // large: through the pinned staging ring
-        if ((rc = d2h_staged(c, out_rows, c->es_out.ptr, bytes, nullptr, nullptr))) return rc;
-    } else {
-        WFA_HIP_CHECK(hipMemcpyAsync(out_rows, c->es_out.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
-    }
+    if ((rc = stream_d2h(c, out_rows, c->es.out.ptr, (size_t)n_out_rows * 84))) return rc;
     WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return WFA_OK;
 }
@@ -2038,10 +2046,7 @@ int wfa_event_stream_end(wfa_ctx* c) {
     int rc = use_device_ht(c);
     if (rc) return rc;
     if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    c->es_carry[0].release();
-    c->es_carry[1].release();
-    c->es_out.release();
-    c->es = wfa_ctx::EventStream{};
+    c->es.release();
     return WFA_OK;
 }
 
@@ -2052,7 +2057,7 @@ int wfa_merge_stream_begin(wfa_ctx* c, double merge_gap_ns, double max_total_wid
     if (!(merge_gap_ns >= 0)) return fail(WFA_E_INVALID, "merge_gap_ns must be >= 0");
     if (!(max_total_width_ns >= 0)) return fail(WFA_E_INVALID, "max_total_width_ns must be >= 0");
     if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    c->ms = wfa_ctx::MergeStream{};  // (a stream left open starts over: empty carry, index 0; the buffers are reused)
+    c->ms.restart();  // (a stream left open starts over: empty carry, index 0; the buffers are reused)
     c->ms.open = true;
     c->ms.gap_ns = merge_gap_ns;
     c->ms.width_ns = max_total_width_ns;
@@ -2065,10 +2070,11 @@ int wfa_merge_stream_push(wfa_ctx* c, const void* hit_rows, int64_t n_rows, doub
     int rc = use_device_ht(c);
     if (rc) return rc;
     wfa_ctx::MergeStream& ms = c->ms;
-    if (!ms.open) return fail(WFA_E_STATE, "no merge stream is open (wfa_merge_stream_begin first)");
-    if (n_rows < 0 || (n_rows > 0 && !hit_rows) || !n_merged || !n_components || !n_carry || !open_start_ps)
-        return fail(WFA_E_INVALID, "bad arguments");
-    const MergeIo io{{&c->ms_carry[0], &c->ms_carry[1]}, {&c->ms_index[0], &c->ms_index[1]}, &c->ms_out_index, &c->ms_out, 18, 0};
+    if ((rc = push_checks(ms.open, "merge", "wfa_merge_stream_begin", &ms.out_merged,
+                          n_rows >= 0 && (n_rows == 0 || hit_rows) && n_merged && n_components && n_carry && open_start_ps,
+                          horizon_ps, ms.horizon, ms.carry.n, n_rows)))
+        return rc;
+    const MergeIo io{&ms.out, 18, 0};
     MergeStepOut r;
     if ((rc = merge_step(c, ms, io, hit_rows, n_rows, horizon_ps, &r))) return rc;
     merge_commit(ms, r, n_rows, horizon_ps);
@@ -2088,17 +2094,9 @@ int wfa_merge_stream_fill(wfa_ctx* c, void* merged_rows, int64_t* hit_index, int
                     (long long)n_merged, (long long)n_components, (long long)c->ms.out_merged, (long long)c->ms.out_components);
     if (n_merged == 0) return WFA_OK;
     if (!merged_rows || !hit_index) return fail(WFA_E_INVALID, "null output");
-    const size_t bytes = (size_t)n_merged * 72, index_bytes = (size_t)n_components * 8;
-    if (bytes >= (4u << 20)) {  // large: through the pinned staging ring
-        if ((rc = d2h_staged(c, merged_rows, c->ms_out.ptr, bytes, nullptr, nullptr))) return rc;
-    } else {
-        WFA_HIP_CHECK(hipMemcpyAsync(merged_rows, c->ms_out.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (index_bytes >= (4u << 20)) {
-        if ((rc = d2h_staged(c, hit_index, c->ms_out_index.ptr, index_bytes, nullptr, nullptr))) return rc;
-    } else {
-        WFA_HIP_CHECK(hipMemcpyAsync(hit_index, c->ms_out_index.ptr, index_bytes, hipMemcpyDeviceToHost, c->stream));
-    }
+    if ((rc = stream_d2h(c, merged_rows, c->ms.out.ptr, (size_t)n_merged * 72)) ||
+        (rc = stream_d2h(c, hit_index, c->ms.out_index.ptr, (size_t)n_components * 8)))
+        return rc;
     WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return WFA_OK;
 }
@@ -2107,8 +2105,7 @@ int wfa_merge_stream_end(wfa_ctx* c) {
     int rc = use_device_ht(c);
     if (rc) return rc;
     if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    for (DevBuf* b : {&c->ms_carry[0], &c->ms_carry[1], &c->ms_index[0], &c->ms_index[1], &c->ms_out, &c->ms_out_index}) b->release();
-    c->ms = wfa_ctx::MergeStream{};
+    c->ms.release();
     return WFA_OK;
 }
 
@@ -2123,7 +2120,7 @@ int wfa_merged_event_stream_begin(wfa_ctx* c, double merge_gap_ns, double max_to
     if (!(horizon_margin_ps >= 0) || horizon_margin_ps == HUGE_VAL)
         return fail(WFA_E_INVALID, "horizon_margin_ps must be >= 0 and finite");
     if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    c->mes = wfa_ctx::MergedEventStream{};  // (a stream left open starts over: empty carries, ids 0; the buffers are reused)
+    c->mes.restart();  // (a stream left open starts over: empty carries, ids 0; the buffers are reused)
     c->mes.open = true;
     c->mes.margin_ps = horizon_margin_ps;
     c->mes.m.gap_ns = merge_gap_ns;
@@ -2140,13 +2137,13 @@ int wfa_merged_event_stream_push(wfa_ctx* c, const void* hit_rows, int64_t n_row
     int rc = use_device_ht(c);
     if (rc) return rc;
     wfa_ctx::MergedEventStream& st = c->mes;
-    if (!st.open) return fail(WFA_E_STATE, "no merged-event stream is open (wfa_merged_event_stream_begin first)");
-    if (n_rows < 0 || (n_rows > 0 && !hit_rows) || !n_out_rows || !n_out_events || !n_clusters || !n_components ||
-        !n_merge_carry || !n_event_carry || !group_horizon_ps)
-        return fail(WFA_E_INVALID, "bad arguments");
+    if ((rc = push_checks(st.open, "merged-event", "wfa_merged_event_stream_begin", &st.e.out_rows,
+                          n_rows >= 0 && (n_rows == 0 || hit_rows) && n_out_rows && n_out_events && n_clusters &&
+                              n_components && n_merge_carry && n_event_carry && group_horizon_ps,
+                          horizon_ps, st.m.horizon, st.m.carry.n, n_rows)))
+        return rc;
     // 1. the merge step; its rows go behind the event carry as 88-byte entries, with their fix windows
-    const MergeIo io{{&c->mes_mcarry[0], &c->mes_mcarry[1]}, {&c->mes_mindex[0], &c->mes_mindex[1]}, &c->mes_mindex_out,
-                     &c->mes_carry[st.e.cur], 22, st.e.n_carry};
+    const MergeIo io{&st.e.carry.table(), 22, st.e.carry.n};
     MergeStepOut m;
     if ((rc = merge_step(c, st.m, io, hit_rows, n_rows, horizon_ps, &m))) return rc;
     // 2. the grouping horizon: no merged row still to come starts below min(H, open_start'), nor below an earlier G
@@ -2156,13 +2153,7 @@ int wfa_merged_event_stream_push(wfa_ctx* c, const void* hit_rows, int64_t n_row
     if (g < st.e.horizon) g = st.e.horizon;
     // 3. the group step over event carry ++ the new merged rows
     GroupStepOut e;
-    if (st.e.n_carry + m.n_closed > 0) {
-        DevBuf* const carry[2] = {&c->mes_carry[0], &c->mes_carry[1]};
-        if ((rc = group_step<18, 22>(c, st.e, carry, c->mes_out, m.n_closed, g, &e))) {
-            st.e.out_rows = -1;  // (the merge step has overwritten the member indices of the last push: nothing to fill)
-            return rc;
-        }
-    }
+    if (st.e.carry.n + m.n_closed > 0 && (rc = group_step<18, 22>(c, st.e, m.n_closed, g, &e))) return rc;
     merge_commit(st.m, m, n_rows, horizon_ps);
     group_commit(st.e, e, g);
     *n_out_rows = e.n_out;
@@ -2184,8 +2175,8 @@ int wfa_merged_event_stream_fill(wfa_ctx* c, void* out_rows, int64_t* hit_index,
         return fail(WFA_E_INVALID, "caller expects %lld rows / %lld components, the last push closed %lld / %lld",
                     (long long)n_out_rows, (long long)n_components, (long long)st.e.out_rows, (long long)st.m.out_components);
     if ((n_out_rows > 0 && !out_rows) || (n_components > 0 && !hit_index)) return fail(WFA_E_INVALID, "null output");
-    if (n_out_rows > 0 && (rc = stream_d2h(c, out_rows, c->mes_out.ptr, (size_t)n_out_rows * 96))) return rc;
-    if (n_components > 0 && (rc = stream_d2h(c, hit_index, c->mes_mindex_out.ptr, (size_t)n_components * 8))) return rc;
+    if (n_out_rows > 0 && (rc = stream_d2h(c, out_rows, st.e.out.ptr, (size_t)n_out_rows * 96))) return rc;
+    if (n_components > 0 && (rc = stream_d2h(c, hit_index, st.m.out_index.ptr, (size_t)n_components * 8))) return rc;
     if (n_out_rows > 0 || n_components > 0) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return WFA_OK;
 }
@@ -2194,10 +2185,7 @@ int wfa_merged_event_stream_end(wfa_ctx* c) {
     int rc = use_device_ht(c);
     if (rc) return rc;
     if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    for (DevBuf* b : {&c->mes_mcarry[0], &c->mes_mcarry[1], &c->mes_mindex[0], &c->mes_mindex[1], &c->mes_mindex_out,
-                      &c->mes_carry[0], &c->mes_carry[1], &c->mes_out})
-        b->release();
-    c->mes = wfa_ctx::MergedEventStream{};
+    c->mes.release();
     return WFA_OK;
 }
 
@@ -2207,7 +2195,7 @@ int wfa_df_event_stream_begin(wfa_ctx* c, double time_window_ps) {
     if (rc) return rc;
     if (!(time_window_ps >= 0)) return fail(WFA_E_INVALID, "time_window_ps must be >= 0");
     if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    c->ds = wfa_ctx::DfEventStream{};  // (a stream left open starts over: empty carry, event id 0; the buffers are reused)
+    c->ds.restart();  // (a stream left open starts over: empty carry, event id 0; the buffers are reused)
     c->ds.open = true;
     c->ds.window_ps = time_window_ps;
     return WFA_OK;
@@ -2218,22 +2206,13 @@ int wfa_df_event_stream_push(wfa_ctx* c, const void* rows, int64_t n_rows, int64
     int rc = use_device_ht(c);
     if (rc) return rc;
     wfa_ctx::DfEventStream& ds = c->ds;
-    if (!ds.open) return fail(WFA_E_STATE, "no df_events stream is open (wfa_df_event_stream_begin first)");
-    ds.out_rows = -1;  // (nothing to fill after a refused push)
-    if (n_rows < 0 || (n_rows > 0 && !rows) || !n_out_rows || !n_out_events || !n_carry) return fail(WFA_E_INVALID, "bad arguments");
-    if (horizon_ts < ds.horizon)
-        return fail(WFA_E_INVALID, "the horizon (%lld ps) lies below the previous push's (%lld ps)", (long long)horizon_ts,
-                    (long long)ds.horizon);
-    if (n_rows >= 0x80000000LL - ds.n_carry)
-        return fail(WFA_E_INVALID, "carry (%lld rows) + pushed rows (%lld) reach the table limit of 2^31 rows",
-                    (long long)ds.n_carry, (long long)n_rows);
-    DfsStepOut r;
+    if ((rc = push_checks(ds.open, "df_events", "wfa_df_event_stream_begin", &ds.out_rows,
+                          n_rows >= 0 && (n_rows == 0 || rows) && n_out_rows && n_out_events && n_carry, horizon_ts, ds.horizon,
+                          ds.carry.n, n_rows)))
+        return rc;
+    GroupStepOut r;
     if ((rc = dfs_step(c, ds, rows, n_rows, horizon_ts, final, &r))) return rc;
-    if (r.flip) ds.cur ^= 1;
-    ds.n_carry = r.n_keep;
-    ds.next_event += r.n_closed;
-    ds.horizon = horizon_ts;
-    ds.out_rows = r.n_out;
+    group_commit(ds, r, horizon_ts);
     *n_out_rows = r.n_out;
     *n_out_events = r.n_closed;
     *n_carry = r.n_keep;
@@ -2249,7 +2228,7 @@ int wfa_df_event_stream_fill(wfa_ctx* c, void* out_rows, int64_t n_out_rows) {
                     (long long)c->ds.out_rows);
     if (n_out_rows == 0) return WFA_OK;
     if (!out_rows) return fail(WFA_E_INVALID, "out_rows is null");
-    if ((rc = stream_d2h(c, out_rows, c->ds_out.ptr, (size_t)n_out_rows * 64))) return rc;
+    if ((rc = stream_d2h(c, out_rows, c->ds.out.ptr, (size_t)n_out_rows * 64))) return rc;
     WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return WFA_OK;
 }
@@ -2258,8 +2237,7 @@ int wfa_df_event_stream_end(wfa_ctx* c) {
     int rc = use_device_ht(c);
     if (rc) return rc;
     if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    for (DevBuf* b : {&c->ds_carry[0], &c->ds_carry[1], &c->ds_out}) b->release();
-    c->ds = wfa_ctx::DfEventStream{};
+    c->ds.release();
     return WFA_OK;
 }
 

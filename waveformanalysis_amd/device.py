@@ -84,6 +84,17 @@ def device_count() -> int:
     return int(n.value)
 
 
+def _push_rows(rows: np.ndarray | None, dtype: np.dtype, refusal: str) -> tuple[np.ndarray | None, int]:
+    """What a stream push hands down: (contiguous rows, their number), or (None, 0) for None / empty rows (a pure
+    flush); rows of another dtype are refused."""
+    n = 0 if rows is None else len(rows)
+    if not n:
+        return None, 0
+    if rows.dtype != dtype:
+        raise ValueError(refusal)
+    return np.ascontiguousarray(rows), n
+
+
 class DeviceSession:
     """Owns a wfa_ctx.  Not thread-safe: use one session per thread (see device_pool)."""
 
@@ -976,12 +987,7 @@ class DeviceSession:
     def event_stream_push(self, rows: np.ndarray | None, horizon: float) -> tuple[np.ndarray, int]:
         """Push THRESHOLD_HIT_DTYPE rows (None / empty: a pure flush) with the horizon (ps, float64) below which no
         later hit starts -> (EVENT_HIT_DTYPE rows of the events this push closed, rows carried on the device)."""
-        n = 0 if rows is None else len(rows)
-        src = None
-        if n:
-            if rows.dtype != THRESHOLD_HIT_DTYPE:
-                raise ValueError("event_stream_push takes THRESHOLD_HIT_DTYPE rows")
-            src = np.ascontiguousarray(rows)
+        src, n = _push_rows(rows, THRESHOLD_HIT_DTYPE, "event_stream_push takes THRESHOLD_HIT_DTYPE rows")
         n_out, n_ev, n_carry = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         _lib.check(self._lib.wfa_event_stream_push(self._h, _ptr(src), n, float(horizon), C.byref(n_out), C.byref(n_ev),
                                                    C.byref(n_carry)))
@@ -1002,12 +1008,7 @@ class DeviceSession:
         """Push THRESHOLD_HIT_DTYPE rows (None / empty: a pure flush) with the horizon (ps, float64) below which no
         later hit starts -> (HIT_MERGED_DTYPE rows of the clusters this push closed, int64 hit_index of their members,
         rows carried on the device, smallest abs_start among the carried rows or +inf)."""
-        n = 0 if rows is None else len(rows)
-        src = None
-        if n:
-            if rows.dtype != THRESHOLD_HIT_DTYPE:
-                raise ValueError("merge_stream_push takes THRESHOLD_HIT_DTYPE rows")
-            src = np.ascontiguousarray(rows)
+        src, n = _push_rows(rows, THRESHOLD_HIT_DTYPE, "merge_stream_push takes THRESHOLD_HIT_DTYPE rows")
         n_merged, n_comp, n_carry, open_start = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_double(0.0)
         _lib.check(self._lib.wfa_merge_stream_push(self._h, _ptr(src), n, float(horizon), C.byref(n_merged), C.byref(n_comp),
                                                    C.byref(n_carry), C.byref(open_start)))
@@ -1033,12 +1034,7 @@ class DeviceSession:
         hit starts -> (EVENT_MERGED_HIT_DTYPE rows of the events this push closed, int64 hit_index of the members of the
         clusters its merge step closed, hits carried by the merge step, merged rows carried by the group step, the
         grouping horizon G)."""
-        n = 0 if rows is None else len(rows)
-        src = None
-        if n:
-            if rows.dtype != THRESHOLD_HIT_DTYPE:
-                raise ValueError("merged_event_stream_push takes THRESHOLD_HIT_DTYPE rows")
-            src = np.ascontiguousarray(rows)
+        src, n = _push_rows(rows, THRESHOLD_HIT_DTYPE, "merged_event_stream_push takes THRESHOLD_HIT_DTYPE rows")
         n_out, n_ev, n_cl, n_comp, n_mc, n_ec = (C.c_int64(0) for _ in range(6))
         g = C.c_double(0.0)
         _lib.check(self._lib.wfa_merged_event_stream_push(self._h, _ptr(src), n, float(horizon), C.byref(n_out), C.byref(n_ev),
@@ -1063,12 +1059,7 @@ class DeviceSession:
         """Push DF_ROW_DTYPE rows (None / empty: a pure flush) with the horizon (ps, int64) below which no later row's
         timestamp lies; `final` closes every event -> (DF_EVENT_ROW_DTYPE rows of the events this push closed, rows carried
         on the device)."""
-        n = 0 if rows is None else len(rows)
-        src = None
-        if n:
-            if rows.dtype != DF_ROW_DTYPE:
-                raise ValueError("df_event_stream_push takes DF_ROW_DTYPE rows")
-            src = np.ascontiguousarray(rows)
+        src, n = _push_rows(rows, DF_ROW_DTYPE, "df_event_stream_push takes DF_ROW_DTYPE rows")
         n_out, n_ev, n_carry = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         _lib.check(self._lib.wfa_df_event_stream_push(self._h, _ptr(src), n, int(horizon_ts), int(bool(final)), C.byref(n_out),
                                                       C.byref(n_ev), C.byref(n_carry)))

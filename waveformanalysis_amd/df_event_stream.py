@@ -24,13 +24,12 @@ from typing import Any
 
 import numpy as np
 
-from .chunk import Chunk
 from .device import DevicePool
 from .dtypes import DF_EVENT_ROW_DTYPE, DF_ROW_DTYPE
-from .event_stream import HitPushStream
 from .features_stream import HipBasicFeaturesStream
 from .plugin_api import Option
 from .plugins.event_analysis import _remember, build_events_frame, pair_events
+from .push_stream import PushStream, later_minima
 
 FEATURE_OPTION_NAMES = tuple(HipBasicFeaturesStream.options)
 HORIZON_END = int(np.iinfo(np.int64).max)   # the horizon of the last push: nothing follows
@@ -59,13 +58,7 @@ def df_rows(records: np.ndarray, features: np.ndarray) -> np.ndarray:
 def chunk_horizons_ts(chunks: list) -> list[int]:
     """One int64 horizon per records chunk: the minimum record timestamp over all records of LATER chunks (a suffix
     minimum, taken once per run; correct for unsorted runs as well); HORIZON_END for the last chunk."""
-    out = [HORIZON_END] * len(chunks)
-    later = HORIZON_END
-    for k in range(len(chunks) - 1, -1, -1):
-        out[k] = later
-        if len(chunks[k].data):
-            later = min(later, int(chunks[k].data["timestamp"].min()))
-    return out
+    return [HORIZON_END if later is None else later for later in later_minima(chunks)]
 
 
 def grouped_events_frame(rows: np.ndarray):
@@ -93,9 +86,9 @@ def paired_events_frame(rows: np.ndarray, time_window_ns: float = 100.0, n_chann
                        start_channel_slice=start_channel_slice)
 
 
-class HipGroupedEventsStream(HitPushStream):
-    """compute() = the df_events rows of the records stream, delivered as their events close (HitPushStream's options,
-    refusals and push loop with wfa_df_event_stream_*).
+class HipGroupedEventsStream(PushStream):
+    """compute() = the df_events rows of the records stream, delivered as their events close (PushStream with
+    wfa_df_event_stream_*).
 
     The records are chunked like hit_threshold_stream; an inner HipBasicFeaturesStream (same options, same chunking
     knobs; serial, or its thread-per-session `_compute_parallel`) computes every chunk's features.  `df_rows` of every
@@ -122,16 +115,10 @@ class HipGroupedEventsStream(HitPushStream):
 
     options = {**HipBasicFeaturesStream.options, "time_window_ns": Option(default=100.0, type=float)}
 
-    def __init__(self, device_pool: DevicePool | None = None, **given):
-        unknown = sorted(set(given) - set(self.options))   # (max_len among them: there is no padded width here)
-        if unknown:
-            raise TypeError(f"{self.provides}: unknown options {unknown}")
-        super().__init__(device_pool, 0, **given)
+    counters = ("events",)
 
-    def _check_pool(self, pool: DevicePool) -> None:
-        if int(pool.max_sessions) < 3:
-            raise ValueError(f"{self.provides} needs a device pool with max_sessions >= 3 (one session for the grouping, "
-                             f"held for the whole run, and two for the features of the chunks), got {pool.max_sessions}")
+    def _sessions(self) -> str:
+        return f"one session for the {self.role}, held for the whole run, and two for the features of the chunks"
 
     def _check_cfg(self, cfg: dict) -> None:
         cfg["time_window_ns"] = float(cfg["time_window_ns"])
@@ -165,8 +152,7 @@ class HipGroupedEventsStream(HitPushStream):
         chunks = numbered
         horizons = chunk_horizons_ts(chunks)
         stats = self.stats = self._new_stats()
-        serial = not self.parallel or (max_workers is not None and int(max_workers) <= 1)
-        if serial:
+        if not self.parallel or (max_workers is not None and int(max_workers) <= 1):
             features = ((c, inner._compute_one(c, context, run_id, inner.cfg)) for c in chunks)
         else:
             # the grouping session is borrowed first and for the whole run: the workers may take what is left, no more
@@ -189,9 +175,6 @@ class HipGroupedEventsStream(HitPushStream):
         finally:
             results.close()
 
-    def _new_stats(self) -> dict:
-        return {"pushes": 0, "rows_in": 0, "rows_out": 0, "events": 0, "max_carry": 0}
-
     def _begin(self, sess, cfg: dict) -> None:
         sess.df_event_stream_begin(cfg["time_window_ns"])
 
@@ -200,18 +183,8 @@ class HipGroupedEventsStream(HitPushStream):
 
     def _push(self, sess, rows, horizon: int, final: bool, run_id: str, stats: dict):
         out, n_carry = sess.df_event_stream_push(rows, horizon, final)
-        stats["pushes"] += 1
-        stats["rows_in"] += 0 if rows is None else len(rows)
-        stats["rows_out"] += len(out)
-        stats["max_carry"] = max(stats["max_carry"], int(n_carry))
-        if len(out) == 0:
-            return None
-        stats["events"] = int(out["event_id"][-1]) + 1
-        result = Chunk(out, int(out["t_min"].min()), int(out["t_max"].max()) + 1, run_id, self.provides,
-                       data_kind=self.output_data_kind, time_field="t_min", endtime_field="t_max",
-                       metadata={"first_event": int(out["event_id"][0]), "n_carry": int(n_carry)})
-        self._validate_chunk(result)
-        return result
+        self._count_push(stats, rows, len(out), n_carry)
+        return self._events_chunk(out, run_id, stats, n_carry=int(n_carry))
 
 
 __all__ = ["HipGroupedEventsStream", "df_rows", "chunk_horizons_ts", "grouped_events_frame", "paired_events_frame",

@@ -23,13 +23,13 @@ from typing import Any
 
 import numpy as np
 
-from .chunk import Chunk
 from .device import DevicePool
 from .dtypes import EVENT_HIT_DTYPE, THRESHOLD_HIT_DTYPE
 from .event_grouping import EVENT_COLUMNS
 from .plugins import _common as K
 from .plugins.hit_grouped import HipHitGroupedPlugin
-from .streaming import _UNSET, HipStreamingPlugin, HipThresholdHitStream, _RecordsChunking
+from .push_stream import PushStream, later_minima
+from .streaming import HipThresholdHitStream
 
 HIT_OPTION_NAMES = tuple(HipThresholdHitStream.options)
 EXACT_LIMIT_PS = 2**53   # below it every int64 ps value, and so every abs window, is exact in float64
@@ -91,14 +91,7 @@ def chunk_horizons(chunks: list, margin: float | None = None) -> list[float]:
     least its record's timestamp."""
     if margin is None:
         margin = run_margin(chunks)
-    out: list[float] = [math.inf] * len(chunks)
-    later = None
-    for k in range(len(chunks) - 1, -1, -1):
-        out[k] = horizon_of(later, margin)
-        if len(chunks[k].data):
-            first = int(chunks[k].data["timestamp"].min())
-            later = first if later is None else min(later, first)
-    return out
+    return [horizon_of(later, margin) for later in later_minima(chunks)]
 
 
 def event_rows(hits: np.ndarray, flat: dict, first_event: int = 0) -> np.ndarray:
@@ -140,61 +133,21 @@ def events_frame(rows: np.ndarray, window_fields: tuple[str, str] = ("edge_start
     return pd.DataFrame(out, columns=EVENT_COLUMNS)
 
 
-class HitPushStream(_RecordsChunking, HipStreamingPlugin):
-    """What the streams that push the hit stream's rows to one more session share (hit_grouped_stream here,
-    hit_merged_stream in merge_stream.py): option resolution, the inner hit stream, the refusals and the push loop.
+class HitPushStream(PushStream):
+    """The push streams over the hit stream's rows (hit_grouped_stream here, hit_merged_stream in merge_stream.py,
+    hit_merged_grouped_stream in merged_event_stream.py): PushStream with the inner hit stream and float horizons.
 
     The records are chunked like hit_threshold_stream; an inner HipThresholdHitStream (same options, same ring of two
     sessions per device, same overlap of upload and kernels) finds every chunk's hits.  Each chunk's rows, empty ones
     included, go in order to ONE more session borrowed for the whole run, with the chunk's horizon (`chunk_horizons`);
-    after the last chunk one push with +inf.  A subclass opens and closes the device stream (`_begin` / `_end`), turns one
-    push into a result chunk or None (`_push`) and names its counters (`_new_stats`).
-
-    Stateful (the carry lives on the device between chunks) and not reset at a time break: what is open may span one.
-    A value given to the constructor wins over the Context, the Context over the option's default.
+    after the last chunk one push with +inf.
 
     The rows travel device -> host -> device once more than necessary: the ring's sessions download a chunk's 60-byte
     rows (the hit stream's product), and the push uploads them to the borrowed session."""
 
-    depends_on = ["records", "wave_pool"]
-    version = "0.1.0+hip1"
-    save_when = "never"
-    chunk_size = 50_000
-    length_field = "event_length"
-    is_stateful = True
-    reset_on_break = False
-    profile_pushes = False   # measurement: kernel timers on the borrowed session, their report in stats["profile"]
-    role = "push"            # what the third session does, for the pool refusal
-
     def __init__(self, device_pool: DevicePool | None = None, max_len: int = 0, **given):
-        super().__init__()
-        unknown = sorted(set(given) - set(self.options))
-        if unknown:
-            raise TypeError(f"{self.provides}: unknown options {unknown}")
-        self._given = {k: v for k, v in given.items() if v is not _UNSET}
-        self.device_pool = device_pool
         self.max_len = int(max_len)
-        self.stats: dict = {}
-        self._configure(None)
-
-    def _configure(self, context: Any) -> dict:
-        """Constructor argument > Context configuration > option default."""
-        def value(name):
-            if name in self._given:
-                return self._given[name]
-            if context is not None and hasattr(context, "get_config"):
-                v = context.get_config(self, name)
-                if v is not None:
-                    return v
-            return self.options[name].default
-
-        cfg = {name: value(name) for name in self.options}
-        self._check_cfg(cfg)
-        self.cfg = cfg
-        return cfg
-
-    def _check_cfg(self, cfg: dict) -> None:
-        """Convert and refuse the subclass's own options, in place."""
+        super().__init__(device_pool, **given)
 
     def _inner(self, cfg: dict, pool: DevicePool) -> HipThresholdHitStream:
         """The hit stream with this stream's resolved options as its constructor values (so they win in its own
@@ -206,31 +159,11 @@ class HitPushStream(_RecordsChunking, HipStreamingPlugin):
         inner.chunk_size, inner.break_threshold_ps = self.chunk_size, self.break_threshold_ps
         return inner
 
-    def _check_scope(self, context: Any) -> None:
-        """Refuse a Context the stream does not cover (before any upload)."""
-
     def _run_margin(self, margin: float) -> None:
         """Told the run's horizon margin (ps; `run_margin`) before `_begin`, for a device stream that takes it."""
 
-    def _check_pool(self, pool: DevicePool) -> None:
-        if int(pool.max_sessions) < 3:
-            raise ValueError(f"{self.provides} needs a device pool with max_sessions >= 3 (two sessions for the hit "
-                             f"ring, one for the {self.role}), got {pool.max_sessions}")
-
-    def compute_chunk(self, chunk: Chunk, context: Any, run_id: str, **_kw):
-        raise NotImplementedError(f"{self.provides} is stateful across chunks: drive it through compute() / run_chunks()")
-
-    def compute(self, context: Any, run_id: str, **kwargs):
-        self._apply_streaming_config(kwargs.pop("streaming_config", None))
-        records = context.get_data(run_id, "records")
-        if not isinstance(records, np.ndarray) or records.dtype.names is None:
-            raise TypeError(f"{self.provides} chunks the structured `records` array")
-        # (refusals first: the chunk list is only cut once the run is known to start)
-        self._configure(context)
-        self._check_scope(context)
-        self._check_pool(self._pool(context))
-        workers = (kwargs.get("executor_config") or {}).get("max_workers") or self.max_workers
-        yield from self.run_chunks(list(self._data_to_chunks(records, run_id)), context, run_id, max_workers=workers)
+    def _sessions(self) -> str:
+        return f"two sessions for the hit ring, one for the {self.role}"
 
     def run_chunks(self, chunks: list, context: Any, run_id: str, max_workers: int | None = None,
                    first_event_time: list | None = None):
@@ -245,8 +178,7 @@ class HitPushStream(_RecordsChunking, HipStreamingPlugin):
         horizons = chunk_horizons(chunks, margin)
         self._run_margin(margin)
         stats = self.stats = self._new_stats()
-        serial = not self.parallel or (max_workers is not None and int(max_workers) <= 1)
-        if serial:
+        if not self.parallel or (max_workers is not None and int(max_workers) <= 1):
             inner._configure(context)
             width, plan = inner._run_width(context, run_id, chunks), inner._run_plan(context, run_id, chunks)
             hits = ((c, inner._compute_one(c, context, run_id, width, plan)) for c in chunks)
@@ -256,42 +188,6 @@ class HitPushStream(_RecordsChunking, HipStreamingPlugin):
             hits = inner._pipeline(chunks, context, run_id, max_workers=min(ring, int(max_workers)) if max_workers else ring)
         yield from self._push_loop(pool, cfg, hits, len(chunks), lambda k, _chunk, raw: (raw.data, horizons[k]),
                                    (None, math.inf), run_id, stats, first_event_time)
-
-    def _push_loop(self, pool: DevicePool, cfg: dict, results, n_chunks: int, push_args, flush_args, run_id: str,
-                   stats: dict, first_event_time: list | None = None):
-        """The push loop: one session borrowed for the whole run, `_begin`, one `_push(sess, *push_args(k, chunk, raw),
-        run_id, stats)` per (chunk, raw result) of `results` in order, then one with `flush_args` (None: the last chunk's
-        push has closed everything), `_end`.  Yields what the pushes return, Nones dropped."""
-        import time
-
-        def deliver(out):
-            if first_event_time is not None and not first_event_time:
-                first_event_time.append(time.perf_counter())
-            return out
-
-        with pool.borrow() as sess:
-            if self.profile_pushes:
-                sess.profile(True)
-            self._begin(sess, cfg)
-            try:
-                k = -1
-                for k, (chunk, raw) in enumerate(results):
-                    out = self._push(sess, *push_args(k, chunk, raw), run_id, stats)
-                    if out is not None:
-                        yield deliver(out)
-                if k + 1 != n_chunks:
-                    raise RuntimeError(f"{self.provides}: {k + 1} results for {n_chunks} chunks")
-                if flush_args is not None:
-                    out = self._push(sess, *flush_args, run_id, stats)
-                    if out is not None:
-                        yield deliver(out)
-            finally:
-                if hasattr(results, "close"):
-                    results.close()   # (gives the ring's sessions back before ours)
-                if self.profile_pushes:
-                    stats["profile"] = sess.profile_report()
-                    sess.profile(False)
-                self._end(sess)
 
 
 class HipHitGroupedStream(HitPushStream):
@@ -334,8 +230,7 @@ class HipHitGroupedStream(HitPushStream):
             raise ValueError(f"hit_grouped_stream: the configuration sets merge_gap_ns = {gap!r} for hit_merged; the static "
                              "hit_grouped would group merged hits, the stream groups threshold hits only")
 
-    def _new_stats(self) -> dict:
-        return {"pushes": 0, "rows_in": 0, "rows_out": 0, "events": 0, "max_carry": 0}
+    counters = ("events",)
 
     def _begin(self, sess, cfg: dict) -> None:
         sess.event_stream_begin(cfg["time_window_ns"])
@@ -345,18 +240,8 @@ class HipHitGroupedStream(HitPushStream):
 
     def _push(self, sess, rows, horizon: float, run_id: str, stats: dict):
         out, n_carry = sess.event_stream_push(rows, horizon)
-        stats["pushes"] += 1
-        stats["rows_in"] += 0 if rows is None else len(rows)
-        stats["rows_out"] += len(out)
-        stats["max_carry"] = max(stats["max_carry"], int(n_carry))
-        if len(out) == 0:
-            return None
-        stats["events"] = int(out["event_id"][-1]) + 1
-        result = Chunk(out, int(out["t_min"].min()), int(out["t_max"].max()) + 1, run_id, self.provides,
-                       data_kind=self.output_data_kind, time_field="t_min", endtime_field="t_max",
-                       metadata={"first_event": int(out["event_id"][0]), "n_carry": int(n_carry)})
-        self._validate_chunk(result)
-        return result
+        self._count_push(stats, rows, len(out), n_carry)
+        return self._events_chunk(out, run_id, stats, n_carry=int(n_carry))
 
 
 __all__ = ["HipHitGroupedStream", "HitPushStream", "events_frame", "event_rows", "chunk_horizons", "horizon_of", "horizon_margin",

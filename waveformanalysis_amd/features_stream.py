@@ -19,7 +19,7 @@ from .dtypes import BASIC_FEATURES_DTYPE
 from .plugin_api import Option
 from .plugins import _common as K
 from .plugins.basic_features import PEAK_RANGE
-from .streaming import _UNSET, HipStreamingPlugin, _RecordsChunking
+from .streaming import HipStreamingPlugin, _RecordsChunking, given_options, option_resolver
 
 
 class HipBasicFeaturesStream(_RecordsChunking, HipStreamingPlugin):
@@ -60,25 +60,14 @@ class HipBasicFeaturesStream(_RecordsChunking, HipStreamingPlugin):
 
     def __init__(self, device_pool: DevicePool | None = None, **given):
         super().__init__()
-        unknown = sorted(set(given) - set(self.options))
-        if unknown:
-            raise TypeError(f"{self.provides}: unknown options {unknown}")
-        self._given = {k: v for k, v in given.items() if v is not _UNSET}
+        self._given = given_options(self, given)
         self.device_pool = device_pool
         self._configure(None)
 
     def _configure(self, context: Any) -> dict:
         """Constructor argument > Context configuration > option default; the refusals.  Worker threads share the
         plugin: a chunk works on the dict it was handed."""
-        def value(name):
-            if name in self._given:
-                return self._given[name]
-            if context is not None and hasattr(context, "get_config"):
-                v = context.get_config(self, name)
-                if v is not None:
-                    return v
-            return self.options[name].default
-
+        value = option_resolver(self, context)
         if bool(value("use_filtered")):
             raise ValueError(f"{self.provides}: use_filtered=True is outside the stream (no filtered pool is built per chunk)")
         if value("fixed_baseline"):

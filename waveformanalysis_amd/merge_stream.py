@@ -106,8 +106,7 @@ class HipHitMergedStream(HitPushStream):
             if not cfg[name] >= 0:
                 raise ValueError(f"{name} must be >= 0")
 
-    def _new_stats(self) -> dict:
-        return {"pushes": 0, "rows_in": 0, "rows_out": 0, "components": 0, "max_carry": 0}
+    counters = ("components",)
 
     def _begin(self, sess, cfg: dict) -> None:
         sess.merge_stream_begin(cfg["merge_gap_ns"], cfg["max_total_width_ns"])
@@ -117,11 +116,8 @@ class HipHitMergedStream(HitPushStream):
 
     def _push(self, sess, rows, horizon: float, run_id: str, stats: dict):
         out, hit_index, n_carry, open_start = sess.merge_stream_push(rows, horizon)
-        stats["pushes"] += 1
-        stats["rows_in"] += 0 if rows is None else len(rows)
-        stats["rows_out"] += len(out)
+        self._count_push(stats, rows, len(out), n_carry)
         stats["components"] += len(hit_index)
-        stats["max_carry"] = max(stats["max_carry"], int(n_carry))
         if len(out) == 0:
             return None
         start, end = merged_bounds(out)

@@ -29,7 +29,6 @@ import math
 
 import numpy as np
 
-from .chunk import Chunk
 from .dtypes import EVENT_MERGED_HIT_DTYPE
 from .event_stream import HitPushStream, events_frame
 from .plugins.hit_grouped import HipHitGroupedPlugin
@@ -102,10 +101,12 @@ class HipHitMergedGroupedStream(HitPushStream):
             if not cfg[name] >= 0:
                 raise ValueError(f"{name} must be >= 0")
 
+    counters = ("events", "components")
+
     def _new_stats(self) -> dict:
         self._pending_index: list = []
         self._delivered_components = 0
-        return {"pushes": 0, "rows_in": 0, "rows_out": 0, "events": 0, "components": 0, "max_carry": 0}
+        return super()._new_stats()
 
     def _run_margin(self, margin: float) -> None:
         self._margin = float(margin)
@@ -119,12 +120,9 @@ class HipHitMergedGroupedStream(HitPushStream):
 
     def _push(self, sess, rows, horizon: float, run_id: str, stats: dict):
         out, hit_index, n_merge_carry, n_event_carry, g = sess.merged_event_stream_push(rows, horizon)
-        stats["pushes"] += 1
-        stats["rows_in"] += 0 if rows is None else len(rows)
-        stats["rows_out"] += len(out)
-        stats["components"] += len(hit_index)
         # (hits of open clusters + merged rows of open events: what the device holds between pushes)
-        stats["max_carry"] = max(stats["max_carry"], int(n_merge_carry) + int(n_event_carry))
+        self._count_push(stats, rows, len(out), int(n_merge_carry) + int(n_event_carry))
+        stats["components"] += len(hit_index)
         if len(hit_index):
             self._pending_index.append(hit_index)
         if len(out) == 0:
@@ -133,14 +131,8 @@ class HipHitMergedGroupedStream(HitPushStream):
         first_component = self._delivered_components
         self._pending_index = []
         self._delivered_components += len(members)
-        stats["events"] = int(out["event_id"][-1]) + 1
-        result = Chunk(out, int(out["t_min"].min()), int(out["t_max"].max()) + 1, run_id, self.provides,
-                       data_kind=self.output_data_kind, time_field="t_min", endtime_field="t_max",
-                       metadata={"first_event": int(out["event_id"][0]), "n_merge_carry": int(n_merge_carry),
-                                 "n_event_carry": int(n_event_carry), "group_horizon": float(g), "hit_index": members,
-                                 "first_component": first_component})
-        self._validate_chunk(result)
-        return result
+        return self._events_chunk(out, run_id, stats, n_merge_carry=int(n_merge_carry), n_event_carry=int(n_event_carry),
+                                  group_horizon=float(g), hit_index=members, first_component=first_component)
 
 
 __all__ = ["HipHitMergedGroupedStream", "merged_events_frame", "group_horizon", "lowered_open_start", "open_start_margin",

@@ -26,7 +26,8 @@ from .plugins.basic_features import PEAK_RANGE, HipBasicFeaturesPlugin
 from .plugins.hit_finder import _dt_values
 from .plugins.s1_s2 import HipS1S2ClassifierPlugin, class_ranges
 from .plugins.wave_pool_filtered import HipWavePoolFilteredPlugin
-from .streaming import _UNSET, HipStreamingPlugin, _RecordsChunking, _channel_keys, _filter_signature
+from .streaming import (HipStreamingPlugin, _RecordsChunking, _channel_keys, _filter_signature, given_options,
+                        option_resolver)
 
 HIT_OPTION_NAMES = ("use_derivative", "height", "distance", "prominence", "width", "threshold", "height_method",
                     "height_window_extension")
@@ -186,10 +187,7 @@ class HipS1S2Stream(_RecordsChunking, HipStreamingPlugin):
 
     def __init__(self, device_pool: DevicePool | None = None, **given):
         super().__init__()
-        unknown = sorted(set(given) - set(self.options))
-        if unknown:
-            raise TypeError(f"s1_s2_stream: unknown options {unknown}")
-        self._given = {k: v for k, v in given.items() if v is not _UNSET}
+        self._given = given_options(self, given)
         self.device_pool = device_pool
         self._ids_of = None  # weak reference to the records array whose record_id column was checked last
         self._plan_of = None  # (weak reference to a records array, config signature, _ChannelPlan): _run_plan's last run
@@ -198,15 +196,7 @@ class HipS1S2Stream(_RecordsChunking, HipStreamingPlugin):
     def _configure(self, context: Any) -> dict:
         """Constructor argument > Context configuration > option default; returns (and keeps) the resolved settings.
         Worker threads share the plugin: a chunk works on the dict it was handed, never on `self.cfg` again."""
-        def value(name):
-            if name in self._given:
-                return self._given[name]
-            if context is not None and hasattr(context, "get_config"):
-                v = context.get_config(self, name)
-                if v is not None:
-                    return v
-            return self.options[name].default
-
+        value = option_resolver(self, context)
         threshold = value("threshold")
         if threshold is not None and not np.isscalar(threshold):
             raise ValueError("s1_s2_stream takes a scalar threshold (a lower bound), or None")

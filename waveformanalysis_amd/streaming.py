@@ -315,6 +315,30 @@ def records_to_chunks(records: np.ndarray, chunk_size: int, run_id: str = "") ->
 _UNSET = object()
 
 
+def given_options(plugin: Any, given: dict) -> dict:
+    """The options a stream's constructor was given: a name that is not one of the plugin's options is a TypeError,
+    values left at _UNSET are dropped."""
+    unknown = sorted(set(given) - set(plugin.options))
+    if unknown:
+        raise TypeError(f"{plugin.provides}: unknown options {unknown}")
+    return {k: v for k, v in given.items() if v is not _UNSET}
+
+
+def option_resolver(plugin: Any, context: Any):
+    """`value(name)` of a stream's `_configure`: constructor argument (`plugin._given`) > Context configuration > option
+    default."""
+    def value(name):
+        if name in plugin._given:
+            return plugin._given[name]
+        if context is not None and hasattr(context, "get_config"):
+            v = context.get_config(plugin, name)
+            if v is not None:
+                return v
+        return plugin.options[name].default
+
+    return value
+
+
 def _filter_signature(context: Any, fplugin: Any):
     """What the registered wave_pool_filtered plugin is configured with, as a comparable value."""
     if fplugin is None:
@@ -489,15 +513,7 @@ class HipThresholdHitStream(_RecordsChunking, HipStreamingPlugin):
 
     def _configure(self, context: Any) -> None:
         """Constructor argument > Context configuration > option default."""
-        def value(name):
-            if name in self._given:
-                return self._given[name]
-            if context is not None and hasattr(context, "get_config"):
-                v = context.get_config(self, name)
-                if v is not None:
-                    return v
-            return self.options[name].default
-
+        value = option_resolver(self, context)
         self.threshold = float(value("threshold"))
         self.le, self.re = max(0, int(value("left_extension"))), max(0, int(value("right_extension")))
         self.use_filtered = bool(value("use_filtered"))
