@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define WFA_ABI_VERSION 11
+#define WFA_ABI_VERSION 12
 
 #define WFA_OK 0
 #define WFA_E_INVALID (-1)   /* bad argument / malformed records (maps to ValueError) */
@@ -720,6 +720,59 @@ int wfa_csv_arena_filled(wfa_ctx* ctx, int64_t* filled, int64_t* capacity);
  * entries.  payload_offset is in bytes from buf; a short header or payload ends the stream like the reference's reader. */
 int wfa_v1725_index(const uint8_t* buf, int64_t n_bytes, int64_t capacity, int16_t* channel, int64_t* timestamp,
                     uint8_t* trunc, uint16_t* baseline, int64_t* payload_offset, int32_t* n_samples, int64_t* n_waves);
+/* The same walk over a window of a file (the same loop: one header decode).  at_file_end != 0: buf ends where the file
+ * ends; wfa_v1725_index's result, *consumed_bytes = n_bytes.  at_file_end == 0: more of the file follows buf; only whole
+ * events are indexed (n_waves counts their waves, no wave of an event that buf cuts), *consumed_bytes = where the last
+ * whole event ends -- the next window starts there -- and 0 when buf holds not even one whole event: the caller reads
+ * more.  Rows of the columns behind n_waves are not meaningful.  A channel block of fewer than 3 words is refused
+ * (WFA_E_INVALID) wherever the walk meets one. */
+int wfa_v1725_index_block(const uint8_t* buf, int64_t n_bytes, int at_file_end, int64_t capacity, int16_t* channel,
+                          int64_t* timestamp, uint8_t* trunc, uint16_t* baseline, int64_t* payload_offset, int32_t* n_samples,
+                          int64_t* n_waves, int64_t* consumed_bytes);
+
+/* Records stream: records and wave_pool from V1725 blocks, block by block (the streamed form of wfa_records_sort +
+ * wfa_pool_gather over a run's files; reference: records_builder.py:797-830 `build_records_from_v1725_files`).  The device
+ * keeps the waves a later block could still precede (the carry) and releases the others as RECORDS_DTYPE rows with their
+ * samples, in the order of the static table: (timestamp, pid = 0, board, channel, seq).
+ * A horizon H is an int64 (ps) such that every wave not yet pushed has timestamp >= H.
+ * _begin(dt_ns): empty carry, next_record = next_sample = 0, horizon = the smallest int64.
+ * _push takes a block's bytes (host memory; they go up through the pinned staging ring like wfa_upload_pool_u16) and the
+ * n_waves new waves as columns: timestamp_ps i8 (ticks * dt_ns * 1000, formed by the caller), seq i8 (the caller's total
+ * order of the waves: file index, then wave index in the file -- a sort key behind channel, since a carried wave of a later
+ * file may tie with a pushed wave of an earlier one), payload_offset i8 (bytes into the block, a multiple of 4), n_samples
+ * i4 (even, >= 0), board i2, channel i2, baseline u2, trunc u1.  n_waves = 0 (block may be NULL) is a pure flush.  Steps:
+ * the new waves go behind the carried ones as 40-byte entries; the table is ordered by (timestamp, board, channel, seq)
+ * with the radix sort of wfa_records_sort; the released waves are the prefix with timestamp < horizon_ps, strictly (a later
+ * wave may tie at the horizon with a smaller board / channel), or the whole table when final != 0; the exclusive scan of
+ * the lengths in that order gives wave_offset = next_sample + scan for the prefix and the offsets in the new sample carry
+ * for the rest; ONE sample pass (k_rs_move) moves every wave's samples from where they are -- the old sample carry or the
+ * block's bytes -- to where they go -- the output pool or the new sample carry; the released rows are written on the device
+ * as packed 102-byte RECORDS_DTYPE rows: timestamp i8 @0, pid i4 @8 = 0, board i2 @12, channel i2 @14, baseline f8 @16 (the
+ * header's uint16), baseline_upstream f8 @24 = NaN, polarity 8 x UCS-4 @32 = "unknown", record_id i8 @64 = next_record + k,
+ * dt i4 @72, trigger_type i2 @76 = 0, flags u4 @78 = trunc, wave_offset i8 @82, event_length i4 @90, time i8 @94 =
+ * floor(timestamp / 1000); the other entries are compacted into the other carry buffer.  Samples keep their int16 bit
+ * patterns; a zero-sample wave moves nothing and still gets a row.
+ * _push reports the records and samples released and those carried; _fill downloads the released rows and samples
+ * (n_out_records x 102 bytes, n_out_samples x 2 bytes); the next push overwrites them.
+ * Host waits of a push: one per key range of the sort, one for the counts, one when the push ends, and one more in a push
+ * that has to grow a carry buffer; _fill waits for its copies.
+ * Refused with WFA_E_INVALID, the stream left exactly as it was (every check is made on the host before anything is
+ * uploaded): dt_ns <= 0 (_begin); a wave whose timestamp lies below the previous push's horizon; a horizon below the
+ * previous one; a payload slice outside the block or not 4-byte aligned; a negative or odd n_samples; carry + pushed waves
+ * >= 2^31.  _push without _begin, _fill before a push or after a refused one: WFA_E_STATE; _fill with other counts:
+ * WFA_E_INVALID.  _begin on an open stream starts over.  A context may hold this stream open beside the event, merge,
+ * merged-event and df_events streams.
+ * State, not scratch: the entry carry (40 B per wave in each of two buffers), the sample carry (two buffers of the carried
+ * samples), the rows and samples of the last push and the buffer of the last block: wfa_release_scratch keeps them,
+ * wfa_scratch_bytes does not count them, _end frees them.  Scratch: the sort's keys and buffers, the scanned lengths. */
+int wfa_records_stream_begin(wfa_ctx* ctx, int32_t dt_ns);
+int wfa_records_stream_push(wfa_ctx* ctx, const uint8_t* block, int64_t n_bytes, int64_t n_waves, const int64_t* timestamp_ps,
+                            const int64_t* seq, const int64_t* payload_offset, const int32_t* n_samples, const int16_t* board,
+                            const int16_t* channel, const uint16_t* baseline, const uint8_t* trunc, int64_t horizon_ps,
+                            int final, int64_t* n_out_records, int64_t* n_out_samples, int64_t* n_carry_records,
+                            int64_t* n_carry_samples);
+int wfa_records_stream_fill(wfa_ctx* ctx, void* out_rows, uint16_t* out_pool, int64_t n_out_records, int64_t n_out_samples);
+int wfa_records_stream_end(wfa_ctx* ctx);
 
 /* K6 integral-quantile width (reference: waveform_width_integral.py:166-227).
  * out: WAVEFORM_WIDTH_INTEGRAL_DTYPE rows (52 B). */

@@ -27,7 +27,7 @@ VIEW_WAVES, VIEW_WAVES_BASELINE, VIEW_SIGNALS = 0, 1, 2
 VIEW_U16, VIEW_F32, VIEW_F64 = 0, 1, 2
 DENSE_I16, DENSE_U16, DENSE_F32 = 0, 1, 2
 S1S2_UNKNOWN, S1S2_PREFER_S1, S1S2_PREFER_S2 = 0, 1, 2
-ABI_VERSION = 11
+ABI_VERSION = 12
 MAX_HIT_GROUPS = 8
 
 _p = C.c_void_p
@@ -110,6 +110,11 @@ SIGNATURES = {
     "wfa_df_event_stream_fill": (_int, [_p, _p, _i64]),
     "wfa_df_event_stream_end": (_int, [_p]),
     "wfa_v1725_index": (_int, [_p, _i64, _i64, _p, _p, _p, _p, _p, _p, C.POINTER(_i64)]),
+    "wfa_v1725_index_block": (_int, [_p, _i64, _int, _i64, _p, _p, _p, _p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)]),
+    "wfa_records_stream_begin": (_int, [_p, _i32]),
+    "wfa_records_stream_push": (_int, [_p, _p, _i64, _i64] + [_p] * 8 + [_i64, _int] + [C.POINTER(_i64)] * 4),
+    "wfa_records_stream_fill": (_int, [_p, _p, _p, _i64, _i64]),
+    "wfa_records_stream_end": (_int, [_p]),
     "wfa_records_sort": (_int, [_p, _i64, _p, _p, _p, _p, _p]),
     "wfa_pool_gather": (_int, [_p, _i64, _p, _p, _p, _i64, _p, _p, _i64]),
     "wfa_st_pack": (_int, [_p, _i64, _int, _p, _i64, _p, _p, _i32] + [_p] * 10 + [_i32, _i64, _p]),

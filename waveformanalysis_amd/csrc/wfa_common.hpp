@@ -338,6 +338,33 @@ struct wfa_ctx {
     };
     using DfEventStream = GroupStream<DfEventRun>;
     DfEventStream ds{40};
+    // records stream (wfa_records_stream_*): the head of the chain.  The waves a later block could still precede: a fixed
+    // 40-byte entry each in `carry` (timestamp, seq, offset of its samples in the sample carry, n_samples | board | channel,
+    // baseline | trunc) and their samples back to back in samples[cur_s] -- a second pair of ping-pong buffers, flipped with
+    // the carry once a whole push has succeeded.  A push releases RECORDS_DTYPE rows (out_rows) and their samples (out_pool)
+    struct RecordsRun {
+        bool open = false;
+        int32_t dt_ns = 0;
+        int64_t horizon = INT64_MIN;   // horizon of the last accepted push (the smallest int64 before the first)
+        int64_t next_record = 0;       // records released so far = record_id of the next one
+        int64_t next_sample = 0;       // samples released so far = wave_offset of the next record
+        int64_t out_records = -1;      // of the last push, waiting in out_rows / out_pool
+        int64_t out_samples = 0;
+    };
+    struct RecordsStream : RecordsRun {
+        wfa::Carry carry{40};
+        wfa::DevBuf samples[2];
+        int cur_s = 0;
+        int64_t n_samples = 0;         // samples carried
+        wfa::DevBuf out_rows, out_pool;
+        wfa::DevBuf block;             // the bytes of the block being pushed (dead once the push returns)
+        std::vector<int64_t> pack;     // host: the pushed waves as carry entries, until their upload has been queued
+        void restart() { RecordsRun::operator=(RecordsRun{}); carry.clear(); cur_s = 0; n_samples = 0; }
+        void release() {
+            restart(); carry.release(); samples[0].release(); samples[1].release(); out_rows.release(); out_pool.release();
+            block.release(); pack = {};
+        }
+    } rs;
     wfa::DevBuf bw_scratch{scratch};  // float64 forward pass of sosfiltfilt, [sample][record-in-batch]
 
     // profiling: HIP events around every launch on the context's stream.  The pairs are only recorded while the

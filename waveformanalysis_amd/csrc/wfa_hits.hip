@@ -1726,6 +1726,310 @@ int dfs_step(wfa_ctx* c, wfa_ctx::DfEventStream& ds, const void* rows_in, int64_
     return WFA_OK;
 }
 
+// ---- records stream (wfa_records_stream_*) ----------------------------------------------------------------------------
+// records and wave_pool from V1725 blocks, block by block.  The table of a push is the carried entries, then the pushed
+// waves; it is ordered by (timestamp, board, channel, seq) -- seq is a key: a carried wave of a later file and a pushed one
+// of an earlier file may tie on the first three -- and the waves with timestamp < horizon (all, when final) are a prefix
+// of that order.  The inclusive scan of the lengths in that order places every wave's samples: the prefix in the output
+// pool, the rest in the new sample carry.  Entry = 5 qwords: timestamp, seq, sample offset (carried: into the sample carry;
+// pushed: into the block; in samples, even), n_samples | board << 32 | channel << 48, baseline | trunc << 16.
+struct RsCtl {
+    unsigned long long n_out;   // waves of the released prefix
+    long long out_samples;      // their samples
+    long long total_samples;    // samples of the whole table
+};
+
+__global__ void k_rs_keys(int64_t n, const int64_t* __restrict__ rows, uint64_t* __restrict__ k_ts, uint64_t* __restrict__ k_bc,
+                          uint64_t* __restrict__ k_seq) {
+    const int64_t i = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t q3 = (uint64_t)rows[i * 5 + 3];
+    k_ts[i] = ord_i64(rows[i * 5]);
+    k_seq[i] = ord_i64(rows[i * 5 + 1]);
+    k_bc[i] = ((uint64_t)((uint16_t)(q3 >> 32) ^ 0x8000u) << 16) | (uint64_t)((uint16_t)(q3 >> 48) ^ 0x8000u);
+}
+
+// lengths in sorted order, and the size of the released prefix
+__global__ __launch_bounds__(kTB) void k_rs_lengths(int64_t n, const int64_t* __restrict__ perm, const int64_t* __restrict__ rows,
+                                                    int64_t horizon, int final, int64_t* __restrict__ len, RsCtl* __restrict__ ctl) {
+    const int64_t j = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    bool out = false;
+    if (j < n) {
+        const int64_t t = perm[j];
+        len[j] = (int64_t)(uint32_t)(uint64_t)rows[t * 5 + 3];
+        out = final || rows[t * 5] < horizon;
+    }
+    const unsigned long long m = __ballot(out);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&ctl->n_out, (unsigned long long)__popcll(m));
+}
+__global__ void k_rs_totals(int64_t n, const int64_t* __restrict__ incl, RsCtl* __restrict__ ctl) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const unsigned long long k = ctl->n_out;
+    ctl->out_samples = k > 0 ? incl[k - 1] : 0;
+    ctl->total_samples = incl[n - 1];
+}
+
+// The sample pass.  Output-stationary: a lane owns 16 bytes (8 samples) of a destination -- the output pool (region 0: the
+// released prefix) or the new sample carry (region 1: the rest) -- and stores them with one aligned dwordx4 store; the
+// buffers are padded to whole chunks and the bytes behind a region's last sample are written as 0.  Every source and
+// destination offset and every length is an even number of samples, so a destination dword is exactly one source dword:
+// the source is read as dwords at 4-byte alignment (four adjacent ones when the chunk lies inside one wave, which the
+// hardware takes as one 16-byte load), never as halfwords.  A wave64 owns kRsTiles consecutive tiles of 64 chunks of one
+// region (region 1 starts on a wave64 boundary of the index space).  Per tile it finds the waves of the tile's first and last
+// dword, wave-uniformly, in the scanned lengths -- one binary search for its first tile, then galloping on from where the
+// tile before ended (one probe when the next tile starts in the same or the next wave: a search per 1 KiB kept the pass at
+// a third of the copy rate) -- and each lane searches between those two: no step at all when the 512 samples lie in one
+// wave, and short waves cost a few steps instead of idle lanes.  Zero-sample waves own no dword and are never found.
+struct RsMoveArgs {
+    const int64_t* incl;        // inclusive scan of the lengths in sorted order
+    const int64_t* perm;        // sorted position -> table row
+    const int64_t* rows;        // the table
+    int64_t n, n_out, n_carry;  // table rows, released prefix, rows [0, n_carry) of the table read the sample carry
+    int64_t out_samples, total_samples;
+    int64_t out_waves;          // wave64s of region 0
+    int64_t n_waves;            // wave64s of both regions
+    const uint32_t* src_carry;
+    const uint32_t* src_block;
+    uint4* dst_out;
+    uint4* dst_keep;
+};
+constexpr int kRsBlock = 256;
+constexpr int kRsTiles = 8;  // 1-KiB tiles a wave64 moves one after another: one search, then a short walk per tile
+constexpr int kWave = 64;
+__device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
+__device__ __forceinline__ int wave_in_block() { return threadIdx.x >> 6; }
+__device__ __forceinline__ int64_t uniform_i64(int64_t v) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)(uint64_t)v);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// first j in [lo, hi) with incl[j] > p; hi when there is none
+__device__ __forceinline__ int64_t rs_find(const int64_t* __restrict__ incl, int64_t lo, int64_t hi, int64_t p) {
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (incl[mid] > p) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
+// the same, from a start that is usually already the answer: probe lo, lo + 1, lo + 3, lo + 7, ... then bisect the last gap
+__device__ __forceinline__ int64_t rs_gallop(const int64_t* __restrict__ incl, int64_t lo, int64_t hi, int64_t p) {
+    int64_t at = lo, step = 1;
+    while (at < hi && incl[at] <= p) {
+        lo = at + 1;
+        at += step;
+        step <<= 1;
+    }
+    return rs_find(incl, lo, at < hi ? at : hi, p);
+}
+
+struct RsSrcA4 {  // four adjacent dwords at 4-byte alignment
+    uint32_t x, y, z, w;
+} __attribute__((packed, aligned(4)));
+
+__global__ __launch_bounds__(kRsBlock) void k_rs_move(RsMoveArgs a) {
+    const int lane = lane_id();
+    const int64_t w = uniform_i64((int64_t)blockIdx.x * (kRsBlock / kWave) + wave_in_block());
+    if (w >= a.n_waves) return;
+    const bool keep = w >= a.out_waves;
+    const int64_t c0 = (keep ? w - a.out_waves : w) * (kWave * kRsTiles);  // first chunk of the wave64 in its region
+    const int64_t base = keep ? a.out_samples : 0;                          // the region in the scan's sample axis: [base, lim)
+    const int64_t lim = keep ? a.total_samples : a.out_samples;
+    const int64_t jhi = keep ? a.n : a.n_out;
+    int64_t jcur = keep ? a.n_out : 0;   // no wave in front of it holds a sample of this tile or a later one
+    uint4* __restrict__ dst = keep ? a.dst_keep : a.dst_out;
+#pragma unroll 1
+    for (int tile = 0; tile < kRsTiles; ++tile) {
+        const int64_t p0 = base + (c0 + (int64_t)tile * kWave) * 8;
+        if (p0 >= lim) break;
+        const int64_t p_last = (p0 + kWave * 8 < lim ? p0 + kWave * 8 : lim) - 2;
+        const int64_t j0 = uniform_i64(tile == 0 ? rs_find(a.incl, jcur, jhi, p0) : rs_gallop(a.incl, jcur, jhi, p0));
+        const int64_t j1 = uniform_i64(rs_gallop(a.incl, j0, jhi, p_last));  // (< jhi: p_last lies in a wave of the region)
+        jcur = j1;
+        const int64_t p = p0 + lane * 8;
+        if (p >= lim) continue;
+        int64_t j = j0 == j1 ? j0 : rs_find(a.incl, j0, j1, p);
+        uint32_t o[4];
+        int64_t end = a.incl[j];
+        int64_t t = a.perm[j];
+        int64_t off = a.rows[t * 5 + 2];
+        int64_t first = end - (int64_t)(uint32_t)(uint64_t)a.rows[t * 5 + 3];  // the wave's first sample on the scan's axis
+        const uint32_t* __restrict__ src = t < a.n_carry ? a.src_carry : a.src_block;
+        if (p + 8 <= end) {
+            const RsSrcA4 v = *reinterpret_cast<const RsSrcA4*>(src + ((off + (p - first)) >> 1));
+            o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+        } else {
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                const int64_t pd = p + 2 * d;
+                uint32_t v = 0;
+                if (pd < lim) {
+                    if (pd >= end) {
+                        do { ++j; end = a.incl[j]; } while (pd >= end);   // (ends at j1 at the latest)
+                        t = a.perm[j];
+                        off = a.rows[t * 5 + 2];
+                        first = end - (int64_t)(uint32_t)(uint64_t)a.rows[t * 5 + 3];
+                        src = t < a.n_carry ? a.src_carry : a.src_block;
+                    }
+                    v = src[(off + (pd - first)) >> 1];
+                }
+                o[d] = v;
+            }
+        }
+        dst[(p - base) >> 3] = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+// the released prefix as packed 102-byte RECORDS_DTYPE rows, 51 halfwords each (fields behind trigger_type are only
+// 2-byte aligned); lanes over halfwords: timestamp 0, pid 4, board 6, channel 7, baseline 8, baseline_upstream 12,
+// polarity 16 (8 UCS-4), record_id 32, dt 36, trigger_type 38, flags 39, wave_offset 41, event_length 45, time 47
+__global__ __launch_bounds__(kTB) void k_rs_rows(int64_t n_out, const int64_t* __restrict__ perm, const int64_t* __restrict__ incl,
+                                                 const int64_t* __restrict__ rows, int64_t next_record, int64_t next_sample,
+                                                 int32_t dt_ns, uint16_t* __restrict__ out) {
+    const int64_t d = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (d >= n_out * 51) return;
+    const int64_t j = d / 51;
+    const int h = (int)(d - j * 51);
+    const int64_t* __restrict__ e = rows + perm[j] * 5;
+    const uint64_t q3 = (uint64_t)e[3];
+    uint64_t v = 0;
+    int k = 0;
+    if (h < 4) { v = (uint64_t)e[0]; k = h; }
+    else if (h < 6) { v = 0; }                                                       // pid
+    else if (h == 6) { v = (q3 >> 32) & 0xffffu; }
+    else if (h == 7) { v = q3 >> 48; }
+    else if (h < 12) { v = (uint64_t)__double_as_longlong((double)(uint32_t)((uint64_t)e[4] & 0xffffu)); k = h - 8; }
+    else if (h < 16) { v = 0x7ff8000000000000ull; k = h - 12; }                      // numpy's nan
+    else if (h < 32) {
+        const int cp = (h - 16) >> 1;
+        v = ((h & 1) == 0 && cp < 7) ? (uint64_t)(uint8_t)"unknown"[cp] : 0;
+    }
+    else if (h < 36) { v = (uint64_t)(next_record + j); k = h - 32; }
+    else if (h < 38) { v = (uint32_t)dt_ns; k = h - 36; }
+    else if (h == 38) { v = 0; }                                                     // trigger_type
+    else if (h < 41) { v = ((uint64_t)e[4] >> 16) & 0xffu; k = h - 39; }            // flags = trunc
+    else if (h < 45) { v = (uint64_t)(next_sample + incl[j] - (int64_t)(uint32_t)q3); k = h - 41; }
+    else if (h < 47) { v = (uint32_t)q3; k = h - 45; }
+    else {
+        const int64_t ts = e[0];
+        int64_t q = ts / 1000;
+        if (ts - q * 1000 < 0) --q;   // floor, as numpy's //
+        v = (uint64_t)q;
+        k = h - 47;
+    }
+    out[d] = (uint16_t)(v >> (16 * k));
+}
+
+// the entries behind the released prefix, in sorted order, into the other carry buffer; their samples now lie in the new
+// sample carry at the scan's offsets
+__global__ void k_rs_keep(int64_t n_keep, int64_t n_out, int64_t out_samples, const int64_t* __restrict__ perm,
+                          const int64_t* __restrict__ incl, const int64_t* __restrict__ rows, int64_t* __restrict__ dst) {
+    const int64_t i = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    if (i >= n_keep) return;
+    const int64_t j = n_out + i;
+    const int64_t* __restrict__ e = rows + perm[j] * 5;
+    dst[i * 5] = e[0];
+    dst[i * 5 + 1] = e[1];
+    dst[i * 5 + 2] = incl[j] - (int64_t)(uint32_t)(uint64_t)e[3] - out_samples;
+    dst[i * 5 + 3] = e[3];
+    dst[i * 5 + 4] = e[4];
+}
+
+struct RecordsStepOut {
+    int64_t n_out = 0, out_samples = 0, n_keep = 0, keep_samples = 0;
+    bool flip = false;
+};
+
+// One push over the table of rs.carry (the pushed waves already packed in rs.pack and checked).  Reads the stream's
+// counters and changes none of them; the caller commits.
+int records_step(wfa_ctx* c, wfa_ctx::RecordsStream& rs, const uint8_t* block, int64_t n_bytes, int64_t n_new, int64_t horizon_ps,
+                 int final, RecordsStepOut* r) {
+    int rc;
+    *r = RecordsStepOut{};
+    const int64_t n_carry = rs.carry.n, n = n_carry + n_new;
+    if (n == 0) return WFA_OK;  // nothing carried, nothing pushed: no launch
+    c->ht_n = -1;  // the scratch slots a static count pass left for its fill are overwritten
+    if ((rc = rs.carry.reserve(c, n_new)) || (rc = rs.carry.upload(c, rs.pack.data(), n_new))) return rc;
+    if (n_new > 0 && n_bytes > 0) {
+        const size_t padded = ((size_t)n_bytes + 3) & ~(size_t)3;
+        if ((rc = rs.block.ensure(padded)) || (rc = h2d_copy(c, rs.block.ptr, block, (size_t)n_bytes))) return rc;
+    }
+    const int64_t* table = rs.carry.table().as<int64_t>();
+    uint64_t *k_ts, *k_bc, *k_seq;
+    int64_t *len, *incl;
+    RsCtl* d_ctl;
+    if ((rc = slot(c, S_K0, n, &k_ts)) || (rc = slot(c, S_K1, n, &k_bc)) || (rc = slot(c, S_K2, n, &k_seq)) ||
+        (rc = slot(c, S_FLAG, n, &len)) || (rc = slot(c, S_ID, n, &incl)) || (rc = slot(c, S_ES, 1, &d_ctl)))
+        return rc;
+    LaunchTimer t(c);
+    RsCtl ctl{0ull, 0, 0};
+    WFA_HIP_CHECK(hipMemcpyAsync(d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_rs_keys, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, table, k_ts, k_bc, k_seq);
+    int64_t* perm = nullptr;
+    {
+        const uint64_t* keys[3] = {k_ts, k_bc, k_seq};
+        if ((rc = lexsort(c, n, keys, 3, &perm))) return rc;  // (its wait covers the upload of `ctl`)
+    }
+    hipLaunchKernelGGL(k_rs_lengths, dim3(blocks_for(n)), dim3(kTB), 0, c->stream, n, perm, table, horizon_ps, final ? 1 : 0, len,
+                       d_ctl);
+    if ((rc = plus_scan(c, len, incl, n))) return rc;
+    hipLaunchKernelGGL(k_rs_totals, dim3(1), dim3(64), 0, c->stream, n, incl, d_ctl);
+    WFA_HIP_CHECK(hipGetLastError());
+    WFA_HIP_CHECK(hipMemcpyAsync(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    const int64_t n_out = (int64_t)ctl.n_out, n_keep = n - n_out;
+    const int64_t out_samples = ctl.out_samples, keep_samples = ctl.total_samples - ctl.out_samples;
+    if (n_out < 0 || n_out > n || out_samples < 0 || keep_samples < 0 || (out_samples & 1) || (keep_samples & 1))
+        return fail(WFA_E_HIP, "records stream: inconsistent counts");
+    if ((rc = t.end("records stream: order, released prefix, offsets"))) return rc;
+    // whole 16-byte chunks: the sample pass stores nothing narrower
+    const int64_t out_chunks = (out_samples + 7) >> 3, keep_chunks = (keep_samples + 7) >> 3;
+    DevBuf& new_samples = rs.samples[rs.cur_s ^ 1];
+    DevBuf& new_carry = rs.carry.buf[rs.carry.cur ^ 1];
+    if ((rc = rs.out_pool.ensure((size_t)(out_chunks > 0 ? out_chunks : 1) * 16)) ||
+        (rc = rs.out_rows.ensure((size_t)(n_out > 0 ? n_out : 1) * 102 + 2)))
+        return rc;
+    if (n_keep > 0 && ((rc = new_samples.ensure((size_t)(keep_chunks > 0 ? keep_chunks : 1) * 16)) ||
+                       (rc = new_carry.ensure((size_t)n_keep * 40))))
+        return rc;
+    if (out_chunks + keep_chunks > 0) {
+        RsMoveArgs a{};
+        a.incl = incl; a.perm = perm; a.rows = table;
+        a.n = n; a.n_out = n_out; a.n_carry = n_carry;
+        a.out_samples = out_samples; a.total_samples = ctl.total_samples;
+        a.out_waves = (out_chunks + kWave * kRsTiles - 1) / (kWave * kRsTiles);
+        a.n_waves = a.out_waves + (keep_chunks + kWave * kRsTiles - 1) / (kWave * kRsTiles);
+        a.src_carry = rs.samples[rs.cur_s].as<uint32_t>();
+        a.src_block = rs.block.as<uint32_t>();
+        a.dst_out = rs.out_pool.as<uint4>();
+        a.dst_keep = new_samples.as<uint4>();
+        const int64_t grid = (a.n_waves + (kRsBlock / kWave) - 1) / (kRsBlock / kWave);
+        if (grid > 0x7fffffff) return fail(WFA_E_LIMIT, "records stream: a push moves too many samples for one launch");
+        LaunchTimer tm(c, true);
+        hipLaunchKernelGGL(k_rs_move, dim3((unsigned)grid), dim3(kRsBlock), 0, c->stream, a);
+        WFA_HIP_CHECK(hipGetLastError());
+        if ((rc = tm.end("k_rs_move"))) return rc;
+    }
+    LaunchTimer t2(c);
+    if (n_out > 0)
+        hipLaunchKernelGGL(k_rs_rows, dim3(blocks_for(n_out * 51)), dim3(kTB), 0, c->stream, n_out, perm, incl, table, rs.next_record,
+                           rs.next_sample, rs.dt_ns, rs.out_rows.as<uint16_t>());
+    if (n_keep > 0)
+        hipLaunchKernelGGL(k_rs_keep, dim3(blocks_for(n_keep)), dim3(kTB), 0, c->stream, n_keep, n_out, out_samples, perm, incl, table,
+                           new_carry.as<int64_t>());
+    WFA_HIP_CHECK(hipGetLastError());
+    if ((rc = t2.end("records stream: rows, carry"))) return rc;
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    r->n_out = n_out;
+    r->out_samples = out_samples;
+    r->n_keep = n_keep;
+    r->keep_samples = keep_samples;
+    r->flip = n_keep > 0;
+    return WFA_OK;
+}
+
 }  // namespace
 }  // namespace wfa
 
@@ -2241,6 +2545,90 @@ int wfa_df_event_stream_end(wfa_ctx* c) {
     return WFA_OK;
 }
 
+// ---- records stream ---------------------------------------------------------------------------------------------------
+int wfa_records_stream_begin(wfa_ctx* c, int32_t dt_ns) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (dt_ns <= 0) return fail(WFA_E_INVALID, "dt_ns must be > 0, got %d", (int)dt_ns);
+    if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->rs.restart();  // (a stream left open starts over: empty carries, record id 0; the buffers are reused)
+    c->rs.open = true;
+    c->rs.dt_ns = dt_ns;
+    return WFA_OK;
+}
+
+int wfa_records_stream_push(wfa_ctx* c, const uint8_t* block, int64_t n_bytes, int64_t n_waves, const int64_t* timestamp_ps,
+                            const int64_t* seq, const int64_t* payload_offset, const int32_t* n_samples, const int16_t* board,
+                            const int16_t* channel, const uint16_t* baseline, const uint8_t* trunc, int64_t horizon_ps, int final,
+                            int64_t* n_out_records, int64_t* n_out_samples, int64_t* n_carry_records, int64_t* n_carry_samples) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    wfa_ctx::RecordsStream& rs = c->rs;
+    const bool cols = timestamp_ps && seq && payload_offset && n_samples && board && channel && baseline && trunc;
+    if ((rc = push_checks(rs.open, "records", "wfa_records_stream_begin", &rs.out_records,
+                          n_waves >= 0 && n_bytes >= 0 && (n_waves == 0 || cols) && (n_bytes == 0 || block) && n_out_records &&
+                              n_out_samples && n_carry_records && n_carry_samples,
+                          horizon_ps, rs.horizon, rs.carry.n, n_waves)))
+        return rc;
+    // every check of the pushed waves is made here, on the host, before anything goes up
+    rs.pack.resize((size_t)n_waves * 5);
+    for (int64_t k = 0; k < n_waves; ++k) {
+        if (timestamp_ps[k] < rs.horizon)
+            return fail(WFA_E_INVALID, "wave %lld: timestamp %lld ps lies below the previous push's horizon (%lld ps)", (long long)k,
+                        (long long)timestamp_ps[k], (long long)rs.horizon);
+        const int64_t len = n_samples[k], at = payload_offset[k];
+        if (len < 0 || (len & 1)) return fail(WFA_E_INVALID, "wave %lld: n_samples %lld is negative or odd", (long long)k, (long long)len);
+        if (at < 0 || (at & 3) || at > n_bytes || 2 * len > n_bytes - at)
+            return fail(WFA_E_INVALID, "wave %lld: payload [%lld, %lld) outside the block of %lld bytes, or not 4-byte aligned",
+                        (long long)k, (long long)at, (long long)(at + 2 * len), (long long)n_bytes);
+        int64_t* e = &rs.pack[(size_t)k * 5];
+        e[0] = timestamp_ps[k];
+        e[1] = seq[k];
+        e[2] = at >> 1;
+        e[3] = (int64_t)((uint64_t)(uint32_t)len | ((uint64_t)(uint16_t)board[k] << 32) | ((uint64_t)(uint16_t)channel[k] << 48));
+        e[4] = (int64_t)((uint64_t)baseline[k] | ((uint64_t)(trunc[k] ? 1u : 0u) << 16));
+    }
+    RecordsStepOut r;
+    if ((rc = records_step(c, rs, block, n_bytes, n_waves, horizon_ps, final, &r))) return rc;
+    rs.carry.commit(r.n_keep, r.flip);
+    if (r.flip) rs.cur_s ^= 1;
+    rs.n_samples = r.keep_samples;
+    rs.next_record += r.n_out;
+    rs.next_sample += r.out_samples;
+    rs.horizon = horizon_ps;
+    rs.out_records = r.n_out;
+    rs.out_samples = r.out_samples;
+    *n_out_records = r.n_out;
+    *n_out_samples = r.out_samples;
+    *n_carry_records = r.n_keep;
+    *n_carry_samples = r.keep_samples;
+    return WFA_OK;
+}
+
+int wfa_records_stream_fill(wfa_ctx* c, void* out_rows, uint16_t* out_pool, int64_t n_out_records, int64_t n_out_samples) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    wfa_ctx::RecordsStream& rs = c->rs;
+    if (!rs.open || rs.out_records < 0) return fail(WFA_E_STATE, "no records stream push has been made");
+    if (n_out_records != rs.out_records || n_out_samples != rs.out_samples)
+        return fail(WFA_E_INVALID, "caller expects %lld records / %lld samples, the last push released %lld / %lld",
+                    (long long)n_out_records, (long long)n_out_samples, (long long)rs.out_records, (long long)rs.out_samples);
+    if (n_out_records == 0) return WFA_OK;
+    if (!out_rows || (n_out_samples > 0 && !out_pool)) return fail(WFA_E_INVALID, "null output");
+    if ((rc = stream_d2h(c, out_rows, rs.out_rows.ptr, (size_t)n_out_records * 102))) return rc;
+    if (n_out_samples > 0 && (rc = stream_d2h(c, out_pool, rs.out_pool.ptr, (size_t)n_out_samples * 2))) return rc;
+    WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return WFA_OK;
+}
+
+int wfa_records_stream_end(wfa_ctx* c) {
+    int rc = use_device_ht(c);
+    if (rc) return rc;
+    if (c->stream) WFA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->rs.release();
+    return WFA_OK;
+}
+
 }  // extern "C"
 
 // every slice is checked before a kernel indexes with it; offsets of the packed pool are the running sum
@@ -2325,6 +2713,20 @@ int wfa_v1725_index(const uint8_t* buf, int64_t n_bytes, int64_t capacity, int16
     char err[160];
     if (host::v1725_index(buf, n_bytes, capacity, channel, timestamp, trunc, baseline, payload_offset, n_samples, n_waves, err,
                           sizeof(err)))
+        return fail(WFA_E_INVALID, "%s", err);
+    return WFA_OK;
+}
+
+int wfa_v1725_index_block(const uint8_t* buf, int64_t n_bytes, int at_file_end, int64_t capacity, int16_t* channel,
+                          int64_t* timestamp, uint8_t* trunc, uint16_t* baseline, int64_t* payload_offset, int32_t* n_samples,
+                          int64_t* n_waves, int64_t* consumed_bytes) {
+    if (n_bytes < 0 || capacity < 0 || !n_waves || !consumed_bytes || (n_bytes > 0 && !buf))
+        return fail(WFA_E_INVALID, "bad arguments");
+    if (capacity > 0 && (!channel || !timestamp || !trunc || !baseline || !payload_offset || !n_samples))
+        return fail(WFA_E_INVALID, "null output column");
+    char err[160];
+    if (host::v1725_index_block(buf, n_bytes, at_file_end != 0, capacity, channel, timestamp, trunc, baseline, payload_offset,
+                                n_samples, n_waves, consumed_bytes, err, sizeof(err)))
         return fail(WFA_E_INVALID, "%s", err);
     return WFA_OK;
 }

@@ -1,7 +1,8 @@
 // Host-only pieces of libwfa_hip.so as plain C++17 (no HIP): the code here is what the library runs on the CPU side of
 // the path, and what `make SANITIZE=1 host_check` builds with AddressSanitizer + UndefinedBehaviorSanitizer behind a
 // stand-in for the device (csrc/host_check.cpp; SURVEY section 5: the reference has no sanitizer run of its own).
-//   * v1725_index: header walk of a CAEN V1725 DAW_DEMO binary stream (reference utils/formats/v1725.py:66-114);
+//   * v1725_index / v1725_index_block: header walk of a CAEN V1725 DAW_DEMO binary stream, whole or block by block
+//     (reference utils/formats/v1725.py:66-114);
 //   * staged_copy: host -> device through two pinned staging buffers, a few host threads filling one while the other is
 //     on the wire (the ring of wfa_upload_pool_u16 / wfa_upload_pool_f32);
 //   * records_uniform / uniform_layout: the uniform-record layout of a records upload (both upload routes);
@@ -71,10 +72,13 @@ inline BaselineWindow baseline_window(int32_t start, int32_t end, int32_t max_le
 
 // Returns 0, or -1 with a message in err (the stream is malformed: a channel block shorter than its own header).
 // capacity = rows the output columns hold (0: count only); *n_waves = waves in the stream either way.
-inline int v1725_index(const uint8_t* buf, int64_t n_bytes, int64_t capacity, int16_t* channel, int64_t* timestamp,
-                       uint8_t* trunc, uint16_t* baseline, int64_t* payload_offset, int32_t* n_samples, int64_t* n_waves,
-                       char* err, size_t err_len) {
-    int64_t pos = 0, k = 0;
+// at_file_end: buf ends where the file ends -- a short header or payload ends the stream, the complete waves of the cut
+// event count, *consumed_bytes = n_bytes.  Otherwise buf is a window into a longer file: only whole events count,
+// *consumed_bytes = where the last whole event ends (0: not even one), and rows behind *n_waves are not meaningful.
+inline int v1725_index_block(const uint8_t* buf, int64_t n_bytes, bool at_file_end, int64_t capacity, int16_t* channel,
+                             int64_t* timestamp, uint8_t* trunc, uint16_t* baseline, int64_t* payload_offset,
+                             int32_t* n_samples, int64_t* n_waves, int64_t* consumed_bytes, char* err, size_t err_len) {
+    int64_t pos = 0, k = 0, whole_pos = 0, whole_k = 0;
     bool stop = false;
     while (!stop && n_bytes - pos >= 16) {  // a short event header ends the stream
         const uint8_t* eh = buf + pos;
@@ -106,9 +110,19 @@ inline int v1725_index(const uint8_t* buf, int64_t n_bytes, int64_t capacity, in
             ++k;
             pos += sig_bytes;
         }
+        if (!stop) { whole_pos = pos; whole_k = k; }
     }
-    *n_waves = k;
+    *n_waves = at_file_end ? k : whole_k;
+    if (consumed_bytes) *consumed_bytes = at_file_end ? n_bytes : whole_pos;
     return 0;
+}
+
+// the whole stream in one buffer
+inline int v1725_index(const uint8_t* buf, int64_t n_bytes, int64_t capacity, int16_t* channel, int64_t* timestamp,
+                       uint8_t* trunc, uint16_t* baseline, int64_t* payload_offset, int32_t* n_samples, int64_t* n_waves,
+                       char* err, size_t err_len) {
+    return v1725_index_block(buf, n_bytes, true, capacity, channel, timestamp, trunc, baseline, payload_offset, n_samples,
+                             n_waves, nullptr, err, err_len);
 }
 
 // ---- dense rows (wfa_upload_dense_rows): the batch / alignment arithmetic and the per-lane body of k_dense_unpack ----

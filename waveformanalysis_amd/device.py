@@ -24,6 +24,7 @@ from .dtypes import (
     EVENT_MERGED_HIT_DTYPE,
     HIT_DTYPE,
     HIT_MERGED_DTYPE,
+    RECORDS_DTYPE,
     S1_S2_CLASSIFIER_DTYPE,
     WAVEFORM_WIDTH_DTYPE,
     THRESHOLD_HIT_DTYPE,
@@ -1070,6 +1071,42 @@ class DeviceSession:
     def df_event_stream_end(self) -> None:
         """Free the carry and close the stream (wfa_df_event_stream_end)."""
         _lib.check(self._lib.wfa_df_event_stream_end(self._h))
+
+    # ---- records stream: records / wave_pool from V1725 blocks, the waves a later block may precede resident ------------
+    RECORDS_STREAM_COLUMNS = (("timestamp_ps", np.int64), ("seq", np.int64), ("payload_offset", np.int64),
+                              ("n_samples", np.int32), ("board", np.int16), ("channel", np.int16), ("baseline", np.uint16),
+                              ("trunc", np.uint8))
+
+    def records_stream_begin(self, dt_ns: int) -> None:
+        """Open the session's records stream (wfa_records_stream_begin): empty carry, record id and sample offset 0."""
+        _lib.check(self._lib.wfa_records_stream_begin(self._h, int(dt_ns)))
+
+    def records_stream_push(self, block: np.ndarray | None, waves: dict | None, horizon_ps: int, final: bool = False):
+        """Push a block's bytes (uint8) and the columns of its waves (RECORDS_STREAM_COLUMNS; None / empty: a pure flush)
+        with the horizon (ps, int64) below which no later wave's timestamp lies; `final` releases everything ->
+        (RECORDS_DTYPE rows released, their samples as uint16, records carried, samples carried).  wave_offset and
+        record_id count through the stream."""
+        n = 0 if not waves else len(waves["timestamp_ps"])
+        cols = []
+        for name, dtype in self.RECORDS_STREAM_COLUMNS:
+            col = None if n == 0 else np.ascontiguousarray(waves[name], dtype=dtype)
+            if col is not None and col.shape != (n,):
+                raise ValueError(f"records_stream_push: column {name} has shape {col.shape}, expected ({n},)")
+            cols.append(col)
+        buf = None if block is None or n == 0 else np.ascontiguousarray(block, dtype=np.uint8)
+        n_bytes = 0 if buf is None else int(buf.size)
+        n_rec, n_smp, c_rec, c_smp = (C.c_int64(0) for _ in range(4))
+        _lib.check(self._lib.wfa_records_stream_push(self._h, _ptr(buf), n_bytes, n, *[_ptr(col) for col in cols],
+                                                     int(horizon_ps), int(bool(final)), C.byref(n_rec), C.byref(n_smp),
+                                                     C.byref(c_rec), C.byref(c_smp)))
+        rows = np.empty(int(n_rec.value), dtype=RECORDS_DTYPE)
+        pool = np.empty(int(n_smp.value), dtype=np.uint16)
+        _lib.check(self._lib.wfa_records_stream_fill(self._h, _ptr(rows), _ptr(pool), len(rows), len(pool)))
+        return rows, pool, int(c_rec.value), int(c_smp.value)
+
+    def records_stream_end(self) -> None:
+        """Free the carries and close the stream (wfa_records_stream_end)."""
+        _lib.check(self._lib.wfa_records_stream_end(self._h))
 
     def hit_merge_clusters_resident(self, n: int, merge_gap_ns: float, max_total_width_ns: float):
         """hit_merge_clusters on the n resident rows: (order, cluster_offset)."""

@@ -94,7 +94,15 @@ def hip_streaming_df_events():
     return hip_streaming() + [HipBasicFeaturesStream(), HipGroupedEventsStream()]
 
 
-__all__ = ["hip_streaming", "hip_streaming_events", "hip_streaming_df_events", "hip_streaming_merged", "hip_streaming_merged_events", "HipWavePoolFilteredPlugin", "HipThresholdHitPlugin", "HipBasicFeaturesPlugin",
+def hip_streaming_records():
+    """hip_streaming() plus records_stream: records and wave_pool from V1725 files, block by block -- the head of the
+    chain; hit_threshold_stream takes its chunks (files -> hits in bounded memory)."""
+    from ..records_stream import HipRecordsStream
+
+    return hip_streaming() + [HipRecordsStream()]
+
+
+__all__ = ["hip_streaming", "hip_streaming_records", "hip_streaming_events", "hip_streaming_df_events", "hip_streaming_merged", "hip_streaming_merged_events", "HipWavePoolFilteredPlugin", "HipThresholdHitPlugin", "HipBasicFeaturesPlugin",
            "HipWaveformWidthIntegralPlugin", "HipHitGroupedPlugin", "HipHitFinderPlugin", "HipFilteredWaveformsPlugin",
            "HipWaveformWidthPlugin", "HipS1S2ClassifierPlugin", "HipHitMergeClustersPlugin",
            "HipHitMergePlugin", "HipHitMergedComponentsPlugin", "HipSignalPeaksStreamPlugin", "HipRecordsPlugin", "HipWavePoolPlugin",

@@ -171,6 +171,28 @@ def v1725_index(blob: np.ndarray) -> dict:
     return out
 
 
+def v1725_index_block(buf: np.ndarray, at_file_end: bool) -> tuple[dict, int]:
+    """(columns of v1725_index, consumed bytes) of a window of a V1725 file (wfa_v1725_index_block): only whole events
+    unless the window ends where the file ends; consumed = where the last whole event ends (0: not even one)."""
+    import ctypes as C
+
+    from . import _lib
+
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    lib = _lib.load()
+    n, used = C.c_int64(0), C.c_int64(0)
+    ptr = buf.ctypes.data_as(C.c_void_p)
+    end = int(bool(at_file_end))
+    _lib.check(lib.wfa_v1725_index_block(ptr, buf.size, end, 0, None, None, None, None, None, None, C.byref(n), C.byref(used)))
+    k = int(n.value)
+    out = {"channel": np.empty(k, np.int16), "timestamp": np.empty(k, np.int64), "trunc": np.empty(k, np.uint8),
+           "baseline": np.empty(k, np.uint16), "payload_offset": np.empty(k, np.int64), "n_samples": np.empty(k, np.int32)}
+    if k:
+        _lib.check(lib.wfa_v1725_index_block(ptr, buf.size, end, k, *[out[f].ctypes.data_as(C.c_void_p) for f in (
+            "channel", "timestamp", "trunc", "baseline", "payload_offset", "n_samples")], C.byref(n), C.byref(used)))
+    return out, int(used.value)
+
+
 def _board_from_path(path) -> int:
     import os
     import re
@@ -457,5 +479,5 @@ def build_records_from_vx2730_files(raw_files, default_dt_ns: int = 1, baseline_
 
 
 __all__ = ["RecordsBundle", "records_sort_order", "build_records_from_st_waveforms", "merge_records_parts",
-           "v1725_index", "build_records_from_v1725_blob", "build_records_from_v1725_files",
+           "v1725_index", "v1725_index_block", "build_records_from_v1725_blob", "build_records_from_v1725_files",
            "build_records_from_vx2730_files", "vx2730_skiprows", "vx2730_body", "vx2730_parts"]

@@ -470,7 +470,16 @@ class HipThresholdHitStream(_RecordsChunking, HipStreamingPlugin):
     with a ValueError before anything is uploaded.  Only a Context that holds no `records` (a caller that hands
     ready-made chunks to run_chunks / compute_chunk with nothing but a wave_pool behind them) keeps the old meaning
     of max_len=0: run_chunks then takes the longest record of the chunks it was given, compute_chunk the chunk's
-    own."""
+    own.
+
+    Chunks that bring their samples.  A chunk whose metadata carries `wave_pool` and `pool_base` (what records_stream
+    delivers: the chunk's samples as a host uint16 array, and the run offset of its first sample) is staged from those
+    samples, its wave_offset reduced by pool_base; the Context is asked for `wave_pool` only when a chunk needs it, so
+    `run_chunks(records stream chunks, a Context that holds neither records nor wave_pool, run_id)` runs files -> hits
+    in bounded memory.  The result chunk's metadata drops the two keys.  Chunks without them behave as before.  With no
+    `records` in the Context the max_len rule above stands: a ragged run needs `max_len` = its longest record given to the
+    constructor to equal the rows of the static hit_threshold (a chunk stream cannot know the run's longest record
+    before its end)."""
 
     provides = "hit_threshold_stream"
     depends_on = ["records", "wave_pool"]
@@ -577,20 +586,39 @@ class HipThresholdHitStream(_RecordsChunking, HipStreamingPlugin):
         return Chunk(np.zeros(0, dtype=THRESHOLD_HIT_DTYPE), chunk.start, chunk.end, run_id, self.provides,
                      data_kind="hits", time_field="timestamp")
 
-    def _stage(self, sess, chunk: Chunk, wave_pool: np.ndarray, max_len: int, plan=None) -> None:
+    POOL_KEYS = ("wave_pool", "pool_base")   # metadata of a chunk that brings its own samples (records_stream)
+
+    @classmethod
+    def _own_pool(cls, chunk: Chunk) -> bool:
+        return all(k in chunk.metadata for k in cls.POOL_KEYS)
+
+    def _chunk_samples(self, chunk: Chunk, wave_pool: np.ndarray | None):
+        """(the chunk's records with wave_offset counted from the returned samples, the samples): the slice of the pool
+        from the chunk's first sample to its last -- exactly its records for time-sorted records packed back to back, with
+        other chunks' samples and gaps in between for any other packing.  The pool is the chunk's own
+        (metadata wave_pool, whose first sample is the run's sample pool_base) when it brings one, else the run's."""
+        recs = chunk.data
+        pool, base, own = wave_pool, 0, self._own_pool(chunk)
+        if own:
+            pool, base = chunk.metadata["wave_pool"], int(chunk.metadata["pool_base"])
+        elif pool is None:
+            raise ValueError(f"{self.provides}: the chunk brings no samples and the Context holds no wave_pool")
+        lo = int(recs["wave_offset"].min()) - base
+        hi = int((recs["wave_offset"].astype(np.int64) + recs["event_length"]).max()) - base
+        if own and (lo < 0 or hi > len(pool)):
+            raise ValueError(f"{self.provides}: the chunk's records reach outside the samples it brings")
+        sub = recs.copy()
+        sub["wave_offset"] -= lo + base
+        return sub, np.ascontiguousarray(pool[lo:hi])
+
+    def _stage(self, sess, chunk: Chunk, wave_pool: np.ndarray | None, max_len: int, plan=None) -> None:
         """Upload the chunk's samples + records and queue its hit pass on `sess` at the run's padded width `max_len`
         (returns without waiting for the kernels once the session has sized its row buffers: wfa_hits_enqueue).
         `plan`: the run's per-channel table (`_run_plan`), None on the default path."""
         if plan is not None:
             return self._stage_planned(sess, chunk, wave_pool, max_len, plan)
-        recs = chunk.data
-        # the slice of the pool from the chunk's first sample to its last: exactly its records for time-sorted records
-        # packed back to back, with other chunks' samples and gaps in between for any other packing
-        lo = int(recs["wave_offset"].min())
-        hi = int((recs["wave_offset"].astype(np.int64) + recs["event_length"]).max())
-        sub = recs.copy()
-        sub["wave_offset"] -= lo
-        sess.upload_pool(np.ascontiguousarray(wave_pool[lo:hi]))   # pinned staging ring: chunk by chunk onto the wire
+        sub, samples = self._chunk_samples(chunk, wave_pool)
+        sess.upload_pool(samples)   # pinned staging ring: chunk by chunk onto the wire
         sess.upload_records(sub, self.threshold)
         if self.use_filtered:
             sess.set_sg_plan(*self.sg)
@@ -599,13 +627,9 @@ class HipThresholdHitStream(_RecordsChunking, HipStreamingPlugin):
     def _stage_planned(self, sess, chunk: Chunk, wave_pool: np.ndarray, max_len: int, plan) -> None:
         """_stage under a per-channel table: per-record thresholds, and with several filter groups the one queued
         grouped pass.  Group g of the run uses plan slot g on every session and in every chunk."""
-        recs = chunk.data
-        lo = int(recs["wave_offset"].min())
-        hi = int((recs["wave_offset"].astype(np.int64) + recs["event_length"]).max())
-        sub = recs.copy()
-        sub["wave_offset"] -= lo
-        group_of_record, thresholds = plan.lookup(recs)
-        sess.upload_pool(np.ascontiguousarray(wave_pool[lo:hi]))
+        sub, samples = self._chunk_samples(chunk, wave_pool)
+        group_of_record, thresholds = plan.lookup(chunk.data)
+        sess.upload_pool(samples)
         sess.upload_records(sub, thresholds)
         keys = plan.keys
         if not keys:  # the raw samples
@@ -622,8 +646,9 @@ class HipThresholdHitStream(_RecordsChunking, HipStreamingPlugin):
         # a record that overlaps the chunk's end (non-strict halo selection) has hits behind it: the result chunk
         # spans every record it was computed from; the driver clips it back to the core range
         end = max(int(chunk.end), int(self._endtime_of(chunk.data, "timestamp").max()) + 1)
+        # (a chunk's own samples do not ride along with its hits)
         return Chunk(hits, chunk.start, end, run_id, self.provides, data_kind="hits", time_field="timestamp",
-                     metadata=dict(chunk.metadata))
+                     metadata={k: v for k, v in chunk.metadata.items() if k not in self.POOL_KEYS})
 
     def compute_chunk(self, chunk: Chunk, context: Any, run_id: str, **_kw) -> Chunk:
         return self._compute_one(chunk, context, run_id, None)
@@ -638,7 +663,7 @@ class HipThresholdHitStream(_RecordsChunking, HipStreamingPlugin):
             max_len = self._run_width(context, run_id)
         if plan is _UNSET:
             plan = self._run_plan(context, run_id, [chunk])
-        wave_pool = context.get_data(run_id, "wave_pool")
+        wave_pool = None if self._own_pool(chunk) else context.get_data(run_id, "wave_pool")
         # worker threads come and go with every compute(): the session is borrowed for this chunk only
         with self._pool(context).borrow() as sess:
             if plan is None:
@@ -661,7 +686,7 @@ class HipThresholdHitStream(_RecordsChunking, HipStreamingPlugin):
         self._configure(context)
         max_len = self._run_width(context, run_id, input_chunks if isinstance(input_chunks, (list, tuple)) else None)
         plan = self._run_plan(context, run_id, input_chunks if isinstance(input_chunks, (list, tuple)) else None)
-        wave_pool = context.get_data(run_id, "wave_pool")
+        wave_pool = _UNSET   # asked of the Context by the first chunk that does not bring its own samples
         pool = self._pool(context)
         n = max(2, 2 * len(pool.device_ids))
         if max_workers:
@@ -689,10 +714,13 @@ class HipThresholdHitStream(_RecordsChunking, HipStreamingPlugin):
                 sess = ring[staged % n]  # free: results are collected in order, at most n - 1 are pending here
                 staged += 1
                 t0 = time.perf_counter()
+                if wave_pool is _UNSET and not self._own_pool(chunk):
+                    wave_pool = context.get_data(run_id, "wave_pool")
+                run_pool = None if wave_pool is _UNSET else wave_pool
                 if plan is None:
-                    self._stage(sess, chunk, wave_pool, max_len)
+                    self._stage(sess, chunk, run_pool, max_len)
                 else:
-                    self._stage(sess, chunk, wave_pool, max_len, plan)
+                    self._stage(sess, chunk, run_pool, max_len, plan)
                 t1 = time.perf_counter()
                 pending.append((k, chunk, sess, (t0, t1)))
                 while len(pending) > n - 1:
